@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- body-pair-interactions/sec of the HIP stepper (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path (forces + collisions + drift + compaction [+ slot all-gather]) over the
@@ -9,13 +9,19 @@ whole body set.  Workload = BASELINE.json configs[3] shape: N=262144 bodies, fp3
 condition (seed 1024), radii 0 (the "positions-only exchange" headline row of SURVEY.md 8d), literal
 reference semantics.  N>1: STRONG scaling - the same 262144 bodies range-partitioned over the ranks, one
 process per GPU, the per-step all-gather over RCCL inside the library; torch.distributed (gloo) only carries
-the 128-byte communicator id, the barriers and the max-over-ranks time.  After the timed region a multi-rank run
-checks ITSELF: the state the ranks hold (collective download) against a single-rank run of the same steps, bit for
-bit (`parity`), so a scaling line always carries its own correctness bit.
+the 128-byte communicator id, the barriers and the max-over-ranks time.
 
-Next to the CPU baseline (the oracle on the host cores, `cpu_baseline`) a 1-GPU fp32 run reports the speed of the
-reference's OWN kernels on the same GPU (`reference_kernels_on_this_gpu`: src/nbody.cu's device code compiled unmodified
-by hipcc, oracle/ref_hip) when that checker library has been built.
+A plain run sets up, warms up, times `--steps` steps and prints the line; nothing else.  `--dump-outputs DIR` then
+writes the body state the last timed step left (what a caller of the stepper downloads) as DIR/<name>.npy, in the
+run's precision; the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds the checks and baselines, all after the timed region:
+  * 1 GPU: the CPU baseline (the oracle on the host cores, `cpu_baseline`), the HIP path's first step against the
+    oracle on that sample (`parity`) and, for a literal run, the speed of the reference's OWN kernels on the same GPU
+    (`reference_kernels_on_this_gpu`: src/nbody.cu's device code compiled unmodified by hipcc, oracle/ref_hip) when
+    that checker library has been built;
+  * N>1 (or --force-comm): the state the ranks hold (collective download) against a single-rank run of the same
+    steps, bit for bit (`parity`, `parity_rccl_path`), so a scaling line carries its own correctness bit.
 
 Prints ONE JSON line on rank 0.  Inputs are resident in HBM before the timed region starts.
 """
@@ -36,6 +42,7 @@ FLOP_PER_PAIR = 20.0            # SURVEY.md 8d convention (18 + sqrt + divide)
 PEAK_FP32_VALU_TFLOPS = 157.3   # MI355X_MICROARCH.md: peak FP32 vector (packed issue)
 PEAK_FP64_VALU_TFLOPS = 78.6
 PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs: larger states are written as a fixed, seeded sample of bodies
 
 
 TRAFFIC_FILE = os.path.join("profiles", "r03_traffic_pmc.json")
@@ -159,12 +166,8 @@ def cpu_baseline(nb, bodies, cfg, budget_s=12.0, semantics=0):
     return base, parity_of_sample(nb, bodies, cfg, lo, count, oP, oV, oM, oR, semantics)
 
 
-def parity_of_ranks(nb, st, bodies, cfg, precision, device, total_steps, rank, semantics=0, dist=None):
-    """world > 1: the state the ranks hold after the run (collective download over RCCL: every rank calls it) against
-    a fresh SINGLE-rank stepper run for the same number of steps on rank 0's GPU.  Sharding changes who computes a
-    body, never what is computed, so the bar is bitwise equality; the single-rank path is the one the 1-GPU line checks
-    against the CPU oracle."""
-    import numpy as np
+def collective_download(nb, st, dist=None):
+    """The state the ranks hold (with a communicator the download is a collective over RCCL: every rank calls it)."""
     if dist is not None:
         # The download is a collective: a rank whose context has already failed must not leave the others waiting in
         # it.  Every rank looks at its own context first and all agree (gloo) on whether to go in.
@@ -178,7 +181,37 @@ def parity_of_ranks(nb, st, bodies, cfg, precision, device, total_steps, rank, s
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         if int(flag[0]) == 0:
             raise RuntimeError("a rank's context reports a device failure: collective download skipped on every rank")
-    got = st.download()
+    return st.download()
+
+
+def dump_outputs(directory, state):
+    """--dump-outputs: the body state after the last timed step, as a caller of the stepper receives it
+    (Stepper.download): positions (n, 2), velocities (n, 2), masses (n), radii (n) in the run's precision, and the body
+    count.  A state above DUMP_LIMIT_BYTES is written as a fixed sample of bodies (seed 0, ascending; its indices in
+    sample_index.npy)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    n = state.numBodies
+    arrays = {"positions": state.Positions, "velocities": state.Velocities, "masses": state.Masses,
+              "radii": state.Radii}
+    per_body = sum(v.itemsize * (v.size // max(n, 1)) for v in arrays.values())
+    if n * per_body + 4096 > DUMP_LIMIT_BYTES:
+        count = (DUMP_LIMIT_BYTES - 4096) // (per_body + 8)   # + 8: the float64 index of each sampled body; .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n, count, replace=False))
+        arrays = {name: v[idx] for name, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    arrays["num_bodies"] = np.array([n], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
+def parity_of_ranks(nb, st, bodies, cfg, precision, device, total_steps, rank, semantics=0, dist=None):
+    """world > 1: the state the ranks hold after the run (collective download over RCCL: every rank calls it) against
+    a fresh SINGLE-rank stepper run for the same number of steps on rank 0's GPU.  Sharding changes who computes a
+    body, never what is computed, so the bar is bitwise equality; the single-rank path is the one the 1-GPU line checks
+    against the CPU oracle."""
+    import numpy as np
+    got = collective_download(nb, st, dist)
     if rank != 0:
         return None
     one = nb.Stepper(cfg, precision=precision, device=device, semantics=semantics)
@@ -273,22 +306,30 @@ def baseline_config_name(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the body state of the last one as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and baselines after the timed region (CPU baseline and parity with the "
+                         "oracle, the reference's kernels on this GPU, multi-rank parity with a single-rank run)")
     ap.add_argument("--bodies", type=int, default=262144)
     ap.add_argument("--stock-radii", action="store_true", help="radii 50-200 (collisions on) instead of 0")
     ap.add_argument("--fp64", action="store_true")
     ap.add_argument("--clean", action="store_true",
                     help="clean semantics (every body active, true all-pairs, j ascending: SURVEY.md 8 f4) instead of "
                          "the reference's literal index semantics")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="world > 1: skip the comparison with a single-rank run")
-    ap.add_argument("--cpu-budget", type=float, default=12.0)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="--full, world > 1: skip the comparison with a single-rank run")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of the CPU baseline sample")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--force-comm", action="store_true",
                     help="take the multi-rank code path (rendezvous, RCCL communicator, slot all-gather) even "
                          "with one rank; used to rehearse the N>1 launch on a 1-GPU box")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -428,6 +469,12 @@ def main():
                 "slot_bytes_per_rank_now": s1.slot_bytes_now,
                 "note": "exchange = one all-gather of {count | records | velocities} slots laid out for the live bound of "
                         "the body count (24 B per body + 32 B header per rank)"}
+            out["config"]["rccl_ranks"] = world
+    if a.dump_outputs:
+        state = collective_download(nb, st, dist)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, state)
+    if rank == 0 and a.full:
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"], out["parity"] = cpu_baseline(nb, bodies, cfg, a.cpu_budget, semantics)
             try:
@@ -436,7 +483,7 @@ def main():
                 ref_gpu = {"error": "%s: %s" % (type(e).__name__, e)}
             if ref_gpu is not None:
                 out["reference_kernels_on_this_gpu"] = ref_gpu
-    if (world > 1 or a.force_comm) and not a.no_parity:
+    if a.full and (world > 1 or a.force_comm) and not a.no_parity:
         # every rank takes part (the download is a collective); rank 0 compares and reports.  A failing check must
         # not take the measured line down with it: it is reported in the line instead.
         try:
@@ -445,7 +492,6 @@ def main():
             par = {"error": "%s: %s" % (type(e).__name__, e), "bitwise_equal": False}
         if rank == 0:
             out["parity" if world > 1 else "parity_rccl_path"] = par
-            out["config"]["rccl_ranks"] = world
     if rank == 0:
         print(json.dumps(out), file=real_stdout, flush=True)
     st.close()

@@ -32,7 +32,7 @@ def test_bench_two_ranks_self_check(ranks):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus",
-           str(ranks), "--steps", "3", "--warmup", "1", "--bodies", "16384", "--stock-radii", "--no-cpu-baseline"]
+           str(ranks), "--steps", "3", "--warmup", "1", "--bodies", "16384", "--stock-radii", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -967,7 +967,7 @@ def test_bench_distributed_control_path_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "1", "--bodies", "16384", "--stock-radii", "--force-comm", "--no-cpu-baseline"]
+           "--warmup", "1", "--bodies", "16384", "--stock-radii", "--force-comm", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -977,6 +977,38 @@ def test_bench_distributed_control_path_one_rank():
     assert d["parity_rccl_path"]["bodies_after"] < 16384          # deletions happened: the slots were ragged
     assert abs(d["roofline"]["algorithmic_bytes_per_launch"] - 48 * 16384) <= 48 * 2000   # 48 B per body (fp32)
     assert 0 < d["roofline"]["valu"]["frac"] < 1
+
+
+def test_bench_plain_run_dumps_last_step(nb, tmp_path):
+    """A plain bench.py run (no --full): one JSON line without the check and baseline legs, and --dump-outputs writes
+    the state the last timed step left, bit-identical to a Stepper run of the same warm-up + timed steps."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--bodies", "16384", "--stock-radii", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "body-pair-interactions/sec" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert not {"cpu_baseline", "parity", "reference_kernels_on_this_gpu"} & set(d)
+    cfg = nb.stock_config(particleCount=16384, totalIterations=3)
+    st = nb.Stepper(cfg, device=0)
+    st.upload(nb.init_bodies(cfg))
+    st.step(1 + 3)
+    want = st.download()
+    st.close()
+    assert np.load(out / "num_bodies.npy").tolist() == [float(want.numBodies)] == [float(d["config"]["bodies_after"])]
+    assert want.numBodies < 16384                                  # deletions happened
+    for name, w in (("positions", want.Positions), ("velocities", want.Velocities), ("masses", want.Masses),
+                    ("radii", want.Radii)):
+        g = np.load(out / (name + ".npy"))
+        assert g.dtype == np.float32 and g.shape == w.shape, (name, g.dtype, g.shape)
+        assert np.array_equal(bits(g), bits(w)), name
 
 
 def test_cli_matches_oracle(nb, tmp_path):
