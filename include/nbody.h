@@ -248,6 +248,33 @@ int nbody_partition(int n, int rank, int world, int* lo, int* cnt);
 void* nbody_ctx_stream(nbody_ctx* ctx);   /* hipStream_t of the context */
 
 /* ---------------------------------------------------------------------------------------------------
+ * Physical diagnostics of the resident state (the reference has none).  Everything in IEEE fp64 (fp32 states are widened
+ * exactly), over the n current bodies, independent of the semantics (a literal context's frozen tail counts like any
+ * other body); G = (double)6.67408e-11f as in the force kernels.
+ *     mass = sum m_i                       momentum = sum m_i v_i             center_of_mass = sum m_i x_i / mass
+ *     angular_momentum = sum m_i (x_i v_iy - y_i v_ix), about the origin      kinetic = 1/2 sum m_i |v_i|^2
+ *     phi_i = -G sum_{j != i, r_ij > 0} m_j / r_ij                            potential = 1/2 sum m_i phi_i
+ * center_of_mass is NaN when mass == 0.  Ordered pairs i != j at distance exactly 0 are left out of phi and counted in
+ * coincident_pairs.  Each term m_j / r_ij is within 4 ulps of its exact value; phi_i is one sum over j ascending, and the
+ * totals are reduced per aligned 128-body tile and then over the tiles in ascending order: the result bits depend on the
+ * state only, not on the rank, the world, the transport or the force kernel.  A call never changes what later steps
+ * compute.  Non-finite inputs may give non-finite outputs.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_diag {
+    int64_t step;              /* steps since upload                                                      */
+    int64_t n_bodies;          /* current global body count                                               */
+    int64_t coincident_pairs;  /* ordered pairs i != j at distance 0, left out of phi and potential       */
+    double mass, momentum[2], center_of_mass[2], angular_momentum, kinetic, potential;
+} nbody_diag;
+/* Synchronises. phi: NULL, or room for `capacity` doubles; receives phi_i in global index order.
+ * On an RCCL context (world > 1) this is a COLLECTIVE, like nbody_download: every rank calls it, every rank
+ * gets the same bits.  A rank of a NBODY_FLAG_GROUP_EXCHANGE group on its own: NBODY_ERR_STATE (use the group form). */
+int nbody_get_diagnostics(nbody_ctx* ctx, nbody_diag* out, double* phi);
+/* The same for a single-process group (ctxs as in nbody_group_step); refuses ranks that were not uploaded and stepped
+ * together. */
+int nbody_group_diagnostics(nbody_ctx** ctxs, int world, nbody_diag* out, double* phi);
+
+/* ---------------------------------------------------------------------------------------------------
  * Reference-shaped launches on caller-owned DEVICE memory: one-to-one replacements of the two <<<>>> sites
  * src/nbody.cu:481-483.  d_bodyData is a device block in the reference layout for numBodies bodies;
  * velocities are updated in place, updatedMasses/updatedRadii are the scratch arrays of :463-464.  The

@@ -69,6 +69,19 @@ class Stats(ctypes.Structure):
                 ("exchange_bytes", ctypes.c_int64), ("slot_bytes_now", ctypes.c_int64)]
 
 
+class Diag(ctypes.Structure):
+    """struct nbody_diag (include/nbody.h): diagnostics of the resident state, fp64."""
+    _fields_ = [("step", ctypes.c_int64), ("n_bodies", ctypes.c_int64), ("coincident_pairs", ctypes.c_int64),
+                ("mass", ctypes.c_double), ("momentum", ctypes.c_double * 2), ("center_of_mass", ctypes.c_double * 2),
+                ("angular_momentum", ctypes.c_double), ("kinetic", ctypes.c_double), ("potential", ctypes.c_double)]
+
+    def as_dict(self):
+        return {"step": self.step, "n_bodies": self.n_bodies, "coincident_pairs": self.coincident_pairs,
+                "mass": self.mass, "momentum": (self.momentum[0], self.momentum[1]),
+                "center_of_mass": (self.center_of_mass[0], self.center_of_mass[1]),
+                "angular_momentum": self.angular_momentum, "kinetic": self.kinetic, "potential": self.potential}
+
+
 class Rng(ctypes.Structure):
     _fields_ = [("u", ctypes.c_uint64), ("v", ctypes.c_uint64), ("w", ctypes.c_uint64)]
 
@@ -123,6 +136,8 @@ SYMBOLS = {
     "nbody_own_range": (_i, [_vp, _ip, _ip]),
     "nbody_partition": (_i, [_i, _i, _i, _ip, _ip]),
     "nbody_ctx_stream": (_vp, [_vp]),
+    "nbody_get_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
+    "nbody_group_diagnostics": (_i, [_pp, _i, ctypes.POINTER(Diag), _vp]),
     "nbody_num_blocks": (_i, [_i]),
     "nbody_launch_compute_forces_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _i, _i, _f, _vp]),
     "nbody_launch_move_bodies_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _vp]),
@@ -290,6 +305,16 @@ def comm_unique_id():
     return buf.raw
 
 
+def _diagnostics(call, capacity, potential):
+    d = Diag()
+    phi = np.zeros(max(capacity, 1), dtype=np.float64) if potential else None
+    _check(call(ctypes.byref(d), phi.ctypes.data if potential else None))
+    out = d.as_dict()
+    if potential:
+        out["phi"] = phi[:d.n_bodies].copy()
+    return out
+
+
 class Stepper:
     """Device-resident stepper: the loop body of src/nbody.cu:460-545 without the per-step host round trip."""
 
@@ -396,6 +421,11 @@ class Stepper:
         _check(lib.nbody_debug_ring_probe(self._ctx, ctypes.byref(out)))
         return list(out)
 
+    def diagnostics(self, potential=False):
+        """nbody_get_diagnostics: mass, momentum, center_of_mass, angular_momentum, kinetic, potential (fp64) and
+        coincident_pairs of the current state; with potential=True also "phi", the per-body potential (n float64)."""
+        return _diagnostics(lambda d, phi: lib.nbody_get_diagnostics(self._ctx, d, phi), self.capacity, potential)
+
     def stats(self):
         s = Stats()
         _check(lib.nbody_get_stats(self._ctx, ctypes.byref(s)))
@@ -428,6 +458,11 @@ class StepperGroup:
         _check(lib.nbody_group_download(self._arr, self.world, out.ptr, ctypes.byref(n)))
         out.numBodies = n.value
         return out
+
+    def diagnostics(self, potential=False):
+        """nbody_group_diagnostics: as Stepper.diagnostics, for the whole group."""
+        return _diagnostics(lambda d, phi: lib.nbody_group_diagnostics(self._arr, self.world, d, phi), self.capacity,
+                            potential)
 
     def close(self):
         for r in self.ranks:

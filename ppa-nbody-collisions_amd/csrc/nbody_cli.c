@@ -4,7 +4,9 @@
  * Image output (:512-539) is produced with --images: iteration_<k>.ppm in cfg.imagePath for every k that is a
  * multiple of save_Image_Every_Xth_Iteration and not the last iteration (the reference saves the image of
  * iteration k during iteration k+1, :513-522, so the last one is never written).  Without --images the run is
- * the pure stepping loop.  Host code in C over the C ABI. */
+ * the pure stepping loop.  --diagnostics K prints one `diag ...` line (nbody_get_diagnostics / nbody_group_diagnostics,
+ * %.17g: the values round-trip) after the upload, after every K-th step and after the last one.  Host code in C over
+ * the C ABI. */
 #include "nbody.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,6 +19,17 @@ static double now(void) {   /* jbutil::gettime, include/jbutil.h:98-104 */
     return (double)tv.tv_sec + (double)tv.tv_usec * 1e-6;
 }
 
+static int print_diag(nbody_ctx** ctxs, int gpus) {
+    nbody_diag d;
+    int rc = gpus > 1 ? nbody_group_diagnostics(ctxs, gpus, &d, NULL) : nbody_get_diagnostics(ctxs[0], &d, NULL);
+    if (rc != NBODY_OK) return rc;
+    printf("diag step=%lld n=%lld mass=%.17g px=%.17g py=%.17g cx=%.17g cy=%.17g L=%.17g kinetic=%.17g potential=%.17g "
+           "coincident=%lld\n",
+           (long long)d.step, (long long)d.n_bodies, d.mass, d.momentum[0], d.momentum[1], d.center_of_mass[0],
+           d.center_of_mass[1], d.angular_momentum, d.kinetic, d.potential, (long long)d.coincident_pairs);
+    return NBODY_OK;
+}
+
 static int die(const char* what, int rc) {
     fprintf(stderr, "%s: %s: %s\n", what, nbody_status_string(rc), nbody_last_error_string());
     return 1;
@@ -24,14 +37,18 @@ static int die(const char* what, int rc) {
 
 int main(int argc, char** argv) {
     const char* path = "nbodyConfig.txt";
-    int precision = NBODY_F32, gpus = 1, dump = 0, images = 0;
+    int precision = NBODY_F32, gpus = 1, dump = 0, images = 0, diag_every = 0;
     for (int a = 1; a < argc; ++a) {
         if (!strcmp(argv[a], "--config") && a + 1 < argc) path = argv[++a];
         else if (!strcmp(argv[a], "--fp64")) precision = NBODY_F64;
         else if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--dump")) dump = 1;
         else if (!strcmp(argv[a], "--images")) images = 1;
-        else { fprintf(stderr, "usage: nbody [--config FILE] [--fp64] [--gpus N] [--dump] [--images]\n"); return 2; }
+        else if (!strcmp(argv[a], "--diagnostics") && a + 1 < argc && atoi(argv[a + 1]) > 0) diag_every = atoi(argv[++a]);
+        else {
+            fprintf(stderr, "usage: nbody [--config FILE] [--fp64] [--gpus N] [--dump] [--images] [--diagnostics K]\n");
+            return 2;
+        }
     }
     if (gpus < 1 || gpus > 64) return 2;
     double startTime = now();
@@ -58,22 +75,35 @@ int main(int argc, char** argv) {
         if (rc != NBODY_OK) return die("upload", rc);
     }
     double t0 = now();
-    if (!images || cfg.save_Image_Every_Xth_Iteration <= 0) {
+    if (diag_every > 0) {
+        rc = print_diag(ctxs, gpus);
+        if (rc != NBODY_OK) return die("diagnostics", rc);
+    }
+    const int every = images ? cfg.save_Image_Every_Xth_Iteration : 0;
+    if (every <= 0 && diag_every <= 0) {
         rc = nbody_group_step(ctxs, gpus, cfg.totalIterations);
         if (rc != NBODY_OK) return die("step", rc);
     } else {
-        unsigned char* img = (unsigned char*)malloc((size_t)cfg.imgWidth * cfg.imgHeight);
-        if (!img) return die("image alloc", NBODY_ERR_NOMEM);
+        unsigned char* img = every > 0 ? (unsigned char*)malloc((size_t)cfg.imgWidth * cfg.imgHeight) : NULL;
+        if (every > 0 && !img) return die("image alloc", NBODY_ERR_NOMEM);
         int done = 0;
         while (done < cfg.totalIterations) {
             /* next iteration whose image the reference would save: k % every == 0 and k + 1 < totalIterations */
-            int k = ((done + cfg.save_Image_Every_Xth_Iteration - 1) / cfg.save_Image_Every_Xth_Iteration) *
-                    cfg.save_Image_Every_Xth_Iteration;
+            int k = every > 0 ? ((done + every - 1) / every) * every : cfg.totalIterations;
             int upto = (k + 1 < cfg.totalIterations) ? k + 1 : cfg.totalIterations;
+            /* and the next step count that gets a diagnostics line: a multiple of diag_every, or the last */
+            if (diag_every > 0) {
+                const int dnext = (done / diag_every + 1) * diag_every;
+                if (dnext < upto) upto = dnext;
+            }
             rc = nbody_group_step(ctxs, gpus, upto - done);
             if (rc != NBODY_OK) return die("step", rc);
             done = upto;
-            if (k + 1 < cfg.totalIterations && done == k + 1) {
+            if (diag_every > 0 && (done % diag_every == 0 || done == cfg.totalIterations)) {
+                rc = print_diag(ctxs, gpus);
+                if (rc != NBODY_OK) return die("diagnostics", rc);
+            }
+            if (every > 0 && k + 1 < cfg.totalIterations && done == k + 1) {
                 char name[NBODY_IMAGE_PATH_MAX + 64];
                 rc = nbody_render_image(ctxs[0], img, cfg.imgWidth, cfg.imgHeight);
                 if (rc != NBODY_OK) return die("render", rc);

@@ -21,6 +21,7 @@
 #include "nbody.h"
 #include "nbody_error.h"
 #include "nbody_kernels.hpp"
+#include "nbody_diag.hpp"
 
 using namespace nbk;
 
@@ -159,6 +160,10 @@ struct nbody_ctx {
     int64_t force_launches = 0;
     double xchg_ms = 0.0;
     int64_t xchg_launches = 0;
+    // diagnostics (nbody_get_diagnostics): allocated on the first call
+    DiagTile* dg_tiles = nullptr;      // per own tile: partial sums (cap_own / 128 records)
+    double* dg_phi = nullptr;          // phi of the own range (cap_own doubles)
+    unsigned char* dg_gather = nullptr;    // world * (tiles | phi) of the padded per-rank areas
 };
 
 namespace {
@@ -446,11 +451,13 @@ int launch_commit(nbody_ctx* c) {
 // same code for both, so the single-GPU group tests execute what a multi-GPU RCCL run executes, the ncclAllGather call
 // itself excepted.
 // ---------------------------------------------------------------------------------------------------------
-enum class Part { Slot, Velocities, MetaBlock };
+enum class Part { Slot, Velocities, MetaBlock, DiagTiles, Potential };
 const unsigned char* part_of(const nbody_ctx* c, Part what) {
     switch (what) {
         case Part::Slot: return c->slot;
         case Part::Velocities: return (const unsigned char*)c->Vown;
+        case Part::DiagTiles: return (const unsigned char*)c->dg_tiles;
+        case Part::Potential: return (const unsigned char*)c->dg_phi;
         default: return (const unsigned char*)c->meta;
     }
 }
@@ -518,12 +525,124 @@ void free_all(nbody_ctx* c) {
     if (c->gather && c->gather != c->slot) hipFree(c->gather);
     hipFree(c->slot);
     hipFree(c->blk_counts); hipFree(c->tile_rmax); hipFree(c->Jt); hipFree(c->meta); hipFree(c->meta_all); hipFree(c->events); hipFree(c->d_img);
+    hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
     if (c->h_counters) hipHostFree(c->h_counters);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Diagnostics (nbody_get_diagnostics / nbody_group_diagnostics, kernels in nbody_diag.hpp)
+// ---------------------------------------------------------------------------------------------------------
+// Padded per-rank areas of the diagnostics gather: laid out for own_upper_of(n) bodies (n is exact and the same on every
+// rank: all have synchronised), like the velocity gather of nbody_download.
+size_t diag_tile_area(const nbody_ctx* c, int n) { return (size_t)(own_upper_of(c, n) / kTile) * sizeof(DiagTile); }
+size_t diag_phi_area(const nbody_ctx* c, int n) { return (size_t)own_upper_of(c, n) * sizeof(double); }
+
+int diag_alloc(nbody_ctx* c) {
+    if (c->dg_gather) return NBODY_OK;
+    const size_t tb = (size_t)(c->cap_own / kTile) * sizeof(DiagTile), pb = (size_t)c->cap_own * sizeof(double);
+    hipError_t e = hipMalloc((void**)&c->dg_tiles, tb);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->dg_phi, pb);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->dg_gather, (tb + pb) * (size_t)c->desc.world);
+    if (e != hipSuccess) {
+        hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
+        c->dg_tiles = nullptr; c->dg_phi = nullptr; c->dg_gather = nullptr;
+        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "diagnostics buffers: %s",
+                          hipGetErrorString(e));
+    }
+    return NBODY_OK;
+}
+
+// The own range's kernels, on the context's stream.  Needs the exact {n, lo, cnt} of a read_meta just before.
+template <typename T>
+int diag_launch_t(nbody_ctx* c) {
+    const int n = c->h_meta->n, lo = c->h_meta->lo, cnt = c->h_meta->cnt;
+    if (cnt <= 0) return NBODY_OK;
+    if (cnt > c->cap_own || lo < 0 || (long long)lo + cnt > n || n > c->cap)
+        return nbody_fail(NBODY_ERR_STATE, "own range [%d, +%d) of %d bodies does not fit the context", lo, cnt, n);
+    const double G = (double)6.67408e-11f;               // src/nbody.cu:37, the float literal widened (make_params)
+    const int tiles = (cnt + kTile - 1) / kTile;
+    hipLaunchKernelGGL((diag_moments<T>), dim3((tiles + kWave - 1) / kWave), dim3(kWave), 0, c->stream,
+                       (const Rec<T>*)c->J, (const Vec2<T>*)c->Vown, lo, cnt, c->dg_tiles);
+    hipLaunchKernelGGL((diag_potential<T>), dim3((cnt + kDiagBlock - 1) / kDiagBlock), dim3(kDiagBlock), 0, c->stream,
+                       (const Rec<T>*)c->J, n, lo, cnt, G, c->dg_phi, c->dg_tiles);
+    HIP_TRY(hipGetLastError());
+    return NBODY_OK;
+}
+int diag_launch(nbody_ctx* c) {
+    int rc = diag_alloc(c);
+    if (rc != NBODY_OK) return rc;
+    return c->desc.precision == NBODY_F64 ? diag_launch_t<double>(c) : diag_launch_t<float>(c);
+}
+
+// Gathers every rank's tiles and phi (the same all-gather interface as the step's exchange: RCCL, peer copies, or a
+// local copy on a single rank), places them by the {lo, cnt} each rank reports, and reduces over the tiles in ascending
+// global order.  An RCCL call is a collective: every rank gathers both parts, whatever its own `phi` argument.
+int diag_collect(nbody_ctx* c, nbody_diag* out, double* phi) {
+    const int n = c->h_meta->n, world = c->desc.world;
+    const int U = own_upper_of(c, n);
+    const size_t tb = diag_tile_area(c, n), pb = diag_phi_area(c, n);
+    unsigned char* gt = c->dg_gather;
+    unsigned char* gp = c->dg_gather + tb * world;
+    std::vector<Meta> h_all(world);
+    if (world == 1 && !c->comm) {
+        h_all[0] = *c->h_meta;
+        if (tb) HIP_TRY(hipMemcpyAsync(gt, c->dg_tiles, tb, hipMemcpyDeviceToDevice, c->stream));
+        if (pb && phi) HIP_TRY(hipMemcpyAsync(gp, c->dg_phi, pb, hipMemcpyDeviceToDevice, c->stream));
+    } else if (c->comm || c->peers) {
+        int rc = tb ? all_gather(c, Part::DiagTiles, gt, tb) : NBODY_OK;    // n is the same on every rank
+        if (rc == NBODY_OK && pb) rc = all_gather(c, Part::Potential, gp, pb);
+        if (rc == NBODY_OK) rc = all_gather(c, Part::MetaBlock, (unsigned char*)c->meta_all, sizeof(Meta));
+        if (rc != NBODY_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(h_all.data(), c->meta_all, sizeof(Meta) * world, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        return nbody_fail(NBODY_ERR_STATE, "rank %d of a %d-rank group on its own cannot see the other ranks' velocities: "
+                                           "call nbody_group_diagnostics", c->desc.rank, world);
+    }
+    std::vector<DiagTile> h_tiles(tb / sizeof(DiagTile) * world);
+    std::vector<double> h_phi(phi ? (size_t)U * world : 0);
+    if (tb) HIP_TRY(hipMemcpyAsync(h_tiles.data(), gt, tb * world, hipMemcpyDeviceToHost, c->stream));
+    if (pb && phi) HIP_TRY(hipMemcpyAsync(h_phi.data(), gp, pb * world, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // every global tile exactly once, from the rank that reports it (the checks of nbody_download)
+    const int nt = (n + kTile - 1) / kTile;
+    std::vector<const DiagTile*> by_tile(nt, nullptr);
+    for (int g = 0; g < world; ++g) {
+        const Meta& m = h_all[g];
+        if (m.n != n || m.lo < 0 || m.cnt < 0 || m.cnt > U || (long long)m.lo + m.cnt > n || m.lo % kTile != 0)
+            return nbody_fail(NBODY_ERR_STATE, "rank %d reports range [%d, +%d) of %d bodies, this rank has %d bodies", g,
+                              m.lo, m.cnt, m.n, n);
+        for (int k = 0; k < (m.cnt + kTile - 1) / kTile; ++k) {
+            const int t = m.lo / kTile + k;
+            if (by_tile[t]) return nbody_fail(NBODY_ERR_STATE, "tile %d is reported by two ranks", t);
+            by_tile[t] = &h_tiles[(size_t)g * (U / kTile) + k];
+        }
+        if (phi) memcpy(phi + m.lo, &h_phi[(size_t)g * U], (size_t)m.cnt * sizeof(double));
+    }
+    double mass = 0, px = 0, py = 0, mx = 0, my = 0, L = 0, K2 = 0, pot = 0;
+    long long coincident = 0;
+    for (int t = 0; t < nt; ++t) {
+        const DiagTile* d = by_tile[t];
+        if (!d) return nbody_fail(NBODY_ERR_STATE, "tile %d of %d bodies is reported by no rank", t, n);
+        mass = mass + d->mass; px = px + d->px; py = py + d->py; mx = mx + d->mx; my = my + d->my;
+        L = L + d->L; K2 = K2 + d->K2; pot = pot + d->pot; coincident += d->coincident;
+    }
+    out->step = c->steps;
+    out->n_bodies = n;
+    out->coincident_pairs = coincident;
+    out->mass = mass;
+    out->momentum[0] = px;
+    out->momentum[1] = py;
+    out->center_of_mass[0] = mass == 0.0 ? NAN : mx / mass;
+    out->center_of_mass[1] = mass == 0.0 ? NAN : my / mass;
+    out->angular_momentum = L;
+    out->kinetic = 0.5 * K2;
+    out->potential = 0.5 * pot;
+    return NBODY_OK;
 }
 
 }  // namespace
@@ -826,6 +945,55 @@ int nbody_group_download(nbody_ctx** ctxs, int world, void* block, int* n_out) {
     }
     ctxs[0]->peers = ctxs;
     int rc = nbody_download(ctxs[0], block, n_out);
+    ctxs[0]->peers = nullptr;
+    return rc;
+}
+
+// Diagnostics of a single context (world 1, or a rank of an RCCL run: a collective).
+int nbody_get_diagnostics(nbody_ctx* c, nbody_diag* out, double* phi) {
+    if (!c || !out) return nbody_fail(NBODY_ERR_INVALID, "nbody_get_diagnostics: NULL argument");
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_get_diagnostics before nbody_upload");
+    if (c->desc.world > 1 && (c->desc.flags & NBODY_FLAG_GROUP_EXCHANGE))
+        return nbody_fail(NBODY_ERR_STATE, "group context: its diagnostics need the whole group (nbody_group_diagnostics)");
+    HIP_TRY(hipSetDevice(c->desc.device));
+    int rc = read_meta(c);
+    if (rc == NBODY_OK) rc = diag_launch(c);
+    if (rc == NBODY_OK) rc = diag_collect(c, out, phi);
+    return rc;
+}
+
+// Diagnostics of a single-process group: every rank runs its own range's kernels, then rank 0 gathers with the peer-copy
+// transport exactly as a rank of an RCCL run does (as nbody_group_download).
+int nbody_group_diagnostics(nbody_ctx** ctxs, int world, nbody_diag* out, double* phi) {
+    if (!ctxs || world < 1 || !out) return nbody_fail(NBODY_ERR_INVALID, "nbody_group_diagnostics: bad argument");
+    int n0 = -1;
+    for (int g = 0; g < world; ++g) {
+        nbody_ctx* c = ctxs[g];
+        if (!c || c->desc.world != world || c->desc.rank != g || !c->uploaded)
+            return nbody_fail(NBODY_ERR_STATE, "nbody_group_diagnostics: context %d is not rank %d of %d (or not uploaded)", g,
+                              g, world);
+        if (c->enq != ctxs[0]->enq || c->xchg_n != ctxs[0]->xchg_n)
+            return nbody_fail(NBODY_ERR_STATE, "nbody_group_diagnostics: context %d is at step %lld, context 0 at step %lld "
+                                               "(upload and step the group together)",
+                              g, (long long)c->enq, (long long)ctxs[0]->enq);
+        HIP_TRY(hipSetDevice(c->desc.device));
+        int rc = read_meta(c);
+        if (rc != NBODY_OK) return rc;
+        if (g == 0) n0 = c->h_meta->n;
+        if (c->h_meta->n != n0) return nbody_fail(NBODY_ERR_STATE, "group ranks disagree on the body count");
+    }
+    for (int g = 0; g < world; ++g) {
+        HIP_TRY(hipSetDevice(ctxs[g]->desc.device));
+        int rc = diag_launch(ctxs[g]);
+        if (rc != NBODY_OK) return rc;
+    }
+    for (int g = 0; g < world; ++g) {                      // the gather reads the peers' buffers
+        HIP_TRY(hipSetDevice(ctxs[g]->desc.device));
+        HIP_TRY(hipStreamSynchronize(ctxs[g]->stream));
+    }
+    HIP_TRY(hipSetDevice(ctxs[0]->desc.device));
+    ctxs[0]->peers = ctxs;
+    int rc = diag_collect(ctxs[0], out, phi);
     ctxs[0]->peers = nullptr;
     return rc;
 }

@@ -1,0 +1,176 @@
+// csrc/nbody_diag.hpp -- physical diagnostics of the resident state (nbody_get_diagnostics, include/nbody.h): the
+// per-body potential phi_i = -G sum_{j != i, r_ij > 0} m_j / r_ij and the O(N) moments, all in fp64 (fp32 inputs are
+// widened exactly).  Included by nbody_ctx.hip after nbody_kernels.hpp.
+//
+// Order contract.  phi_i is ONE running sum over j = 0, 1, ..., n-1 in ascending order, whatever the
+// launch: it depends on (i, n) only, never on the rank, the world, the own count or the CU count.  The totals are
+// reduced per aligned 128-body tile (nbody_partition's unit) in ascending order inside the tile, and the host then adds
+// the tiles in ascending global order: a call gives the same bits for every partition of the same state.
+//
+// diag_potential: one lane per row i of the own range, 256-lane workgroups.  The j stream is wave-uniform: every
+// workgroup walks the replica tile by tile; a tile's {x, y, m} are widened to fp64 ONCE, into LDS (double-buffered, one
+// barrier per tile), and read back as broadcasts.  Per pair:
+//     dx = xj - xi;  dy = yj - yi;  d2 = fma(dx, dx, dy*dy)                               (4)
+//     y = v_rsq_f64(d2);  t = y*y;  e = fma(-d2, t, 1);  r = fma(y*e, fma(e, 3/8, 1/2), y)  (1 trans + 5)
+//     acc = fma(mj, r, acc)                                                                (1)
+// One third-order step takes v_rsq_f64's estimate to 1/sqrt(d2) within about 1 u (u = 2^-53): with d2 within 4 u of
+// dx^2 + dy^2 of the exact differences, each term m_j / r_ij is within 3 u (3 ulps) of its exact value while d2 stays
+// in [2^-1000, 2^1000] (any pair of an fp32 state).
+// Self term and coincident pairs cost nothing per pair in the common case:
+//   * j == i can only occur in the tile of i's own rows, which is wave-uniform; that ONE tile takes a checked loop
+//     (self term -> m = 0, d2 = 1: adds an exact +0).
+//   * d2 == 0 for j != i gives e = fma(-0, inf, 1) = NaN, and so do the degenerate d2 the fast chain cannot take
+//     (t = y*y overflowing or 0): the row's accumulator is then not finite.  After the walk, exactly those rows are
+//     redone with the general code (IEEE sqrt and divide, hypot outside the normal range, coincident pairs counted and
+//     left out) - again one ascending walk over j, so the row's value still depends on (i, n) only.
+// Each workgroup also writes, per row tile, the partial sum of m_i phi_i and the coincident count (rows ascending).
+//
+// diag_moments: one lane per own tile, a sequential walk over the tile's rows: mass, momentum, sum m x, angular momentum
+// about the origin, sum m v^2.
+#pragma once
+#include <float.h>
+
+#pragma clang fp contract(off)
+
+namespace nbk {
+
+struct DiagTile {             // per aligned 128-body tile of the own range (sums over its rows, ascending)
+    double mass, px, py, mx, my, L, K2, pot;   // K2 = sum m v^2, pot = sum m_i phi_i
+    long long coincident;                      // ordered pairs (i, j), i in the tile, j != i, at distance 0
+};
+static_assert(sizeof(DiagTile) == 72, "DiagTile layout");
+
+constexpr int kDiagBlock = 256;               // four waves, two row tiles
+
+// v_rsq_f64 is good to about 2^-25 only (one Newton step left 10 u on the MI355X): a third-order step,
+// y (1 + e/2 + 3e^2/8) with e = 1 - d2 y^2, leaves O(e^3) ~ 2^-75 plus the roundings of t and of the last fma, about 1 u.
+__device__ __forceinline__ double diag_rinv(double d2) {
+    const double y = __builtin_amdgcn_rsq(d2);
+    const double t = y * y;
+    const double e = __builtin_fma(-d2, t, 1.0);
+    const double p = __builtin_fma(e, 0.375, 0.5);
+    return __builtin_fma(y * e, p, y);
+}
+
+// The general code of a flagged row: exact on the whole range, coincident pairs counted and skipped.
+struct DiagRow { double s; long long coincident; };
+template <typename T>
+__device__ __forceinline__ DiagRow diag_row_general(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi) {
+    double s = 0.0;
+    long long c = 0;
+    for (int j = 0; j < n; ++j) {
+        if (j == i) continue;
+        const Rec<T> r = J[j];
+        const double dx = (double)r.x - xi, dy = (double)r.y - yi;
+        if (dx == 0.0 && dy == 0.0) { ++c; continue; }
+        const double d2 = __builtin_fma(dx, dx, dy * dy);
+        const double d = (d2 >= DBL_MIN && d2 <= DBL_MAX) ? __builtin_sqrt(d2) : hypot(dx, dy);
+        s = s + (double)r.m / d;
+    }
+    return DiagRow{s, c};
+}
+
+template <typename T>
+__global__ __launch_bounds__(kDiagBlock) void diag_potential(const Rec<T>* __restrict__ J, int n, int lo, int cnt,
+                                                             double G, double* __restrict__ phi,
+                                                             DiagTile* __restrict__ tiles) {
+    __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
+    __shared__ double wpot[kDiagBlock];
+    __shared__ long long wcoin[kDiagBlock];
+    const int tid = threadIdx.x;
+    const int row0 = blockIdx.x * kDiagBlock;                    // first own row of the workgroup
+    const int k = row0 + tid;                                    // own row of this lane
+    const bool valid = k < cnt;
+    const int i = lo + k;
+    double xi = 0.0, yi = 0.0, mi = 0.0;
+    if (valid) {
+        const Rec<T> r = J[i];
+        xi = (double)r.x; yi = (double)r.y; mi = (double)r.m;
+    }
+    // global tile of this wave's rows (lo is tile-aligned): the one j tile that holds their self terms
+    const int self_tile = (lo + row0 + (tid & ~(kWave - 1))) / kTile;
+    const int jtiles = (n + kTile - 1) / kTile;
+    double acc = 0.0;
+    for (int t = 0; t < jtiles; ++t) {
+        const int b = t & 1;
+        const int j0 = t * kTile;
+        const int jn = n - j0 < kTile ? n - j0 : kTile;
+        if (tid < jn) {
+            const Rec<T> r = J[j0 + tid];
+            sx[b][tid] = (double)r.x; sy[b][tid] = (double)r.y; sm[b][tid] = (double)r.m;
+        }
+        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
+        __syncthreads();
+        if (t != self_tile) {
+            int q = 0;
+            for (; q + 4 <= jn; q += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const double dx = sx[b][q + u] - xi, dy = sy[b][q + u] - yi;
+                    const double d2 = __builtin_fma(dx, dx, dy * dy);
+                    acc = __builtin_fma(sm[b][q + u], diag_rinv(d2), acc);
+                }
+            }
+            for (; q < jn; ++q) {
+                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
+                const double d2 = __builtin_fma(dx, dx, dy * dy);
+                acc = __builtin_fma(sm[b][q], diag_rinv(d2), acc);
+            }
+        } else {
+            for (int q = 0; q < jn; ++q) {
+                const bool self = j0 + q == i;
+                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
+                const double d2 = self ? 1.0 : __builtin_fma(dx, dx, dy * dy);
+                acc = __builtin_fma(self ? 0.0 : sm[b][q], diag_rinv(d2), acc);
+            }
+        }
+    }
+    long long coin = 0;
+    if (valid && !__builtin_isfinite(acc)) {
+        const DiagRow g = diag_row_general<T>(J, n, i, xi, yi);
+        acc = g.s;
+        coin = g.coincident;
+    }
+    const double p = -G * acc;
+    if (valid) phi[k] = p;
+    wpot[tid] = mi * p;
+    wcoin[tid] = coin;
+    __syncthreads();
+    if ((tid & (kTile - 1)) == 0) {                             // one lane per row tile: its rows in ascending order
+        const int r0 = row0 + tid;
+        if (r0 < cnt) {
+            const int rn = cnt - r0 < kTile ? cnt - r0 : kTile;
+            double s = 0.0;
+            long long c = 0;
+            for (int q = 0; q < rn; ++q) { s = s + wpot[tid + q]; c += wcoin[tid + q]; }
+            tiles[r0 / kTile].pot = s;
+            tiles[r0 / kTile].coincident = c;
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kWave) void diag_moments(const Rec<T>* __restrict__ J, const Vec2<T>* __restrict__ Vown,
+                                                      int lo, int cnt, DiagTile* __restrict__ tiles) {
+    const int t = blockIdx.x * kWave + threadIdx.x;
+    const int r0 = t * kTile;
+    if (r0 >= cnt) return;
+    const int rn = cnt - r0 < kTile ? cnt - r0 : kTile;
+    double mass = 0.0, px = 0.0, py = 0.0, mx = 0.0, my = 0.0, L = 0.0, K2 = 0.0;
+    for (int q = 0; q < rn; ++q) {
+        const Rec<T> r = J[lo + r0 + q];
+        const Vec2<T> v = Vown[r0 + q];
+        const double x = r.x, y = r.y, m = r.m, vx = v.x, vy = v.y;
+        mass = mass + m;
+        px = px + m * vx;
+        py = py + m * vy;
+        mx = mx + m * x;
+        my = my + m * y;
+        L = L + m * (x * vy - y * vx);
+        K2 = K2 + m * (vx * vx + vy * vy);
+    }
+    DiagTile& d = tiles[t];
+    d.mass = mass; d.px = px; d.py = py; d.mx = mx; d.my = my; d.L = L; d.K2 = K2;
+}
+
+}  // namespace nbk
