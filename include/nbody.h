@@ -187,7 +187,8 @@ typedef struct nbody_event {  /* one collision event, in the index space of the 
 } nbody_event;
 /* Copies up to cap logged events (unordered within a step) and the total number logged since the last
  * clear; total > cap means the caller's buffer was too small, total > event_capacity means the log
- * overflowed (extra events were counted, not stored). */
+ * overflowed (extra events were counted, not stored).  nbody_upload (and so nbody_state_load) clears the log and
+ * restarts the total: events carry step numbers of the current upload only. */
 int nbody_get_events(nbody_ctx* ctx, nbody_event* out, int cap, int64_t* total);
 int nbody_clear_events(nbody_ctx* ctx);
 
@@ -320,6 +321,11 @@ int nbody_selftest_lds_record(int device, int iters, uint64_t result[3]);
  * results land in the staging buffers and are never committed, so the state does not change (the pair and event
  * counters do count).  Lets one rank's kernel of a G-rank partition be timed / profiled in steady state on one GPU. */
 int nbody_debug_force_only(nbody_ctx* ctx, int reps);
+
+/* Testing aid: the bookkeeping the fp32 ring kernel's screens rest on, for the CURRENT replica (synchronises).
+ * summary = Meta::summary; tile_rmax receives min(cap, n_tiles) floats (largest |radius| per aligned 128-body
+ * tile, 0 for tiles past the end); *n_tiles = entries the context keeps.  Any output pointer may be NULL. */
+int nbody_debug_screen_state(nbody_ctx* ctx, int* summary, float* tile_rmax, int cap, int* n_tiles);
 
 /* Tuning aid (kernel_variant 58 only): cycle totals of the ring kernel's phases since upload, summed over waves:
  * {evaluate, wait, chain+publish, window check, polls, turns, shader clocks of one wave's life, the same in 100 MHz

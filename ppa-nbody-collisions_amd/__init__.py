@@ -148,6 +148,7 @@ SYMBOLS = {
     "nbody_selftest_lds_record": (_i, [_i, _i, ctypes.POINTER(ctypes.c_uint64 * 3)]),
     "nbody_debug_ring_probe": (_i, [_vp, ctypes.POINTER(ctypes.c_uint64 * 8)]),
     "nbody_debug_force_only": (_i, [_vp, _i]),
+    "nbody_debug_screen_state": (_i, [_vp, _ip, _vp, _i, _ip]),
 }
 
 
@@ -420,6 +421,14 @@ class Stepper:
         out = (ctypes.c_uint64 * 8)()
         _check(lib.nbody_debug_ring_probe(self._ctx, ctypes.byref(out)))
         return list(out)
+
+    def screen_state(self):
+        """nbody_debug_screen_state: (Meta::summary, the per-tile largest |radius| the context keeps, float32)."""
+        summary, n_tiles = ctypes.c_int(0), ctypes.c_int(0)
+        _check(lib.nbody_debug_screen_state(self._ctx, None, None, 0, ctypes.byref(n_tiles)))
+        rmax = np.zeros(n_tiles.value, dtype=np.float32)
+        _check(lib.nbody_debug_screen_state(self._ctx, ctypes.byref(summary), rmax.ctypes.data, n_tiles.value, None))
+        return summary.value, rmax
 
     def diagnostics(self, potential=False):
         """nbody_get_diagnostics: mass, momentum, center_of_mass, angular_momentum, kinetic, potential (fp64) and

@@ -1343,6 +1343,22 @@ int nbody_debug_force_only(nbody_ctx* c, int reps) {
     return NBODY_OK;
 }
 
+int nbody_debug_screen_state(nbody_ctx* c, int* summary, float* tile_rmax, int cap, int* n_tiles) {
+    if (!c || cap < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_debug_screen_state: bad argument");
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_debug_screen_state before nbody_upload");
+    HIP_TRY(hipSetDevice(c->desc.device));
+    int rc = read_meta(c);
+    if (rc != NBODY_OK) return rc;
+    if (summary) *summary = c->h_meta->summary;
+    if (n_tiles) *n_tiles = c->n_tiles;
+    const int k = cap < c->n_tiles ? cap : c->n_tiles;
+    if (tile_rmax && k > 0) {                              // the entries are the bits of non-negative floats
+        HIP_TRY(hipMemcpyAsync(tile_rmax, c->tile_rmax, sizeof(float) * (size_t)k, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return NBODY_OK;
+}
+
 int nbody_debug_ring_probe(nbody_ctx* c, uint64_t out[8]) {
     if (!c || !out) return nbody_fail(NBODY_ERR_INVALID, "nbody_debug_ring_probe: NULL");
     HIP_TRY(hipSetDevice(c->desc.device));

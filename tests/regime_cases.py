@@ -1,0 +1,345 @@
+"""The bookkeeping the fp32 ring kernel's screens rest on, stated independently of the kernels, and the states that make
+it change DURING a run.  Imported by CPU and GPU tests; uses the host side of the product (initial conditions) and the
+CPU oracle only, never a device.
+
+Meta::summary describes the whole replica of the current step (csrc/nbody_kernels.hpp):
+    bit 0 (1)  some coordinate is not below the coordinate bound in magnitude (NaN included): 2^38 (fp32), 2^249 (fp64)
+    bit 1 (2)  some radius is not +0 (-0.0 is not +0)
+    bit 2 (4)  fp32 contexts only: some coordinate is below 2^-16 in magnitude (zero and NaN included)
+    bit 3 (8)  fp32 contexts only: some mass is not below 2^90 in magnitude (NaN included)
+tile_rmax[k] is the largest |radius| of the aligned 128-body tile k (NaN radii ignored, inf kept), 0 past the end.
+
+Every builder below returns a case: the initial arrays, the parameters and THE SEQUENCE OF summary VALUES the oracle's
+trajectory must show (case["summaries"][s] = summary after step s + 1; case["summary0"] at upload).  The sequences are
+written down here, not computed: tests/test_regime_cases_cpu.py steps the oracle and asserts them, so a case that no
+longer reaches its regime fails there, on the CPU, by name - and the GPU tests cannot pass vacuously."""
+import functools
+
+import numpy as np
+
+import oracle_lib as ol
+
+F32, F64 = 0, 1
+UNBOUNDED, RADIUS, SMALL, MASS = 1, 2, 4, 8
+TILE = 128
+
+
+def _nb():
+    import ppa_nbody_collisions_amd as nb
+    return nb
+
+
+def expected_summary(P, M, R, precision):
+    """Meta::summary from its documented meaning, in numpy."""
+    f64 = precision == F64
+    t = np.float64 if f64 else np.float32
+    c = np.abs(np.asarray(P, dtype=t)).ravel()
+    m = np.abs(np.asarray(M, dtype=t)).ravel()
+    r = np.ascontiguousarray(np.asarray(R, dtype=t)).ravel()
+    with np.errstate(invalid="ignore"):
+        s = 0
+        if not bool(np.all(c < t(2.0) ** (249 if f64 else 38))):          # a NaN is not below the bound
+            s |= UNBOUNDED
+        if bool(np.any(r.view(np.uint64 if f64 else np.uint32) != 0)):    # anything but the bits of +0
+            s |= RADIUS
+        if not f64:
+            if not bool(np.all(c >= t(2.0) ** -16)):                      # a NaN is not at or above the floor
+                s |= SMALL
+            if not bool(np.all(m < t(2.0) ** 90)):
+                s |= MASS
+    return s
+
+
+def expected_tile_rmax(R, n_tiles):
+    """float32[n_tiles]: largest |radius| per aligned 128-body tile; NaN radii ignored, inf kept, 0 for unused tiles."""
+    with np.errstate(over="ignore"):
+        a = np.abs(np.asarray(R).ravel()).astype(np.float32)
+    out = np.zeros(n_tiles, dtype=np.float32)
+    for k in range((len(a) + TILE - 1) // TILE):
+        t = a[k * TILE:(k + 1) * TILE]
+        t = t[~np.isnan(t)]
+        if len(t):
+            out[k] = t.max()
+    return out
+
+
+def assert_screen_state(stepper_or_group, bodies, what=""):
+    """The accessor of the context - of EVERY rank of a group - equals the numpy statement for `bodies` (the downloaded
+    state, or what was just uploaded): summary exactly (a superset is a failure), tile_rmax bit for bit for the tiles in
+    use and 0 for every later one (fp32 contexts; fp64 contexts keep bounds rounded to float for nobody: summary only)."""
+    ranks = getattr(stepper_or_group, "ranks", None) or [stepper_or_group]
+    n = bodies.numBodies
+    want = expected_summary(bodies.Positions, bodies.Masses, bodies.Radii, bodies.precision)
+    for g, r in enumerate(ranks):
+        summary, rmax = r.screen_state()
+        assert summary == want, "%s rank %d: summary %d, expected %d" % (what, g, summary, want)
+        if bodies.precision == F32:
+            assert len(rmax) >= (n + TILE - 1) // TILE
+            wr = expected_tile_rmax(bodies.Radii, len(rmax))
+            if not np.array_equal(rmax.view(np.uint32), wr.view(np.uint32)):
+                bad = np.nonzero(rmax.view(np.uint32) != wr.view(np.uint32))[0]
+                raise AssertionError("%s rank %d: tile_rmax differs in tiles %s: got %s, expected %s (%d tiles in use)" % (
+                    what, g, bad[:8], rmax[bad[:8]], wr[bad[:8]], (n + TILE - 1) // TILE))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# cases
+# ---------------------------------------------------------------------------------------------------------
+def _case(name, bodies, summaries, summary0=0, dt=0.2, growth=0.1, field=100000, semantics=ol.LITERAL, **marks):
+    precision = bodies.precision
+    real = float if precision == F64 else np.float32
+    c = dict(name=name, bodies=bodies, n=bodies.numBodies, precision=precision, dt=real(dt), growth=real(growth),
+             field=field, semantics=semantics, summary0=summary0, summaries=list(summaries), steps=len(summaries))
+    c.update(marks)
+    return c
+
+
+def make_stepper(nb, case, world=1, capacity=None, **kw):
+    """A StepperGroup of `world` ranks (world == 1: one plain context) with the case's parameters."""
+    return nb.StepperGroup(world, capacity=capacity or case["n"], precision=case["precision"],
+                           semantics=case["semantics"], timestep=float(case["dt"]), growthRate=float(case["growth"]),
+                           fieldWidth=case["field"], fieldHeight=case["field"], **kw)
+
+
+def oracle_trajectory(case, want_events=False):
+    """[(n, block copy, absorb pairs, deleted)] after every step of the case's horizon, from the CPU oracle."""
+    blk = case["bodies"].block.copy()
+    cur = case["n"]
+    out = []
+    for _ in range(case["steps"]):
+        cur, _, ab, de, _ = ol.port_step(blk, cur, case["dt"], case["field"], case["field"], case["growth"],
+                                         semantics=case["semantics"], want_events=want_events)
+        out.append((cur, blk[:6 * cur].copy(), ab.copy(), de.copy()))
+    return out
+
+
+def summaries_of(case, traj=None):
+    traj = traj if traj is not None else oracle_trajectory(case)
+    out = []
+    for cur, blk, _, _ in traj:
+        P, _, M, R = ol.carve(blk, cur)
+        out.append(expected_summary(P, M, R, case["precision"]))
+    return out
+
+
+def _calm(n, precision=F32, max_mass=1e5, **kw):
+    """Stock initial condition (v = 0) with all radii +0; a small mass range keeps the velocity change of a step far
+    below half an ulp of a velocity of order 1, so planted bodies fly ballistically: x' = RN(x + RN(dt * v))."""
+    nb = _nb()
+    cfg = nb.stock_config(particleCount=n, minRadius=0.0, maxRadius=0.0, maxRandBodyMass=max_mass, **kw)
+    return nb.init_bodies(cfg, precision)
+
+
+@functools.lru_cache(maxsize=None)
+def case_small_enters_and_leaves():
+    """a: body 300 lands on x = 2^-20 and body 1700 exactly on y = 0 after step 2 (vx = vy = -5: RN(0.2f * 5.0f) is 1, the
+    positions 2 + 2^-20 -> 1 + 2^-20 -> 2^-20 and 2 -> 1 -> 0 are exact), both are a unit away again after step 3."""
+    b = _calm(2048)
+    P, V = b.Positions, b.Velocities
+    P[300] = [np.float32(2.0) + np.float32(2.0 ** -20), 300.0]
+    V[300] = [-5.0, 0.0]
+    P[1700] = [700.0, 2.0]
+    V[1700] = [0.0, -5.0]
+    return _case("small-enters-and-leaves", b, [0, SMALL, 0, 0, 0, 0], small_bodies=(300, 1700))
+
+
+@functools.lru_cache(maxsize=None)
+def case_small_pair_below_the_chain_domain():
+    """a, the pair: bodies 900 and 901 (mass 1e-25 each, same y) drift through x = 0 with displacements of about
+    -0.42 * 2^-16 per step.  A pair with 0 < d2 < 2^-80 needs both on the 2^-41 grid, i.e. below 2^-17; a body that was at
+    or above 2^-16 one step earlier sits on the 2^-40 grid at best (its position is a multiple of 2^-39, its displacement
+    then exceeds 2^-17), so from a summary == 0 state the pair cannot get there in ONE step: it enters [2^-17, 2^-16) after
+    step 2 (bit 2 goes on), lies on ADJACENT floats below 2^-17 after step 3 (d2 = 2^-82, evaluated by step 4 while bit 2
+    is set), and has left (-2^-16, 2^-16) after step 7.  With 1e-25 the mutual pull at that distance is about two ulps
+    of the pair's velocities: enough to show in the state (step 4 changes both), too little to keep them from leaving."""
+    b = _calm(2048)
+    P, V, M = b.Positions, b.Velocities, b.Masses
+    u = np.float32(2.0 ** -16)
+    x0 = np.float32(1.75) * u
+    sP = np.float32(-0.42) * u
+    f = np.float32
+
+    def fly(x, s, k):
+        for _ in range(k):
+            x = f(x + s)
+        return x
+    x0q = np.nextafter(x0, f(0))                            # distinct at upload: one float (2^-39) apart in x
+    dt = f(0.2)
+    vP = f(sP / dt)
+    found, vQ = None, vP
+    for j in range(1, 64):                                  # the second body's velocity: a few ulps slower
+        vQ = np.nextafter(vQ, f(0))
+        a, c = fly(x0, f(dt * vP), 3), fly(x0q, f(dt * vQ), 3)
+        if 0 < a < u / 2 and 0 < c < u / 2 and abs(float(c) - float(a)) == 2.0 ** -41:
+            found = vQ
+            break
+    assert found is not None, "no velocity lands the pair on adjacent floats"
+    P[900] = [x0, -500.0]
+    P[901] = [x0q, -500.0]
+    V[900] = [vP, 0.0]
+    V[901] = [found, 0.0]
+    M[900] = M[901] = 1e-25
+    return _case("small-pair-below-the-chain-domain", b, [0, SMALL, SMALL, SMALL, SMALL, SMALL, 0, 0], pair=(900, 901),
+                 pair_step=3)
+
+
+@functools.lru_cache(maxsize=None)
+def case_body_leaves_the_bound(where, precision=F32):
+    """b: one body with |v| of order 1e13 (fp64: 1e76) is beyond the coordinate bound after step 1; outside the walls its
+    velocity is negated (finish_body), which brings it back with step 2, and so on.  n = 3000 is not a multiple of 128; the
+    body sits in tile 0, mid-replica or in the truncated last tile (whose bodies only move under NBODY_CLEAN: the literal
+    semantics freeze the tail past the last whole block)."""
+    n = 3000
+    b = _calm(n, precision, fieldWidth=200000, fieldHeight=200000)
+    i = {"tile0": 5, "middle": 1500, "last-tile": 2990}[where]
+    b.Positions[i] = [100000.0, 300.0]
+    b.Velocities[i] = [1e76 if precision == F64 else 1e13, 0.0]
+    return _case("body-leaves-the-bound[%s%s]" % (where, "-f64" if precision == F64 else ""), b,
+                 [UNBOUNDED, 0, UNBOUNDED, 0, UNBOUNDED, 0],
+                 field=200000, semantics=ol.CLEAN if where == "last-tile" else ol.LITERAL, body=i)
+
+
+@functools.lru_cache(maxsize=None)
+def case_masses_merge_past_the_bound():
+    """c: bodies 40 / 1819 coincide with mass 2^89 each (equal: both absorb, both survive with 2^90), bodies 75 / 1100
+    coincide with 2^89 and 1.5 * 2^89 (the survivor gets 2.5 * 2^89): every mass is below 2^90 at upload, not after
+    step 1.  Stock mass range, forces matter; 1819 and 75 are the two most isolated bodies of the initial condition
+    (nearest neighbour 7000 away), which keeps the state finite for four steps (the equal pair stays coincident and doubles
+    every step).  After step 4 two bodies that fell into the heavy ones have been flung past 2^38: m * dx overflows there,
+    and steps 5 and 6 compare a state that is mostly NaN (which says little about the values, but the summary - 13 - and
+    the counts still have to be right)."""
+    b = _calm(2048, max_mass=1e17)
+    P, M = b.Positions, b.Masses
+    P[40] = P[1819]
+    M[40] = M[1819] = 2.0 ** 89
+    P[1100] = P[75]
+    M[75] = 2.0 ** 89
+    M[1100] = 1.5 * 2.0 ** 89
+    return _case("masses-merge-past-the-bound", b, [MASS, MASS, MASS, MASS | UNBOUNDED] + [MASS | UNBOUNDED | SMALL] * 2,
+                 equal=(40, 1819), unequal=(75, 1100))
+
+
+@functools.lru_cache(maxsize=None)
+def case_last_radius_disappears(growth, precision=F32):
+    """d: every radius is +0 but the lightest body's (500), which flies at 200 per step towards a heavier body 800 away:
+    in reach (400 <= 500) after step 2, so step 3 deletes it.  growth 0: the absorber's radius stays +0, summary 2 -> 0 and
+    every tile_rmax entry is 0 from then on (the NaN-sum screen switches ON mid-run); growth 0.1: the absorber takes a radius
+    of 50, summary stays 2 and the non-zero entry moves to the absorber's tile.  Bodies 1200 (moving one unit per step) and
+    1201 (at rest four units ahead) coincide after step 4 and collide in step 5, after the switch (fp64: all masses are
+    scaled by 1e-10, so that the body at rest stays put in double precision too)."""
+    b = _calm(2048, precision)
+    P, V, M, R = b.Positions, b.Velocities, b.Masses, b.Radii
+    if precision == F64:
+        M *= 1e-10
+    P[1200] = [1000.0, 2000.0]
+    V[1200] = [-5.0, 0.0]
+    P[1201] = [996.0, 2000.0]
+    light = int(np.argmin(M))
+    host = 100 if light // TILE != 0 else 1000              # the absorber lives in another tile
+    assert M[host] > M[light] and light not in (1200, 1201)
+    P[light] = P[host] + np.array([800.0, 0.0], dtype=P.dtype)
+    V[light] = [-1000.0, 0.0]
+    R[light] = 500.0
+    keeps = growth != 0
+    return _case("last-radius-disappears[growth %g%s]" % (growth, "-f64" if precision == F64 else ""), b,
+                 [RADIUS, RADIUS] + [RADIUS if keeps else 0] * 6, summary0=RADIUS, growth=growth, light=light, host=host,
+                 pair=(1200, 1201))
+
+
+def radius_bounds_bodies(n):
+    """The state of test_collision_screen_radius_bounds (tests/test_gpu_parity.py): a giant, a negative, a NaN, an infinite
+    and a denormal radius, a giant in the last tile, a NaN mass inside a giant's reach."""
+    nb = _nb()
+    field = 20000
+    cfg = nb.stock_config(particleCount=n, fieldWidth=field, fieldHeight=field, minRadius=0.0, maxRadius=0.0)
+    bodies = nb.init_bodies(cfg)
+    P, M, R = bodies.Positions, bodies.Masses, bodies.Radii
+    R[10] = 3000.0
+    P[12] = P[10] + np.float32([100.0, 0.0])
+    M[12] = np.nan
+    R[200] = -400.0
+    R[777] = np.nan
+    R[1500] = 1e-42
+    R[2100] = np.inf
+    R[n - 1] = 2500.0
+    R[130:140] = 60.0
+    return cfg, bodies, field
+
+
+def coincident_bodies(n=4096, small=False):
+    """The fp32 state of test_coincident_bodies_at_zero_radii."""
+    b = _calm(n, max_mass=1e17)
+    P, M = b.Positions, b.Masses
+    P[70] = P[5]
+    P[200] = P[130]
+    P[1000] = P[300]
+    P[4090] = P[3]
+    P[2000] = P[2001] = P[2002]
+    P[2500] = P[2600]
+    M[2500] = M[2600]
+    P[129] = P[128]
+    if small:
+        P[3500, 1] = 1e-6
+    return b
+
+
+def extreme_bodies(n=2048):
+    """The state of test_extreme_values_take_the_general_path."""
+    b = _calm(n, max_mass=1e17)
+    P, V, M, R = b.Positions, b.Velocities, b.Masses, b.Radii
+    P[100] = [1e20, -3e25]
+    P[300] = [np.inf, 5.0]
+    P[301] = [np.nan, 7.0]
+    P[500] = P[499]
+    P[700] = P[699] + np.float32([1e-30, 0])
+    P[900] = [3e-25, 1e-26]
+    P[901] = [3e-25 + 1e-31, 1e-26]
+    P[1100] = [1.0e-3, 0]
+    P[1101] = [1.0e-3 + 2.0e-11, 0]
+    M[1300] = np.nan
+    M[1301] = np.inf
+    R[1500] = np.inf
+    R[1501] = np.nan
+    V[1700] = [1e30, -1e30]
+    return b
+
+
+def mid_run_cases_f32():
+    return [case_small_enters_and_leaves(), case_small_pair_below_the_chain_domain(),
+            case_body_leaves_the_bound("tile0"), case_body_leaves_the_bound("middle"),
+            case_body_leaves_the_bound("last-tile"), case_masses_merge_past_the_bound(),
+            case_last_radius_disappears(0.0), case_last_radius_disappears(0.1)]
+
+
+def mid_run_cases_f64():
+    return [case_body_leaves_the_bound("tile0", F64), case_body_leaves_the_bound("middle", F64),
+            case_body_leaves_the_bound("last-tile", F64), case_last_radius_disappears(0.0, F64),
+            case_last_radius_disappears(0.1, F64)]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# one context, several states
+# ---------------------------------------------------------------------------------------------------------
+REUSE_FIELD = 30000          # dense: at n = 8000 the count falls by 2291 within 8 steps - and is still far above 1500, so
+                             # the smaller state that follows finds tiles past its end that the larger one had in use
+REUSE_CAPACITY = 8192
+
+
+def reuse_states():
+    """[(name, bodies, steps)] for the context-reuse test: S1 dense, stock radii, one out-of-range coordinate and one NaN
+    radius; S2 small, calm, radii 0 (summary 0, every tile_rmax entry 0); S3 fills the capacity."""
+    nb = _nb()
+    mk = lambda n, **kw: nb.init_bodies(nb.stock_config(particleCount=n, fieldWidth=REUSE_FIELD, fieldHeight=REUSE_FIELD, **kw))
+    s1 = mk(8000)
+    s1.Positions[4321] = [3e12, 5.0]
+    s1.Radii[6000] = np.nan
+    s2 = mk(1500, minRadius=0.0, maxRadius=0.0, maxRandBodyMass=1e5)
+    s3 = mk(8192)
+    return [("S1", s1, 8), ("S2", s2, 5), ("S3", s3, 6)]
+
+
+def exchange_stride(n, world):
+    """Bytes of one rank's slot when the slots are laid out for at most n bodies (fp32): a 32-byte header, 24 bytes per
+    body of the largest own range of the block-aligned partition, rounded up to 256."""
+    own_upper = ((n + TILE - 1) // TILE + world - 1) // world * TILE
+    return (32 + own_upper * 24 + 255) // 256 * 256

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from regime_cases import assert_screen_state
 
 pytestmark = pytest.mark.gpu
 
@@ -286,7 +287,9 @@ def test_random_small_cases_match_oracle(nb):
         for s in range(5):
             grp.step(1)
             cur, *_ = ol.port_step(blk, cur, dt, field, field, gr, semantics=sem, want_events=False)
-            assert_bodies_equal(grp.download(), blk, cur, "%s step %d" % (what, s))
+            out = grp.download()
+            assert_bodies_equal(out, blk, cur, "%s step %d" % (what, s))
+            assert_screen_state(grp, out, "%s step %d" % (what, s))
             if cur == 0:
                 break
         grp.close()
@@ -312,8 +315,11 @@ def test_random_medium_cases_match_oracle(nb):
         for s in range(3):
             grp.step(1)
             cur, *_ = ol.port_step(blk, cur, DT, field, field, GROWTH, semantics=sem, want_events=False)
-            assert_bodies_equal(grp.download(), blk, cur, "case %d: n=%d field=%d max_r=%g sem=%d variant=%d "
-                                "world=%d step %d" % (case, n, field, max_r, sem, variant, world, s))
+            out = grp.download()
+            what = "case %d: n=%d field=%d max_r=%g sem=%d variant=%d world=%d step %d" % (case, n, field, max_r, sem,
+                                                                                          variant, world, s)
+            assert_bodies_equal(out, blk, cur, what)
+            assert_screen_state(grp, out, what)
         grp.close()
 
 
@@ -356,6 +362,7 @@ def test_extreme_values_take_the_general_path(nb, variant):
         out = st.download()
         assert out.numBodies == cur, "step %d" % s
         assert _nan_aware_equal(out.block, blk[:6 * cur]), "step %d" % s
+        assert_screen_state(st, out, "step %d" % s)
     st.close()
 
 
@@ -440,20 +447,24 @@ def test_non_finite_sums_under_the_nan_screen(nb, variant, masses):
         out = st.download()
         assert out.numBodies == cur, "step %d" % s
         assert _nan_aware_equal(out.block, blk[:6 * cur]), "step %d" % s
+        assert_screen_state(st, out, "step %d" % s)
     if masses == "finite":
         assert not np.isfinite(blk[:6 * cur]).all(), "the case is meant to produce non-finite state"
     st.close()
 
 
-@pytest.mark.parametrize("variant", [0, 50, 52, 54, 31])
+@pytest.mark.parametrize("variant,world", [(0, 1), (50, 1), (52, 1), (54, 1), (31, 1), (0, 2), (0, 3)],
+                         ids=["0", "50", "52", "54", "31", "0-world2", "0-world3"])
 @pytest.mark.parametrize("n", [3000, 4096])
-def test_collision_screen_radius_bounds(nb, variant, n):
+def test_collision_screen_radius_bounds(nb, variant, n, world):
     """The ring kernel screens a turn for collisions with ONE threshold per lane, fma(R, R, 2^-80), R = |ri| + the largest
     |radius| of the aligned 128-body tiles the window touches (kept per tile by nbody_upload / unpack_slots); flagged
     lanes then get the exact status of their pairs.  Bounded coordinates, so that path is the one in use.  A giant, a
     negative, a NaN, an infinite and a denormal radius, a giant in the last (partial, wrapped-into) tile, a NaN mass
     inside a giant's reach (a hit the reference's if / else-if does not handle: the force term stays), over enough steps
-    for deletions to move bodies from tile to tile; N = 3000 makes windows straddle two tiles and wrap."""
+    for deletions to move bodies from tile to tile; N = 3000 makes windows straddle two tiles and wrap.  After every step
+    the per-tile bounds and Meta::summary of every rank are the numpy statement of the downloaded state; with 2 and 3 ranks
+    a wave of unpack_slots starts at a slot offset that is no multiple of 64 and straddles two tiles."""
     field = 20000
     cfg = nb.stock_config(particleCount=n, fieldWidth=field, fieldHeight=field, minRadius=0.0, maxRadius=0.0)
     bodies = nb.init_bodies(cfg)
@@ -467,20 +478,23 @@ def test_collision_screen_radius_bounds(nb, variant, n):
     R[2100] = np.inf
     R[n - 1] = 2500.0
     R[130:140] = 60.0
-    st = nb.Stepper(cfg, kernel_variant=variant, record_events=True, event_capacity=1 << 20)
+    kw = dict(kernel_variant=variant, record_events=True, event_capacity=1 << 20)
+    st = nb.Stepper(cfg, **kw) if world == 1 else nb.StepperGroup(world, cfg=cfg, **kw)
     st.upload(bodies)
+    assert_screen_state(st, bodies, "upload")
     blk = bodies.contiguousData.copy()
     cur = n
     for s in range(5):
         st.step(1)
         cur, stats, ab, de, _ = ol.port_step(blk, cur, DT, field, field, GROWTH)
-        ev = st.events()
+        ev = np.concatenate([r.events() for r in getattr(st, "ranks", [st])])
         ev = ev[ev["step"] == s]
         assert sorted((int(e["i"]), int(e["j"])) for e in ev[ev["kind"] == 0]) == \
             sorted((int(x), int(y)) for x, y in ab), "E_t step %d" % s
         assert sorted(set(int(e["i"]) for e in ev[ev["kind"] == 1])) == sorted(int(x) for x in de), "D_t step %d" % s
         out = st.download()
         assert out.numBodies == cur and _nan_aware_equal(out.block, blk[:6 * cur]), "step %d" % s
+        assert_screen_state(st, out, "step %d" % s)
     st.close()
 
 
@@ -508,6 +522,7 @@ def test_unbounded_tile_mid_walk(nb, variant):
             sorted((int(x), int(y)) for x, y in ab), "E_t step %d" % s
         out = st.download()
         assert out.numBodies == cur and _nan_aware_equal(out.block, blk[:6 * cur]), "step %d" % s
+        assert_screen_state(st, out, "step %d" % s)
     st.close()
 
 
@@ -1195,4 +1210,5 @@ def test_fp64_extreme_values(nb):
             cur, *_ = ol.port_step(blk, cur, float(DT), 100000, 100000, float(GROWTH), want_events=False)
         assert out.numBodies == cur
         assert _nan_aware_equal(out.block, blk[:6 * cur]), "variant %d" % variant
+        assert_screen_state(st, out, "variant %d" % variant)
         st.close()
