@@ -116,6 +116,9 @@ double nbody_rng_fval_range(nbody_rng* g, double a, double b); /* fval(a,b)  jbu
 /* Fills a block of cfg->particleCount bodies: seed 1024, draws x,y,m,r per body in that order, v = 0.
  * fp32 rounds each draw to float exactly where the reference does; fp64 keeps the double draws. */
 int nbody_init_bodies(const nbody_config* cfg, void* block, int precision);
+/* nbody_init_bodies with the seed as an argument (the reference fixes 1024, src/nbody.cu:401-416): other realisations
+ * of the same configuration, e.g. the members of an ensemble.  nbody_init_bodies is the seed-1024 call of it. */
+int nbody_init_bodies_seeded(const nbody_config* cfg, void* block, int precision, uint64_t seed);
 
 /* ---------------------------------------------------------------------------------------------------
  * Stepper context -- replaces the per-iteration host loop src/nbody.cu:460-545 (cudaMalloc scratch,
@@ -274,6 +277,66 @@ int nbody_get_diagnostics(nbody_ctx* ctx, nbody_diag* out, double* phi);
 /* The same for a single-process group (ctxs as in nbody_group_step); refuses ranks that were not uploaded and stepped
  * together. */
 int nbody_group_diagnostics(nbody_ctx** ctxs, int world, nbody_diag* out, double* phi);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
+ * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
+ * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and
+ * S host waits per ensemble step.  A batch costs two launches per ensemble step (three when a system has more than 1024
+ * bodies), whatever S is, no device-to-host copy and no host wait.
+ *
+ * System s of a batch is, bit for bit, what an nbody_ctx with the same precision, semantics and parameters gives after
+ * the same upload and the same number of steps: state, survivor count and order, pair counter, and (with
+ * NBODY_FLAG_RECORD_EVENTS) the event set of every step.  Systems never see each other: each has its own count, step
+ * counter, counters and event slice; the literal index quirks follow from each system's own live count.
+ *
+ * Where it stops paying (one MI355X, us per ensemble step, S nbody_ctx with a stream each against one batch, stock radii /
+ * radii 0; profiles/batch_probe.txt): 1024 x 256 bodies 18878 / 19093 against 108 / 118; 256 x 1024 5135 / 5704 against
+ * 214 / 216; 64 x 4096 1345 / 1768 against 350 / 590 (3.8x / 3.0x); 16 x 16384 831 / 2096 against 1108 / 2037 (0.75x /
+ * 1.03x).  So from about 16384 bodies per system one nbody_ctx per system - the ring-of-waves kernel, which then fills the
+ * chip on its own - is level or faster, and a batch (the one-lane-per-body kernel) is the tool below that.
+ *
+ * Argument errors (NBODY_ERR_INVALID) are found before any device call.  systems <= 65535: the system index is gridDim.y.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_batch nbody_batch;
+typedef struct nbody_batch_params {   /* per system: the kernel arguments of src/nbody.cu:482 */
+    double timestep, growthRate;
+    int fieldWidth, fieldHeight;
+} nbody_batch_params;
+typedef struct nbody_batch_desc {
+    int precision;       /* NBODY_F32 only in this version; NBODY_F64 -> NBODY_ERR_INVALID                        */
+    int semantics;       /* nbody_semantics, one for the whole batch                                              */
+    int systems;         /* S, 1..65535                                                                           */
+    int capacity;        /* max bodies PER SYSTEM; systems * capacity <= 2^28                                     */
+    int device;          /* HIP device ordinal                                                                    */
+    uint32_t flags;      /* NBODY_FLAG_RECORD_EVENTS only; the exchange flags -> NBODY_ERR_INVALID                */
+    int event_capacity;  /* max logged events per system (0: default, 2^24 / systems clamped to 1024..2^20)       */
+    int kernel_variant;  /* 0 automatic (from systems * capacity); otherwise lanes per body, 1, 2, 4 or 8 (A/B)   */
+} nbody_batch_desc;
+
+/* params: one entry per system.  NBODY_ERR_NO_DEVICE without a gfx950 device. */
+int nbody_batch_create(nbody_batch** out, const nbody_batch_desc* d, const nbody_batch_params* params);
+int nbody_batch_destroy(nbody_batch* b);
+/* S times BodiesData::uploadToDevice (src/nbody.cu:88-96): blocks[s] is a host block of counts[s] bodies in the
+ * reference layout.  counts[s] == 0 is legal (the system stays empty; blocks[s] must still be a pointer); counts[s] < 0
+ * or > capacity and a NULL blocks[s] are NBODY_ERR_INVALID.  Clears every system's event log and counters and restarts
+ * the step numbers, as nbody_upload does. */
+int nbody_batch_upload(nbody_batch* b, const void* const* blocks, const int* counts);
+/* nsteps ensemble steps (src/nbody.cu:463-510 for every system), asynchronous: enqueue only. */
+int nbody_batch_step(nbody_batch* b, int nsteps);
+/* CUDA_SYNC_CHECK (src/nbody.cu:20-33,546).  A device-side failure of any system (a count that failed its index
+ * check) is reported by this and every other synchronising call as NBODY_ERR_HIP, with the system's number. */
+int nbody_batch_sync(nbody_batch* b);
+int nbody_batch_counts(nbody_batch* b, int* counts);          /* current body count of every system; synchronises */
+/* As nbody_download, for one system: the survivors' re-carved block (src/nbody.cu:486,496-510); block must hold
+ * `capacity` bodies.  Synchronises. */
+int nbody_batch_download(nbody_batch* b, int system, void* block, int* n);
+/* As nbody_get_events, for one system's slice of the log; step numbers count from the last upload. */
+int nbody_batch_get_events(nbody_batch* b, int system, nbody_event* out, int cap, int64_t* total);
+/* steps, pairs and n_bodies of one system; every other field 0.  Synchronises. */
+int nbody_batch_get_stats(nbody_batch* b, int system, nbody_stats* out);
+/* Which force kernel the batch launches (static string; reporting only). */
+const char* nbody_batch_kernel_name(nbody_batch* b);
 
 /* ---------------------------------------------------------------------------------------------------
  * Reference-shaped launches on caller-owned DEVICE memory: one-to-one replacements of the two <<<>>> sites

@@ -62,6 +62,17 @@ class _CtxDesc(ctypes.Structure):
                 ("comm_id", ctypes.c_void_p), ("kernel_variant", ctypes.c_int)]
 
 
+class _BatchParams(ctypes.Structure):
+    _fields_ = [("timestep", ctypes.c_double), ("growthRate", ctypes.c_double), ("fieldWidth", ctypes.c_int),
+                ("fieldHeight", ctypes.c_int)]
+
+
+class _BatchDesc(ctypes.Structure):
+    _fields_ = [("precision", ctypes.c_int), ("semantics", ctypes.c_int), ("systems", ctypes.c_int),
+                ("capacity", ctypes.c_int), ("device", ctypes.c_int), ("flags", ctypes.c_uint32),
+                ("event_capacity", ctypes.c_int), ("kernel_variant", ctypes.c_int)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("steps", ctypes.c_int64), ("pairs", ctypes.c_int64), ("force_kernel_ms", ctypes.c_double),
                 ("force_kernel_launches", ctypes.c_int64), ("n_bodies", ctypes.c_int), ("n_own", ctypes.c_int),
@@ -110,6 +121,7 @@ SYMBOLS = {
     "nbody_rng_fval": (_d, [ctypes.POINTER(Rng)]),
     "nbody_rng_fval_range": (_d, [ctypes.POINTER(Rng), _d, _d]),
     "nbody_init_bodies": (_i, [ctypes.POINTER(ConfigData), _vp, _i]),
+    "nbody_init_bodies_seeded": (_i, [ctypes.POINTER(ConfigData), _vp, _i, ctypes.c_uint64]),
     "nbody_ctx_desc_from_config": (None, [ctypes.POINTER(_CtxDesc), ctypes.POINTER(ConfigData), _i]),
     "nbody_ctx_create": (_i, [_pp, ctypes.POINTER(_CtxDesc)]),
     "nbody_ctx_destroy": (_i, [_vp]),
@@ -138,6 +150,16 @@ SYMBOLS = {
     "nbody_ctx_stream": (_vp, [_vp]),
     "nbody_get_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_group_diagnostics": (_i, [_pp, _i, ctypes.POINTER(Diag), _vp]),
+    "nbody_batch_create": (_i, [_pp, ctypes.POINTER(_BatchDesc), ctypes.POINTER(_BatchParams)]),
+    "nbody_batch_destroy": (_i, [_vp]),
+    "nbody_batch_upload": (_i, [_vp, _pp, _ip]),
+    "nbody_batch_step": (_i, [_vp, _i]),
+    "nbody_batch_sync": (_i, [_vp]),
+    "nbody_batch_counts": (_i, [_vp, _ip]),
+    "nbody_batch_download": (_i, [_vp, _i, _vp, _ip]),
+    "nbody_batch_get_events": (_i, [_vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int64)]),
+    "nbody_batch_get_stats": (_i, [_vp, _i, ctypes.POINTER(Stats)]),
+    "nbody_batch_kernel_name": (ctypes.c_char_p, [_vp]),
     "nbody_num_blocks": (_i, [_i]),
     "nbody_launch_compute_forces_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _i, _i, _f, _vp]),
     "nbody_launch_move_bodies_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _vp]),
@@ -277,10 +299,11 @@ class BodiesData:
         return b
 
 
-def init_bodies(cfg, precision=F32):
-    """The initial-condition loop of src/nbody.cu:401-416 (seed 1024; x, y, m, r per body; v = 0)."""
+def init_bodies(cfg, precision=F32, seed=1024):
+    """The initial-condition loop of src/nbody.cu:401-416 (x, y, m, r per body; v = 0).  The reference's seed is 1024;
+    other seeds give other realisations of the same configuration (nbody_init_bodies_seeded)."""
     b = BodiesData(cfg.particleCount, precision)
-    _check(lib.nbody_init_bodies(ctypes.byref(cfg), b.ptr, precision))
+    _check(lib.nbody_init_bodies_seeded(ctypes.byref(cfg), b.ptr, precision, seed))
     return b
 
 
@@ -476,3 +499,92 @@ class StepperGroup:
     def close(self):
         for r in self.ranks:
             r.close()
+
+
+class StepperBatch:
+    """S independent systems stepped together (nbody_batch_*): S copies of the loop body of src/nbody.cu:463-510 per
+    launch.  System s is bit for bit what a Stepper with the same parameters gives.  fp32 only.
+
+    params: one (timestep, growthRate, fieldWidth, fieldHeight) tuple, or an object with those attributes (a ConfigData),
+    per system; or cfg=..., the same configuration for every system."""
+
+    def __init__(self, systems, capacity, params=None, cfg=None, semantics=LITERAL, record_events=False,
+                 event_capacity=0, kernel_variant=0, device=0, precision=F32):
+        if params is None and cfg is not None:
+            params = [cfg] * max(int(systems), 0)
+        arr = None
+        if params is not None:
+            if len(params) != systems:
+                raise ValueError("%d parameter sets for %d systems" % (len(params), systems))
+            arr = (_BatchParams * max(len(params), 1))()
+            for s, p in enumerate(params):
+                if not isinstance(p, (tuple, list)):
+                    p = (p.timestep, p.growthRate, p.fieldWidth, p.fieldHeight)
+                arr[s].timestep, arr[s].growthRate, arr[s].fieldWidth, arr[s].fieldHeight = p
+        d = _BatchDesc()
+        d.precision, d.semantics, d.systems, d.capacity, d.device = precision, semantics, systems, capacity, device
+        d.flags = FLAG_RECORD_EVENTS if record_events else 0
+        d.event_capacity = event_capacity
+        d.kernel_variant = kernel_variant
+        self.systems, self.capacity, self.precision = systems, capacity, precision
+        self._b = ctypes.c_void_p()
+        _check(lib.nbody_batch_create(ctypes.byref(self._b), ctypes.byref(d), arr))
+
+    def close(self):
+        if getattr(self, "_b", None) and lib is not None:     # `lib` is gone at interpreter shutdown
+            lib.nbody_batch_destroy(self._b)
+            self._b = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def upload(self, bodies):
+        """One BodiesData per system (an empty one, BodiesData(0), leaves its system empty)."""
+        if len(bodies) != self.systems:
+            raise ValueError("%d bodies sets for %d systems" % (len(bodies), self.systems))
+        assert all(b.precision == self.precision for b in bodies)
+        ptrs = (ctypes.c_void_p * self.systems)(*[b.ptr for b in bodies])
+        counts = (ctypes.c_int * self.systems)(*[b.numBodies for b in bodies])
+        _check(lib.nbody_batch_upload(self._b, ptrs, counts))
+
+    def step(self, nsteps=1):
+        _check(lib.nbody_batch_step(self._b, nsteps))
+
+    def sync(self):
+        _check(lib.nbody_batch_sync(self._b))
+
+    def counts(self):
+        out = np.zeros(self.systems, dtype=np.int32)
+        _check(lib.nbody_batch_counts(self._b, out.ctypes.data_as(_ip)))
+        return out
+
+    def download(self, system):
+        out = BodiesData(0, self.precision, self.capacity)
+        n = ctypes.c_int(0)
+        _check(lib.nbody_batch_download(self._b, system, out.ptr, ctypes.byref(n)))
+        out.numBodies = n.value
+        return out
+
+    def download_all(self):
+        return [self.download(s) for s in range(self.systems)]
+
+    def events(self, system, cap=1 << 20):
+        buf = np.zeros(cap, dtype=EVENT_DTYPE)
+        total = ctypes.c_int64(0)
+        _check(lib.nbody_batch_get_events(self._b, system, buf.ctypes.data, cap, ctypes.byref(total)))
+        if total.value > cap:
+            raise NbodyError(-7, "event log holds %d events, buffer %d" % (total.value, cap))
+        return buf[:total.value]
+
+    def stats(self, system):
+        s = Stats()
+        _check(lib.nbody_batch_get_stats(self._b, system, ctypes.byref(s)))
+        return s
+
+    def kernel_name(self):
+        return lib.nbody_batch_kernel_name(self._b).decode()

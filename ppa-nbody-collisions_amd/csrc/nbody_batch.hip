@@ -1,0 +1,426 @@
+// csrc/nbody_batch.hip -- host side of the batched stepper (nbody_batch_*, include/nbody.h).
+//
+// S independent systems share every launch: per ensemble step one force launch and one commit launch (two when a
+// system does not fit one commit workgroup), whatever S is, and nothing else - no device-to-host copy, no host wait.
+// Grids are sized from the uploaded counts.  A system's body count only shrinks (bodies are deleted, never made), so
+// the grid of the upload covers every later step; each kernel takes the exact count from the system's device-side Meta
+// and workgroups past it exit at once (the argument of launch_compute in nbody_ctx.hip, without its refresh of the
+// bound: a batch is small systems, the idle workgroups cost less than a host wait would).
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <new>
+
+#include "nbody.h"
+#include "nbody_error.h"
+#include "nbody_batch_kernels.hpp"
+
+using namespace nbk;
+
+#define HIP_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e__ = (expr);                                                                          \
+        if (e__ != hipSuccess)                                                                            \
+            return nbody_fail(NBODY_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__),      \
+                              __FILE__, __LINE__);                                                        \
+    } while (0)
+
+struct nbody_batch {
+    nbody_batch_desc desc{};
+    int S = 0;                  // systems
+    int cap = 0;                // bodies per system = distance between two systems in every per-body array
+    int ev_cap = 0;             // events per system (0: not recorded)
+    int K = 1;                  // lanes per body of the force kernel
+    int num_cus = 256;
+    hipStream_t stream = nullptr;
+    // device memory
+    Rec<float>* J = nullptr;            // [S * cap]
+    Vec2<float>* V = nullptr;           // [S * cap]
+    Rec<float>* S_J = nullptr;          // [S * cap] staged step results, step-t index space
+    Vec2<float>* S_V = nullptr;
+    Meta* meta = nullptr;               // [S]
+    Counters* counters = nullptr;       // [S]
+    StepParams<float>* params = nullptr;   // [S]
+    Event* events = nullptr;            // [S * ev_cap]
+    int* blk_counts = nullptr;          // [S * ceil(cap / 1024)]
+    // host
+    Meta* h_meta = nullptr;             // pinned [S]
+    Counters* h_counters = nullptr;     // pinned [S]
+    unsigned char* h_stage = nullptr;   // upload: records then velocities of all systems; download: one system
+    size_t h_stage_bytes = 0;
+    int n_upper = 0;                    // largest uploaded count: sizes every grid until the next upload
+    bool uploaded = false;
+    int64_t steps = 0;
+};
+
+namespace {
+
+constexpr int kCommitSmall = 256, kCommitLarge = 1024;     // threads of a commit workgroup
+
+void free_all(nbody_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->desc.device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    (void)hipFree(b->J); (void)hipFree(b->V); (void)hipFree(b->S_J); (void)hipFree(b->S_V);
+    (void)hipFree(b->meta); (void)hipFree(b->counters); (void)hipFree(b->params); (void)hipFree(b->events);
+    (void)hipFree(b->blk_counts);
+    if (b->h_meta) (void)hipHostFree(b->h_meta);
+    if (b->h_counters) (void)hipHostFree(b->h_counters);
+    free(b->h_stage);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    (void)hipGetLastError();
+    delete b;
+}
+
+// Lanes per body when the caller leaves it to the library, from the most the batch can hold (S x capacity bodies): K
+// doubles until S x capacity x K reaches 512 lanes per CU (two waves per SIMD) or K = 4.  Measured on an MI355X (256
+// CUs: 131072 lanes), S systems of N = 1024, stock configuration, us per ensemble step for K = 1 / 2 / 4 / 8
+// (csrc/tune/batch_probe.py --variants, profiles/batch_probe.txt):
+//     S =  16 ( 16384 bodies):  48.5 /  40.5 /  39.3 /  54.7   -> 4
+//     S =  64 ( 65536 bodies):  63.0 /  60.9 / 102.6 / 224.8   -> 2
+//     S = 128 (131072 bodies):  76.6 /  93.7 / 218.1 / 432.2   -> 1
+//     S = 256 (262144 bodies): 127.2 / 220.6 / 444.1 / 847.3   -> 1
+// K = 8 won nowhere and is left to kernel_variant; batches of fewer than 16384 bodies have not been measured.
+int automatic_lanes(long long bodies, int num_cus) {
+    const long long fill = (long long)num_cus * 512;
+    int K = 1;
+    while (K < 4 && bodies * K < fill) K *= 2;
+    return K;
+}
+
+template <int K>
+void launch_forces_k(nbody_batch* b, int nblocks, bool log) {
+    const dim3 grid((nblocks * K + 1) / 2, b->S);          // two 128-lane groups of one system per workgroup
+#define NB_BATCH_ARGS b->J, b->V, b->S_J, b->S_V, (const Meta*)b->meta, (const StepParams<float>*)b->params, \
+                      b->events, b->ev_cap, b->counters, b->cap
+    if (log) hipLaunchKernelGGL((forces_batch_f32<K, true>), grid, dim3(2 * kTile), 0, b->stream, NB_BATCH_ARGS);
+    else hipLaunchKernelGGL((forces_batch_f32<K, false>), grid, dim3(2 * kTile), 0, b->stream, NB_BATCH_ARGS);
+#undef NB_BATCH_ARGS
+}
+
+template <int B>
+void launch_commit_b(nbody_batch* b, int nblk) {
+    const dim3 grid(nblk, b->S);
+    if (nblk > 1)
+        hipLaunchKernelGGL((batch_count<B>), grid, dim3(B), 0, b->stream, (const Rec<float>*)b->S_J, b->meta,
+                           b->blk_counts, b->cap);
+    hipLaunchKernelGGL((batch_commit<B>), grid, dim3(B), 0, b->stream, (const Rec<float>*)b->S_J,
+                       (const Vec2<float>*)b->S_V, b->J, b->V, b->meta, (const int*)b->blk_counts, b->counters, b->cap);
+}
+
+// One ensemble step: 2 launches when the largest uploaded system fits one commit workgroup (1024 bodies), 3 otherwise.
+int enqueue_step(nbody_batch* b) {
+    const int n = b->n_upper;
+    const int nblocks = (n + kTile - 1) / kTile > 0 ? (n + kTile - 1) / kTile : 1;   // reference blocks, frozen tail included
+    const bool log = b->ev_cap > 0;
+    switch (b->K) {
+        case 1: launch_forces_k<1>(b, nblocks, log); break;
+        case 2: launch_forces_k<2>(b, nblocks, log); break;
+        case 4: launch_forces_k<4>(b, nblocks, log); break;
+        default: launch_forces_k<8>(b, nblocks, log); break;
+    }
+    if (n <= kCommitSmall) launch_commit_b<kCommitSmall>(b, 1);
+    else launch_commit_b<kCommitLarge>(b, (n + kCommitLarge - 1) / kCommitLarge);
+    HIP_TRY(hipGetLastError());
+    return NBODY_OK;
+}
+
+// Synchronises and refreshes the host copies of every system's Meta and Counters; a device-side failure of any system
+// is reported here, with the system's number.
+int read_meta(nbody_batch* b) {
+    HIP_TRY(hipMemcpyAsync(b->h_meta, b->meta, sizeof(Meta) * (size_t)b->S, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->h_counters, b->counters, sizeof(Counters) * (size_t)b->S, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (int s = 0; s < b->S; ++s)
+        if (b->h_counters[s].errors != 0)
+            return nbody_fail(NBODY_ERR_HIP, "system %d of the batch: device reported %llu failed index check(s) (the system "
+                                             "was emptied instead of indexed with a bad count): upload again",
+                              s, b->h_counters[s].errors / kIndexError);
+    return NBODY_OK;
+}
+
+int check_system(const nbody_batch* b, int system, const char* who) {
+    if (!b) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL batch", who);
+    if (system < 0 || system >= b->S)
+        return nbody_fail(NBODY_ERR_INVALID, "%s: system %d out of range (the batch has %d)", who, system, b->S);
+    return NBODY_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbody_batch_create(nbody_batch** out, const nbody_batch_desc* d, const nbody_batch_params* params) {
+    if (!out || !d) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: NULL argument");
+    *out = nullptr;
+    if (!params) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: NULL params (one nbody_batch_params per system)");
+    if (d->systems < 1 || d->systems > kBatchMaxSystems)
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: %d systems (1..%d: the system index is gridDim.y)",
+                          d->systems, kBatchMaxSystems);
+    if (d->capacity < 1) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: capacity %d per system", d->capacity);
+    if ((long long)d->systems * d->capacity > (1ll << 28))
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: %d systems x %d bodies is more than 2^28 bodies",
+                          d->systems, d->capacity);
+    if (d->precision == NBODY_F64)
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: fp64 batches are not implemented (NBODY_F32 only); "
+                                             "step fp64 systems with one nbody_ctx each");
+    if (d->precision != NBODY_F32) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: bad precision");
+    if (d->semantics != NBODY_LITERAL && d->semantics != NBODY_CLEAN)
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: bad semantics");
+    if (d->flags & ~(uint32_t)NBODY_FLAG_RECORD_EVENTS)
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: flags 0x%x (only NBODY_FLAG_RECORD_EVENTS: a batch "
+                                             "has no exchange)", d->flags);
+    if (d->event_capacity < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: negative event_capacity");
+    if (d->kernel_variant != 0 && d->kernel_variant != 1 && d->kernel_variant != 2 && d->kernel_variant != 4 &&
+        d->kernel_variant != 8)
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: kernel_variant %d (0 automatic, or 1, 2, 4, 8 lanes "
+                                             "per body)", d->kernel_variant);
+    const bool log = (d->flags & NBODY_FLAG_RECORD_EVENTS) != 0;
+    // default event slice: 2^24 events over the whole batch, at least 1024 and at most 2^20 per system
+    int ev_cap = 0;
+    if (log) {
+        ev_cap = d->event_capacity;
+        if (ev_cap == 0) {
+            ev_cap = (1 << 24) / d->systems;
+            if (ev_cap < 1024) ev_cap = 1024;
+            if (ev_cap > (1 << 20)) ev_cap = 1 << 20;
+        }
+    }
+
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return nbody_fail(NBODY_ERR_NO_DEVICE, "no HIP device visible (%s); this library has no CPU path",
+                          e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+    if (d->device < 0 || d->device >= ndev)
+        return nbody_fail(NBODY_ERR_INVALID, "device ordinal %d out of range (0..%d)", d->device, ndev - 1);
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, d->device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return nbody_fail(NBODY_ERR_NO_DEVICE, "device %d is %s; kernels are built for gfx950 only", d->device,
+                          prop.gcnArchName);
+    HIP_TRY(hipSetDevice(d->device));
+
+    nbody_batch* b = new (std::nothrow) nbody_batch();
+    if (!b) return nbody_fail(NBODY_ERR_NOMEM, "nbody_batch_create: out of host memory");
+    b->desc = *d;
+    b->S = d->systems;
+    b->cap = d->capacity;
+    b->ev_cap = ev_cap;
+    b->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    b->K = d->kernel_variant ? d->kernel_variant : automatic_lanes((long long)b->S * b->cap, b->num_cus);
+    const size_t bodies = (size_t)b->S * (size_t)b->cap;
+
+#define BATCH_TRY(expr)                                                                                   \
+    do {                                                                                                  \
+        hipError_t e__ = (expr);                                                                          \
+        if (e__ != hipSuccess) {                                                                          \
+            int rc__ = nbody_fail(e__ == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP,           \
+                                  "%s failed: %s", #expr, hipGetErrorString(e__));                        \
+            free_all(b);                                                                                  \
+            return rc__;                                                                                  \
+        }                                                                                                 \
+    } while (0)
+    BATCH_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    BATCH_TRY(hipMalloc((void**)&b->J, bodies * sizeof(Rec<float>)));
+    BATCH_TRY(hipMalloc((void**)&b->V, bodies * sizeof(Vec2<float>)));
+    BATCH_TRY(hipMalloc((void**)&b->S_J, bodies * sizeof(Rec<float>)));
+    BATCH_TRY(hipMalloc((void**)&b->S_V, bodies * sizeof(Vec2<float>)));
+    BATCH_TRY(hipMalloc((void**)&b->meta, sizeof(Meta) * (size_t)b->S));
+    BATCH_TRY(hipMalloc((void**)&b->counters, sizeof(Counters) * (size_t)b->S));
+    BATCH_TRY(hipMalloc((void**)&b->params, sizeof(StepParams<float>) * (size_t)b->S));
+    BATCH_TRY(hipMalloc((void**)&b->blk_counts, sizeof(int) * (size_t)b->S * (size_t)(b->cap / kCommitLarge + 1)));
+    if (log) BATCH_TRY(hipMalloc((void**)&b->events, sizeof(Event) * (size_t)b->S * (size_t)ev_cap));
+    BATCH_TRY(hipHostMalloc((void**)&b->h_meta, sizeof(Meta) * (size_t)b->S, hipHostMallocDefault));
+    BATCH_TRY(hipHostMalloc((void**)&b->h_counters, sizeof(Counters) * (size_t)b->S, hipHostMallocDefault));
+    memset(b->h_meta, 0, sizeof(Meta) * (size_t)b->S);
+    memset(b->h_counters, 0, sizeof(Counters) * (size_t)b->S);
+    b->h_stage_bytes = bodies * (sizeof(Rec<float>) + sizeof(Vec2<float>));
+    if (b->h_stage_bytes < sizeof(StepParams<float>) * (size_t)b->S) b->h_stage_bytes = sizeof(StepParams<float>) * (size_t)b->S;
+    b->h_stage = (unsigned char*)malloc(b->h_stage_bytes);
+    if (!b->h_stage) {
+        const size_t wanted = b->h_stage_bytes;
+        free_all(b);
+        return nbody_fail(NBODY_ERR_NOMEM, "nbody_batch_create: out of host memory (%zu bytes of staging)", wanted);
+    }
+    {   // the kernel arguments of src/nbody.cu:482, once per system; G, the walls and the semantics as make_params has them
+        StepParams<float>* hp = reinterpret_cast<StepParams<float>*>(b->h_stage);
+        for (int s = 0; s < b->S; ++s) {
+            StepParams<float> p;
+            p.dt = (float)params[s].timestep;
+            p.growth = (float)params[s].growthRate;
+            p.G = 6.67408e-11f;
+            p.wall_hi_x = (float)params[s].fieldWidth;
+            p.wall_lo_x = (float)(-params[s].fieldWidth);
+            p.wall_hi_y = (float)params[s].fieldHeight;
+            p.wall_lo_y = (float)(-params[s].fieldHeight);
+            p.literal = d->semantics == NBODY_LITERAL;
+            p.spin_limit = 0;
+            p.rotate_priority = 0;
+            hp[s] = p;
+        }
+        BATCH_TRY(hipMemcpyAsync(b->params, hp, sizeof(StepParams<float>) * (size_t)b->S, hipMemcpyHostToDevice, b->stream));
+    }
+    BATCH_TRY(hipMemsetAsync(b->meta, 0, sizeof(Meta) * (size_t)b->S, b->stream));
+    BATCH_TRY(hipMemsetAsync(b->counters, 0, sizeof(Counters) * (size_t)b->S, b->stream));
+    BATCH_TRY(hipStreamSynchronize(b->stream));
+#undef BATCH_TRY
+    *out = b;
+    return NBODY_OK;
+}
+
+int nbody_batch_destroy(nbody_batch* b) {
+    free_all(b);
+    return NBODY_OK;
+}
+
+int nbody_batch_upload(nbody_batch* b, const void* const* blocks, const int* counts) {
+    if (!b || !blocks || !counts) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_upload: NULL argument");
+    for (int s = 0; s < b->S; ++s) {
+        if (counts[s] < 0 || counts[s] > b->cap)
+            return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_upload: system %d has %d bodies (0..capacity %d)", s,
+                              counts[s], b->cap);
+        if (!blocks[s]) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_upload: system %d has no block", s);
+    }
+    HIP_TRY(hipSetDevice(b->desc.device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    // pack every [P|V|M|R] block (src/nbody.cu:66-77) into {x,y,m,r} records and velocities, `cap` apart
+    const size_t bodies = (size_t)b->S * (size_t)b->cap;
+    Rec<float>* st = reinterpret_cast<Rec<float>*>(b->h_stage);
+    Vec2<float>* sv = reinterpret_cast<Vec2<float>*>(b->h_stage + bodies * sizeof(Rec<float>));
+    int n_upper = 0;
+    for (int s = 0; s < b->S; ++s) {
+        const int n = counts[s];
+        const float* P = (const float*)blocks[s];
+        const float* V = P + 2 * (size_t)n;
+        const float* M = V + 2 * (size_t)n;
+        const float* R = M + (size_t)n;
+        Rec<float>* r = st + (size_t)s * b->cap;
+        Vec2<float>* v = sv + (size_t)s * b->cap;
+        for (int i = 0; i < n; ++i) {
+            r[i] = Rec<float>{P[2 * i], P[2 * i + 1], M[i], R[i]};
+            v[i] = Vec2<float>{V[2 * i], V[2 * i + 1]};
+        }
+        if (n < b->cap) {                                  // never read; defined all the same
+            memset(r + n, 0, (size_t)(b->cap - n) * sizeof(Rec<float>));
+            memset(v + n, 0, (size_t)(b->cap - n) * sizeof(Vec2<float>));
+        }
+        Meta& m = b->h_meta[s];
+        m.n = n; m.lo = 0; m.cnt = n; m.step = 0; m.n_prev = n; m.summary = 0; m.pad[0] = m.pad[1] = 0;
+        if (n > n_upper) n_upper = n;
+    }
+    HIP_TRY(hipMemcpyAsync(b->J, st, bodies * sizeof(Rec<float>), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->V, sv, bodies * sizeof(Vec2<float>), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->meta, b->h_meta, sizeof(Meta) * (size_t)b->S, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemsetAsync(b->counters, 0, sizeof(Counters) * (size_t)b->S, b->stream));   // pairs, events, errors
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    memset(b->h_counters, 0, sizeof(Counters) * (size_t)b->S);
+    b->n_upper = n_upper;
+    b->uploaded = true;
+    b->steps = 0;
+    return NBODY_OK;
+}
+
+int nbody_batch_step(nbody_batch* b, int nsteps) {
+    if (!b || nsteps < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_step: bad argument");
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_step before nbody_batch_upload");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    for (int s = 0; s < nsteps; ++s) {
+        int rc = enqueue_step(b);
+        if (rc != NBODY_OK) return rc;
+        b->steps += 1;
+    }
+    return NBODY_OK;
+}
+
+int nbody_batch_sync(nbody_batch* b) {
+    if (!b) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_sync: NULL batch");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    HIP_TRY(hipGetLastError());
+    return read_meta(b);
+}
+
+int nbody_batch_counts(nbody_batch* b, int* counts) {
+    if (!b || !counts) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_counts: NULL argument");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    int rc = read_meta(b);
+    if (rc != NBODY_OK) return rc;
+    for (int s = 0; s < b->S; ++s) counts[s] = b->h_meta[s].n;
+    return NBODY_OK;
+}
+
+int nbody_batch_download(nbody_batch* b, int system, void* block, int* n_out) {
+    int rc = check_system(b, system, "nbody_batch_download");
+    if (rc != NBODY_OK) return rc;
+    if (!block || !n_out) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_download: NULL argument");
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_download before nbody_batch_upload");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    rc = read_meta(b);
+    if (rc != NBODY_OK) return rc;
+    const int n = b->h_meta[system].n;
+    if (n < 0 || n > b->cap) return nbody_fail(NBODY_ERR_STATE, "system %d reports %d bodies, capacity %d", system, n, b->cap);
+    Rec<float>* st = reinterpret_cast<Rec<float>*>(b->h_stage);
+    Vec2<float>* sv = reinterpret_cast<Vec2<float>*>(b->h_stage + (size_t)b->cap * sizeof(Rec<float>));
+    const size_t base = (size_t)system * (size_t)b->cap;
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(st, b->J + base, (size_t)n * sizeof(Rec<float>), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(sv, b->V + base, (size_t)n * sizeof(Vec2<float>), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+    }
+    float* P = (float*)block;                              // the survivors' re-carved block, src/nbody.cu:496-510
+    float* V = P + 2 * (size_t)n;
+    float* M = V + 2 * (size_t)n;
+    float* R = M + (size_t)n;
+    for (int i = 0; i < n; ++i) {
+        P[2 * i] = st[i].x; P[2 * i + 1] = st[i].y;
+        V[2 * i] = sv[i].x; V[2 * i + 1] = sv[i].y;
+        M[i] = st[i].m;
+        R[i] = st[i].r;
+    }
+    *n_out = n;
+    return NBODY_OK;
+}
+
+int nbody_batch_get_events(nbody_batch* b, int system, nbody_event* out, int cap, int64_t* total) {
+    int rc = check_system(b, system, "nbody_batch_get_events");
+    if (rc != NBODY_OK) return rc;
+    if (!total || cap < 0 || (cap > 0 && !out)) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_get_events: bad argument");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    rc = read_meta(b);
+    if (rc != NBODY_OK) return rc;
+    const unsigned long long tot = b->h_counters[system].events;
+    *total = (int64_t)tot;
+    unsigned long long ncopy = tot;
+    if (ncopy > (unsigned long long)b->ev_cap) ncopy = b->ev_cap;
+    if (ncopy > (unsigned long long)cap) ncopy = cap;
+    static_assert(sizeof(nbody_event) == sizeof(Event), "event layouts must match");
+    if (ncopy) HIP_TRY(hipMemcpy(out, b->events + (size_t)system * (size_t)b->ev_cap, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
+    return NBODY_OK;
+}
+
+int nbody_batch_get_stats(nbody_batch* b, int system, nbody_stats* out) {
+    int rc = check_system(b, system, "nbody_batch_get_stats");
+    if (rc != NBODY_OK) return rc;
+    if (!out) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_get_stats: NULL");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    rc = read_meta(b);
+    if (rc != NBODY_OK) return rc;
+    memset(out, 0, sizeof(*out));
+    out->steps = b->steps;
+    out->pairs = (int64_t)b->h_counters[system].pairs;
+    out->n_bodies = b->h_meta[system].n;
+    return NBODY_OK;
+}
+
+const char* nbody_batch_kernel_name(nbody_batch* b) {
+    if (!b) return "";
+    switch (b->K) {
+        case 1: return "forces_batch_f32 (1 lane per body)";
+        case 2: return "forces_batch_f32 (2 lanes per body)";
+        case 4: return "forces_batch_f32 (4 lanes per body)";
+        default: return "forces_batch_f32 (8 lanes per body)";
+    }
+}
+
+}  // extern "C"

@@ -127,7 +127,7 @@ double nbody_rng_fval(nbody_rng* g) { return 5.42101086242752217E-20 * (double)n
 
 double nbody_rng_fval_range(nbody_rng* g, double a, double b) { return nbody_rng_fval(g) * (b - a) + a; }
 
-int nbody_init_bodies(const nbody_config* cfg, void* block, int precision) {
+int nbody_init_bodies_seeded(const nbody_config* cfg, void* block, int precision, uint64_t seed) {
     if (!cfg || !block || cfg->particleCount < 0)
         return nbody_fail(NBODY_ERR_INVALID, "nbody_init_bodies: bad argument");
     const int n = cfg->particleCount;
@@ -135,7 +135,7 @@ int nbody_init_bodies(const nbody_config* cfg, void* block, int precision) {
     const int doubleFieldWidth = fieldWidth << 1;       /* src/nbody.cu:388 */
     const int doubleFieldHeight = fieldHeight << 1;     /* :390 */
     nbody_rng gen;
-    nbody_rng_seed(&gen, 1024);                         /* :403 */
+    nbody_rng_seed(&gen, seed);                         /* :403, where the seed is 1024 */
     if (precision == NBODY_F64) {
         nbody_vec2 *P, *V; double *M, *R;
         nbody_block_carve_f64(block, n, &P, &V, &M, &R);
@@ -162,6 +162,10 @@ int nbody_init_bodies(const nbody_config* cfg, void* block, int precision) {
         }
     }
     return NBODY_OK;
+}
+
+int nbody_init_bodies(const nbody_config* cfg, void* block, int precision) {
+    return nbody_init_bodies_seeded(cfg, block, precision, 1024);     /* src/nbody.cu:403 */
 }
 
 void nbody_ctx_desc_from_config(nbody_ctx_desc* d, const nbody_config* cfg, int precision) {

@@ -642,6 +642,7 @@ __device__ __forceinline__ double dpp_row_shl(double v) {   // K > 1 is fp32 onl
 #undef NB_V3_KEEP
 #undef NB_V3_COUNT
 
+#ifndef NBK_TEMPLATES_ONLY   // kernels that are not templates: defined by nbody_ctx.hip alone
 // The same kernel (256-thread form) on the reference's device block [P|V|M|R] and its two scratch arrays: drop-in
 // for the ComputeForces<<<>>> site when it is launched with the reference's own block count
 // (src/nbody.cu:473,481-482).  Velocities are updated in place (:264), updatedMasses / updatedRadii written
@@ -691,6 +692,7 @@ __device__ __forceinline__ double dpp_row_shl(double v) {   // K > 1 is fp32 onl
 #undef NB_V3_PUT
 #undef NB_V3_KEEP
 #undef NB_V3_COUNT
+#endif  // NBK_TEMPLATES_ONLY
 
 // ---------------------------------------------------------------------------------------------------------
 // Force + collision + drift kernel, variant "ring" (fp32): the fp32 force kernel at every size.
@@ -1406,10 +1408,12 @@ __device__ __forceinline__ void store_tiled(float* __restrict__ Jt, int i, const
     float* t = Jt + (size_t)(i / kTile) * (4 * kTile) + (i % kTile);
     t[0] = (float)r.x; t[kTile] = (float)r.y; t[2 * kTile] = (float)r.m; t[3 * kTile] = (float)r.r;
 }
+#ifndef NBK_TEMPLATES_ONLY   // kernels that are not templates: defined by nbody_ctx.hip alone
 __global__ __launch_bounds__(256) void records_to_tiles_f32(const Rec<float>* __restrict__ J, int n, float* __restrict__ Jt) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) store_tiled(Jt, i, J[i]);
 }
+#endif  // NBK_TEMPLATES_ONLY
 
 template <typename T>
 __global__ __launch_bounds__(kCompactBlock) void compact_count(const Rec<T>* __restrict__ S_J,
@@ -1566,6 +1570,7 @@ __global__ __launch_bounds__(256) void unpack_slots(const unsigned char* __restr
     }
 }
 
+#ifndef NBK_TEMPLATES_ONLY   // kernels that are not templates: defined by nbody_ctx.hip alone
 // ---------------------------------------------------------------------------------------------------------
 // Reference-shaped kernels on the reference's device block layout (drop-in for the <<<>>> sites
 // src/nbody.cu:481-483): velocities updated in place, updatedMasses / updatedRadii scratch written.
@@ -1695,6 +1700,7 @@ __global__ __launch_bounds__(kTile) void ref_layout_move_f32(void* bodyData, con
         R[j] = updR[j];                                                       // :290
     }
 }
+#endif  // NBK_TEMPLATES_ONLY
 
 // ---------------------------------------------------------------------------------------------------------
 // Image rasteriser: generateImage, src/nbody.cu:294-348, one lane per body, filled discs of value 0 into an
@@ -1733,6 +1739,7 @@ __global__ __launch_bounds__(256) void render_discs(const Rec<T>* __restrict__ J
         }
 }
 
+#ifndef NBK_TEMPLATES_ONLY   // kernels that are not templates: defined by nbody_ctx.hip alone
 // ---------------------------------------------------------------------------------------------------------
 // Device self-test of the assumption behind the ring kernel's hand-off: a 16-byte LDS record written by one lane
 // with ds_write_b128 is seen by a ds_read_b128 of another wave entirely old or entirely new.  Wave 0 of every
@@ -1861,5 +1868,6 @@ __global__ __launch_bounds__(256) void selftest_rcp_ones_f64(unsigned long long*
     atomicAdd(&out[3], (unsigned long long)((unsigned)__double_as_longlong(c) != 0xffffffffu || !significand_all_ones(c)));
     atomicAdd(&out[4], 1ull);
 }
+#endif  // NBK_TEMPLATES_ONLY
 
 }  // namespace nbk
