@@ -338,6 +338,34 @@ int nbody_batch_get_stats(nbody_batch* b, int system, nbody_stats* out);
 /* Which force kernel the batch launches (static string; reporting only). */
 const char* nbody_batch_kernel_name(nbody_batch* b);
 
+/* Per-system diagnostics of a batch.  out[s] is exactly what nbody_get_diagnostics returns for an nbody_ctx holding system
+ * s's state - the same bits in every field, phi included: step (steps since the batch's upload), n_bodies, coincident_pairs,
+ * the centre of mass and every sum, by the order contract above (phi_i one running sum over j ascending, totals per aligned
+ * 128-body tile and then over the tiles).  Two launches per call, whatever S is.  An empty system gives n_bodies = 0, every
+ * sum +0, no coincident pairs and center_of_mass NaN (the rule for mass == 0).
+ * out: room for `systems` records.  phi: NULL, or room for systems * capacity doubles; system s's phi goes to
+ * phi + s * capacity, one value per current body, the rest of that slice is left unchanged.  Synchronises.  The device
+ * buffers are allocated on the first call (the phi buffer, systems * capacity doubles, on the first call that asks for phi):
+ * a batch that never asks keeps its footprint.
+ * Against the route without this call (per system: nbody_batch_download, nbody_upload into one reused nbody_ctx,
+ * nbody_get_diagnostics; one MI355X, ms per call, stock radii; profiles/batch_diag_probe.txt): 1024 x 256 bodies 190.4 against
+ * 0.64, 256 x 1024 56.0 against 0.39, 64 x 4096 22.9 against 0.63, 16 x 16384 14.1 against 2.11 - unlike the stepping, no
+ * shape of these favours one nbody_ctx per system.  A record costs 0.66 (256 x 1024) to 0.74 (64 x 4096) of an ensemble step. */
+int nbody_batch_diagnostics(nbody_batch* b, nbody_diag* out, double* phi);
+/* A recorded series: samples are enqueued between steps into a device-side log and read back once at the end.
+ * nbody_batch_diag_reserve allocates (or re-allocates) a log of samples x systems records and empties it; samples = 0
+ * frees it; samples < 0 or a log above 2^31 bytes: NBODY_ERR_INVALID, found before any device call.
+ * nbody_batch_diag_record is enqueue-only, like nbody_batch_step: it launches the kernels that write the current sample of
+ * every system into the next row (no phi is kept), with no device-to-host copy and no synchronisation.  A full log is
+ * NBODY_ERR_CAPACITY, found on the host: nothing is enqueued and the earlier rows stay.  No reservation, or no upload yet:
+ * NBODY_ERR_STATE.  nbody_batch_upload restarts the log at row 0 and keeps the reservation.
+ * nbody_batch_diag_read synchronises, copies min(recorded, cap_samples) rows (out[k * systems + s]) and stores the number
+ * recorded in *n_samples.  Row k is what nbody_batch_diagnostics would have returned at the moment it was recorded: step and
+ * n_bodies come from each system's device-side state. */
+int nbody_batch_diag_reserve(nbody_batch* b, int samples);
+int nbody_batch_diag_record(nbody_batch* b);
+int nbody_batch_diag_read(nbody_batch* b, nbody_diag* out, int cap_samples, int* n_samples);
+
 /* ---------------------------------------------------------------------------------------------------
  * Reference-shaped launches on caller-owned DEVICE memory: one-to-one replacements of the two <<<>>> sites
  * src/nbody.cu:481-483.  d_bodyData is a device block in the reference layout for numBodies bodies;

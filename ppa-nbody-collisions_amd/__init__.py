@@ -98,6 +98,10 @@ class Rng(ctypes.Structure):
 
 
 EVENT_DTYPE = np.dtype([("step", np.int32), ("i", np.int32), ("j", np.int32), ("kind", np.int32)])
+# struct nbody_diag as a numpy record (StepperBatch.diagnostics_log)
+DIAG_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64), ("coincident_pairs", np.int64), ("mass", np.float64),
+                       ("momentum", np.float64, (2,)), ("center_of_mass", np.float64, (2,)),
+                       ("angular_momentum", np.float64), ("kinetic", np.float64), ("potential", np.float64)])
 
 # every symbol include/nbody.h declares: name -> (restype, argtypes)
 _vp, _ip, _i, _f, _d, _sz = (ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_float,
@@ -160,6 +164,10 @@ SYMBOLS = {
     "nbody_batch_get_events": (_i, [_vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_get_stats": (_i, [_vp, _i, ctypes.POINTER(Stats)]),
     "nbody_batch_kernel_name": (ctypes.c_char_p, [_vp]),
+    "nbody_batch_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
+    "nbody_batch_diag_reserve": (_i, [_vp, _i]),
+    "nbody_batch_diag_record": (_i, [_vp]),
+    "nbody_batch_diag_read": (_i, [_vp, _vp, _i, _ip]),
     "nbody_num_blocks": (_i, [_i]),
     "nbody_launch_compute_forces_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _i, _i, _f, _vp]),
     "nbody_launch_move_bodies_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _vp]),
@@ -527,6 +535,7 @@ class StepperBatch:
         d.event_capacity = event_capacity
         d.kernel_variant = kernel_variant
         self.systems, self.capacity, self.precision = systems, capacity, precision
+        self._log_cap = 0                                       # samples reserved for the recorded series
         self._b = ctypes.c_void_p()
         _check(lib.nbody_batch_create(ctypes.byref(self._b), ctypes.byref(d), arr))
 
@@ -552,11 +561,55 @@ class StepperBatch:
         counts = (ctypes.c_int * self.systems)(*[b.numBodies for b in bodies])
         _check(lib.nbody_batch_upload(self._b, ptrs, counts))
 
-    def step(self, nsteps=1):
-        _check(lib.nbody_batch_step(self._b, nsteps))
+    def step(self, nsteps=1, record_every=0):
+        """nsteps ensemble steps, enqueue only.  record_every = k > 0: a sample of the recorded series after every k-th
+        step of this call (for i in 1..nsteps: step(1); if i % k == 0: record_diagnostics()), enqueue only as well."""
+        if record_every < 0:
+            raise ValueError("record_every %d" % record_every)
+        if not record_every:
+            _check(lib.nbody_batch_step(self._b, nsteps))
+            return
+        done = 0
+        while done < nsteps:
+            chunk = min(record_every, nsteps - done)
+            _check(lib.nbody_batch_step(self._b, chunk))
+            done += chunk
+            if done % record_every == 0:
+                _check(lib.nbody_batch_diag_record(self._b))
 
     def sync(self):
         _check(lib.nbody_batch_sync(self._b))
+
+    def diagnostics(self, potential=False):
+        """nbody_batch_diagnostics: one dict per system, in the form (and with the bits) of Stepper.diagnostics; with
+        potential=True also "phi", the per-body potential of the system's current bodies."""
+        out = (Diag * self.systems)()
+        phi = np.zeros(self.systems * self.capacity, dtype=np.float64) if potential else None
+        _check(lib.nbody_batch_diagnostics(self._b, out, phi.ctypes.data if potential else None))
+        res = []
+        for s in range(self.systems):
+            d = out[s].as_dict()
+            if potential:
+                d["phi"] = phi[s * self.capacity:s * self.capacity + d["n_bodies"]].copy()
+            res.append(d)
+        return res
+
+    def reserve_diagnostics(self, samples):
+        """Room for `samples` recorded samples of every system on the device (0 frees it); empties the series."""
+        _check(lib.nbody_batch_diag_reserve(self._b, samples))
+        self._log_cap = samples
+
+    def record_diagnostics(self):
+        """Enqueues one sample of every system into the recorded series: no copy, no host wait."""
+        _check(lib.nbody_batch_diag_record(self._b))
+
+    def diagnostics_log(self):
+        """The recorded series: a DIAG_DTYPE array of shape (recorded, systems).  Synchronises."""
+        cap = self._log_cap
+        buf = np.zeros((max(cap, 1), self.systems), dtype=DIAG_DTYPE)
+        n = ctypes.c_int(0)
+        _check(lib.nbody_batch_diag_read(self._b, buf.ctypes.data, cap, ctypes.byref(n)))
+        return buf[:min(n.value, cap)].copy()
 
     def counts(self):
         out = np.zeros(self.systems, dtype=np.int32)

@@ -6,6 +6,8 @@
 // the grid of the upload covers every later step; each kernel takes the exact count from the system's device-side Meta
 // and workgroups past it exit at once (the argument of launch_compute in nbody_ctx.hip, without its refresh of the
 // bound: a batch is small systems, the idle workgroups cost less than a host wait would).
+// Diagnostics of every system (nbody_batch_diagnostics) and the recorded series (nbody_batch_diag_*) are two launches per
+// call or record on the same stream, sized the same way; a record is enqueue-only like a step (nbody_batch_diag.hpp).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,6 +17,7 @@
 #include "nbody.h"
 #include "nbody_error.h"
 #include "nbody_batch_kernels.hpp"
+#include "nbody_batch_diag.hpp"
 
 using namespace nbk;
 
@@ -52,6 +55,15 @@ struct nbody_batch {
     int n_upper = 0;                    // largest uploaded count: sizes every grid until the next upload
     bool uploaded = false;
     int64_t steps = 0;
+    // diagnostics (nbody_batch_diagnostics, nbody_batch_diag_*): nothing is allocated until one of them is called
+    DiagTile* dg_tiles = nullptr;       // [S * ceil(cap / 128)] tile partials, first diagnostics call of any kind
+    DiagOut* dg_out = nullptr;          // [S] records of one nbody_batch_diagnostics call
+    DiagOut* h_dg_out = nullptr;        // pinned [S]
+    double* dg_phi = nullptr;           // [S * cap], first call that asks for phi
+    double* h_dg_phi = nullptr;         // pinned [S * cap]
+    DiagOut* dg_log = nullptr;          // [log_cap * S] recorded series (nbody_batch_diag_reserve)
+    int log_cap = 0;                    // samples reserved
+    int log_rows = 0;                   // samples recorded since the reservation or the last upload: the next row
 };
 
 namespace {
@@ -65,6 +77,9 @@ void free_all(nbody_batch* b) {
     (void)hipFree(b->J); (void)hipFree(b->V); (void)hipFree(b->S_J); (void)hipFree(b->S_V);
     (void)hipFree(b->meta); (void)hipFree(b->counters); (void)hipFree(b->params); (void)hipFree(b->events);
     (void)hipFree(b->blk_counts);
+    (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
+    if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
+    if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
     if (b->h_meta) (void)hipHostFree(b->h_meta);
     if (b->h_counters) (void)hipHostFree(b->h_counters);
     free(b->h_stage);
@@ -144,6 +159,52 @@ int check_system(const nbody_batch* b, int system, const char* who) {
     if (!b) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL batch", who);
     if (system < 0 || system >= b->S)
         return nbody_fail(NBODY_ERR_INVALID, "%s: system %d out of range (the batch has %d)", who, system, b->S);
+    return NBODY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Diagnostics (kernels in nbody_batch_diag.hpp)
+// ---------------------------------------------------------------------------------------------------------
+static_assert(sizeof(nbody_diag) == sizeof(DiagOut), "nbody_diag and its device mirror");
+static_assert(offsetof(nbody_diag, step) == offsetof(DiagOut, step) && offsetof(nbody_diag, n_bodies) == offsetof(DiagOut, n_bodies) &&
+              offsetof(nbody_diag, coincident_pairs) == offsetof(DiagOut, coincident_pairs) &&
+              offsetof(nbody_diag, mass) == offsetof(DiagOut, mass) && offsetof(nbody_diag, momentum) == offsetof(DiagOut, momentum) &&
+              offsetof(nbody_diag, center_of_mass) == offsetof(DiagOut, center_of_mass) &&
+              offsetof(nbody_diag, angular_momentum) == offsetof(DiagOut, angular_momentum) &&
+              offsetof(nbody_diag, kinetic) == offsetof(DiagOut, kinetic) &&
+              offsetof(nbody_diag, potential) == offsetof(DiagOut, potential), "nbody_diag and its device mirror");
+
+int diag_fail_alloc(hipError_t e, const char* what) {
+    (void)hipGetLastError();
+    return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "batch diagnostics, %s: %s", what,
+                      hipGetErrorString(e));
+}
+
+// The tile partials: S * ceil(cap / 128) records, cleared once so that no later read sees memory nobody wrote.
+int diag_alloc_tiles(nbody_batch* b) {
+    if (b->dg_tiles) return NBODY_OK;
+    const size_t bytes = (size_t)b->S * (size_t)batch_diag_tiles(b->cap) * sizeof(DiagTile);
+    hipError_t e = hipMalloc((void**)&b->dg_tiles, bytes);
+    if (e != hipSuccess) { b->dg_tiles = nullptr; return diag_fail_alloc(e, "tile partials"); }
+    HIP_TRY(hipMemsetAsync(b->dg_tiles, 0, bytes, b->stream));
+    return NBODY_OK;
+}
+
+// The two launches of one sample of every system: rows of `out` are S records; phi may be NULL.
+int enqueue_diagnostics(nbody_batch* b, DiagOut* out, double* phi) {
+    const double G = (double)6.67408e-11f;               // src/nbody.cu:37, the float literal widened (as in nbody_ctx.hip)
+    if (b->n_upper > 0) {
+        const dim3 grid((b->n_upper + kDiagBlock - 1) / kDiagBlock, b->S);
+        if (phi)
+            hipLaunchKernelGGL((batch_diag_potential<true>), grid, dim3(kDiagBlock), 0, b->stream, (const Rec<float>*)b->J,
+                               (const Vec2<float>*)b->V, (const Meta*)b->meta, b->cap, G, phi, b->dg_tiles);
+        else
+            hipLaunchKernelGGL((batch_diag_potential<false>), grid, dim3(kDiagBlock), 0, b->stream, (const Rec<float>*)b->J,
+                               (const Vec2<float>*)b->V, (const Meta*)b->meta, b->cap, G, (double*)nullptr, b->dg_tiles);
+    }
+    hipLaunchKernelGGL((batch_diag_reduce<kWave>), dim3((b->S + kWave - 1) / kWave), dim3(kWave), 0, b->stream,
+                       (const DiagTile*)b->dg_tiles, (const Meta*)b->meta, b->counters, b->S, b->cap, out);
+    HIP_TRY(hipGetLastError());
     return NBODY_OK;
 }
 
@@ -319,6 +380,7 @@ int nbody_batch_upload(nbody_batch* b, const void* const* blocks, const int* cou
     b->n_upper = n_upper;
     b->uploaded = true;
     b->steps = 0;
+    b->log_rows = 0;                                       // the recorded series restarts, the reservation stays
     return NBODY_OK;
 }
 
@@ -410,6 +472,95 @@ int nbody_batch_get_stats(nbody_batch* b, int system, nbody_stats* out) {
     out->steps = b->steps;
     out->pairs = (int64_t)b->h_counters[system].pairs;
     out->n_bodies = b->h_meta[system].n;
+    return NBODY_OK;
+}
+
+int nbody_batch_diagnostics(nbody_batch* b, nbody_diag* out, double* phi) {
+    if (!b || !out) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diagnostics: NULL argument");
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_diagnostics before nbody_batch_upload");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    int rc = diag_alloc_tiles(b);
+    if (rc != NBODY_OK) return rc;
+    if (!b->dg_out) {
+        hipError_t e = hipMalloc((void**)&b->dg_out, sizeof(DiagOut) * (size_t)b->S);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_dg_out, sizeof(DiagOut) * (size_t)b->S, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipFree(b->dg_out);
+            b->dg_out = nullptr; b->h_dg_out = nullptr;
+            return diag_fail_alloc(e, "output records");
+        }
+    }
+    const size_t bodies = (size_t)b->S * (size_t)b->cap;
+    if (phi && !b->dg_phi) {
+        hipError_t e = hipMalloc((void**)&b->dg_phi, bodies * sizeof(double));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_dg_phi, bodies * sizeof(double), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipFree(b->dg_phi);
+            b->dg_phi = nullptr; b->h_dg_phi = nullptr;
+            return diag_fail_alloc(e, "potential buffer");
+        }
+    }
+    rc = enqueue_diagnostics(b, b->dg_out, phi ? b->dg_phi : nullptr);
+    if (rc != NBODY_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(b->h_dg_out, b->dg_out, sizeof(DiagOut) * (size_t)b->S, hipMemcpyDeviceToHost, b->stream));
+    if (phi) HIP_TRY(hipMemcpyAsync(b->h_dg_phi, b->dg_phi, bodies * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    rc = read_meta(b);                                     // synchronises; a system whose count failed its check ends here
+    if (rc != NBODY_OK) return rc;
+    memcpy(out, b->h_dg_out, sizeof(DiagOut) * (size_t)b->S);
+    if (phi)
+        for (int s = 0; s < b->S; ++s) {
+            const long long n = b->h_dg_out[s].n_bodies;   // what the kernels used: 0..cap
+            if (n > 0) memcpy(phi + (size_t)s * b->cap, b->h_dg_phi + (size_t)s * b->cap, (size_t)n * sizeof(double));
+        }
+    return NBODY_OK;
+}
+
+int nbody_batch_diag_reserve(nbody_batch* b, int samples) {
+    if (!b) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diag_reserve: NULL batch");
+    if (samples < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diag_reserve: %d samples", samples);
+    const unsigned long long bytes = (unsigned long long)samples * (unsigned long long)b->S * sizeof(DiagOut);
+    if (bytes > (1ull << 31))
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diag_reserve: %d samples of %d systems are %llu bytes (at most 2^31)",
+                          samples, b->S, bytes);
+    HIP_TRY(hipSetDevice(b->desc.device));
+    HIP_TRY(hipStreamSynchronize(b->stream));              // records in flight write the log that is about to go
+    if (b->dg_log) HIP_TRY(hipFree(b->dg_log));
+    b->dg_log = nullptr;
+    b->log_cap = 0;
+    b->log_rows = 0;
+    if (samples == 0) return NBODY_OK;
+    int rc = diag_alloc_tiles(b);                          // here, so that a record allocates nothing
+    if (rc != NBODY_OK) return rc;
+    hipError_t e = hipMalloc((void**)&b->dg_log, (size_t)bytes);
+    if (e != hipSuccess) { b->dg_log = nullptr; return diag_fail_alloc(e, "recorded series"); }
+    HIP_TRY(hipMemsetAsync(b->dg_log, 0, (size_t)bytes, b->stream));
+    b->log_cap = samples;
+    return NBODY_OK;
+}
+
+int nbody_batch_diag_record(nbody_batch* b) {
+    if (!b) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diag_record: NULL batch");
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_diag_record before nbody_batch_upload");
+    if (!b->dg_log) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_diag_record without a reservation (nbody_batch_diag_reserve)");
+    if (b->log_rows >= b->log_cap)
+        return nbody_fail(NBODY_ERR_CAPACITY, "nbody_batch_diag_record: the log holds its %d samples already", b->log_cap);
+    HIP_TRY(hipSetDevice(b->desc.device));
+    int rc = enqueue_diagnostics(b, b->dg_log + (size_t)b->log_rows * (size_t)b->S, nullptr);
+    if (rc != NBODY_OK) return rc;
+    b->log_rows += 1;
+    return NBODY_OK;
+}
+
+int nbody_batch_diag_read(nbody_batch* b, nbody_diag* out, int cap_samples, int* n_samples) {
+    if (!b || !out || !n_samples) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diag_read: NULL argument");
+    if (cap_samples < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diag_read: cap_samples %d", cap_samples);
+    HIP_TRY(hipSetDevice(b->desc.device));
+    int rc = read_meta(b);                                 // synchronises: every enqueued record has been written
+    if (rc != NBODY_OK) return rc;
+    const int rows = b->log_rows < cap_samples ? b->log_rows : cap_samples;
+    if (rows > 0)
+        HIP_TRY(hipMemcpy(out, b->dg_log, (size_t)rows * (size_t)b->S * sizeof(DiagOut), hipMemcpyDeviceToHost));
+    *n_samples = b->log_rows;
     return NBODY_OK;
 }
 
