@@ -133,9 +133,11 @@ enum { /* nbody_ctx_desc.flags */
     NBODY_FLAG_RECORD_EVENTS = 1u << 0,   /* keep the collision event log (E_t, D_t of SURVEY.md A.2)   */
     NBODY_FLAG_GROUP_EXCHANGE = 1u << 1,  /* world>1, every rank is a context of this process: the       */
                                           /* exchange is done by nbody_group_step with peer copies        */
-    NBODY_FLAG_FORCE_COMM = 1u << 2       /* create the RCCL communicator and run the slot all-gather    */
+    NBODY_FLAG_FORCE_COMM = 1u << 2,      /* create the RCCL communicator and run the slot all-gather    */
                                           /* even when world == 1 (exercises the multi-rank path on one  */
                                           /* GPU)                                                         */
+    NBODY_FLAG_TRACK_IDS = 1u << 3        /* keep the index -> identity map on the device (nbody_get_ids, */
+                                          /* nbody_get_lineage); world == 1 without an exchange flag only */
 };
 
 typedef struct nbody_ctx nbody_ctx;
@@ -194,6 +196,32 @@ typedef struct nbody_event {  /* one collision event, in the index space of the 
  * restarts the total: events carry step numbers of the current upload only. */
 int nbody_get_events(nbody_ctx* ctx, nbody_event* out, int cap, int64_t* total);
 int nbody_clear_events(nbody_ctx* ctx);
+
+/* Body identities (NBODY_FLAG_TRACK_IDS).  Every step ends with a stable compaction on `mass != 0`, so index
+ * i names a different body afterwards.  With the flag the context keeps, on the device, the identity of every current body:
+ * its index in the last nbody_upload, 0 .. n-1 (nbody_state_load uploads, so it restarts identities).  The map follows the
+ * compaction itself, not the log: a body uploaded with mass 0 disappears at the first step without any event, a NaN mass
+ * stays.  The compaction is stable, so the identities of the survivors are strictly increasing in i.  Two more launches per
+ * step (one without NBODY_FLAG_RECORD_EVENTS), no device-to-host copy, no host wait; a context without the flag allocates and
+ * launches nothing.  The flag needs world == 1 and neither NBODY_FLAG_GROUP_EXCHANGE nor NBODY_FLAG_FORCE_COMM (the other
+ * ranks' keep flags are not in the slot): anything else is NBODY_ERR_INVALID from nbody_ctx_create, found before any device
+ * call.  Both calls below: NBODY_ERR_STATE without the flag or before an upload, NBODY_ERR_INVALID for a NULL pointer or
+ * cap < 0; both synchronise.
+ * nbody_get_ids: ids[i] = identity of current body i; *n = current count, min(cap, n) entries are written. */
+int nbody_get_ids(nbody_ctx* ctx, int32_t* ids, int cap, int* n);
+typedef struct nbody_lineage {  /* an nbody_event in identity space                                    */
+    int32_t step;               /* as nbody_event                                                      */
+    int32_t id_i;               /* identity of the body that had index i in that step                  */
+    int32_t id_j;               /* identity of the body that had index j in that step                  */
+    int32_t kind;               /* as nbody_event: 0 id_i absorbs id_j, 1 id_i deleted because of id_j */
+} nbody_lineage;
+/* The event log translated through the map of the step each event happened in (needs NBODY_FLAG_RECORD_EVENTS as well:
+ * NBODY_ERR_STATE without).  Record k is event k of nbody_get_events: same position, same step and kind; total, cap and the
+ * overflow rules are those of nbody_get_events, and nbody_clear_events / nbody_upload empty both.  Only events of committed
+ * steps are covered: what nbody_debug_force_only logs after the last step reads -1 / -1, and the tuning records of
+ * kernel_variant 58 are outside the contract.  An event index outside [0, n) of its step is never used as an address: the
+ * record gets -1 and the context fails its next synchronising call like after any failed index check. */
+int nbody_get_lineage(nbody_ctx* ctx, nbody_lineage* out, int cap, int64_t* total);
 
 typedef struct nbody_stats {
     int64_t steps;            /* steps enqueued since upload                                           */
@@ -309,7 +337,7 @@ typedef struct nbody_batch_desc {
     int systems;         /* S, 1..65535                                                                           */
     int capacity;        /* max bodies PER SYSTEM; systems * capacity <= 2^28                                     */
     int device;          /* HIP device ordinal                                                                    */
-    uint32_t flags;      /* NBODY_FLAG_RECORD_EVENTS only; the exchange flags -> NBODY_ERR_INVALID                */
+    uint32_t flags;      /* NBODY_FLAG_RECORD_EVENTS and / or NBODY_FLAG_TRACK_IDS; anything else -> NBODY_ERR_INVALID */
     int event_capacity;  /* max logged events per system (0: default, 2^24 / systems clamped to 1024..2^20)       */
     int kernel_variant;  /* 0 automatic (from systems * capacity); otherwise lanes per body, 1, 2, 4 or 8 (A/B)   */
 } nbody_batch_desc;
@@ -333,6 +361,12 @@ int nbody_batch_counts(nbody_batch* b, int* counts);          /* current body co
 int nbody_batch_download(nbody_batch* b, int system, void* block, int* n);
 /* As nbody_get_events, for one system's slice of the log; step numbers count from the last upload. */
 int nbody_batch_get_events(nbody_batch* b, int system, nbody_event* out, int cap, int64_t* total);
+/* As nbody_get_ids and nbody_get_lineage, for one system (NBODY_FLAG_TRACK_IDS in nbody_batch_desc.flags): identities are
+ * the indices 0 .. counts[s]-1 of the last nbody_batch_upload, per system; system s gives what an nbody_ctx with the flag
+ * gives for the same upload and steps (the lineage as a set per step, like the events).  At most two more launches per
+ * ensemble step, whatever S is.  Same errors; a bad system number is NBODY_ERR_INVALID. */
+int nbody_batch_get_ids(nbody_batch* b, int system, int32_t* ids, int cap, int* n);
+int nbody_batch_get_lineage(nbody_batch* b, int system, nbody_lineage* out, int cap, int64_t* total);
 /* steps, pairs and n_bodies of one system; every other field 0.  Synchronises. */
 int nbody_batch_get_stats(nbody_batch* b, int system, nbody_stats* out);
 /* Which force kernel the batch launches (static string; reporting only). */

@@ -22,6 +22,7 @@ LITERAL, CLEAN = 0, 1
 FLAG_RECORD_EVENTS = 1
 FLAG_GROUP_EXCHANGE = 2
 FLAG_FORCE_COMM = 4
+FLAG_TRACK_IDS = 8
 COMM_ID_BYTES = 128
 IMAGE_PATH_MAX = 1024
 
@@ -98,6 +99,8 @@ class Rng(ctypes.Structure):
 
 
 EVENT_DTYPE = np.dtype([("step", np.int32), ("i", np.int32), ("j", np.int32), ("kind", np.int32)])
+# struct nbody_lineage: an event in identity space (Stepper.lineage, StepperBatch.lineage)
+LINEAGE_DTYPE = np.dtype([("step", np.int32), ("id_i", np.int32), ("id_j", np.int32), ("kind", np.int32)])
 # struct nbody_diag as a numpy record (StepperBatch.diagnostics_log)
 DIAG_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64), ("coincident_pairs", np.int64), ("mass", np.float64),
                        ("momentum", np.float64, (2,)), ("center_of_mass", np.float64, (2,)),
@@ -136,6 +139,8 @@ SYMBOLS = {
     "nbody_sync": (_i, [_vp]),
     "nbody_get_events": (_i, [_vp, _vp, _i, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_clear_events": (_i, [_vp]),
+    "nbody_get_ids": (_i, [_vp, _vp, _i, _ip]),
+    "nbody_get_lineage": (_i, [_vp, _vp, _i, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_get_stats": (_i, [_vp, ctypes.POINTER(Stats)]),
     "nbody_set_kernel_timing": (_i, [_vp, _i]),
     "nbody_force_kernel_name": (ctypes.c_char_p, [_vp]),
@@ -162,6 +167,8 @@ SYMBOLS = {
     "nbody_batch_counts": (_i, [_vp, _ip]),
     "nbody_batch_download": (_i, [_vp, _i, _vp, _ip]),
     "nbody_batch_get_events": (_i, [_vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int64)]),
+    "nbody_batch_get_ids": (_i, [_vp, _i, _vp, _i, _ip]),
+    "nbody_batch_get_lineage": (_i, [_vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_get_stats": (_i, [_vp, _i, ctypes.POINTER(Stats)]),
     "nbody_batch_kernel_name": (ctypes.c_char_p, [_vp]),
     "nbody_batch_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
@@ -337,6 +344,22 @@ def comm_unique_id():
     return buf.raw
 
 
+def _ids(call, capacity):
+    buf = np.zeros(max(capacity, 1), dtype=np.int32)
+    n = ctypes.c_int(0)
+    _check(call(buf.ctypes.data, capacity, ctypes.byref(n)))
+    return buf[:n.value].copy()
+
+
+def _lineage(call, cap):
+    buf = np.zeros(max(cap, 1), dtype=LINEAGE_DTYPE)
+    total = ctypes.c_int64(0)
+    _check(call(buf.ctypes.data, cap, ctypes.byref(total)))
+    if total.value > cap:
+        raise NbodyError(-7, "event log holds %d events, buffer %d" % (total.value, cap))
+    return buf[:total.value]
+
+
 def _diagnostics(call, capacity, potential):
     d = Diag()
     phi = np.zeros(max(capacity, 1), dtype=np.float64) if potential else None
@@ -352,7 +375,8 @@ class Stepper:
 
     def __init__(self, cfg=None, capacity=None, precision=F32, semantics=LITERAL, device=0, rank=0, world=1,
                  record_events=False, group=False, comm_id=None, timestep=None, growthRate=None,
-                 fieldWidth=None, fieldHeight=None, event_capacity=0, kernel_variant=0, force_comm=False):
+                 fieldWidth=None, fieldHeight=None, event_capacity=0, kernel_variant=0, force_comm=False,
+                 track_ids=False):
         d = _CtxDesc()
         if cfg is not None:
             lib.nbody_ctx_desc_from_config(ctypes.byref(d), ctypes.byref(cfg), precision)
@@ -364,7 +388,7 @@ class Stepper:
             if val is not None:
                 setattr(d, name, val)
         d.flags = ((FLAG_RECORD_EVENTS if record_events else 0) | (FLAG_GROUP_EXCHANGE if group else 0) |
-                   (FLAG_FORCE_COMM if force_comm else 0))
+                   (FLAG_FORCE_COMM if force_comm else 0) | (FLAG_TRACK_IDS if track_ids else 0))
         d.event_capacity = event_capacity
         d.kernel_variant = kernel_variant
         self._comm_id = ctypes.create_string_buffer(comm_id, COMM_ID_BYTES) if comm_id else None
@@ -438,6 +462,15 @@ class Stepper:
 
     def clear_events(self):
         _check(lib.nbody_clear_events(self._ctx))
+
+    def ids(self):
+        """nbody_get_ids (track_ids=True): int32[n], ids()[i] = index that current body i had in the last upload."""
+        return _ids(lambda buf, cap, n: lib.nbody_get_ids(self._ctx, buf, cap, n), self.capacity)
+
+    def lineage(self, cap=1 << 20):
+        """nbody_get_lineage (track_ids=True and record_events=True): a LINEAGE_DTYPE array, record k is events()[k]
+        with the identities that its i and j had in that step."""
+        return _lineage(lambda buf, c, total: lib.nbody_get_lineage(self._ctx, buf, c, total), cap)
 
     def force_kernel_name(self):
         return lib.nbody_force_kernel_name(self._ctx).decode()
@@ -517,7 +550,7 @@ class StepperBatch:
     per system; or cfg=..., the same configuration for every system."""
 
     def __init__(self, systems, capacity, params=None, cfg=None, semantics=LITERAL, record_events=False,
-                 event_capacity=0, kernel_variant=0, device=0, precision=F32):
+                 event_capacity=0, kernel_variant=0, device=0, precision=F32, track_ids=False):
         if params is None and cfg is not None:
             params = [cfg] * max(int(systems), 0)
         arr = None
@@ -531,7 +564,7 @@ class StepperBatch:
                 arr[s].timestep, arr[s].growthRate, arr[s].fieldWidth, arr[s].fieldHeight = p
         d = _BatchDesc()
         d.precision, d.semantics, d.systems, d.capacity, d.device = precision, semantics, systems, capacity, device
-        d.flags = FLAG_RECORD_EVENTS if record_events else 0
+        d.flags = (FLAG_RECORD_EVENTS if record_events else 0) | (FLAG_TRACK_IDS if track_ids else 0)
         d.event_capacity = event_capacity
         d.kernel_variant = kernel_variant
         self.systems, self.capacity, self.precision = systems, capacity, precision
@@ -633,6 +666,14 @@ class StepperBatch:
         if total.value > cap:
             raise NbodyError(-7, "event log holds %d events, buffer %d" % (total.value, cap))
         return buf[:total.value]
+
+    def ids(self, system):
+        """nbody_batch_get_ids (track_ids=True): as Stepper.ids, for one system."""
+        return _ids(lambda buf, cap, n: lib.nbody_batch_get_ids(self._b, system, buf, cap, n), self.capacity)
+
+    def lineage(self, system, cap=1 << 20):
+        """nbody_batch_get_lineage (track_ids=True and record_events=True): as Stepper.lineage, for one system."""
+        return _lineage(lambda buf, c, total: lib.nbody_batch_get_lineage(self._b, system, buf, c, total), cap)
 
     def stats(self, system):
         s = Stats()

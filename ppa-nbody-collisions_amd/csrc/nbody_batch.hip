@@ -13,11 +13,13 @@
 #include <stdlib.h>
 #include <string.h>
 #include <new>
+#include <vector>
 
 #include "nbody.h"
 #include "nbody_error.h"
 #include "nbody_batch_kernels.hpp"
 #include "nbody_batch_diag.hpp"
+#include "nbody_ids.hpp"
 
 using namespace nbk;
 
@@ -64,11 +66,16 @@ struct nbody_batch {
     DiagOut* dg_log = nullptr;          // [log_cap * S] recorded series (nbody_batch_diag_reserve)
     int log_cap = 0;                    // samples reserved
     int log_rows = 0;                   // samples recorded since the reservation or the last upload: the next row
+    // identities (NBODY_FLAG_TRACK_IDS, nbody_ids.hpp): nothing is allocated without the flag
+    IdsState ids;                       // the map [S * cap] twice, the lineage [S * ev_cap], [S] translated-up-to counters
 };
 
 namespace {
 
 constexpr int kCommitSmall = 256, kCommitLarge = 1024;     // threads of a commit workgroup
+// Identities (NBODY_FLAG_TRACK_IDS), defined at the end of this file (see nbody_ids.hpp for why there).
+void ids_step(nbody_batch* b, int nblk, int threads);   // before the commit; the commit's geometry
+int ids_restart(nbody_batch* b);                        // nbody_batch_upload
 
 void free_all(nbody_batch* b) {
     if (!b) return;
@@ -77,6 +84,7 @@ void free_all(nbody_batch* b) {
     (void)hipFree(b->J); (void)hipFree(b->V); (void)hipFree(b->S_J); (void)hipFree(b->S_V);
     (void)hipFree(b->meta); (void)hipFree(b->counters); (void)hipFree(b->params); (void)hipFree(b->events);
     (void)hipFree(b->blk_counts);
+    (void)hipFree(b->ids.map[0]); (void)hipFree(b->ids.map[1]); (void)hipFree(b->ids.lineage); (void)hipFree(b->ids.done);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -120,6 +128,10 @@ void launch_commit_b(nbody_batch* b, int nblk) {
     if (nblk > 1)
         hipLaunchKernelGGL((batch_count<B>), grid, dim3(B), 0, b->stream, (const Rec<float>*)b->S_J, b->meta,
                            b->blk_counts, b->cap);
+    // identities: before the commit, where Meta::n and the map are still those of step t and S_J is staged; the events of
+    // this step go through the map of this step, then the map follows the compaction (batch_count's partials above one
+    // workgroup per system, its own count otherwise)
+    if (b->ids.on()) ids_step(b, nblk, B);
     hipLaunchKernelGGL((batch_commit<B>), grid, dim3(B), 0, b->stream, (const Rec<float>*)b->S_J,
                        (const Vec2<float>*)b->S_V, b->J, b->V, b->meta, (const int*)b->blk_counts, b->counters, b->cap);
 }
@@ -229,9 +241,9 @@ int nbody_batch_create(nbody_batch** out, const nbody_batch_desc* d, const nbody
     if (d->precision != NBODY_F32) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: bad precision");
     if (d->semantics != NBODY_LITERAL && d->semantics != NBODY_CLEAN)
         return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: bad semantics");
-    if (d->flags & ~(uint32_t)NBODY_FLAG_RECORD_EVENTS)
-        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: flags 0x%x (only NBODY_FLAG_RECORD_EVENTS: a batch "
-                                             "has no exchange)", d->flags);
+    if (d->flags & ~(uint32_t)(NBODY_FLAG_RECORD_EVENTS | NBODY_FLAG_TRACK_IDS))
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: flags 0x%x (only NBODY_FLAG_RECORD_EVENTS and "
+                                             "NBODY_FLAG_TRACK_IDS: a batch has no exchange)", d->flags);
     if (d->event_capacity < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_create: negative event_capacity");
     if (d->kernel_variant != 0 && d->kernel_variant != 1 && d->kernel_variant != 2 && d->kernel_variant != 4 &&
         d->kernel_variant != 8)
@@ -293,6 +305,15 @@ int nbody_batch_create(nbody_batch** out, const nbody_batch_desc* d, const nbody
     BATCH_TRY(hipMalloc((void**)&b->params, sizeof(StepParams<float>) * (size_t)b->S));
     BATCH_TRY(hipMalloc((void**)&b->blk_counts, sizeof(int) * (size_t)b->S * (size_t)(b->cap / kCommitLarge + 1)));
     if (log) BATCH_TRY(hipMalloc((void**)&b->events, sizeof(Event) * (size_t)b->S * (size_t)ev_cap));
+    if (d->flags & NBODY_FLAG_TRACK_IDS) {
+        BATCH_TRY(hipMalloc((void**)&b->ids.map[0], bodies * sizeof(int32_t)));
+        BATCH_TRY(hipMalloc((void**)&b->ids.map[1], bodies * sizeof(int32_t)));
+        if (log) {
+            BATCH_TRY(hipMalloc((void**)&b->ids.lineage, sizeof(IdPair) * (size_t)b->S * (size_t)ev_cap));
+            BATCH_TRY(hipMalloc((void**)&b->ids.done, sizeof(unsigned long long) * (size_t)b->S));
+            BATCH_TRY(hipMemsetAsync(b->ids.done, 0, sizeof(unsigned long long) * (size_t)b->S, b->stream));
+        }
+    }
     BATCH_TRY(hipHostMalloc((void**)&b->h_meta, sizeof(Meta) * (size_t)b->S, hipHostMallocDefault));
     BATCH_TRY(hipHostMalloc((void**)&b->h_counters, sizeof(Counters) * (size_t)b->S, hipHostMallocDefault));
     memset(b->h_meta, 0, sizeof(Meta) * (size_t)b->S);
@@ -375,6 +396,10 @@ int nbody_batch_upload(nbody_batch* b, const void* const* blocks, const int* cou
     HIP_TRY(hipMemcpyAsync(b->V, sv, bodies * sizeof(Vec2<float>), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(b->meta, b->h_meta, sizeof(Meta) * (size_t)b->S, hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemsetAsync(b->counters, 0, sizeof(Counters) * (size_t)b->S, b->stream));   // pairs, events, errors
+    if (b->ids.on()) {                                     // identity = index of this upload; both logs start empty
+        int ri = ids_restart(b);
+        if (ri != NBODY_OK) return ri;
+    }
     HIP_TRY(hipStreamSynchronize(b->stream));
     memset(b->h_counters, 0, sizeof(Counters) * (size_t)b->S);
     b->n_upper = n_upper;
@@ -458,6 +483,55 @@ int nbody_batch_get_events(nbody_batch* b, int system, nbody_event* out, int cap
     if (ncopy > (unsigned long long)cap) ncopy = cap;
     static_assert(sizeof(nbody_event) == sizeof(Event), "event layouts must match");
     if (ncopy) HIP_TRY(hipMemcpy(out, b->events + (size_t)system * (size_t)b->ev_cap, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
+    return NBODY_OK;
+}
+
+int nbody_batch_get_ids(nbody_batch* b, int system, int32_t* ids, int cap, int* n_out) {
+    int rc = check_system(b, system, "nbody_batch_get_ids");
+    if (rc != NBODY_OK) return rc;
+    if (!n_out || cap < 0 || (cap > 0 && !ids)) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_get_ids: bad argument");
+    if (!b->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_ids: the batch was created without NBODY_FLAG_TRACK_IDS");
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_ids before nbody_batch_upload");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    rc = read_meta(b);
+    if (rc != NBODY_OK) return rc;
+    const int n = b->h_meta[system].n;
+    if (n < 0 || n > b->cap) return nbody_fail(NBODY_ERR_STATE, "system %d reports %d bodies, capacity %d", system, n, b->cap);
+    const int k = n < cap ? n : cap;
+    if (k > 0)
+        HIP_TRY(hipMemcpy(ids, b->ids.map[b->ids.cur] + (size_t)system * (size_t)b->cap, sizeof(int32_t) * (size_t)k,
+                          hipMemcpyDeviceToHost));
+    *n_out = n;
+    return NBODY_OK;
+}
+
+int nbody_batch_get_lineage(nbody_batch* b, int system, nbody_lineage* out, int cap, int64_t* total) {
+    int rc = check_system(b, system, "nbody_batch_get_lineage");
+    if (rc != NBODY_OK) return rc;
+    if (!total || cap < 0 || (cap > 0 && !out)) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_get_lineage: bad argument");
+    if (!b->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_lineage: the batch was created without NBODY_FLAG_TRACK_IDS");
+    if (!b->ids.lineage) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_lineage: the batch was created without NBODY_FLAG_RECORD_EVENTS");
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_lineage before nbody_batch_upload");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    rc = read_meta(b);                                     // synchronises; a failed index check of a translation ends here
+    if (rc != NBODY_OK) return rc;
+    unsigned long long done = 0;
+    HIP_TRY(hipMemcpy(&done, b->ids.done + system, sizeof(done), hipMemcpyDeviceToHost));
+    const unsigned long long tot = b->h_counters[system].events;
+    *total = (int64_t)tot;
+    unsigned long long ncopy = tot;
+    if (ncopy > (unsigned long long)b->ev_cap) ncopy = b->ev_cap;
+    if (ncopy > (unsigned long long)cap) ncopy = cap;
+    if (!ncopy) return NBODY_OK;
+    std::vector<Event> ev((size_t)ncopy);
+    std::vector<IdPair> who((size_t)ncopy);
+    const size_t first = (size_t)system * (size_t)b->ev_cap;
+    HIP_TRY(hipMemcpy(ev.data(), b->events + first, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(who.data(), b->ids.lineage + first, ncopy * sizeof(IdPair), hipMemcpyDeviceToHost));
+    for (unsigned long long k = 0; k < ncopy; ++k) {
+        const bool have = k < done;
+        out[k] = nbody_lineage{ev[k].step, have ? who[k].id_i : -1, have ? who[k].id_j : -1, ev[k].kind};
+    }
     return NBODY_OK;
 }
 
@@ -575,3 +649,28 @@ const char* nbody_batch_kernel_name(nbody_batch* b) {
 }
 
 }  // extern "C"
+
+namespace {
+
+constexpr int kIdsTranslateGrid = 2;                       // workgroups of ids_translate per system (a grid-stride loop)
+
+template <int B>
+void ids_step_b(nbody_batch* b, int nblk) {
+    ids_enqueue_step<float, B>(b->ids, b->stream, nblk, b->S, kIdsTranslateGrid, (const Rec<float>*)b->S_J,
+                               (const Meta*)b->meta, (const int*)b->blk_counts, b->cap, b->counters,
+                               (const Event*)b->events, b->ev_cap);
+}
+
+void ids_step(nbody_batch* b, int nblk, int threads) {
+    if (threads == kCommitSmall) ids_step_b<kCommitSmall>(b, nblk);
+    else ids_step_b<kCommitLarge>(b, nblk);
+}
+
+int ids_restart(nbody_batch* b) {
+    ids_enqueue_fill<kIdsBlock>(b->ids, b->stream, b->S, b->cap);
+    HIP_TRY(hipGetLastError());
+    if (b->ids.done) HIP_TRY(hipMemsetAsync(b->ids.done, 0, sizeof(unsigned long long) * (size_t)b->S, b->stream));
+    return NBODY_OK;
+}
+
+}  // namespace

@@ -4,7 +4,10 @@
  * Image output (:512-539) is produced with --images: iteration_<k>.ppm in cfg.imagePath for every k that is a
  * multiple of save_Image_Every_Xth_Iteration and not the last iteration (the reference saves the image of
  * iteration k during iteration k+1, :513-522, so the last one is never written).  Without --images the run is
- * the pure stepping loop.  --diagnostics K prints one `diag ...` line (nbody_get_diagnostics / nbody_group_diagnostics,
+ * the pure stepping loop.  --lineage PATH (single GPU) runs with NBODY_FLAG_RECORD_EVENTS | NBODY_FLAG_TRACK_IDS and writes
+ * the merger history in identity space after the run: one line `step kind id_i id_j` per record of nbody_get_lineage,
+ * sorted by (step, kind, id_i, id_j), then one line `survivors` and the identities of the final bodies, one per line in
+ * index order.  --diagnostics K prints one `diag ...` line (nbody_get_diagnostics / nbody_group_diagnostics,
  * %.17g: the values round-trip) after the upload, after every K-th step and after the last one.  Host code in C over
  * the C ABI. */
 #include "nbody.h"
@@ -30,6 +33,51 @@ static int print_diag(nbody_ctx** ctxs, int gpus) {
     return NBODY_OK;
 }
 
+static int cmp_lineage(const void* pa, const void* pb) {   /* by (step, kind, id_i, id_j) */
+    const nbody_lineage *a = (const nbody_lineage*)pa, *b = (const nbody_lineage*)pb;
+    if (a->step != b->step) return a->step < b->step ? -1 : 1;
+    if (a->kind != b->kind) return a->kind < b->kind ? -1 : 1;
+    if (a->id_i != b->id_i) return a->id_i < b->id_i ? -1 : 1;
+    if (a->id_j != b->id_j) return a->id_j < b->id_j ? -1 : 1;
+    return 0;
+}
+
+static int write_lineage(nbody_ctx* ctx, const char* path, int capacity) {
+    int64_t total = 0;
+    int rc = nbody_get_lineage(ctx, NULL, 0, &total);
+    if (rc != NBODY_OK) return rc;
+    nbody_ctx_desc d;
+    rc = nbody_ctx_info(ctx, &d, NULL);
+    if (rc != NBODY_OK) return rc;
+    const int ev_cap = d.event_capacity > 0 ? d.event_capacity : (1 << 20);   /* the default of nbody_ctx_create */
+    if (total > ev_cap) {
+        fprintf(stderr, "lineage: %lld events were logged, the log holds %d: the history is incomplete\n", (long long)total,
+                ev_cap);
+        return NBODY_ERR_CAPACITY;
+    }
+    nbody_lineage* rec = (nbody_lineage*)malloc(sizeof(nbody_lineage) * (size_t)(total > 0 ? total : 1));
+    int32_t* ids = (int32_t*)malloc(sizeof(int32_t) * (size_t)(capacity > 0 ? capacity : 1));
+    int n = 0;
+    if (!rec || !ids) { free(rec); free(ids); return NBODY_ERR_NOMEM; }
+    rc = nbody_get_lineage(ctx, rec, (int)total, &total);
+    if (rc == NBODY_OK) rc = nbody_get_ids(ctx, ids, capacity, &n);
+    FILE* f = rc == NBODY_OK ? fopen(path, "w") : NULL;
+    if (rc == NBODY_OK && !f) {
+        fprintf(stderr, "lineage: cannot write %s\n", path);
+        rc = NBODY_ERR_IO;
+    }
+    if (f) {
+        qsort(rec, (size_t)total, sizeof(nbody_lineage), cmp_lineage);
+        for (int64_t k = 0; k < total; ++k) fprintf(f, "%d %d %d %d\n", rec[k].step, rec[k].kind, rec[k].id_i, rec[k].id_j);
+        fprintf(f, "survivors\n");
+        for (int i = 0; i < n; ++i) fprintf(f, "%d\n", ids[i]);
+        if (fclose(f) != 0) rc = NBODY_ERR_IO;
+    }
+    free(rec);
+    free(ids);
+    return rc;
+}
+
 static int die(const char* what, int rc) {
     fprintf(stderr, "%s: %s: %s\n", what, nbody_status_string(rc), nbody_last_error_string());
     return 1;
@@ -37,6 +85,7 @@ static int die(const char* what, int rc) {
 
 int main(int argc, char** argv) {
     const char* path = "nbodyConfig.txt";
+    const char* lineage_path = NULL;
     int precision = NBODY_F32, gpus = 1, dump = 0, images = 0, diag_every = 0;
     for (int a = 1; a < argc; ++a) {
         if (!strcmp(argv[a], "--config") && a + 1 < argc) path = argv[++a];
@@ -44,13 +93,19 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--dump")) dump = 1;
         else if (!strcmp(argv[a], "--images")) images = 1;
+        else if (!strcmp(argv[a], "--lineage") && a + 1 < argc) lineage_path = argv[++a];
         else if (!strcmp(argv[a], "--diagnostics") && a + 1 < argc && atoi(argv[a + 1]) > 0) diag_every = atoi(argv[++a]);
         else {
-            fprintf(stderr, "usage: nbody [--config FILE] [--fp64] [--gpus N] [--dump] [--images] [--diagnostics K]\n");
+            fprintf(stderr, "usage: nbody [--config FILE] [--fp64] [--gpus N] [--dump] [--images] [--diagnostics K] "
+                            "[--lineage FILE]\n");
             return 2;
         }
     }
     if (gpus < 1 || gpus > 64) return 2;
+    if (lineage_path && gpus > 1) {
+        fprintf(stderr, "nbody: --lineage needs a single GPU (identities are not tracked across ranks)\n");
+        return 2;
+    }
     double startTime = now();
     printf("Running simulation with the following settings:\n");
     nbody_config cfg;
@@ -69,6 +124,7 @@ int main(int argc, char** argv) {
         nbody_ctx_desc_from_config(&d, &cfg, precision);
         d.device = g; d.rank = g; d.world = gpus;
         d.flags = gpus > 1 ? NBODY_FLAG_GROUP_EXCHANGE : 0;
+        if (lineage_path) d.flags |= NBODY_FLAG_RECORD_EVENTS | NBODY_FLAG_TRACK_IDS;
         rc = nbody_ctx_create(&ctxs[g], &d);
         if (rc != NBODY_OK) return die("ctx_create", rc);
         rc = nbody_upload(ctxs[g], block, cfg.particleCount);
@@ -117,6 +173,10 @@ int main(int argc, char** argv) {
     rc = nbody_group_download(ctxs, gpus, block, &n);
     if (rc != NBODY_OK) return die("download", rc);
     double t1 = now();
+    if (lineage_path) {
+        rc = write_lineage(ctxs[0], lineage_path, cfg.particleCount);
+        if (rc != NBODY_OK) return die("lineage", rc);
+    }
     long long pairs = 0;
     for (int g = 0; g < gpus; ++g) {
         nbody_stats s;

@@ -22,6 +22,7 @@
 #include "nbody_error.h"
 #include "nbody_kernels.hpp"
 #include "nbody_diag.hpp"
+#include "nbody_ids.hpp"
 
 using namespace nbk;
 
@@ -164,6 +165,8 @@ struct nbody_ctx {
     DiagTile* dg_tiles = nullptr;      // per own tile: partial sums (cap_own / 128 records)
     double* dg_phi = nullptr;          // phi of the own range (cap_own doubles)
     unsigned char* dg_gather = nullptr;    // world * (tiles | phi) of the padded per-rank areas
+    // identities (NBODY_FLAG_TRACK_IDS, nbody_ids.hpp): nothing is allocated without the flag
+    IdsState ids;                          // the map [cap_own] twice, the lineage [ev_cap], the translated-up-to counter
 };
 
 namespace {
@@ -494,8 +497,14 @@ int do_exchange(nbody_ctx* c) {
     return NBODY_OK;
 }
 
+// Identities (NBODY_FLAG_TRACK_IDS; world == 1), defined at the end of this file (see nbody_ids.hpp for why there).
+int ids_step(nbody_ctx* c);      // between launch_compute and launch_commit
+int ids_restart(nbody_ctx* c);   // nbody_upload
+
 int compute_phase(nbody_ctx* c) {
-    return c->desc.precision == NBODY_F64 ? launch_compute<double>(c) : launch_compute<float>(c);
+    int rc = c->desc.precision == NBODY_F64 ? launch_compute<double>(c) : launch_compute<float>(c);
+    if (rc != NBODY_OK || !c->ids.on()) return rc;
+    return ids_step(c);
 }
 int commit_phase(nbody_ctx* c) {
     int rc = c->desc.precision == NBODY_F64 ? launch_commit<double>(c) : launch_commit<float>(c);
@@ -526,6 +535,7 @@ void free_all(nbody_ctx* c) {
     hipFree(c->slot);
     hipFree(c->blk_counts); hipFree(c->tile_rmax); hipFree(c->Jt); hipFree(c->meta); hipFree(c->meta_all); hipFree(c->events); hipFree(c->d_img);
     hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
+    hipFree(c->ids.map[0]); hipFree(c->ids.map[1]); hipFree(c->ids.lineage); hipFree(c->ids.done);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -669,6 +679,10 @@ int nbody_ctx_create(nbody_ctx** out, const nbody_ctx_desc* d) {
         return nbody_fail(NBODY_ERR_INVALID, "nbody_ctx_create: bad precision");
     if (d->semantics != NBODY_LITERAL && d->semantics != NBODY_CLEAN)
         return nbody_fail(NBODY_ERR_INVALID, "nbody_ctx_create: bad semantics");
+    if ((d->flags & NBODY_FLAG_TRACK_IDS) &&
+        (d->world > 1 || (d->flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM))))
+        return nbody_fail(NBODY_ERR_INVALID, "nbody_ctx_create: NBODY_FLAG_TRACK_IDS needs world == 1 and no exchange flag "
+                                             "(the other ranks' keep flags are not in the slot)");
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -736,6 +750,15 @@ int nbody_ctx_create(nbody_ctx** out, const nbody_ctx_desc* d) {
         memset(L.block, 0, kMetaBlockBytes);
     }
     CTX_TRY(hipMalloc((void**)&c->events, sizeof(Event) * (size_t)c->ev_cap));
+    if (d->flags & NBODY_FLAG_TRACK_IDS) {
+        CTX_TRY(hipMalloc((void**)&c->ids.map[0], sizeof(int32_t) * (size_t)c->cap_own));
+        CTX_TRY(hipMalloc((void**)&c->ids.map[1], sizeof(int32_t) * (size_t)c->cap_own));
+        if (d->flags & NBODY_FLAG_RECORD_EVENTS) {
+            CTX_TRY(hipMalloc((void**)&c->ids.lineage, sizeof(IdPair) * (size_t)c->ev_cap));
+            CTX_TRY(hipMalloc((void**)&c->ids.done, sizeof(unsigned long long)));
+            CTX_TRY(hipMemsetAsync(c->ids.done, 0, sizeof(unsigned long long), c->stream));
+        }
+    }
     // on the context's own stream and waited for: hipMemset() on device memory runs on the NULL stream and may
     // return before the fill has executed; the context's stream is non-blocking, so a late fill could land
     // after nbody_upload's copy of Meta (seen once as a step that found n = 0)
@@ -833,6 +856,10 @@ int nbody_upload(nbody_ctx* c, const void* block, int n) {
     *c->h_meta_async = *c->h_meta;
     HIP_TRY(hipMemcpyAsync(c->meta, c->h_meta, sizeof(Meta), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(Counters), c->stream));
+    if (c->ids.on()) {                                     // identity = index of this upload; both logs start empty
+        int ri = ids_restart(c);
+        if (ri != NBODY_OK) return ri;
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->n_upper = n; c->own_upper = own_upper_of(c, n);
     c->xchg_n = n; c->enq = 0; c->xchg_bytes = 0;
@@ -1171,6 +1198,49 @@ int nbody_clear_events(nbody_ctx* c) {
     if (!c) return nbody_fail(NBODY_ERR_INVALID, "NULL context");
     HIP_TRY(hipSetDevice(c->desc.device));
     HIP_TRY(hipMemsetAsync(&c->counters->events, 0, sizeof(unsigned long long), c->stream));
+    if (c->ids.done) HIP_TRY(hipMemsetAsync(c->ids.done, 0, sizeof(unsigned long long), c->stream));   // the lineage with it
+    return NBODY_OK;
+}
+
+int nbody_get_ids(nbody_ctx* c, int32_t* ids, int cap, int* n_out) {
+    if (!c || !n_out || cap < 0 || (cap > 0 && !ids)) return nbody_fail(NBODY_ERR_INVALID, "nbody_get_ids: bad argument");
+    if (!c->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_get_ids: the context was created without NBODY_FLAG_TRACK_IDS");
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_get_ids before nbody_upload");
+    HIP_TRY(hipSetDevice(c->desc.device));
+    int rc = read_meta(c);
+    if (rc != NBODY_OK) return rc;
+    const int n = c->h_meta->n;
+    if (n < 0 || n > c->cap_own) return nbody_fail(NBODY_ERR_STATE, "nbody_get_ids: %d bodies, capacity %d", n, c->cap_own);
+    const int k = n < cap ? n : cap;
+    if (k > 0) HIP_TRY(hipMemcpy(ids, c->ids.map[c->ids.cur], sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost));
+    *n_out = n;
+    return NBODY_OK;
+}
+
+int nbody_get_lineage(nbody_ctx* c, nbody_lineage* out, int cap, int64_t* total) {
+    if (!c || !total || cap < 0 || (cap > 0 && !out)) return nbody_fail(NBODY_ERR_INVALID, "nbody_get_lineage: bad argument");
+    if (!c->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_get_lineage: the context was created without NBODY_FLAG_TRACK_IDS");
+    if (!c->ids.lineage) return nbody_fail(NBODY_ERR_STATE, "nbody_get_lineage: the context was created without NBODY_FLAG_RECORD_EVENTS");
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_get_lineage before nbody_upload");
+    HIP_TRY(hipSetDevice(c->desc.device));
+    int rc = read_meta(c);                                 // synchronises; a failed index check of a translation ends here
+    if (rc != NBODY_OK) return rc;
+    unsigned long long done = 0;
+    HIP_TRY(hipMemcpy(&done, c->ids.done, sizeof(done), hipMemcpyDeviceToHost));
+    const unsigned long long tot = c->h_counters->events;
+    *total = (int64_t)tot;
+    unsigned long long ncopy = tot;
+    if (ncopy > (unsigned long long)c->ev_cap) ncopy = c->ev_cap;
+    if (ncopy > (unsigned long long)cap) ncopy = cap;
+    if (!ncopy) return NBODY_OK;
+    std::vector<Event> ev((size_t)ncopy);
+    std::vector<IdPair> who((size_t)ncopy);
+    HIP_TRY(hipMemcpy(ev.data(), c->events, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(who.data(), c->ids.lineage, ncopy * sizeof(IdPair), hipMemcpyDeviceToHost));
+    for (unsigned long long k = 0; k < ncopy; ++k) {       // events past `done` belong to no committed step
+        const bool have = k < done;
+        out[k] = nbody_lineage{ev[k].step, have ? who[k].id_i : -1, have ? who[k].id_j : -1, ev[k].kind};
+    }
     return NBODY_OK;
 }
 
@@ -1449,3 +1519,37 @@ int nbody_selftest_rcp_ones_f64(int device, uint64_t result[5]) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Identities (NBODY_FLAG_TRACK_IDS; world == 1).  ids_step runs between launch_compute and launch_commit, where S_J holds
+// the staged masses, blk_counts the survivors per block of compact_count's geometry, and Meta and the map are still those
+// of step t: the events of this step are translated through the map of this step, then the map follows the compaction.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kIdsTranslateGrid = 32;                      // workgroups of ids_translate: a grid-stride loop, whatever was logged
+
+template <typename T>
+void ids_step_t(nbody_ctx* c) {
+    const int nblk = (c->own_upper + kCompactBlock - 1) / kCompactBlock > 0
+                         ? (c->own_upper + kCompactBlock - 1) / kCompactBlock : 1;   // as launch_compute
+    ids_enqueue_step<T, kCompactBlock>(c->ids, c->stream, nblk, 1, kIdsTranslateGrid, (const Rec<T>*)c->S_J,
+                                       (const Meta*)c->meta, (const int*)c->blk_counts, c->cap_own, c->counters,
+                                       (const Event*)c->events, c->ev_cap);
+}
+
+int ids_step(nbody_ctx* c) {
+    if (c->desc.precision == NBODY_F64) ids_step_t<double>(c);
+    else ids_step_t<float>(c);
+    HIP_TRY(hipGetLastError());
+    return NBODY_OK;
+}
+
+int ids_restart(nbody_ctx* c) {
+    ids_enqueue_fill<kIdsBlock>(c->ids, c->stream, 1, c->cap_own);
+    HIP_TRY(hipGetLastError());
+    if (c->ids.done) HIP_TRY(hipMemsetAsync(c->ids.done, 0, sizeof(unsigned long long), c->stream));
+    return NBODY_OK;
+}
+
+}  // namespace

@@ -1,0 +1,153 @@
+// csrc/nbody_ids.hpp -- gfx950 device code of body identities (NBODY_FLAG_TRACK_IDS, include/nbody.h):
+// an index -> identity map that follows the per-step compaction, and the collision log translated through it while the
+// map of the step is still valid.  Shared by the one-system stepper (nbody_ctx.hip: one system, blockIdx.y = 0) and the
+// batched stepper (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride` apart, like every other batch kernel).
+//
+// The identity of a body is its index in the last upload.  ids_cur[i] is the identity of the body at index i of step t;
+// both kernels run after the force kernel of step t and BEFORE the commit, so Meta is still that of step t, S_J holds
+// the staged masses of step t and the event log holds every event of step t in the index space of step t.
+//   ids_translate : lineage[k] = {ids_cur[ev[k].i], ids_cur[ev[k].j]} for the events [done, min(events, ev_cap)) -
+//                   the ones logged since the last translation.  Reads `done`, never writes it.
+//   ids_scatter   : ids_next[offset of q among the survivors] = ids_cur[q], the offsets of compact_scatter /
+//                   batch_commit (same keep test, same stable order); one thread advances `done`.  Never reads `done`.
+// The host swaps ids_cur and ids_next after the pair.  Every kernel here is a template: both translation units include
+// this file (NBK_TEMPLATES_ONLY in nbody_batch.hip).
+#pragma once
+#include "nbody_kernels.hpp"
+
+namespace nbk {
+
+struct IdPair { int32_t id_i, id_j; };                     // one lineage record next to event k: who i and j were
+
+constexpr int kIdsBlock = 256;                             // threads of ids_fill / ids_translate workgroups
+
+// A count outside [0, stride] never becomes an index (batch_checked_count's rule): the system is treated as empty.
+__device__ __forceinline__ int ids_checked_count(int n, int stride) { return (n < 0 || n > stride) ? 0 : n; }
+
+// Upload: identity = index.  grid = (ceil(stride / B), S); the whole slice is written, so no later read sees memory
+// nobody wrote.
+template <int B>
+__global__ __launch_bounds__(B) void ids_fill(int32_t* __restrict__ ids_all, int stride) {
+    const int q = blockIdx.x * B + threadIdx.x;
+    if (q < stride) ids_all[(size_t)blockIdx.y * (size_t)stride + q] = q;
+}
+
+// grid = (any fixed number of workgroups, S): a grid-stride loop over the system's untranslated events.  An event index
+// outside [0, n_t) is not used as an address: the record gets -1 and the system's Counters::errors gets kIndexError.
+template <int B>
+__global__ __launch_bounds__(B) void ids_translate(const Event* __restrict__ ev_all, int ev_cap,
+                                                   Counters* __restrict__ ctr_all,
+                                                   const unsigned long long* __restrict__ done_all,
+                                                   const Meta* __restrict__ meta_all,
+                                                   const int32_t* __restrict__ ids_cur_all, int stride,
+                                                   IdPair* __restrict__ lineage_all) {
+    const int sys = blockIdx.y;
+    const int n = ids_checked_count(meta_all[sys].n, stride);
+    const unsigned long long logged = ctr_all[sys].events;
+    const unsigned long long end = logged < (unsigned long long)ev_cap ? logged : (unsigned long long)ev_cap;
+    const Event* __restrict__ ev = ev_all + (size_t)sys * (size_t)ev_cap;
+    IdPair* __restrict__ lineage = lineage_all + (size_t)sys * (size_t)ev_cap;
+    const int32_t* __restrict__ ids = ids_cur_all + (size_t)sys * (size_t)stride;
+    unsigned bad = 0;
+    for (unsigned long long k = done_all[sys] + blockIdx.x * B + threadIdx.x; k < end; k += (unsigned long long)gridDim.x * B) {
+        const Event e = ev[k];
+        const bool ok_i = (unsigned)e.i < (unsigned)n, ok_j = (unsigned)e.j < (unsigned)n;
+        lineage[k] = IdPair{ok_i ? ids[e.i] : -1, ok_j ? ids[e.j] : -1};
+        bad += (ok_i ? 0u : 1u) + (ok_j ? 0u : 1u);
+    }
+    if (bad) atomicAdd(&ctr_all[sys].errors, kIndexError * bad);
+}
+
+// grid = (nblk, S), B threads: workgroup x of system s covers bodies [x * B, (x + 1) * B) of that system.  blk_counts
+// holds the survivors of every workgroup of the same geometry (compact_count / batch_count, [s * nblk + x]); it is read
+// only for workgroups above the first, so a system that fits one workgroup counts by itself.  done_all == NULL: the
+// context keeps no event log.
+template <typename T, int B>
+__global__ __launch_bounds__(B) void ids_scatter(const Rec<T>* __restrict__ S_J_all, const Meta* __restrict__ meta_all,
+                                                 const int* __restrict__ blk_counts,
+                                                 const int32_t* __restrict__ ids_cur_all,
+                                                 int32_t* __restrict__ ids_next_all, int stride,
+                                                 const Counters* __restrict__ ctr_all,
+                                                 unsigned long long* __restrict__ done_all, int ev_cap) {
+    __shared__ int wsum[B / kWave];
+    __shared__ int red[B / kWave];
+    __shared__ int base_s;
+    const int sys = blockIdx.y;
+    const int nblk = gridDim.x;
+    const int cnt = ids_checked_count(meta_all[sys].n, stride);
+    const size_t base = (size_t)sys * (size_t)stride;
+    // offset of this workgroup = survivors of all lower workgroups of this system
+    int part = 0;
+    {
+        const int* __restrict__ mine = blk_counts + (size_t)sys * nblk;
+        for (int bidx = threadIdx.x; bidx < (int)blockIdx.x; bidx += B) part += mine[bidx];
+        for (int sh = kWave / 2; sh > 0; sh >>= 1) part += __shfl_down(part, sh, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = part;
+
+    const int q = blockIdx.x * B + threadIdx.x;
+    int32_t id = 0;
+    bool keep = false;
+    if (q < cnt) {
+        id = ids_cur_all[base + q];
+        keep = S_J_all[base + q].m != (T)0;                // the keep test of the compaction: a NaN mass stays
+    }
+    const unsigned long long bal = __ballot(keep);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wid = threadIdx.x / kWave;
+    if (lane == 0) wsum[wid] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int w = 0; w < B / kWave; ++w) s += red[w];
+        base_s = s;
+        if (blockIdx.x == 0 && done_all != nullptr) {      // everything logged so far is translated (ids_translate, before)
+            const unsigned long long logged = ctr_all[sys].events;
+            done_all[sys] = logged < (unsigned long long)ev_cap ? logged : (unsigned long long)ev_cap;
+        }
+    }
+    __syncthreads();
+    if (keep) {
+        int off = base_s;
+        for (int w = 0; w < wid; ++w) off += wsum[w];
+        off += __popcll(bal & ((1ull << lane) - 1ull));
+        ids_next_all[base + off] = id;                     // off < survivors <= cnt <= stride
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Host side shared by the two steppers: the device state of one context or batch, and the launches.
+// Both translation units name these templates in functions at the END of the file (declared further up): the compiler
+// emits kernels in the order the host code first names them, so the kernels of this file come after every kernel that
+// existed before and those keep their place, and their label numbers, in the assembly of `make asm`.
+// ---------------------------------------------------------------------------------------------------------
+struct IdsState {
+    int32_t* map[2] = {nullptr, nullptr};   // [systems * stride] each; map[cur][s * stride + i] = identity of system s's body i
+    int cur = 0;                            // swapped by the host after every step's ids_scatter
+    IdPair* lineage = nullptr;              // [systems * ev_cap], next to the event buffer (with NBODY_FLAG_RECORD_EVENTS)
+    unsigned long long* done = nullptr;     // [systems] events translated so far
+    bool on() const { return map[0] != nullptr; }
+};
+
+// Upload: identity = index, for every system; the caller empties `done` with the event counters.
+template <int B>
+void ids_enqueue_fill(IdsState& st, hipStream_t stream, int systems, int stride) {
+    st.cur = 0;
+    hipLaunchKernelGGL((ids_fill<B>), dim3((stride + B - 1) / B, systems), dim3(B), 0, stream, st.map[0], stride);
+}
+
+// One step: after the force kernel (and the per-workgroup count, where there is more than one workgroup per system) and
+// before the commit.  nblk workgroups of B threads per system, the geometry of the count that filled blk_counts.
+template <typename T, int B>
+void ids_enqueue_step(IdsState& st, hipStream_t stream, int nblk, int systems, int translate_grid, const Rec<T>* S_J,
+                      const Meta* meta, const int* blk_counts, int stride, Counters* ctr, const Event* ev, int ev_cap) {
+    if (st.lineage)
+        hipLaunchKernelGGL((ids_translate<kIdsBlock>), dim3(translate_grid, systems), dim3(kIdsBlock), 0, stream, ev, ev_cap,
+                           ctr, (const unsigned long long*)st.done, meta, (const int32_t*)st.map[st.cur], stride, st.lineage);
+    hipLaunchKernelGGL((ids_scatter<T, B>), dim3(nblk, systems), dim3(B), 0, stream, S_J, meta, blk_counts,
+                       (const int32_t*)st.map[st.cur], st.map[st.cur ^ 1], stride, (const Counters*)ctr,
+                       st.lineage ? st.done : nullptr, ev_cap);
+    st.cur ^= 1;
+}
+
+}  // namespace nbk
