@@ -223,6 +223,47 @@ typedef struct nbody_lineage {  /* an nbody_event in identity space             
  * record gets -1 and the context fails its next synchronising call like after any failed index check. */
 int nbody_get_lineage(nbody_ctx* ctx, nbody_lineage* out, int cap, int64_t* total);
 
+/* Track log (NBODY_FLAG_TRACK_IDS): where was body k at each sample, how heavy was it, when did it vanish.
+ * A device-side table of `samples` rows x `columns` identities.  nbody_track_record enqueues one row - one launch, two with
+ * NBODY_TRACK_PHI - with no device-to-host copy and no host wait; the table is read back once, instead of nbody_download +
+ * nbody_get_ids (two synchronising calls and a copy of the whole state) after every sample.
+ * Row contract.  Column c stands for identity sel[c].  If a current body i has that identity: index[c] = i, rec[c] =
+ * {x, y, vx, vy, m, r} of body i in the context's precision - the bits nbody_download followed by nbody_get_ids would give at
+ * that moment - and, with NBODY_TRACK_PHI, phi[c] = the bits nbody_get_diagnostics puts in phi[i] (the order contract above:
+ * one running sum over j ascending).  Otherwise index[c] = -1, every byte of rec[c] is 0 and phi[c] = +0.  Presence is read
+ * from index, never from a field: a NaN mass is a present body, and a body uploaded with mass 0 is present in a row recorded
+ * before the first step.  step and n_bodies of the row header come from the device-side state, like the recorded
+ * diagnostics' rows.  A count outside [0, capacity] never becomes an index: the row is all absent with n_bodies = 0 and the
+ * context fails its next synchronising call, like after any failed index check.
+ * nbody_track_reserve allocates (or re-allocates) the log and empties it; samples = 0 frees it; it may be called before the
+ * first upload.  ids == NULL: columns = capacity and column c is identity c; otherwise k columns, ids strictly increasing
+ * within [0, capacity) (an identity at or above the uploaded count is simply always absent).  NBODY_ERR_INVALID, found before
+ * any device call: k <= 0 with ids, an unsorted, repeated or out-of-range id, samples < 0, unknown `fields` bits, a log above
+ * 2^31 bytes in all.  NBODY_ERR_STATE: a context created without NBODY_FLAG_TRACK_IDS.
+ * nbody_track_record is enqueue-only on the context's stream, like nbody_step.  A full log is NBODY_ERR_CAPACITY, found on the
+ * host: nothing is enqueued and the earlier rows stay.  No reservation, or no upload yet: NBODY_ERR_STATE.  nbody_upload (and
+ * so nbody_state_load) restarts the log at row 0 and keeps the reservation.
+ * nbody_track_read synchronises, copies min(recorded, cap_samples) rows and stores the number recorded and the columns.  Any of
+ * rows, rec, index, phi may be NULL; rows[s], and rec / index / phi [s * columns + c]; rec is nbody_track_f32 or
+ * nbody_track_f64 by the context's precision.  A non-NULL phi on a log reserved without NBODY_TRACK_PHI: NBODY_ERR_STATE.
+ * A context that never reserves allocates nothing and launches nothing more, and the kernels it runs keep their code.
+ * Cost (one MI355X, fp32, stock radii, ms per sample over plain stepping, median of 3 rounds (spread), the one read at the end
+ * included; profiles/track_probe.txt), against nbody_download + nbody_get_ids after every step: N = 262144 with 64 columns
+ * 0.064 (0.089) against 0.974 (0.167); a batch of 256 x 1024 with all columns 2.32 (0.05) against 27.74 (0.15); N = 262144 with
+ * all columns 2.18 (0.38) against 2.21 (0.51), and 2.29 against 1.90 in an earlier run - there the log moves capacity columns
+ * per sample where a download moves the current count, and what it buys is a loop without host waits.  On the device a record
+ * is one launch of 6 to 9 us.  A potential row is a serial chain over j by contract, so NBODY_TRACK_PHI on k columns costs about
+ * one wave's walk over the n bodies, not k/n of nbody_get_diagnostics: 64 columns at n = 102089 4.11 ms (spread 0.05) against
+ * 6.89 ms for the full call. */
+enum { NBODY_TRACK_PHI = 1u << 0 };   /* nbody_track_reserve fields */
+typedef struct nbody_track_f32 { float  x, y, vx, vy, m, r; } nbody_track_f32;   /* 24 bytes */
+typedef struct nbody_track_f64 { double x, y, vx, vy, m, r; } nbody_track_f64;   /* 48 bytes */
+typedef struct nbody_track_row { int64_t step, n_bodies; } nbody_track_row;
+int nbody_track_reserve(nbody_ctx* ctx, int samples, const int32_t* ids, int k, uint32_t fields);
+int nbody_track_record(nbody_ctx* ctx);
+int nbody_track_read(nbody_ctx* ctx, nbody_track_row* rows, void* rec, int32_t* index, double* phi,
+                     int cap_samples, int* n_samples, int* columns);
+
 typedef struct nbody_stats {
     int64_t steps;            /* steps enqueued since upload                                           */
     int64_t pairs;            /* ordered (i,j) pairs evaluated by THIS rank since upload (device count) */
@@ -399,6 +440,16 @@ int nbody_batch_diagnostics(nbody_batch* b, nbody_diag* out, double* phi);
 int nbody_batch_diag_reserve(nbody_batch* b, int samples);
 int nbody_batch_diag_record(nbody_batch* b);
 int nbody_batch_diag_read(nbody_batch* b, nbody_diag* out, int cap_samples, int* n_samples);
+/* The track log of a batch (NBODY_FLAG_TRACK_IDS in nbody_batch_desc.flags): nbody_track_reserve / _record / _read for every
+ * system at once, with the one selection for all of them and `capacity` per system.  The same row contract per system - system
+ * s's table is what an nbody_ctx gives for the same upload, steps and records, phi having the bits of
+ * nbody_batch_diagnostics - and the same errors; one launch per record, two with NBODY_TRACK_PHI, whatever S is.  A sample is S
+ * rows: rows[s * S + sys], and rec / index / phi [(s * S + sys) * columns + c].  nbody_batch_upload restarts the log at row 0
+ * and keeps the reservation. */
+int nbody_batch_track_reserve(nbody_batch* b, int samples, const int32_t* ids, int k, uint32_t fields);
+int nbody_batch_track_record(nbody_batch* b);
+int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int32_t* index, double* phi,
+                           int cap_samples, int* n_samples, int* columns);
 
 /* ---------------------------------------------------------------------------------------------------
  * Reference-shaped launches on caller-owned DEVICE memory: one-to-one replacements of the two <<<>>> sites

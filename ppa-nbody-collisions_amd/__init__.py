@@ -23,6 +23,7 @@ FLAG_RECORD_EVENTS = 1
 FLAG_GROUP_EXCHANGE = 2
 FLAG_FORCE_COMM = 4
 FLAG_TRACK_IDS = 8
+TRACK_PHI = 1
 COMM_ID_BYTES = 128
 IMAGE_PATH_MAX = 1024
 
@@ -106,6 +107,11 @@ DIAG_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64), ("coincident_
                        ("momentum", np.float64, (2,)), ("center_of_mass", np.float64, (2,)),
                        ("angular_momentum", np.float64), ("kinetic", np.float64), ("potential", np.float64)])
 
+# struct nbody_track_row, nbody_track_f32 / nbody_track_f64: the planes of the track log (Stepper.tracks, StepperBatch.tracks)
+TRACK_ROW_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64)])
+TRACK_FIELDS = ("x", "y", "vx", "vy", "m", "r")
+TRACK_DTYPE = {F32: np.dtype([(f, np.float32) for f in TRACK_FIELDS]), F64: np.dtype([(f, np.float64) for f in TRACK_FIELDS])}
+
 # every symbol include/nbody.h declares: name -> (restype, argtypes)
 _vp, _ip, _i, _f, _d, _sz = (ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_float,
                              ctypes.c_double, ctypes.c_size_t)
@@ -141,6 +147,9 @@ SYMBOLS = {
     "nbody_clear_events": (_i, [_vp]),
     "nbody_get_ids": (_i, [_vp, _vp, _i, _ip]),
     "nbody_get_lineage": (_i, [_vp, _vp, _i, ctypes.POINTER(ctypes.c_int64)]),
+    "nbody_track_reserve": (_i, [_vp, _i, _vp, _i, ctypes.c_uint32]),
+    "nbody_track_record": (_i, [_vp]),
+    "nbody_track_read": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _ip, _ip]),
     "nbody_get_stats": (_i, [_vp, ctypes.POINTER(Stats)]),
     "nbody_set_kernel_timing": (_i, [_vp, _i]),
     "nbody_force_kernel_name": (ctypes.c_char_p, [_vp]),
@@ -175,6 +184,9 @@ SYMBOLS = {
     "nbody_batch_diag_reserve": (_i, [_vp, _i]),
     "nbody_batch_diag_record": (_i, [_vp]),
     "nbody_batch_diag_read": (_i, [_vp, _vp, _i, _ip]),
+    "nbody_batch_track_reserve": (_i, [_vp, _i, _vp, _i, ctypes.c_uint32]),
+    "nbody_batch_track_record": (_i, [_vp]),
+    "nbody_batch_track_read": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _ip, _ip]),
     "nbody_num_blocks": (_i, [_i]),
     "nbody_launch_compute_forces_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _i, _i, _f, _vp]),
     "nbody_launch_move_bodies_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _vp]),
@@ -370,6 +382,36 @@ def _diagnostics(call, capacity, potential):
     return out
 
 
+def _reserve_tracks(call, samples, ids, potential):
+    """-> (samples, has_phi): what tracks() needs to size its buffers."""
+    k = 0 if ids is None else len(ids)
+    sel = np.zeros(max(k, 1), dtype=np.int32)                   # an empty selection is still a pointer: refused by the library
+    sel[:k] = [] if ids is None else ids
+    _check(call(samples, None if ids is None else sel.ctypes.data, k, TRACK_PHI if potential else 0))
+    return samples, bool(potential)
+
+
+def _tracks(call, reserved, systems, precision):
+    """Reads the track log: a dict of numpy arrays, (samples, systems, columns) (rows: (samples, systems))."""
+    cap, has_phi = reserved
+    n, cols = ctypes.c_int(0), ctypes.c_int(0)
+    _check(call(None, None, None, None, 0, ctypes.byref(n), ctypes.byref(cols)))   # how much there is
+    take, k = min(n.value, cap), cols.value
+    rows = np.zeros((take, systems), dtype=TRACK_ROW_DTYPE)
+    rec = np.zeros((take, systems, k), dtype=TRACK_DTYPE[precision])
+    index = np.zeros((take, systems, k), dtype=np.int32)
+    phi = np.zeros((take, systems, k), dtype=np.float64) if has_phi else None
+    if take:
+        _check(call(rows.ctypes.data, rec.ctypes.data, index.ctypes.data, phi.ctypes.data if has_phi else None, take,
+                    ctypes.byref(n), ctypes.byref(cols)))
+    out = {"step": rows["step"].copy(), "n_bodies": rows["n_bodies"].copy(), "index": index}
+    for f in TRACK_FIELDS:
+        out[f] = np.ascontiguousarray(rec[f])
+    if has_phi:
+        out["phi"] = phi
+    return out
+
+
 class Stepper:
     """Device-resident stepper: the loop body of src/nbody.cu:460-545 without the per-step host round trip."""
 
@@ -396,6 +438,9 @@ class Stepper:
         self.precision = precision
         self.capacity = d.capacity
         self.world, self.rank = world, rank
+        self._tracks = (0, False)                               # (samples, potential) of the track log's reservation
+        self._tracks_all = False                                # reserved with ids=None: tracks() trims to the uploaded count
+        self._uploaded = 0
         self._ctx = ctypes.c_void_p()
         _check(lib.nbody_ctx_create(ctypes.byref(self._ctx), ctypes.byref(d)))
 
@@ -415,6 +460,7 @@ class Stepper:
 
     def load_state(self, path):
         _check(lib.nbody_state_load(self._ctx, os.fsencode(path)))
+        self._uploaded = self.body_count()                      # a load is an upload: identities restart
 
     __del__ = close
 
@@ -428,9 +474,46 @@ class Stepper:
         """BodiesData::uploadToDevice, src/nbody.cu:88-96."""
         assert bodies.precision == self.precision
         _check(lib.nbody_upload(self._ctx, bodies.ptr, bodies.numBodies))
+        self._uploaded = bodies.numBodies
 
-    def step(self, nsteps=1):
-        _check(lib.nbody_step(self._ctx, nsteps))
+    def step(self, nsteps=1, track_every=0):
+        """nsteps steps, enqueue only.  track_every = k > 0: a row of the track log after every k-th step of this call
+        (for i in 1..nsteps: step(1); if i % k == 0: record_tracks()), enqueue only as well."""
+        if track_every < 0:
+            raise ValueError("track_every %d" % track_every)
+        if not track_every:
+            _check(lib.nbody_step(self._ctx, nsteps))
+            return
+        done = 0
+        while done < nsteps:
+            chunk = min(track_every, nsteps - done)
+            _check(lib.nbody_step(self._ctx, chunk))
+            done += chunk
+            if done % track_every == 0:
+                _check(lib.nbody_track_record(self._ctx))
+
+    def reserve_tracks(self, samples, ids=None, potential=False):
+        """Room for `samples` rows of the track log on the device (0 frees it); empties the log.  ids: the identities to
+        follow, strictly increasing (None: every identity 0 .. capacity-1); potential: keep the per-body potential too.
+        Needs track_ids=True."""
+        self._tracks = _reserve_tracks(lambda *a: lib.nbody_track_reserve(self._ctx, *a), samples, ids, potential)
+        self._tracks_all = ids is None
+
+    def record_tracks(self):
+        """Enqueues one row of the track log: no copy, no host wait."""
+        _check(lib.nbody_track_record(self._ctx))
+
+    def tracks(self):
+        """The track log, a dict of numpy arrays of shape (recorded, columns): index (current index of the identity, -1:
+        absent), x, y, vx, vy, m, r (0 where absent), phi (if reserved with potential=True); step and n_bodies of shape
+        (recorded,).  Reserved with ids=None, the columns are trimmed to the uploaded count.  Synchronises."""
+        out = _tracks(lambda *a: lib.nbody_track_read(self._ctx, *a), self._tracks, 1, self.precision)
+        out = {k: v[:, 0] for k, v in out.items()}
+        if self._tracks_all:
+            for k in out:
+                if out[k].ndim == 2:
+                    out[k] = np.ascontiguousarray(out[k][:, :self._uploaded])
+        return out
 
     def sync(self):
         _check(lib.nbody_sync(self._ctx))
@@ -569,6 +652,7 @@ class StepperBatch:
         d.kernel_variant = kernel_variant
         self.systems, self.capacity, self.precision = systems, capacity, precision
         self._log_cap = 0                                       # samples reserved for the recorded series
+        self._tracks = (0, False)                               # (samples, potential) of the track log's reservation
         self._b = ctypes.c_void_p()
         _check(lib.nbody_batch_create(ctypes.byref(self._b), ctypes.byref(d), arr))
 
@@ -594,21 +678,39 @@ class StepperBatch:
         counts = (ctypes.c_int * self.systems)(*[b.numBodies for b in bodies])
         _check(lib.nbody_batch_upload(self._b, ptrs, counts))
 
-    def step(self, nsteps=1, record_every=0):
+    def step(self, nsteps=1, record_every=0, track_every=0):
         """nsteps ensemble steps, enqueue only.  record_every = k > 0: a sample of the recorded series after every k-th
-        step of this call (for i in 1..nsteps: step(1); if i % k == 0: record_diagnostics()), enqueue only as well."""
+        step of this call (for i in 1..nsteps: step(1); if i % k == 0: record_diagnostics()), enqueue only as well.
+        track_every = k > 0: the same for rows of the track log (record_tracks()); both may be given."""
         if record_every < 0:
             raise ValueError("record_every %d" % record_every)
-        if not record_every:
+        if track_every < 0:
+            raise ValueError("track_every %d" % track_every)
+        if not record_every and not track_every:
             _check(lib.nbody_batch_step(self._b, nsteps))
             return
         done = 0
         while done < nsteps:
-            chunk = min(record_every, nsteps - done)
+            chunk = min(nsteps - done, *[k - done % k for k in (record_every, track_every) if k])
             _check(lib.nbody_batch_step(self._b, chunk))
             done += chunk
-            if done % record_every == 0:
+            if record_every and done % record_every == 0:
                 _check(lib.nbody_batch_diag_record(self._b))
+            if track_every and done % track_every == 0:
+                _check(lib.nbody_batch_track_record(self._b))
+
+    def reserve_tracks(self, samples, ids=None, potential=False):
+        """As Stepper.reserve_tracks, with the one selection for every system (None: identities 0 .. capacity-1)."""
+        self._tracks = _reserve_tracks(lambda *a: lib.nbody_batch_track_reserve(self._b, *a), samples, ids, potential)
+
+    def record_tracks(self):
+        """Enqueues one row of the track log for every system: no copy, no host wait."""
+        _check(lib.nbody_batch_track_record(self._b))
+
+    def tracks(self):
+        """As Stepper.tracks, with the system axis after the sample axis: (recorded, systems, columns), and step and
+        n_bodies of shape (recorded, systems).  Synchronises."""
+        return _tracks(lambda *a: lib.nbody_batch_track_read(self._b, *a), self._tracks, self.systems, self.precision)
 
     def sync(self):
         _check(lib.nbody_batch_sync(self._b))

@@ -20,6 +20,7 @@
 #include "nbody_batch_kernels.hpp"
 #include "nbody_batch_diag.hpp"
 #include "nbody_ids.hpp"
+#include "nbody_tracks.hpp"
 
 using namespace nbk;
 
@@ -68,6 +69,8 @@ struct nbody_batch {
     int log_rows = 0;                   // samples recorded since the reservation or the last upload: the next row
     // identities (NBODY_FLAG_TRACK_IDS, nbody_ids.hpp): nothing is allocated without the flag
     IdsState ids;                       // the map [S * cap] twice, the lineage [S * ev_cap], [S] translated-up-to counters
+    // track log (nbody_batch_track_*, nbody_tracks.hpp): nothing is allocated without a reservation
+    TrackState trk;
 };
 
 namespace {
@@ -85,6 +88,7 @@ void free_all(nbody_batch* b) {
     (void)hipFree(b->meta); (void)hipFree(b->counters); (void)hipFree(b->params); (void)hipFree(b->events);
     (void)hipFree(b->blk_counts);
     (void)hipFree(b->ids.map[0]); (void)hipFree(b->ids.map[1]); (void)hipFree(b->ids.lineage); (void)hipFree(b->ids.done);
+    (void)hipFree(b->trk.buf); (void)hipFree(b->trk.sel);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -406,6 +410,7 @@ int nbody_batch_upload(nbody_batch* b, const void* const* blocks, const int* cou
     b->uploaded = true;
     b->steps = 0;
     b->log_rows = 0;                                       // the recorded series restarts, the reservation stays
+    b->trk.recorded = 0;                                   // and so does the track log
     return NBODY_OK;
 }
 
@@ -674,3 +679,36 @@ int ids_restart(nbody_batch* b) {
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------------------
+// Track log (nbody_batch_track_*; kernels and the shared host code in nbody_tracks.hpp): one selection for every system,
+// system = blockIdx.y.  At the end of the file for the reason the identities are.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int nbody_batch_track_reserve(nbody_batch* b, int samples, const int32_t* ids, int k, uint32_t fields) {
+    if (!b) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_track_reserve: NULL batch");
+    return track_reserve(b->trk, b->stream, b->desc.device, "nbody_batch_track_reserve", b->ids.on(), b->S, b->cap,
+                         sizeof(TrackRec<float>), samples, ids, k, fields);
+}
+
+int nbody_batch_track_record(nbody_batch* b) {
+    if (!b) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_track_record: NULL batch");
+    if (!b->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_track_record: the batch was created without NBODY_FLAG_TRACK_IDS");
+    return track_record<float>(b->trk, b->stream, b->desc.device, "nbody_batch_track_record", b->uploaded,
+                               (const Rec<float>*)b->J, (const Vec2<float>*)b->V, (const Meta*)b->meta, b->counters,
+                               (const int32_t*)b->ids.map[b->ids.cur], b->cap);
+}
+
+int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int32_t* index, double* phi, int cap_samples,
+                           int* n_samples, int* columns) {
+    if (!b) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_track_read: NULL batch");
+    if (cap_samples < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_track_read: cap_samples %d", cap_samples);
+    if (!b->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_track_read: the batch was created without NBODY_FLAG_TRACK_IDS");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    int rc = read_meta(b);                                 // synchronises: every enqueued record has been written
+    if (rc != NBODY_OK) return rc;
+    return track_read(b->trk, "nbody_batch_track_read", rows, rec, index, phi, cap_samples, n_samples, columns);
+}
+
+}  // extern "C"

@@ -23,6 +23,7 @@
 #include "nbody_kernels.hpp"
 #include "nbody_diag.hpp"
 #include "nbody_ids.hpp"
+#include "nbody_tracks.hpp"
 
 using namespace nbk;
 
@@ -167,6 +168,8 @@ struct nbody_ctx {
     unsigned char* dg_gather = nullptr;    // world * (tiles | phi) of the padded per-rank areas
     // identities (NBODY_FLAG_TRACK_IDS, nbody_ids.hpp): nothing is allocated without the flag
     IdsState ids;                          // the map [cap_own] twice, the lineage [ev_cap], the translated-up-to counter
+    // track log (nbody_track_*, nbody_tracks.hpp): nothing is allocated without a reservation
+    TrackState trk;
 };
 
 namespace {
@@ -536,6 +539,7 @@ void free_all(nbody_ctx* c) {
     hipFree(c->blk_counts); hipFree(c->tile_rmax); hipFree(c->Jt); hipFree(c->meta); hipFree(c->meta_all); hipFree(c->events); hipFree(c->d_img);
     hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
     hipFree(c->ids.map[0]); hipFree(c->ids.map[1]); hipFree(c->ids.lineage); hipFree(c->ids.done);
+    hipFree(c->trk.buf); hipFree(c->trk.sel);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -869,6 +873,7 @@ int nbody_upload(nbody_ctx* c, const void* block, int n) {
     c->device_failed = false;
     c->uploaded = true;
     c->steps = 0;
+    c->trk.recorded = 0;                                   // the track log restarts, the reservation stays
     int rt = resolve_timing(c);
     if (rt != NBODY_OK) return rt;
     c->force_ms = 0; c->force_launches = 0; c->xchg_ms = 0; c->xchg_launches = 0;
@@ -1553,3 +1558,45 @@ int ids_restart(nbody_ctx* c) {
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------------------
+// Track log (nbody_track_*; kernels and the shared host code in nbody_tracks.hpp).  Here, at the end, for the reason the
+// identities are: the kernels above keep their place and their code.  NBODY_FLAG_TRACK_IDS means world == 1, so the own
+// range is everything: Vown is indexed like J, and the map like both.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int nbody_track_reserve(nbody_ctx* c, int samples, const int32_t* ids, int k, uint32_t fields) {
+    if (!c) return nbody_fail(NBODY_ERR_INVALID, "nbody_track_reserve: NULL context");
+    return track_reserve(c->trk, c->stream, c->desc.device, "nbody_track_reserve", c->ids.on(), 1, c->cap,
+                         c->desc.precision == NBODY_F64 ? sizeof(TrackRec<double>) : sizeof(TrackRec<float>), samples, ids, k,
+                         fields);
+}
+
+int nbody_track_record(nbody_ctx* c) {
+    if (!c) return nbody_fail(NBODY_ERR_INVALID, "nbody_track_record: NULL context");
+    if (!c->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_track_record: the context was created without NBODY_FLAG_TRACK_IDS");
+    const int32_t* map = c->ids.map[c->ids.cur];
+    if (c->desc.precision == NBODY_F64)
+        return track_record<double>(c->trk, c->stream, c->desc.device, "nbody_track_record", c->uploaded,
+                                    (const Rec<double>*)c->J, (const Vec2<double>*)c->Vown, (const Meta*)c->meta, c->counters, map, c->cap);
+    return track_record<float>(c->trk, c->stream, c->desc.device, "nbody_track_record", c->uploaded,
+                               (const Rec<float>*)c->J, (const Vec2<float>*)c->Vown, (const Meta*)c->meta, c->counters, map, c->cap);
+}
+
+int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* index, double* phi, int cap_samples,
+                     int* n_samples, int* columns) {
+    if (!c) return nbody_fail(NBODY_ERR_INVALID, "nbody_track_read: NULL context");
+    if (cap_samples < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_track_read: cap_samples %d", cap_samples);
+    if (!c->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_track_read: the context was created without NBODY_FLAG_TRACK_IDS");
+    HIP_TRY(hipSetDevice(c->desc.device));
+    if (c->uploaded) {                                     // synchronises: every enqueued record has been written
+        int rc = read_meta(c);
+        if (rc != NBODY_OK) return rc;
+    } else {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return track_read(c->trk, "nbody_track_read", rows, rec, index, phi, cap_samples, n_samples, columns);
+}
+
+}  // extern "C"
