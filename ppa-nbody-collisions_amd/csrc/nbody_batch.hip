@@ -181,15 +181,6 @@ int check_system(const nbody_batch* b, int system, const char* who) {
 // ---------------------------------------------------------------------------------------------------------
 // Diagnostics (kernels in nbody_batch_diag.hpp)
 // ---------------------------------------------------------------------------------------------------------
-static_assert(sizeof(nbody_diag) == sizeof(DiagOut), "nbody_diag and its device mirror");
-static_assert(offsetof(nbody_diag, step) == offsetof(DiagOut, step) && offsetof(nbody_diag, n_bodies) == offsetof(DiagOut, n_bodies) &&
-              offsetof(nbody_diag, coincident_pairs) == offsetof(DiagOut, coincident_pairs) &&
-              offsetof(nbody_diag, mass) == offsetof(DiagOut, mass) && offsetof(nbody_diag, momentum) == offsetof(DiagOut, momentum) &&
-              offsetof(nbody_diag, center_of_mass) == offsetof(DiagOut, center_of_mass) &&
-              offsetof(nbody_diag, angular_momentum) == offsetof(DiagOut, angular_momentum) &&
-              offsetof(nbody_diag, kinetic) == offsetof(DiagOut, kinetic) &&
-              offsetof(nbody_diag, potential) == offsetof(DiagOut, potential), "nbody_diag and its device mirror");
-
 int diag_fail_alloc(hipError_t e, const char* what) {
     (void)hipGetLastError();
     return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "batch diagnostics, %s: %s", what,
@@ -208,7 +199,7 @@ int diag_alloc_tiles(nbody_batch* b) {
 
 // The two launches of one sample of every system: rows of `out` are S records; phi may be NULL.
 int enqueue_diagnostics(nbody_batch* b, DiagOut* out, double* phi) {
-    const double G = (double)6.67408e-11f;               // src/nbody.cu:37, the float literal widened (as in nbody_ctx.hip)
+    const double G = (double)kG;
     if (b->n_upper > 0) {
         const dim3 grid((b->n_upper + kDiagBlock - 1) / kDiagBlock, b->S);
         if (phi)
@@ -330,22 +321,11 @@ int nbody_batch_create(nbody_batch** out, const nbody_batch_desc* d, const nbody
         free_all(b);
         return nbody_fail(NBODY_ERR_NOMEM, "nbody_batch_create: out of host memory (%zu bytes of staging)", wanted);
     }
-    {   // the kernel arguments of src/nbody.cu:482, once per system; G, the walls and the semantics as make_params has them
+    {   // once per system; the hand-off limit is the ring kernel's and a batch has none
         StepParams<float>* hp = reinterpret_cast<StepParams<float>*>(b->h_stage);
-        for (int s = 0; s < b->S; ++s) {
-            StepParams<float> p;
-            p.dt = (float)params[s].timestep;
-            p.growth = (float)params[s].growthRate;
-            p.G = 6.67408e-11f;
-            p.wall_hi_x = (float)params[s].fieldWidth;
-            p.wall_lo_x = (float)(-params[s].fieldWidth);
-            p.wall_hi_y = (float)params[s].fieldHeight;
-            p.wall_lo_y = (float)(-params[s].fieldHeight);
-            p.literal = d->semantics == NBODY_LITERAL;
-            p.spin_limit = 0;
-            p.rotate_priority = 0;
-            hp[s] = p;
-        }
+        for (int s = 0; s < b->S; ++s)
+            hp[s] = make_params<float>(params[s].timestep, params[s].growthRate, params[s].fieldWidth, params[s].fieldHeight,
+                                       d->semantics, 0);
         BATCH_TRY(hipMemcpyAsync(b->params, hp, sizeof(StepParams<float>) * (size_t)b->S, hipMemcpyHostToDevice, b->stream));
     }
     BATCH_TRY(hipMemsetAsync(b->meta, 0, sizeof(Meta) * (size_t)b->S, b->stream));
@@ -483,10 +463,7 @@ int nbody_batch_get_events(nbody_batch* b, int system, nbody_event* out, int cap
     if (rc != NBODY_OK) return rc;
     const unsigned long long tot = b->h_counters[system].events;
     *total = (int64_t)tot;
-    unsigned long long ncopy = tot;
-    if (ncopy > (unsigned long long)b->ev_cap) ncopy = b->ev_cap;
-    if (ncopy > (unsigned long long)cap) ncopy = cap;
-    static_assert(sizeof(nbody_event) == sizeof(Event), "event layouts must match");
+    const unsigned long long ncopy = log_prefix(tot, b->ev_cap, cap);
     if (ncopy) HIP_TRY(hipMemcpy(out, b->events + (size_t)system * (size_t)b->ev_cap, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
     return NBODY_OK;
 }
@@ -520,23 +497,11 @@ int nbody_batch_get_lineage(nbody_batch* b, int system, nbody_lineage* out, int 
     HIP_TRY(hipSetDevice(b->desc.device));
     rc = read_meta(b);                                     // synchronises; a failed index check of a translation ends here
     if (rc != NBODY_OK) return rc;
-    unsigned long long done = 0;
-    HIP_TRY(hipMemcpy(&done, b->ids.done + system, sizeof(done), hipMemcpyDeviceToHost));
     const unsigned long long tot = b->h_counters[system].events;
     *total = (int64_t)tot;
-    unsigned long long ncopy = tot;
-    if (ncopy > (unsigned long long)b->ev_cap) ncopy = b->ev_cap;
-    if (ncopy > (unsigned long long)cap) ncopy = cap;
-    if (!ncopy) return NBODY_OK;
-    std::vector<Event> ev((size_t)ncopy);
-    std::vector<IdPair> who((size_t)ncopy);
+    const unsigned long long ncopy = log_prefix(tot, b->ev_cap, cap);
     const size_t first = (size_t)system * (size_t)b->ev_cap;
-    HIP_TRY(hipMemcpy(ev.data(), b->events + first, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(who.data(), b->ids.lineage + first, ncopy * sizeof(IdPair), hipMemcpyDeviceToHost));
-    for (unsigned long long k = 0; k < ncopy; ++k) {
-        const bool have = k < done;
-        out[k] = nbody_lineage{ev[k].step, have ? who[k].id_i : -1, have ? who[k].id_j : -1, ev[k].kind};
-    }
+    if (ncopy) HIP_TRY(lineage_read(b->events + first, b->ids.lineage + first, b->ids.done + system, ncopy, out));
     return NBODY_OK;
 }
 

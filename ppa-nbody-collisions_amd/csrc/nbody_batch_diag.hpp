@@ -3,17 +3,18 @@
 // bit for bit, for every system of the batch in two launches, whatever S is.  Included by nbody_batch.hip after
 // nbody_batch_kernels.hpp.
 //
-// The order contract is the one of nbody_diag.hpp, and diag_rinv, diag_row_general and DiagTile are taken
-// from there, not restated: phi_i is one running fma chain over j = 0, 1, ..., n-1; the totals are summed per aligned
-// 128-body tile with rows ascending, then over the tiles ascending; then mx / mass, 0.5 * K2, 0.5 * pot.  A system is a
-// rank that owns everything (lo = 0, cnt = n).
+// The order contract is the one of nbody_diag.hpp, and its code is called, not restated: phi_i is
+// diag_walk's running fma chain over j = 0, 1, ..., n-1 (diag_row_general for a flagged row); the totals are summed per
+// aligned 128-body tile with rows ascending, then over the tiles ascending by diag_add, and finished by diag_finish (mx /
+// mass, 0.5 * K2, 0.5 * pot), the two functions nbody_get_diagnostics runs on the host.  A system is a rank that owns
+// everything (lo = 0, cnt = n).
 //
 // The system index is blockIdx.y.  Grids are sized from the largest uploaded count; each kernel takes the exact count
 // from the system's Meta through batch_checked_count, workgroups past it leave at once (as whole workgroups, before the
 // first barrier), a count outside [0, stride] is treated as 0 and batch_diag_reduce adds kIndexError to the system's
 // Counters::errors.
 //
-// batch_diag_potential: diag_potential's walk on the system's slice of J.  What differs: the phi store is optional (kPhi:
+// batch_diag_potential: diag_potential on the system's slice of J.  What differs: the phi store is optional (kPhi:
 // a record and a call without `phi` keep no per-body values), and the per-tile epilogue also sums the moments of
 // diag_moments - every lane forms the seven products of its own row (the very expressions of diag_moments, velocities
 // from the batch's V) and leaves them in LDS, and nine lanes per row tile each add one quantity over the tile's rows in
@@ -32,17 +33,6 @@
 
 namespace nbk {
 
-// Device mirror of struct nbody_diag (include/nbody.h); nbody_batch.hip checks the two against each other.
-struct DiagOut {
-    long long step, n_bodies, coincident_pairs;
-    double mass, momentum[2], center_of_mass[2], angular_momentum, kinetic, potential;
-};
-static_assert(sizeof(DiagOut) == 88, "nbody_diag layout");
-static_assert(offsetof(DiagOut, step) == 0 && offsetof(DiagOut, n_bodies) == 8 && offsetof(DiagOut, coincident_pairs) == 16 &&
-              offsetof(DiagOut, mass) == 24 && offsetof(DiagOut, momentum) == 32 && offsetof(DiagOut, center_of_mass) == 48 &&
-              offsetof(DiagOut, angular_momentum) == 64 && offsetof(DiagOut, kinetic) == 72 &&
-              offsetof(DiagOut, potential) == 80, "nbody_diag layout");
-
 constexpr int kDiagSums = 8;                  // the doubles of a DiagTile, in its order: mass px py mx my L K2 pot
 static_assert(offsetof(DiagTile, pot) == 7 * sizeof(double) && offsetof(DiagTile, coincident) == 8 * sizeof(double),
               "the epilogue stores a DiagTile's sums by index");
@@ -55,7 +45,6 @@ __global__ __launch_bounds__(kDiagBlock) void batch_diag_potential(const Rec<flo
                                                                    const Meta* __restrict__ meta_all, int stride, double G,
                                                                    double* __restrict__ phi_all,
                                                                    DiagTile* __restrict__ tiles_all) {
-    __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
     __shared__ double wsum[kDiagSums][kDiagBlock];
     __shared__ long long wcoin[kDiagBlock];
     const int sys = blockIdx.y;
@@ -76,43 +65,7 @@ __global__ __launch_bounds__(kDiagBlock) void batch_diag_potential(const Rec<flo
         vx = (double)v.x; vy = (double)v.y;
     }
     // tile of this wave's rows: the one j tile that holds their self terms
-    const int self_tile = (row0 + (tid & ~(kWave - 1))) / kTile;
-    const int jtiles = (n + kTile - 1) / kTile;
-    double acc = 0.0;
-    for (int t = 0; t < jtiles; ++t) {
-        const int b = t & 1;
-        const int j0 = t * kTile;
-        const int jn = n - j0 < kTile ? n - j0 : kTile;
-        if (tid < jn) {
-            const Rec<float> r = J[j0 + tid];
-            sx[b][tid] = (double)r.x; sy[b][tid] = (double)r.y; sm[b][tid] = (double)r.m;
-        }
-        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
-        __syncthreads();
-        if (t != self_tile) {
-            int q = 0;
-            for (; q + 4 <= jn; q += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double dx = sx[b][q + u] - xi, dy = sy[b][q + u] - yi;
-                    const double d2 = __builtin_fma(dx, dx, dy * dy);
-                    acc = __builtin_fma(sm[b][q + u], diag_rinv(d2), acc);
-                }
-            }
-            for (; q < jn; ++q) {
-                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
-                const double d2 = __builtin_fma(dx, dx, dy * dy);
-                acc = __builtin_fma(sm[b][q], diag_rinv(d2), acc);
-            }
-        } else {
-            for (int q = 0; q < jn; ++q) {
-                const bool self = j0 + q == i;
-                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
-                const double d2 = self ? 1.0 : __builtin_fma(dx, dx, dy * dy);
-                acc = __builtin_fma(self ? 0.0 : sm[b][q], diag_rinv(d2), acc);
-            }
-        }
-    }
+    double acc = diag_walk<false>(J, n, i, xi, yi, (row0 + (tid & ~(kWave - 1))) / kTile);
     long long coin = 0;
     if (valid && !__builtin_isfinite(acc)) {
         const DiagRow g = diag_row_general<float>(J, n, i, xi, yi);
@@ -150,8 +103,8 @@ __global__ __launch_bounds__(kDiagBlock) void batch_diag_potential(const Rec<flo
     }
 }
 
-// One lane per system: tiles ascending, then the final divisions and halves of diag_collect (nbody_ctx.hip).  B lanes per
-// workgroup (a template so that it is emitted after the stepping kernels, whose code then stays byte for byte the same).
+// One lane per system: diag_add over the system's tiles ascending, then diag_finish.  B lanes per workgroup (a template
+// so that it is emitted after the stepping kernels, whose code then stays byte for byte the same).
 template <int B>
 __global__ __launch_bounds__(B) void batch_diag_reduce(const DiagTile* __restrict__ tiles_all,
                                                        const Meta* __restrict__ meta_all, Counters* __restrict__ ctr_all,
@@ -164,26 +117,9 @@ __global__ __launch_bounds__(B) void batch_diag_reduce(const DiagTile* __restric
     if (chk < 0) atomicAdd(&ctr_all[sys].errors, kIndexError);
     const DiagTile* __restrict__ tiles = tiles_all + (size_t)sys * batch_diag_tiles(stride);
     const int nt = (n + kTile - 1) / kTile;
-    double mass = 0, px = 0, py = 0, mx = 0, my = 0, L = 0, K2 = 0, pot = 0;
-    long long coincident = 0;
-    for (int t = 0; t < nt; ++t) {
-        const DiagTile d = tiles[t];
-        mass = mass + d.mass; px = px + d.px; py = py + d.py; mx = mx + d.mx; my = my + d.my;
-        L = L + d.L; K2 = K2 + d.K2; pot = pot + d.pot; coincident += d.coincident;
-    }
-    DiagOut o;
-    o.step = m.step;
-    o.n_bodies = n;
-    o.coincident_pairs = coincident;
-    o.mass = mass;
-    o.momentum[0] = px;
-    o.momentum[1] = py;
-    o.center_of_mass[0] = mass == 0.0 ? __builtin_nan("") : mx / mass;
-    o.center_of_mass[1] = mass == 0.0 ? __builtin_nan("") : my / mass;
-    o.angular_momentum = L;
-    o.kinetic = 0.5 * K2;
-    o.potential = 0.5 * pot;
-    out[sys] = o;
+    DiagTile total{};
+    for (int t = 0; t < nt; ++t) diag_add(total, tiles[t]);
+    out[sys] = diag_finish(total, m.step, n);
 }
 
 }  // namespace nbk

@@ -82,7 +82,9 @@ constexpr int kBatchMaxSystems = 65535;                    // gridDim.y
 
 // ---------------------------------------------------------------------------------------------------------
 // Commit: stable compaction of every system on `mass != 0` (src/nbody.cu:488-510) from the staging buffers into the
-// state, and the system's new Meta.  grid = (nblk, S), B threads; nblk covers the largest uploaded count.
+// state, and the system's new Meta.  The keep test, the per-workgroup count and the offsets are those of the one-system
+// compaction (compact_keep, compact_block_count, compact_offset, nbody_kernels.hpp).  grid = (nblk, S), B threads; nblk
+// covers the largest uploaded count.
 //   nblk == 1 : batch_commit alone counts, scatters and writes Meta (one workgroup sees the whole system).
 //   nblk  > 1 : batch_count leaves the survivors per block and saves the old count in Meta::n_prev; batch_commit adds up
 //               the blocks below its own, scatters, and its LAST block writes Meta.  No block of batch_commit reads
@@ -96,20 +98,14 @@ __device__ __forceinline__ int batch_checked_count(int n, int stride) { return (
 template <int B>
 __global__ __launch_bounds__(B) void batch_count(const Rec<float>* __restrict__ S_J_all, Meta* __restrict__ meta_all,
                                                  int* __restrict__ blk_counts, int stride) {
-    __shared__ int wsum[B / kWave];
     const int sys = blockIdx.y;
     const int n_old = meta_all[sys].n;
     const int chk = batch_checked_count(n_old, stride);
     const int cnt = chk < 0 ? 0 : chk;
     const Rec<float>* __restrict__ S_J = S_J_all + (size_t)sys * (size_t)stride;
     const int q = blockIdx.x * B + threadIdx.x;
-    const bool keep = q < cnt && S_J[q].m != 0.0f;
-    const unsigned long long bal = __ballot(keep);
-    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = __popcll(bal);
-    __syncthreads();
+    const int s = compact_block_count<B>(q < cnt && compact_keep(S_J[q].m));
     if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < B / kWave; ++w) s += wsum[w];
         blk_counts[(size_t)sys * gridDim.x + blockIdx.x] = s;
         if (blockIdx.x == 0) meta_all[sys].n_prev = n_old;   // nothing in this kernel reads n_prev
     }
@@ -121,9 +117,6 @@ __global__ __launch_bounds__(B) void batch_commit(const Rec<float>* __restrict__
                                                   Rec<float>* __restrict__ J_all, Vec2<float>* __restrict__ V_all,
                                                   Meta* __restrict__ meta_all, const int* __restrict__ blk_counts,
                                                   Counters* __restrict__ ctr_all, int stride) {
-    __shared__ int wsum[B / kWave];
-    __shared__ int red[B / kWave];
-    __shared__ int base_s;
     const int sys = blockIdx.y;
     const int nblk = gridDim.x;
     const bool single = nblk == 1;
@@ -131,15 +124,6 @@ __global__ __launch_bounds__(B) void batch_commit(const Rec<float>* __restrict__
     const int chk = batch_checked_count(n_old, stride);
     const int cnt = chk < 0 ? 0 : chk;
     const size_t base = (size_t)sys * (size_t)stride;
-    // offset of this block = sum of the counts of all lower blocks of this system
-    int part = 0;
-    if (!single) {
-        const int* __restrict__ mine = blk_counts + (size_t)sys * nblk;
-        for (int bidx = threadIdx.x; bidx < (int)blockIdx.x; bidx += B) part += mine[bidx];
-        for (int sh = kWave / 2; sh > 0; sh >>= 1) part += __shfl_down(part, sh, kWave);
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = part;
-
     const int q = blockIdx.x * B + threadIdx.x;
     Rec<float> rec{};
     Vec2<float> vel{};
@@ -147,37 +131,26 @@ __global__ __launch_bounds__(B) void batch_commit(const Rec<float>* __restrict__
     if (q < cnt) {
         rec = S_J_all[base + q];
         vel = S_V_all[base + q];
-        keep = rec.m != 0.0f;
+        keep = compact_keep(rec.m);
     }
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wid = threadIdx.x / kWave;
-    if (lane == 0) wsum[wid] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < B / kWave; ++w) s += red[w];
-        base_s = s;
-        if ((int)blockIdx.x == nblk - 1) {                 // every lower block's count is in s: the system's new Meta
-            int tot = s;
-            for (int w = 0; w < B / kWave; ++w) tot += wsum[w];
-            Meta* m = meta_all + sys;
-            if (single) m->n_prev = n_old;                 // nblk > 1: batch_count did, and other blocks are reading it
-            m->n = tot;
-            m->lo = 0;
-            m->cnt = tot;
-            m->step = m->step + 1;
-            m->summary = 0;
-            if (chk < 0) atomicAdd(&ctr_all[sys].errors, kIndexError);
-        }
+    // a single workgroup has none below it and reads no count
+    const CompactOffset o = compact_offset<B>(keep, blk_counts + (size_t)sys * nblk);
+    // The last block knows the total: the system's new Meta.  single: every thread of this (only) block has read Meta::n
+    // by now (compact_offset's barriers).  nblk > 1: the other blocks read n_prev alone, which is not written here.
+    if (threadIdx.x == 0 && (int)blockIdx.x == nblk - 1) {
+        const int tot = o.below + o.here;
+        Meta* m = meta_all + sys;
+        if (single) m->n_prev = n_old;                     // nblk > 1: batch_count did, and other blocks are reading it
+        m->n = tot;
+        m->lo = 0;
+        m->cnt = tot;
+        m->step = m->step + 1;
+        m->summary = 0;
+        if (chk < 0) atomicAdd(&ctr_all[sys].errors, kIndexError);
     }
-    __syncthreads();
     if (keep) {
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wsum[w];
-        off += __popcll(bal & ((1ull << lane) - 1ull));
-        J_all[base + off] = rec;
-        V_all[base + off] = vel;
+        J_all[base + o.off] = rec;
+        V_all[base + o.off] = vel;
     }
 }
 

@@ -187,18 +187,7 @@ inline bool not_plus_zero_host(double x) { uint64_t u; memcpy(&u, &x, 8); return
 
 template <typename T>
 StepParams<T> make_params(const nbody_ctx_desc& d, int spin_limit = 1 << 24) {
-    StepParams<T> p;
-    p.dt = (T)d.timestep;            // cfg values are floats; double holds them exactly
-    p.growth = (T)d.growthRate;
-    p.G = (T)6.67408e-11f;           // src/nbody.cu:37, float literal (widened for fp64: SURVEY.md H6)
-    p.wall_hi_x = (T)d.fieldWidth;
-    p.wall_lo_x = (T)(-d.fieldWidth);
-    p.wall_hi_y = (T)d.fieldHeight;
-    p.wall_lo_y = (T)(-d.fieldHeight);
-    p.literal = d.semantics == NBODY_LITERAL;
-    p.spin_limit = spin_limit;
-    p.rotate_priority = 0;
-    return p;
+    return nbk::make_params<T>(d.timestep, d.growthRate, d.fieldWidth, d.fieldHeight, d.semantics, spin_limit);
 }
 
 // Timing events come from a pool that nbody_set_kernel_timing fills: nothing is created inside a timed region.  A pool
@@ -578,12 +567,11 @@ int diag_launch_t(nbody_ctx* c) {
     if (cnt <= 0) return NBODY_OK;
     if (cnt > c->cap_own || lo < 0 || (long long)lo + cnt > n || n > c->cap)
         return nbody_fail(NBODY_ERR_STATE, "own range [%d, +%d) of %d bodies does not fit the context", lo, cnt, n);
-    const double G = (double)6.67408e-11f;               // src/nbody.cu:37, the float literal widened (make_params)
     const int tiles = (cnt + kTile - 1) / kTile;
     hipLaunchKernelGGL((diag_moments<T>), dim3((tiles + kWave - 1) / kWave), dim3(kWave), 0, c->stream,
                        (const Rec<T>*)c->J, (const Vec2<T>*)c->Vown, lo, cnt, c->dg_tiles);
     hipLaunchKernelGGL((diag_potential<T>), dim3((cnt + kDiagBlock - 1) / kDiagBlock), dim3(kDiagBlock), 0, c->stream,
-                       (const Rec<T>*)c->J, n, lo, cnt, G, c->dg_phi, c->dg_tiles);
+                       (const Rec<T>*)c->J, n, lo, cnt, (double)kG, c->dg_phi, c->dg_tiles);
     HIP_TRY(hipGetLastError());
     return NBODY_OK;
 }
@@ -637,25 +625,13 @@ int diag_collect(nbody_ctx* c, nbody_diag* out, double* phi) {
         }
         if (phi) memcpy(phi + m.lo, &h_phi[(size_t)g * U], (size_t)m.cnt * sizeof(double));
     }
-    double mass = 0, px = 0, py = 0, mx = 0, my = 0, L = 0, K2 = 0, pot = 0;
-    long long coincident = 0;
+    DiagTile total{};
     for (int t = 0; t < nt; ++t) {
-        const DiagTile* d = by_tile[t];
-        if (!d) return nbody_fail(NBODY_ERR_STATE, "tile %d of %d bodies is reported by no rank", t, n);
-        mass = mass + d->mass; px = px + d->px; py = py + d->py; mx = mx + d->mx; my = my + d->my;
-        L = L + d->L; K2 = K2 + d->K2; pot = pot + d->pot; coincident += d->coincident;
+        if (!by_tile[t]) return nbody_fail(NBODY_ERR_STATE, "tile %d of %d bodies is reported by no rank", t, n);
+        diag_add(total, *by_tile[t]);
     }
-    out->step = c->steps;
-    out->n_bodies = n;
-    out->coincident_pairs = coincident;
-    out->mass = mass;
-    out->momentum[0] = px;
-    out->momentum[1] = py;
-    out->center_of_mass[0] = mass == 0.0 ? NAN : mx / mass;
-    out->center_of_mass[1] = mass == 0.0 ? NAN : my / mass;
-    out->angular_momentum = L;
-    out->kinetic = 0.5 * K2;
-    out->potential = 0.5 * pot;
+    const DiagOut o = diag_finish(total, c->steps, n);
+    memcpy(out, &o, sizeof(o));
     return NBODY_OK;
 }
 
@@ -1191,10 +1167,7 @@ int nbody_get_events(nbody_ctx* c, nbody_event* out, int cap, int64_t* total) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     const unsigned long long tot = c->h_counters->events;
     *total = (int64_t)tot;
-    unsigned long long ncopy = tot;
-    if (ncopy > (unsigned long long)c->ev_cap) ncopy = c->ev_cap;
-    if (ncopy > (unsigned long long)cap) ncopy = cap;
-    static_assert(sizeof(nbody_event) == sizeof(Event), "event layouts must match");
+    const unsigned long long ncopy = log_prefix(tot, c->ev_cap, cap);
     if (ncopy) HIP_TRY(hipMemcpy(out, c->events, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
     return NBODY_OK;
 }
@@ -1230,22 +1203,10 @@ int nbody_get_lineage(nbody_ctx* c, nbody_lineage* out, int cap, int64_t* total)
     HIP_TRY(hipSetDevice(c->desc.device));
     int rc = read_meta(c);                                 // synchronises; a failed index check of a translation ends here
     if (rc != NBODY_OK) return rc;
-    unsigned long long done = 0;
-    HIP_TRY(hipMemcpy(&done, c->ids.done, sizeof(done), hipMemcpyDeviceToHost));
     const unsigned long long tot = c->h_counters->events;
     *total = (int64_t)tot;
-    unsigned long long ncopy = tot;
-    if (ncopy > (unsigned long long)c->ev_cap) ncopy = c->ev_cap;
-    if (ncopy > (unsigned long long)cap) ncopy = cap;
-    if (!ncopy) return NBODY_OK;
-    std::vector<Event> ev((size_t)ncopy);
-    std::vector<IdPair> who((size_t)ncopy);
-    HIP_TRY(hipMemcpy(ev.data(), c->events, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(who.data(), c->ids.lineage, ncopy * sizeof(IdPair), hipMemcpyDeviceToHost));
-    for (unsigned long long k = 0; k < ncopy; ++k) {       // events past `done` belong to no committed step
-        const bool have = k < done;
-        out[k] = nbody_lineage{ev[k].step, have ? who[k].id_i : -1, have ? who[k].id_j : -1, ev[k].kind};
-    }
+    const unsigned long long ncopy = log_prefix(tot, c->ev_cap, cap);
+    if (ncopy) HIP_TRY(lineage_read(c->events, c->ids.lineage, c->ids.done, ncopy, out));
     return NBODY_OK;
 }
 

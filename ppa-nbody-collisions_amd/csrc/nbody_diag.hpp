@@ -1,15 +1,17 @@
 // csrc/nbody_diag.hpp -- physical diagnostics of the resident state (nbody_get_diagnostics, include/nbody.h): the
 // per-body potential phi_i = -G sum_{j != i, r_ij > 0} m_j / r_ij and the O(N) moments, all in fp64 (fp32 inputs are
-// widened exactly).  Included by nbody_ctx.hip after nbody_kernels.hpp.
+// widened exactly).  Included after nbody_kernels.hpp.  What every potential kernel and every finish of the totals must
+// agree on bit for bit lives here once: diag_walk (the sum over j; also batch_diag_potential's and track_potential's),
+// diag_row_general, and diag_add / diag_finish (host and device: diag_collect in nbody_ctx.hip, batch_diag_reduce).
 //
 // Order contract.  phi_i is ONE running sum over j = 0, 1, ..., n-1 in ascending order, whatever the
 // launch: it depends on (i, n) only, never on the rank, the world, the own count or the CU count.  The totals are
 // reduced per aligned 128-body tile (nbody_partition's unit) in ascending order inside the tile, and the host then adds
 // the tiles in ascending global order: a call gives the same bits for every partition of the same state.
 //
-// diag_potential: one lane per row i of the own range, 256-lane workgroups.  The j stream is wave-uniform: every
-// workgroup walks the replica tile by tile; a tile's {x, y, m} are widened to fp64 ONCE, into LDS (double-buffered, one
-// barrier per tile), and read back as broadcasts.  Per pair:
+// diag_potential: one lane per row i of the own range, 256-lane workgroups.  diag_walk: the j stream is wave-uniform:
+// every workgroup walks the replica tile by tile; a tile's {x, y, m} are widened to fp64 ONCE, into LDS (double-buffered,
+// one barrier per tile), and read back as broadcasts.  Per pair:
 //     dx = xj - xi;  dy = yj - yi;  d2 = fma(dx, dx, dy*dy)                               (4)
 //     y = v_rsq_f64(d2);  t = y*y;  e = fma(-d2, t, 1);  r = fma(y*e, fma(e, 3/8, 1/2), y)  (1 trans + 5)
 //     acc = fma(mj, r, acc)                                                                (1)
@@ -17,8 +19,10 @@
 // dx^2 + dy^2 of the exact differences, each term m_j / r_ij is within 3 u (3 ulps) of its exact value while d2 stays
 // in [2^-1000, 2^1000] (any pair of an fp32 state).
 // Self term and coincident pairs cost nothing per pair in the common case:
-//   * j == i can only occur in the tile of i's own rows, which is wave-uniform; that ONE tile takes a checked loop
-//     (self term -> m = 0, d2 = 1: adds an exact +0).
+//   * j == i can only occur in the tile of i's own rows; a wave takes a checked loop in the tiles that hold a self term
+//     of one of its lanes (self term -> m = 0, d2 = 1: adds an exact +0; the other pairs as in the unchecked loop, so
+//     which loop a wave took does not show in the bits) and the unchecked loop elsewhere.  Contiguous rows: that is ONE
+//     tile, known wave-uniformly.  Gathered rows (track_potential): the lanes vote per tile.
 //   * d2 == 0 for j != i gives e = fma(-0, inf, 1) = NaN, and so do the degenerate d2 the fast chain cannot take
 //     (t = y*y overflowing or 0): the row's accumulator is then not finite.  After the walk, exactly those rows are
 //     redone with the general code (IEEE sqrt and divide, hypot outside the normal range, coincident pairs counted and
@@ -29,6 +33,9 @@
 // about the origin, sum m v^2.
 #pragma once
 #include <float.h>
+#include <stddef.h>
+
+#include "nbody.h"
 
 #pragma clang fp contract(off)
 
@@ -39,6 +46,48 @@ struct DiagTile {             // per aligned 128-body tile of the own range (sum
     long long coincident;                      // ordered pairs (i, j), i in the tile, j != i, at distance 0
 };
 static_assert(sizeof(DiagTile) == 72, "DiagTile layout");
+
+// The finished record: struct nbody_diag (include/nbody.h) as device code writes it.
+struct DiagOut {
+    long long step, n_bodies, coincident_pairs;
+    double mass, momentum[2], center_of_mass[2], angular_momentum, kinetic, potential;
+};
+static_assert(sizeof(DiagOut) == 88 && sizeof(nbody_diag) == sizeof(DiagOut), "nbody_diag layout");
+static_assert(offsetof(DiagOut, step) == 0 && offsetof(DiagOut, n_bodies) == 8 && offsetof(DiagOut, coincident_pairs) == 16 &&
+              offsetof(DiagOut, mass) == 24 && offsetof(DiagOut, momentum) == 32 && offsetof(DiagOut, center_of_mass) == 48 &&
+              offsetof(DiagOut, angular_momentum) == 64 && offsetof(DiagOut, kinetic) == 72 &&
+              offsetof(DiagOut, potential) == 80, "nbody_diag layout");
+static_assert(offsetof(nbody_diag, step) == offsetof(DiagOut, step) && offsetof(nbody_diag, n_bodies) == offsetof(DiagOut, n_bodies) &&
+              offsetof(nbody_diag, coincident_pairs) == offsetof(DiagOut, coincident_pairs) &&
+              offsetof(nbody_diag, mass) == offsetof(DiagOut, mass) && offsetof(nbody_diag, momentum) == offsetof(DiagOut, momentum) &&
+              offsetof(nbody_diag, center_of_mass) == offsetof(DiagOut, center_of_mass) &&
+              offsetof(nbody_diag, angular_momentum) == offsetof(DiagOut, angular_momentum) &&
+              offsetof(nbody_diag, kinetic) == offsetof(DiagOut, kinetic) &&
+              offsetof(nbody_diag, potential) == offsetof(DiagOut, potential), "nbody_diag and its device mirror");
+
+// The end of the diagnostics, the same operations on the host (one context, a group) and on the device (a batch): the
+// tiles are added into a zero-initialised DiagTile in ascending global order, then the record is finished.
+__host__ __device__ inline void diag_add(DiagTile& total, const DiagTile& d) {
+    total.mass = total.mass + d.mass; total.px = total.px + d.px; total.py = total.py + d.py;
+    total.mx = total.mx + d.mx; total.my = total.my + d.my;
+    total.L = total.L + d.L; total.K2 = total.K2 + d.K2; total.pot = total.pot + d.pot;
+    total.coincident += d.coincident;
+}
+__host__ __device__ inline DiagOut diag_finish(const DiagTile& total, long long step, long long n) {
+    DiagOut o;
+    o.step = step;
+    o.n_bodies = n;
+    o.coincident_pairs = total.coincident;
+    o.mass = total.mass;
+    o.momentum[0] = total.px;
+    o.momentum[1] = total.py;
+    o.center_of_mass[0] = total.mass == 0.0 ? __builtin_nan("") : total.mx / total.mass;   // an empty system has none
+    o.center_of_mass[1] = total.mass == 0.0 ? __builtin_nan("") : total.my / total.mass;
+    o.angular_momentum = total.L;
+    o.kinetic = 0.5 * total.K2;
+    o.potential = 0.5 * total.pot;
+    return o;
+}
 
 constexpr int kDiagBlock = 256;               // four waves, two row tiles
 
@@ -70,25 +119,19 @@ __device__ __forceinline__ DiagRow diag_row_general(const Rec<T>* __restrict__ J
     return DiagRow{s, c};
 }
 
-template <typename T>
-__global__ __launch_bounds__(kDiagBlock) void diag_potential(const Rec<T>* __restrict__ J, int n, int lo, int cnt,
-                                                             double G, double* __restrict__ phi,
-                                                             DiagTile* __restrict__ tiles) {
+// The sum over j of row i at (xi, yi), j = 0 .. n-1 ascending: every potential kernel's inner walk.  Called by all
+// kDiagBlock lanes of the workgroup (it owns the tile buffers and the barriers), lanes without a row included.
+// self_tile: the j tile that holds the lane's self term j == i.
+// kGatheredRows = false: the rows of a wave are contiguous and within one tile; self_tile is that tile, wave-uniform
+//                        (lanes past the last row carry it too: they compute and are not stored).
+// kGatheredRows = true : any row per lane, -1 for a lane without one; the wave votes per tile, and a wave without any row
+//                        only loads tiles.
+template <bool kGatheredRows, typename T>
+__device__ __forceinline__ double diag_walk(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi,
+                                            int self_tile) {
     __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
-    __shared__ double wpot[kDiagBlock];
-    __shared__ long long wcoin[kDiagBlock];
     const int tid = threadIdx.x;
-    const int row0 = blockIdx.x * kDiagBlock;                    // first own row of the workgroup
-    const int k = row0 + tid;                                    // own row of this lane
-    const bool valid = k < cnt;
-    const int i = lo + k;
-    double xi = 0.0, yi = 0.0, mi = 0.0;
-    if (valid) {
-        const Rec<T> r = J[i];
-        xi = (double)r.x; yi = (double)r.y; mi = (double)r.m;
-    }
-    // global tile of this wave's rows (lo is tile-aligned): the one j tile that holds their self terms
-    const int self_tile = (lo + row0 + (tid & ~(kWave - 1))) / kTile;
+    const bool wave_works = !kGatheredRows || __any(self_tile >= 0);
     const int jtiles = (n + kTile - 1) / kTile;
     double acc = 0.0;
     for (int t = 0; t < jtiles; ++t) {
@@ -101,7 +144,8 @@ __global__ __launch_bounds__(kDiagBlock) void diag_potential(const Rec<T>* __res
         }
         // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
         __syncthreads();
-        if (t != self_tile) {
+        if (!wave_works) continue;
+        if (kGatheredRows ? !__any(self_tile == t) : t != self_tile) {
             int q = 0;
             for (; q + 4 <= jn; q += 4) {
 #pragma unroll
@@ -125,6 +169,27 @@ __global__ __launch_bounds__(kDiagBlock) void diag_potential(const Rec<T>* __res
             }
         }
     }
+    return acc;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kDiagBlock) void diag_potential(const Rec<T>* __restrict__ J, int n, int lo, int cnt,
+                                                             double G, double* __restrict__ phi,
+                                                             DiagTile* __restrict__ tiles) {
+    __shared__ double wpot[kDiagBlock];
+    __shared__ long long wcoin[kDiagBlock];
+    const int tid = threadIdx.x;
+    const int row0 = blockIdx.x * kDiagBlock;                    // first own row of the workgroup
+    const int k = row0 + tid;                                    // own row of this lane
+    const bool valid = k < cnt;
+    const int i = lo + k;
+    double xi = 0.0, yi = 0.0, mi = 0.0;
+    if (valid) {
+        const Rec<T> r = J[i];
+        xi = (double)r.x; yi = (double)r.y; mi = (double)r.m;
+    }
+    // global tile of this wave's rows (lo is tile-aligned): the one j tile that holds their self terms
+    double acc = diag_walk<false>(J, n, i, xi, yi, (lo + row0 + (tid & ~(kWave - 1))) / kTile);
     long long coin = 0;
     if (valid && !__builtin_isfinite(acc)) {
         const DiagRow g = diag_row_general<T>(J, n, i, xi, yi);

@@ -8,11 +8,15 @@
 // the staged masses of step t and the event log holds every event of step t in the index space of step t.
 //   ids_translate : lineage[k] = {ids_cur[ev[k].i], ids_cur[ev[k].j]} for the events [done, min(events, ev_cap)) -
 //                   the ones logged since the last translation.  Reads `done`, never writes it.
-//   ids_scatter   : ids_next[offset of q among the survivors] = ids_cur[q], the offsets of compact_scatter /
-//                   batch_commit (same keep test, same stable order); one thread advances `done`.  Never reads `done`.
+//   ids_scatter   : ids_next[offset of q among the survivors] = ids_cur[q].  The keep test and the offset are the
+//                   commit's own (compact_keep, compact_offset, nbody_kernels.hpp), so the map follows the bodies; one
+//                   thread advances `done`.  Never reads `done`.
 // The host swaps ids_cur and ids_next after the pair.  Every kernel here is a template: both translation units include
 // this file (NBK_TEMPLATES_ONLY in nbody_batch.hip).
 #pragma once
+#include <vector>
+
+#include "nbody.h"
 #include "nbody_kernels.hpp"
 
 namespace nbk {
@@ -23,6 +27,11 @@ constexpr int kIdsBlock = 256;                             // threads of ids_fil
 
 // A count outside [0, stride] never becomes an index (batch_checked_count's rule): the system is treated as empty.
 __device__ __forceinline__ int ids_checked_count(int n, int stride) { return (n < 0 || n > stride) ? 0 : n; }
+
+// Events of a log that are stored: the counter runs on past the capacity (overflow is counted, not stored).
+__host__ __device__ inline unsigned long long log_stored(unsigned long long logged, int ev_cap) {
+    return logged < (unsigned long long)ev_cap ? logged : (unsigned long long)ev_cap;
+}
 
 // Upload: identity = index.  grid = (ceil(stride / B), S); the whole slice is written, so no later read sees memory
 // nobody wrote.
@@ -43,8 +52,7 @@ __global__ __launch_bounds__(B) void ids_translate(const Event* __restrict__ ev_
                                                    IdPair* __restrict__ lineage_all) {
     const int sys = blockIdx.y;
     const int n = ids_checked_count(meta_all[sys].n, stride);
-    const unsigned long long logged = ctr_all[sys].events;
-    const unsigned long long end = logged < (unsigned long long)ev_cap ? logged : (unsigned long long)ev_cap;
+    const unsigned long long end = log_stored(ctr_all[sys].events, ev_cap);
     const Event* __restrict__ ev = ev_all + (size_t)sys * (size_t)ev_cap;
     IdPair* __restrict__ lineage = lineage_all + (size_t)sys * (size_t)ev_cap;
     const int32_t* __restrict__ ids = ids_cur_all + (size_t)sys * (size_t)stride;
@@ -69,50 +77,20 @@ __global__ __launch_bounds__(B) void ids_scatter(const Rec<T>* __restrict__ S_J_
                                                  int32_t* __restrict__ ids_next_all, int stride,
                                                  const Counters* __restrict__ ctr_all,
                                                  unsigned long long* __restrict__ done_all, int ev_cap) {
-    __shared__ int wsum[B / kWave];
-    __shared__ int red[B / kWave];
-    __shared__ int base_s;
     const int sys = blockIdx.y;
-    const int nblk = gridDim.x;
     const int cnt = ids_checked_count(meta_all[sys].n, stride);
     const size_t base = (size_t)sys * (size_t)stride;
-    // offset of this workgroup = survivors of all lower workgroups of this system
-    int part = 0;
-    {
-        const int* __restrict__ mine = blk_counts + (size_t)sys * nblk;
-        for (int bidx = threadIdx.x; bidx < (int)blockIdx.x; bidx += B) part += mine[bidx];
-        for (int sh = kWave / 2; sh > 0; sh >>= 1) part += __shfl_down(part, sh, kWave);
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = part;
-
     const int q = blockIdx.x * B + threadIdx.x;
     int32_t id = 0;
     bool keep = false;
     if (q < cnt) {
         id = ids_cur_all[base + q];
-        keep = S_J_all[base + q].m != (T)0;                // the keep test of the compaction: a NaN mass stays
+        keep = compact_keep(S_J_all[base + q].m);
     }
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wid = threadIdx.x / kWave;
-    if (lane == 0) wsum[wid] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < B / kWave; ++w) s += red[w];
-        base_s = s;
-        if (blockIdx.x == 0 && done_all != nullptr) {      // everything logged so far is translated (ids_translate, before)
-            const unsigned long long logged = ctr_all[sys].events;
-            done_all[sys] = logged < (unsigned long long)ev_cap ? logged : (unsigned long long)ev_cap;
-        }
-    }
-    __syncthreads();
-    if (keep) {
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wsum[w];
-        off += __popcll(bal & ((1ull << lane) - 1ull));
-        ids_next_all[base + off] = id;                     // off < survivors <= cnt <= stride
-    }
+    const CompactOffset o = compact_offset<B>(keep, blk_counts + (size_t)sys * gridDim.x);
+    if (keep) ids_next_all[base + o.off] = id;             // off < survivors <= cnt <= stride
+    if (q == 0 && done_all != nullptr)                     // everything logged so far is translated (ids_translate, before)
+        done_all[sys] = log_stored(ctr_all[sys].events, ev_cap);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -128,6 +106,32 @@ struct IdsState {
     unsigned long long* done = nullptr;     // [systems] events translated so far
     bool on() const { return map[0] != nullptr; }
 };
+
+// Reading a log back (nbody_get_events / nbody_get_lineage and their batch twins): the first min(total, ev_cap, cap)
+// records - what was stored and fits the caller's buffer.
+static_assert(sizeof(nbody_event) == sizeof(Event), "event layouts must match");
+inline unsigned long long log_prefix(unsigned long long total, int ev_cap, int cap) {
+    const unsigned long long stored = log_stored(total, ev_cap);
+    return stored < (unsigned long long)cap ? stored : (unsigned long long)cap;
+}
+
+// The first ncopy (> 0) lineage records of one system: ev / who / done point at that system's slices.  An event past
+// `done` belongs to no committed step and has not been translated: it reads -1.
+inline hipError_t lineage_read(const Event* ev_dev, const IdPair* who_dev, const unsigned long long* done_dev,
+                               unsigned long long ncopy, nbody_lineage* out) {
+    unsigned long long done = 0;
+    std::vector<Event> ev((size_t)ncopy);
+    std::vector<IdPair> who((size_t)ncopy);
+    hipError_t e = hipMemcpy(&done, done_dev, sizeof(done), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(ev.data(), ev_dev, ncopy * sizeof(Event), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(who.data(), who_dev, ncopy * sizeof(IdPair), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (unsigned long long k = 0; k < ncopy; ++k) {
+        const bool have = k < done;
+        out[k] = nbody_lineage{ev[k].step, have ? who[k].id_i : -1, have ? who[k].id_j : -1, ev[k].kind};
+    }
+    return hipSuccess;
+}
 
 // Upload: identity = index, for every system; the caller empties `done` with the event counters.
 template <int B>

@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "nbody.h"
 #include "nbody_partition.h"
 
 #pragma clang fp contract(off)
@@ -78,6 +79,8 @@ struct SlotHeader {
 };
 static_assert(sizeof(SlotHeader) == 32, "slot header is 32 bytes so fp64 records stay 32-byte aligned");
 
+constexpr float kG = 6.67408e-11f;   // src/nbody.cu:37, a float literal; fp64 code widens it
+
 template <typename T>
 struct StepParams {
     T dt;
@@ -89,6 +92,25 @@ struct StepParams {
     int spin_limit;           // ring kernel: polls of a hand-off record before the wait is declared failed
     int rotate_priority;      // one-lane kernels built with NB_V3_ROTATE_PRIORITY: the launch is a single round
 };
+
+// The kernel arguments of src/nbody.cu:482 for one system.  The configuration's values are floats and ints: either T
+// holds them exactly.
+template <typename T>
+inline StepParams<T> make_params(double timestep, double growth, int field_width, int field_height, int semantics,
+                                 int spin_limit) {
+    StepParams<T> p;
+    p.dt = (T)timestep;
+    p.growth = (T)growth;
+    p.G = (T)kG;
+    p.wall_hi_x = (T)field_width;
+    p.wall_lo_x = (T)(-field_width);
+    p.wall_hi_y = (T)field_height;
+    p.wall_lo_y = (T)(-field_height);
+    p.literal = semantics == NBODY_LITERAL;
+    p.spin_limit = spin_limit;
+    p.rotate_priority = 0;
+    return p;
+}
 
 template <typename T> __device__ __forceinline__ T ieee_sqrt(T x);
 template <> __device__ __forceinline__ float ieee_sqrt<float>(float x) { return __builtin_sqrtf(x); }
@@ -1415,25 +1437,71 @@ __global__ __launch_bounds__(256) void records_to_tiles_f32(const Rec<float>* __
 }
 #endif  // NBK_TEMPLATES_ONLY
 
+// The rule of the compaction, once, for every kernel that compacts or follows the compaction (here, the batch's
+// batch_count / batch_commit and the identities' ids_scatter): they agree bit for bit because they call these.
+// The keep test: a NaN mass stays.
+template <typename T>
+__device__ __forceinline__ bool compact_keep(T mass) { return mass != (T)0; }
+
+// Survivors of this workgroup of B threads.  The value is thread 0's alone; one barrier.
+template <int B>
+__device__ __forceinline__ int compact_block_count(bool keep) {
+    __shared__ int wsum[B / kWave];
+    const unsigned long long bal = __ballot(keep);
+    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = __popcll(bal);
+    __syncthreads();
+    int s = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < B / kWave; ++w) s += wsum[w];
+    return s;
+}
+
+// Where a survivor goes (stable order): the survivors of the lower workgroups of its system (lower_counts[0 .. blockIdx.x),
+// what compact_block_count left there in a launch of the same geometry), plus the lower waves of its workgroup, plus the
+// lower lanes of its wave.  `off` is meaningful where keep is set; `below` (survivors of the lower workgroups) and `here`
+// (of this one) are the same in every thread.  Two barriers: whatever the caller read before the call, every thread of
+// the workgroup has read by the time the call returns.
+struct CompactOffset { int off, below, here; };
+template <int B>
+__device__ __forceinline__ CompactOffset compact_offset(bool keep, const int* __restrict__ lower_counts) {
+    static_assert(B / kWave >= 2, "red[] carries the two totals");
+    __shared__ int wsum[B / kWave];
+    __shared__ int red[B / kWave];                         // per wave: its share of the lower workgroups' counts
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wid = threadIdx.x / kWave;
+    int part = 0;
+    for (int bidx = threadIdx.x; bidx < (int)blockIdx.x; bidx += B) part += lower_counts[bidx];
+    for (int sh = kWave / 2; sh > 0; sh >>= 1) part += __shfl_down(part, sh, kWave);
+    if (lane == 0) red[wid] = part;
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wsum[wid] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) {                                // nobody else reads red[] between the barriers: the totals go there
+        int s = 0, t = 0;
+        for (int w = 0; w < B / kWave; ++w) s += red[w];
+        for (int w = 0; w < B / kWave; ++w) t += wsum[w];
+        red[0] = s;
+        red[1] = t;
+    }
+    __syncthreads();
+    const int below = red[0], here = red[1];
+    int off = below;
+    for (int w = 0; w < wid; ++w) off += wsum[w];
+    off += __popcll(bal & ((1ull << lane) - 1ull));
+    return CompactOffset{off, below, here};
+}
+
 template <typename T>
 __global__ __launch_bounds__(kCompactBlock) void compact_count(const Rec<T>* __restrict__ S_J,
                                                                const Meta* __restrict__ meta,
                                                                int* __restrict__ blk_counts,
                                                                unsigned* __restrict__ tile_rmax, int n_tiles) {
-    __shared__ int wsum[kCompactBlock / kWave];
     const int cnt = meta->cnt;
     const int q = blockIdx.x * kCompactBlock + threadIdx.x;
     if (q == 0) const_cast<Meta*>(meta)->summary = 0;      // the force kernel of this step is done with it
     for (int k = q; k < n_tiles; k += gridDim.x * kCompactBlock) tile_rmax[k] = 0u;   // ... and with these: unpack_slots refills
-    const bool keep = q < cnt && S_J[q].m != (T)0;
-    const unsigned long long bal = __ballot(keep);
-    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kCompactBlock / kWave; ++w) s += wsum[w];
-        blk_counts[blockIdx.x] = s;
-    }
+    const int s = compact_block_count<kCompactBlock>(q < cnt && compact_keep(S_J[q].m));
+    if (threadIdx.x == 0) blk_counts[blockIdx.x] = s;
 }
 
 template <typename T>
@@ -1444,16 +1512,7 @@ __global__ __launch_bounds__(kCompactBlock) void compact_scatter(const Rec<T>* _
                                                                  SlotHeader* __restrict__ slot_hdr,
                                                                  Rec<T>* __restrict__ slot_recs,
                                                                  Vec2<T>* __restrict__ slot_vels) {
-    __shared__ int wsum[kCompactBlock / kWave];
-    __shared__ int red[kCompactBlock / kWave];
-    __shared__ int base_s;
     const int cnt = meta->cnt;
-    // offset of this block = sum of the counts of all lower blocks
-    int part = 0;
-    for (int bidx = threadIdx.x; bidx < (int)blockIdx.x; bidx += kCompactBlock) part += blk_counts[bidx];
-    for (int sh = kWave / 2; sh > 0; sh >>= 1) part += __shfl_down(part, sh, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = part;
-
     const int q = blockIdx.x * kCompactBlock + threadIdx.x;
     Rec<T> rec{};
     Vec2<T> vel{};
@@ -1461,31 +1520,16 @@ __global__ __launch_bounds__(kCompactBlock) void compact_scatter(const Rec<T>* _
     if (q < cnt) {
         rec = S_J[q];
         vel = S_V[q];
-        keep = rec.m != (T)0;
+        keep = compact_keep(rec.m);
     }
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wid = threadIdx.x / kWave;
-    if (lane == 0) wsum[wid] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kCompactBlock / kWave; ++w) s += red[w];
-        base_s = s;
-        if ((int)blockIdx.x == nblk - 1) {
-            int tot = s;
-            for (int w = 0; w < kCompactBlock / kWave; ++w) tot += wsum[w];
-            slot_hdr->count = tot;
-            slot_hdr->layout = (int)(reinterpret_cast<const Rec<T>*>(slot_vels) - slot_recs);
-        }
+    const CompactOffset o = compact_offset<kCompactBlock>(keep, blk_counts);
+    if (threadIdx.x == 0 && (int)blockIdx.x == nblk - 1) {     // the last workgroup knows the total: the slot header
+        slot_hdr->count = o.below + o.here;
+        slot_hdr->layout = (int)(reinterpret_cast<const Rec<T>*>(slot_vels) - slot_recs);
     }
-    __syncthreads();
     if (keep) {
-        int off = base_s;
-        for (int w = 0; w < wid; ++w) off += wsum[w];
-        off += __popcll(bal & ((1ull << lane) - 1ull));
-        slot_recs[off] = rec;
-        slot_vels[off] = vel;
+        slot_recs[o.off] = rec;
+        slot_vels[o.off] = vel;
     }
 }
 

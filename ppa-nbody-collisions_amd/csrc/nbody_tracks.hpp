@@ -13,14 +13,11 @@
 //                     written exactly once per record: no memset of the row, no atomics on it.  Lane 0 of a system writes
 //                     the row header from Meta.
 //   track_potential : one lane per column, working for the columns track_gather found present (it reads `index`, written
-//                     by the launch before it on the same stream).  The walk over j is diag_potential's (nbody_diag.hpp;
-//                     diag_rinv and diag_row_general are taken from there): tiles widened to fp64 once into
-//                     double-buffered LDS, one barrier per tile, one fma chain over j ascending.  What differs: rows are
-//                     gathered, so the tile that holds a lane's self term is not wave-uniform.  A wave takes the checked
-//                     loop in every tile that holds the self index of ANY of its lanes and the unchecked loop elsewhere;
-//                     the per-pair operations are the same in both (the self term adds fma(0, rinv(1), acc)), so phi has
-//                     the bits diag_potential gives that row.  Workgroups without a present column leave before the
-//                     first tile; absent columns get +0.
+//                     by the launch before it on the same stream).  The sum over j is diag_walk (nbody_diag.hpp) in its
+//                     form for gathered rows - the tile that holds a lane's self term is not wave-uniform, so the lanes
+//                     of a wave vote per tile - and diag_row_general for a flagged row: phi has the bits diag_potential
+//                     gives that row.  Workgroups without a present column leave before the first tile; absent columns
+//                     get +0.
 // A count outside [0, stride] never becomes an index or a search bound (ids_checked_count's rule): the row is all absent,
 // n_bodies = 0, and the system's Counters::errors gets kIndexError.
 //
@@ -93,7 +90,6 @@ __global__ __launch_bounds__(kDiagBlock) void track_potential(const Rec<T>* __re
                                                               const Meta* __restrict__ meta_all, int stride, double G,
                                                               const int32_t* __restrict__ index, int columns,
                                                               double* __restrict__ phi) {
-    __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
     const int sys = blockIdx.y;
     const int n = ids_checked_count(meta_all[sys].n, stride);
     const int tid = threadIdx.x;
@@ -109,45 +105,7 @@ __global__ __launch_bounds__(kDiagBlock) void track_potential(const Rec<T>* __re
         const Rec<T> r = J[i];
         xi = (double)r.x; yi = (double)r.y;
     }
-    const int self_tile = valid ? i / kTile : -1;            // differs from lane to lane: the rows are gathered
-    const bool wave_works = __any(valid);                    // a wave without a present column only loads tiles
-    const int jtiles = (n + kTile - 1) / kTile;
-    double acc = 0.0;
-    for (int t = 0; t < jtiles; ++t) {
-        const int b = t & 1;
-        const int j0 = t * kTile;
-        const int jn = n - j0 < kTile ? n - j0 : kTile;
-        if (tid < jn) {
-            const Rec<T> r = J[j0 + tid];
-            sx[b][tid] = (double)r.x; sy[b][tid] = (double)r.y; sm[b][tid] = (double)r.m;
-        }
-        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
-        __syncthreads();
-        if (!wave_works) continue;
-        if (!__any(self_tile == t)) {                        // no lane of this wave has its self term here
-            int q = 0;
-            for (; q + 4 <= jn; q += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double dx = sx[b][q + u] - xi, dy = sy[b][q + u] - yi;
-                    const double d2 = __builtin_fma(dx, dx, dy * dy);
-                    acc = __builtin_fma(sm[b][q + u], diag_rinv(d2), acc);
-                }
-            }
-            for (; q < jn; ++q) {
-                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
-                const double d2 = __builtin_fma(dx, dx, dy * dy);
-                acc = __builtin_fma(sm[b][q], diag_rinv(d2), acc);
-            }
-        } else {
-            for (int q = 0; q < jn; ++q) {
-                const bool self = j0 + q == i;
-                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
-                const double d2 = self ? 1.0 : __builtin_fma(dx, dx, dy * dy);
-                acc = __builtin_fma(self ? 0.0 : sm[b][q], diag_rinv(d2), acc);
-            }
-        }
-    }
+    double acc = diag_walk<true>(J, n, i, xi, yi, valid ? i / kTile : -1);   // the self tile differs from lane to lane
     if (!valid) return;
     if (!__builtin_isfinite(acc)) acc = diag_row_general<T>(J, n, i, xi, yi).s;
     phi[out] = -G * acc;
@@ -254,9 +212,8 @@ int track_record(TrackState& st, hipStream_t stream, int device, const char* who
                        dim3(kTrackBlock), 0, stream, J, V, meta, ctr, ids_cur, stride, (const int32_t*)st.sel, st.columns,
                        st.rows + row, reinterpret_cast<TrackRec<T>*>(st.rec) + cell, index);
     if (st.phi) {
-        const double G = (double)6.67408e-11f;              // src/nbody.cu:37, the float literal widened (as the diagnostics)
         hipLaunchKernelGGL((track_potential<T>), dim3((st.columns + kDiagBlock - 1) / kDiagBlock, st.systems),
-                           dim3(kDiagBlock), 0, stream, J, meta, stride, G, (const int32_t*)index, st.columns, st.phi + cell);
+                           dim3(kDiagBlock), 0, stream, J, meta, stride, (double)kG, (const int32_t*)index, st.columns, st.phi + cell);
     }
     NBK_TRACK_TRY(hipGetLastError());
     st.recorded += 1;

@@ -1,0 +1,271 @@
+#!/usr/bin/env python3
+"""This library against the parent commit's, on the work of the kernels that share a rule with another kernel: the
+compaction's offsets (compact_count / compact_scatter, batch_count / batch_commit, ids_scatter), the potential's walk
+(diag_potential, batch_diag_potential, track_potential) and the finish of the diagnostics (batch_diag_reduce).
+
+    python3 csrc/tune/ab_parent.py --baseline-root DIR [--lines a,b256,...] [--rounds 3] [--out FILE]
+    python3 csrc/tune/ab_parent.py --trace [--root DIR]     (every line once, target of rocprofv3 --kernel-trace --stats)
+
+DIR is a built checkout of the parent commit (make -C ppa-nbody-collisions_amd/csrc).  Three child processes, each loading
+one library by path (two builds of one library do not share a process), stay alive and take turns round by round in the same
+GPU call:
+    parent     the baseline library
+    control    the baseline library once more: what two processes on ONE library differ by (buffers land elsewhere)
+    candidate  this library
+Every line is warmed up on every side, and the results of the three sides must be bit-equal (sha256) in every round before
+a time is taken.  Time is a host clock around work that ends in a synchronise; a window repeats the call often enough to
+last 0.1 s or more.  Round r starts with side r mod 3, so that with 3 rounds every side has had every place in the turn.
+
+Lines (fp32, literal, stock configuration with stock radii):
+    a         Stepper N = 262144, diagnostics(potential=True)                              ms per call
+    b256, b64 StepperBatch 256 x 1024 / 64 x 4096 after 3 steps: diagnostics() and         ms per call
+              diagnostics(potential=True) (lines b256, b256phi, b64, b64phi)
+    c         Stepper N = 262144 after 8 steps, record_tracks() with phi on 64 evenly      ms per record
+              spread identities
+    d...      stepping with record_events and track_ids from a fresh upload: dctx262144    us per step
+              (20 steps), dctx1024 (2000), d256x1024 (1000), d64x4096 (500)
+A line passes when the candidate's median is not above the parent's median by more than max(the parent's round spread
+(max - min), |control median - parent median|).  Exit status 1 if a line does not pass.
+"""
+import argparse
+import hashlib
+import json
+import os
+import select
+import statistics
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.abspath(os.path.join(HERE, "..", "..", ".."))
+REPLY_TIMEOUT_S = 240           # a side that does not answer within this is killed and the probe fails
+LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024", "d256x1024", "d64x4096")
+BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
+STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
+N_BIG = 262144
+
+
+def load_package(root):
+    sys.path.insert(0, root)
+    try:
+        import torch  # noqa: F401  (one ROCm runtime per process: tests/conftest.py)
+    except ImportError:
+        pass
+    import ppa_nbody_collisions_amd as nb
+    assert os.path.abspath(nb.__file__).startswith(os.path.abspath(root) + os.sep), (nb.__file__, root)
+    return nb
+
+
+def digest_of(parts):
+    h = hashlib.sha256()
+    for p in parts:
+        h.update(p if isinstance(p, bytes) else repr(p).encode())
+    return h.hexdigest()
+
+
+def diag_parts(d):
+    out = []
+    for k in sorted(d):
+        out.append(d[k].tobytes() if hasattr(d[k], "tobytes") else repr(d[k]).encode())
+    return out
+
+
+class Line:
+    """One line of the table: setup() builds the state, window() times the work once and digests what it gave."""
+
+    def __init__(self, nb, name, short=False):
+        import numpy as np
+        self.nb, self.name, self.np = nb, name, np
+        self.batch = None
+        if name == "a" or name == "c":
+            cfg = nb.stock_config(particleCount=N_BIG)
+            self.st = nb.Stepper(cfg, track_ids=(name == "c"))
+            self.st.upload(nb.init_bodies(cfg, seed=1))
+            self.unit, self.reps = ("ms per call", 5) if name == "a" else ("ms per record", 32)
+            if name == "c":
+                self.st.step(8)
+                self.sel = [int(x) for x in np.unique(np.linspace(0, N_BIG - 1, 64).astype(np.int32))]
+        elif name in STEPS:
+            shape = name[1:]
+            self.steps = 200 if short else STEPS[name]
+            self.unit, self.reps = "us per step", self.steps
+            kw = dict(record_events=True, track_ids=True)
+            if shape.startswith("ctx"):
+                cfg = nb.stock_config(particleCount=int(shape[3:]))
+                self.bodies = nb.init_bodies(cfg, seed=1)
+                self.st = nb.Stepper(cfg, **kw)
+            else:
+                S, N = (int(x) for x in shape.split("x"))
+                cfg = nb.stock_config(particleCount=N)
+                self.bodies = [nb.init_bodies(cfg, seed=1 + s) for s in range(S)]
+                self.st = self.batch = nb.StepperBatch(S, N, cfg=cfg, **kw)
+        else:
+            S, N = BATCH[name.replace("phi", "")]
+            cfg = nb.stock_config(particleCount=N)
+            self.st = self.batch = nb.StepperBatch(S, N, cfg=cfg)
+            self.st.upload([nb.init_bodies(cfg, seed=1 + s) for s in range(S)])
+            self.st.step(3)
+            self.phi = name.endswith("phi")
+            self.unit, self.reps = "ms per call", 200
+        self.st.sync()
+
+    def window(self):
+        """-> (seconds, digest)"""
+        st, name = self.st, self.name
+        if name in STEPS:
+            st.upload(self.bodies)
+            st.sync()
+            t0 = time.perf_counter()
+            st.step(self.steps)
+            st.sync()
+            seconds = time.perf_counter() - t0
+            parts = []
+            for s in range(self.batch.systems if self.batch else 1):
+                o, ids = (st.download(s), st.ids(s)) if self.batch else (st.download(), st.ids())
+                parts += [b"%d:" % o.numBodies, o.block.tobytes(), ids.tobytes()]
+            return seconds, digest_of(parts)
+        if name == "c":
+            st.reserve_tracks(self.reps, ids=self.sel, potential=True)      # empties the log; synchronises
+            t0 = time.perf_counter()
+            for _ in range(self.reps):
+                st.record_tracks()
+            st.sync()
+            seconds = time.perf_counter() - t0
+            t = st.tracks()
+            return seconds, digest_of([t[k].tobytes() for k in sorted(t)])
+        t0 = time.perf_counter()
+        for _ in range(self.reps):                                          # each call ends in a copy back and a synchronise
+            d = st.diagnostics(potential=True) if name == "a" else st.diagnostics(potential=self.phi)
+        seconds = time.perf_counter() - t0
+        return seconds, digest_of(diag_parts(d) if name == "a" else [p for e in d for p in diag_parts(e)])
+
+    def value(self, seconds):
+        return seconds / self.reps * (1e6 if self.unit.startswith("us") else 1e3)
+
+    def close(self):
+        self.st.close()
+
+
+def child(root):
+    nb = load_package(root)
+    line = None
+    for text in sys.stdin:
+        cmd = json.loads(text)
+        if cmd["op"] == "setup":
+            if line is not None:
+                line.close()
+            line = Line(nb, cmd["line"])
+            line.window()                                                   # warm: code objects, lazy buffers
+            reply = {"unit": line.unit}
+        elif cmd["op"] == "window":
+            seconds, digest = line.window()
+            reply = {"value": line.value(seconds), "digest": digest}
+        else:
+            break
+        sys.stdout.write(json.dumps(reply) + "\n")
+        sys.stdout.flush()
+    if line is not None:
+        line.close()
+
+
+class Child:
+    def __init__(self, root):
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--child", root], stdin=subprocess.PIPE,
+                                  stdout=subprocess.PIPE, text=True, bufsize=1)
+
+    def ask(self, **cmd):
+        self.p.stdin.write(json.dumps(cmd) + "\n")
+        self.p.stdin.flush()
+        ready, _, _ = select.select([self.p.stdout], [], [], REPLY_TIMEOUT_S)
+        text = self.p.stdout.readline() if ready else ""
+        if not text:
+            self.p.kill()
+            raise SystemExit("child process did not answer %r (exit status %r): nothing more is started" % (cmd, self.p.poll()))
+        return json.loads(text)
+
+    def close(self):
+        try:
+            self.p.stdin.write(json.dumps({"op": "quit"}) + "\n")
+            self.p.stdin.flush()
+            self.p.wait(timeout=60)
+        except Exception:
+            self.p.kill()
+
+
+def probe_line(sides, name, rounds):
+    unit = [side.ask(op="setup", line=name)["unit"] for side in sides.values()][0]
+    t = {k: [] for k in sides}
+    order = list(sides)
+    for r in range(rounds):                                                 # the sides take turns, the first place too
+        got = {k: sides[k].ask(op="window") for k in order[r % 3:] + order[:r % 3]}
+        if len({g["digest"] for g in got.values()}) != 1:
+            raise SystemExit("%s round %d: the results differ between the sides - no time is reported" % (name, r))
+        for k, g in got.items():
+            t[k].append(round(g["value"], 4))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    spread = max(t["parent"]) - min(t["parent"])
+    offset = abs(med["control"] - med["parent"])
+    margin = max(spread, offset)
+    return {"line": name, "unit": unit, "results_bit_equal": True, "parent": t["parent"], "control": t["control"],
+            "candidate": t["candidate"], "parent_median": med["parent"], "control_median": med["control"],
+            "candidate_median": med["candidate"], "parent_spread": round(spread, 4),
+            "control_minus_parent": round(med["control"] - med["parent"], 4), "margin": round(margin, 4),
+            "candidate_minus_parent": round(med["candidate"] - med["parent"], 4),
+            "within_margin": med["candidate"] - med["parent"] <= margin}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    ap.add_argument("--baseline-root")
+    ap.add_argument("--lines", default=",".join(LINES))
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--root", default=ROOT, help="--trace: the checkout whose library is traced (default: this one)")
+    ap.add_argument("--out", help="append the result lines to this file as well")
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child)
+    names = a.lines.split(",")
+    unknown = [n for n in names if n not in LINES]
+    if unknown:
+        ap.error("unknown lines %s (of %s)" % (unknown, ", ".join(LINES)))
+    out = []
+
+    def emit(rec):
+        text = json.dumps(rec)
+        print(text, flush=True)
+        out.append(text)
+
+    ok = True
+    if a.trace:
+        nb = load_package(os.path.abspath(a.root))
+        for name in names:
+            line = Line(nb, name, short=True)
+            seconds, _ = line.window()
+            emit({"trace": name, "root": os.path.abspath(a.root), "unit": line.unit, "value": round(line.value(seconds), 4)})
+            line.close()
+    else:
+        if not a.baseline_root:
+            ap.error("--baseline-root DIR (a built checkout of the parent commit)")
+        if a.rounds < 3:
+            ap.error("at least 3 rounds")
+        base = os.path.abspath(a.baseline_root)
+        sides = {"parent": Child(base), "control": Child(base), "candidate": Child(ROOT)}
+        try:
+            for name in names:
+                rec = probe_line(sides, name, a.rounds)
+                ok = ok and rec["within_margin"]
+                emit(rec)
+        finally:
+            for side in sides.values():
+                side.close()
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(out) + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

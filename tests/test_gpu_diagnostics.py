@@ -370,3 +370,118 @@ def test_cli_diagnostics_lines(nb, tmp_path):
                 d["angular_momentum"], d["kinetic"], d["potential"]]
         assert np.array_equal(np.array(got).view(np.uint64), np.array(want).view(np.uint64)), (p, d)
     st.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 9. the bits, pinned
+# ---------------------------------------------------------------------------------------------------------------------
+# The three potential kernels (diag_potential, batch_diag_potential, track_potential) share one walk over j and host and
+# device share one finish, so the cross-checks between them compare a function with itself.  tests/golden/diag_pins.npz
+# holds states and what the library gave for them when the fixture was recorded (tests/golden/make_diag_pins.py): the bits
+# may not move.  n = 1: a lone body; 129: a j tile of one body; 256: exactly one full workgroup of rows; 300: an odd tile
+# count, a partial last tile and a partial second workgroup, with bodies 5 and 200 at one position (general rows, the
+# coincident count).
+PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "diag_pins.npz")
+PIN_SIZES = (1, 129, 256, 300)
+PIN_BATCH_SIZES = (0, 1, 129, 256, 300)
+PIN_BATCH_CAPACITY = 384
+PIN_TRACK_IDS = (0, 5, 127, 128, 200, 255, 256, 299)
+PIN_TRACK_KEYS = ("step", "n_bodies", "index", "x", "y", "vx", "vy", "m", "r", "phi")
+
+
+def pin_tag(nb, precision):
+    return "f64" if precision == nb.F64 else "f32"
+
+
+def pin_bits(a):
+    """Any array as its bit pattern: what the fixture stores and what the test compares."""
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]).copy()
+
+
+def pin_bodies(nb, pins, precision, n):
+    """The recorded input state: the [P | V | M | R] block as stored, never derived again."""
+    if n == 0:
+        return nb.BodiesData(0, precision)
+    dt = np.float64 if precision == nb.F64 else np.float32
+    return nb.BodiesData.from_block(pins["in_%s_n%d" % (pin_tag(nb, precision), n)].view(dt), n, precision)
+
+
+def pin_record(d):
+    return np.array(diag_bits({k: v for k, v in d.items() if k != "phi"}), dtype=np.uint64)
+
+
+def pin_stepper(nb, pins, precision, n):
+    """-> {key: bits} of diagnostics(potential=True) straight after the upload."""
+    tag = "ctx_%s_n%d" % (pin_tag(nb, precision), n)
+    with nb.Stepper(nb.stock_config(particleCount=n), precision=precision) as st:
+        st.upload(pin_bodies(nb, pins, precision, n))
+        d = st.diagnostics(potential=True)
+    return {tag + "_rec": pin_record(d), tag + "_phi": pin_bits(d["phi"])}
+
+
+def pin_batch(nb, pins):
+    """One fp32 batch of PIN_BATCH_SIZES: the records with and without phi (two instantiations), phi, and a track row."""
+    out = {}
+    cfg = nb.stock_config(particleCount=PIN_BATCH_CAPACITY)
+    with nb.StepperBatch(len(PIN_BATCH_SIZES), PIN_BATCH_CAPACITY, cfg=cfg, track_ids=True) as b:
+        b.upload([pin_bodies(nb, pins, nb.F32, n) for n in PIN_BATCH_SIZES])
+        ds = b.diagnostics(potential=True)
+        out["batch_rec"] = np.stack([pin_record(d) for d in ds])
+        out["batch_rec_without_phi"] = np.stack([pin_record(d) for d in b.diagnostics()])
+        for n, d in zip(PIN_BATCH_SIZES, ds):
+            out["batch_phi_n%d" % n] = pin_bits(d["phi"])
+        b.reserve_tracks(1, ids=list(PIN_TRACK_IDS), potential=True)
+        b.record_tracks()
+        t = b.tracks()
+    for k in PIN_TRACK_KEYS:
+        out["batch_track_" + k] = pin_bits(t[k])
+    return out
+
+
+def pin_tracks(nb, pins, precision):
+    """One track record with the potential on the n = 300 state."""
+    n = PIN_SIZES[-1]
+    with nb.Stepper(nb.stock_config(particleCount=n), precision=precision, track_ids=True) as st:
+        st.reserve_tracks(1, ids=list(PIN_TRACK_IDS), potential=True)
+        st.upload(pin_bodies(nb, pins, precision, n))
+        st.record_tracks()
+        t = st.tracks()
+    return {"track_%s_%s" % (pin_tag(nb, precision), k): pin_bits(t[k]) for k in PIN_TRACK_KEYS}
+
+
+def check_pins(pins, got):
+    assert got, "nothing was computed"
+    for key, bits in got.items():
+        want = pins[key]
+        assert want.dtype == bits.dtype and want.shape == bits.shape, (key, want.dtype, bits.dtype, want.shape, bits.shape)
+        assert np.array_equal(want, bits), (key, np.nonzero(want != bits)[0][:8])
+
+
+@pytest.fixture(scope="module")
+def pins():
+    with np.load(PINS) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.mark.parametrize("n", PIN_SIZES)
+@pytest.mark.parametrize("precision", [0, 1])
+def test_pinned_bits_stepper(nb, pins, precision, n):
+    check_pins(pins, pin_stepper(nb, pins, precision, n))
+
+
+def test_pinned_bits_batch(nb, pins):
+    got = pin_batch(nb, pins)
+    check_pins(pins, got)
+    # the record of a system does not depend on whether phi is kept, and an empty system reads NaN for its centre
+    assert np.array_equal(got["batch_rec"], got["batch_rec_without_phi"])
+    assert got["batch_rec"][0, 1] == 0 and got["batch_rec"][4, 2] == 2          # n_bodies of system 0; the pair (5, 200) twice
+
+
+@pytest.mark.parametrize("precision", [0, 1])
+def test_pinned_bits_tracks(nb, pins, precision):
+    got = pin_tracks(nb, pins, precision)
+    check_pins(pins, got)
+    # the track's phi is the diagnostics' phi of the same rows (identity = index straight after the upload)
+    phi = pins["ctx_%s_n%d_phi" % (pin_tag(nb, precision), PIN_SIZES[-1])]
+    assert np.array_equal(got["track_%s_phi" % pin_tag(nb, precision)][0], phi[list(PIN_TRACK_IDS)])
