@@ -158,8 +158,8 @@ typedef struct nbody_ctx_desc {
     int kernel_variant;     /* 0 = automatic (by own-range size); tuning / A-B testing only: 1 general kernel,  */
                             /* 11/12/14/18 one-lane..eight-lanes-per-body kernel, 31/32 its 256-thread form,    */
                             /* 50/52/54 ring-of-waves kernel with 2x8 / 4x4 / 1x8 (rings x waves) workgroups    */
-                            /* (53, 55, 56, 58: its tuning forms).  fp64: 1 selects the general kernel, anything else */
-                            /* the fp64 production kernel                                                       */
+                            /* (53, 55, 56, 58, 59: its tuning forms).  fp64: 1 selects the general kernel, anything   */
+                            /* else the fp64 production kernel                                                  */
 } nbody_ctx_desc;
 
 void nbody_ctx_desc_from_config(nbody_ctx_desc* d, const nbody_config* cfg, int precision);
@@ -219,7 +219,7 @@ typedef struct nbody_lineage {  /* an nbody_event in identity space             
  * NBODY_ERR_STATE without).  Record k is event k of nbody_get_events: same position, same step and kind; total, cap and the
  * overflow rules are those of nbody_get_events, and nbody_clear_events / nbody_upload empty both.  Only events of committed
  * steps are covered: what nbody_debug_force_only logs after the last step reads -1 / -1, and the tuning records of
- * kernel_variant 58 are outside the contract.  An event index outside [0, n) of its step is never used as an address: the
+ * kernel_variant 58 / 59 are outside the contract.  An event index outside [0, n) of its step is never used as an address: the
  * record gets -1 and the context fails its next synchronising call like after any failed index check. */
 int nbody_get_lineage(nbody_ctx* ctx, nbody_lineage* out, int cap, int64_t* total);
 
@@ -503,7 +503,7 @@ int nbody_debug_force_only(nbody_ctx* ctx, int reps);
  * tile, 0 for tiles past the end); *n_tiles = entries the context keeps.  Any output pointer may be NULL. */
 int nbody_debug_screen_state(nbody_ctx* ctx, int* summary, float* tile_rmax, int cap, int* n_tiles);
 
-/* Tuning aid (kernel_variant 58 only): cycle totals of the ring kernel's phases since upload, summed over waves:
+/* Tuning aid (kernel_variant 58 and 59 only): cycle totals of the ring kernel's phases since upload, summed over waves:
  * {evaluate, wait, chain+publish, window check, polls, turns, shader clocks of one wave's life, the same in 100 MHz
  * ticks}. */
 int nbody_debug_ring_probe(nbody_ctx* ctx, uint64_t out[8]);

@@ -115,6 +115,13 @@ struct nbody_ctx {
     unsigned* tile_rmax = nullptr;  // per aligned 128-body tile of J: bits of max |radius| (NaN skipped); see unpack_slots
     float* Jt = nullptr;            // fp32 contexts: the replica once more, tile by tile component-major (see store_tiled)
     int n_tiles = 0;                // cap / 128 + 2
+    // fp32 contexts, the ring kernel's persistent form: the item counter, and per ring of a launch the done word
+    // and the chain state between two segments of its walk.  Cleared once, here; kept clean by the kernel itself.
+    unsigned* q_head = nullptr;             // {next item, slots that have left}
+    unsigned long long* q_done = nullptr;   // [q_rings_cap]: launch number << 32 | segments done
+    unsigned long long* q_state = nullptr;  // [q_rings_cap][4][64]: 32 bytes per body
+    int q_rings_cap = 0;
+    unsigned q_launches = 0;                // persistent force launches so far
     Meta* meta = nullptr;
     Meta* meta_all = nullptr;       // RCCL contexts: every rank's Meta, all-gathered by nbody_download
     Counters* counters = nullptr;
@@ -262,7 +269,7 @@ int read_meta(nbody_ctx* c) {
 // kernel_variant: 0 automatic | 1 v1 (one body per lane, compiler IEEE sqrt/div) |
 //                 11,12,14,18 v3 with K = 1,2,4,8 lanes per body, 128-thread workgroups |
 //                 31,32 v3 K = 1 with 256-thread workgroups, registers sized for 4 / 2 waves per SIMD |
-//                 50,52,54 ring of waves with 2x8, 4x4, 1x8 (rings x waves) per workgroup; 53,55,56,58 its tuning forms
+//                 50,52,54 ring of waves with 2x8, 4x4, 1x8 (rings x waves) per workgroup; 53,55,56,58,59 its tuning forms
 // Where a force launch goes: the context's own stream and velocities, or - the reference-shaped launch through the
 // workspace context - the caller's stream and the velocities where they lie in the caller's block.
 struct LaunchTarget {
@@ -312,10 +319,19 @@ void launch_v3w(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log,
     else hipLaunchKernelGGL((forces_v3w_f32<K, false, kOcc>), dim3(grid), dim3(2 * kTile), 0, to.stream, NB_FORCES_ARGS(float));
 }
 
-template <int kW, int kT, int kSleep, bool kProbe, int kRings>
-void launch_ring(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to) {
-    const int grid = (nblocks * 2 + kRings - 1) / kRings;  // a workgroup serves kRings rings of 64 bodies, two per reference block
-    RingArgs a;
+// seg_tiles > 0: the persistent form (kQueue) with the walks of the last `cut` rings in segments of seg_tiles tiles.
+template <int kW, int kT, int kSleep, bool kProbe, int kRings, bool kQueue = false>
+void launch_ring(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to, int cut = 0, int seg_tiles = 0) {
+    const int rings = nblocks * 2;                         // rings of 64 bodies, two per reference block
+    int grid = (rings + kRings - 1) / kRings;              // a workgroup serves kRings rings
+    RingArgs a{};
+    if (kQueue) {                                          // one workgroup per CU, its rings pull items until none is left
+        grid = grid < c->num_cus ? grid : c->num_cus;
+        c->q_launches += 1;
+        if (c->q_launches == 0) c->q_launches = 1;
+        a.q_head = c->q_head; a.q_done = c->q_done; a.q_state = c->q_state; a.q_launch = c->q_launches;
+        a.q_rings = rings; a.q_whole = rings - (cut < rings ? cut : rings); a.q_seg_tiles = seg_tiles > 0 ? seg_tiles : 1;
+    }
     a.Vown = (const Vec2<float>*)to.vown; a.S_J = (Rec<float>*)c->S_J; a.S_V = (Vec2<float>*)c->S_V;
     a.meta = c->meta; a.p = p; a.ev = c->events; a.ev_cap = c->ev_cap; a.ctr = c->counters;
     a.tile_rmax = (const float*)c->tile_rmax; a.Jt = c->Jt; a.cap_own = c->cap_own; a.n_tiles = c->n_tiles;
@@ -325,8 +341,28 @@ void launch_ring(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log
         if (e[0] == 't') a.n_tiles = 1;
         if (e[0] == 'q') a.cap_own = 1;
     }
-    if (log) hipLaunchKernelGGL((forces_ring_f32<true, kW, kT, kSleep, kProbe, kRings>), dim3(grid), dim3(kRings * kW * kWave), 0, to.stream, a);
-    else hipLaunchKernelGGL((forces_ring_f32<false, kW, kT, kSleep, kProbe, kRings>), dim3(grid), dim3(kRings * kW * kWave), 0, to.stream, a);
+    if (log) hipLaunchKernelGGL((forces_ring_f32<true, kW, kT, kSleep, kProbe, kRings, kQueue>), dim3(grid), dim3(kRings * kW * kWave), 0, to.stream, a);
+    else hipLaunchKernelGGL((forces_ring_f32<false, kW, kT, kSleep, kProbe, kRings, kQueue>), dim3(grid), dim3(kRings * kW * kWave), 0, to.stream, a);
+}
+// The persistent 4 x 4 form as production runs it: whole walks first, and only the rings of the LAST round - as many as
+// there are ring slots - cut into 32 segments, because only near the end does a CU that is ahead find work to take over
+// (measured on MI355X at N = 262144, profiles/ring_queue_probe.txt: the last 1024 rings in 12 / 24 / 32 / 48 / 96 segments
+// -0.09 / -0.2 / -0.25 / -0.23 / -0.15 ms of 29.2; the last 1536 in 32: -0.20; the last 512 in 24: +0.14; every walk in 16:
+// -0.03).  Returns false where that does not apply - fewer than two rounds of rings, so that a segment would be a large
+// part of the launch -: the caller launches the one-shot form.
+constexpr int kQueueSegments = 32;
+int ring_queue_slots(const nbody_ctx* c, int nblocks) {    // ring slots of the persistent launch, 0 where it does not apply
+    const int rings = nblocks * 2;
+    const int slots = 4 * (c->num_cus < (rings + 3) / 4 ? c->num_cus : (rings + 3) / 4);
+    return rings < 2 * slots || rings > c->q_rings_cap ? 0 : slots;
+}
+template <bool kProbe>
+bool launch_ring_queue(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to) {
+    const int slots = ring_queue_slots(c, nblocks);
+    if (slots == 0) return false;
+    const int tiles = c->n_upper / kTile > 0 ? c->n_upper / kTile : 1;
+    launch_ring<4, 32, 8, kProbe, 4, true>(c, p, nblocks, log, to, slots, (tiles + kQueueSegments - 1) / kQueueSegments);
+    return true;
 }
 template <>
 void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to) {
@@ -348,12 +384,18 @@ void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks,
         case 55: launch_ring<8, 32, 2, false, 2>(c, p, nblocks, log, to); return;   // tuning: 2 x 8 with a 128-cycle poll interval
         case 56: launch_ring<8, 32, 4, false, 2>(c, p, nblocks, log, to); return;   // tuning: 2 x 8 with a 256-cycle poll interval
         case 58: launch_ring<8, 32, 8, true, 2>(c, p, nblocks, log, to); return;    // tuning: in-kernel phase stamps
+        case 59: launch_ring<4, 32, 8, true, 4>(c, p, nblocks, log, to); return;    // tuning: the same stamps at 4 x 4
+        case 60: if (launch_ring_queue<false>(c, p, nblocks, log, to)) return; break;  // 4 x 4 persistent where it applies
+        case 61: launch_ring<4, 32, 8, false, 4, true>(c, p, nblocks, log, to, nblocks * 2, 1); return;   // ... every walk in segments of 1 tile
+        case 62: launch_ring<4, 32, 8, false, 4, true>(c, p, nblocks, log, to, nblocks * 2, 3); return;   // ... of 3 tiles
+        case 63: if (launch_ring_queue<true>(c, p, nblocks, log, to)) return; break;   // tuning: stamps of the persistent form
         default: break;
     }
     // default: chosen by how many bodies this rank owns, i.e. how many ordered chains there are to fill the chip with
     // (measured on MI355X with csrc/tune/ring_probe.py, profiles/r02_ring_*):
     //   >= 48k bodies : ring kernel, workgroups of 4 rings x 4 waves (256 bodies): 32.2 ms at 262144 own bodies
-    //                   (one lane per body: 33.6), 16.6 / 8.4 ms at 131072 / 65536 (18.5 / 10.2)
+    //                   (one lane per body: 33.6), 16.6 / 8.4 ms at 131072 / 65536 (18.5 / 10.2); from two rounds of rings
+    //                   on (131072 own bodies on 256 CUs) in its persistent form (launch_ring_queue)
     //   >= 24k bodies : ring kernel, workgroups of 2 rings x 8 waves (128 bodies): fills the chip with half the bodies
     //                   (4.35 ms at 32768 own bodies of 262144; 4 x 4: 5.4)
     //   below         : ring kernel, one ring of 8 waves per workgroup: twice the workgroups to spread over the CUs
@@ -361,8 +403,9 @@ void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks,
     // Poll interval of the hand-off wait: s_sleep 8 (512 cycles) where the launch is bound by evaluation - a poll takes
     // issue slots from the waves that evaluate: -0.5 ... -1 % against s_sleep 2 -, s_sleep 2 for the small launches, which
     // are bound by the chain (N = 16384: 0.185 ms; with s_sleep 8: 0.218).
-    if (c->own_upper >= 49152) launch_ring<4, 32, 8, false, 4>(c, p, nblocks, log, to);
-    else if (c->own_upper >= 24576) launch_ring<8, 32, 8, false, 2>(c, p, nblocks, log, to);
+    if (c->own_upper >= 49152) {
+        if (!launch_ring_queue<false>(c, p, nblocks, log, to)) launch_ring<4, 32, 8, false, 4>(c, p, nblocks, log, to);
+    } else if (c->own_upper >= 24576) launch_ring<8, 32, 8, false, 2>(c, p, nblocks, log, to);
     else launch_ring<8, 32, 2, false, 1>(c, p, nblocks, log, to);
 }
 
@@ -525,7 +568,7 @@ void free_all(nbody_ctx* c) {
     hipFree(c->J); hipFree(c->Vown); hipFree(c->S_J); hipFree(c->S_V);
     if (c->gather && c->gather != c->slot) hipFree(c->gather);
     hipFree(c->slot);
-    hipFree(c->blk_counts); hipFree(c->tile_rmax); hipFree(c->Jt); hipFree(c->meta); hipFree(c->meta_all); hipFree(c->events); hipFree(c->d_img);
+    hipFree(c->blk_counts); hipFree(c->tile_rmax); hipFree(c->Jt); hipFree(c->q_head); hipFree(c->q_done); hipFree(c->q_state); hipFree(c->meta); hipFree(c->meta_all); hipFree(c->events); hipFree(c->d_img);
     hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
     hipFree(c->ids.map[0]); hipFree(c->ids.map[1]); hipFree(c->ids.lineage); hipFree(c->ids.done);
     hipFree(c->trk.buf); hipFree(c->trk.sel);
@@ -719,6 +762,12 @@ int nbody_ctx_create(nbody_ctx** out, const nbody_ctx_desc* d) {
     if (d->precision != NBODY_F64) {
         CTX_TRY(hipMalloc((void**)&c->Jt, sizeof(float) * 4 * kTile * (size_t)c->n_tiles));
         CTX_TRY(hipMemset(c->Jt, 0, sizeof(float) * 4 * kTile * (size_t)c->n_tiles));
+        c->q_rings_cap = 2 * (c->cap_own / kTile + 2);
+        CTX_TRY(hipMalloc((void**)&c->q_head, 64));
+        CTX_TRY(hipMemset(c->q_head, 0, 64));
+        CTX_TRY(hipMalloc((void**)&c->q_done, sizeof(unsigned long long) * (size_t)c->q_rings_cap));
+        CTX_TRY(hipMemset(c->q_done, 0, sizeof(unsigned long long) * (size_t)c->q_rings_cap));
+        CTX_TRY(hipMalloc((void**)&c->q_state, sizeof(unsigned long long) * 4 * 64 * (size_t)c->q_rings_cap));
     }
     // Meta and Counters share one device block (and one pinned host block): the per-step look at them is ONE copy
     CTX_TRY(hipMalloc((void**)&c->meta, kMetaBlockBytes));
@@ -1355,12 +1404,19 @@ const char* nbody_force_kernel_name(nbody_ctx* c) {
         case 11: case 12: case 14: case 18: return "forces_v3_f32";
         case 31: case 32: return "forces_v3w_f32";
         case 50: case 55: case 56: case 58: return "forces_ring_f32 (2 rings x 8 waves per workgroup)";
-        case 52: return "forces_ring_f32 (4 rings x 4 waves per workgroup)";
+        case 52: case 59: return "forces_ring_f32 (4 rings x 4 waves per workgroup)";
+        case 61: case 62: return "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)";
+        case 60: case 63:
+            if (ring_queue_slots(c, c->own_upper / kTile > 0 ? c->own_upper / kTile : 1) != 0)
+                return "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)";
+            break;
         case 53: return "forces_ring_f32 (2 rings x 8 waves, 16-position turns)";
         case 54: return "forces_ring_f32 (1 ring x 8 waves per workgroup)";
         default: break;
     }
-    if (c->own_upper >= 49152) return "forces_ring_f32 (4 rings x 4 waves per workgroup)";
+    if (c->own_upper >= 49152)
+        return ring_queue_slots(c, c->own_upper / kTile) != 0 ? "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)"
+                                                              : "forces_ring_f32 (4 rings x 4 waves per workgroup)";
     if (c->own_upper >= 24576) return "forces_ring_f32 (2 rings x 8 waves per workgroup)";
     return "forces_ring_f32 (1 ring x 8 waves per workgroup)";
 }

@@ -755,6 +755,10 @@ __device__ __forceinline__ double dpp_row_shl(double v) {   // K > 1 is fp32 onl
 // A wait that exceeds p.spin_limit polls is reported (Counters::errors, sticky on the host) and POISONS the chain:
 // the state becomes NaN and a dead mark travels with the sequence number, so every later turn passes at once and
 // the step's output cannot be mistaken for a result.
+// kQueue (4 x 4 only): the PERSISTENT form.  One workgroup per CU; every ring of it is a slot that pulls items - whole walks,
+// then segments of the last round's walks - from a device counter, so that a CU that is ahead takes work over from one that is
+// behind.  A walk that changes slots travels as its two LDS records per lane through global memory.  The turn loop is the
+// one-shot form's; everything else is described where the item loop starts.
 // ---------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* LdsPtr;
 typedef int Int4 __attribute__((ext_vector_type(4)));
@@ -806,7 +810,18 @@ struct RingArgs {
     const float* Jt;
     int cap_own;                 // entries of Vown / S_J / S_V
     int n_tiles;                 // entries of tile_rmax, 2 KiB tiles of Jt
+    // the persistent form (kQueue) only; all of it is loaded where it is used
+    unsigned* q_head;            // {next item, ring slots that have left}: both 0 between launches (the last slot clears them)
+    unsigned long long* q_done;  // per ring of the launch: launch number << 32 | segments of its walk that are done
+    unsigned long long* q_state; // per ring: the two LDS records of its 64 lanes between segments, [ring][4][64] x 8 bytes
+    unsigned q_launch;           // number of this force launch on the context, never 0: done words need no clearing
+    int q_rings;                 // rings of the launch
+    int q_whole;                 // the first q_whole rings are one item each ...
+    int q_seg_tiles;             // ... the walks of the others are cut into segments of this many tiles
 };
+typedef __attribute__((address_space(1))) unsigned* GlobalU32Ptr;
+typedef __attribute__((address_space(1))) unsigned long long* GlobalU64Ptr;
+typedef volatile __attribute__((address_space(3))) long long* LdsI64Ptr;
 template <typename A>
 __device__ __forceinline__ A ring_late_arg(unsigned byte_offset) {
 #if defined(__HIP_DEVICE_COMPILE__)                        // (the host pass of hipcc only needs the declaration)
@@ -822,7 +837,7 @@ __device__ __forceinline__ A ring_late_arg(unsigned byte_offset) {
 #define NB_RING_LATE(field) \
     ring_late_arg<decltype(((const RingArgs*)nullptr)->field)>((unsigned)__builtin_offsetof(RingArgs, field))
 
-template <bool kLog, int kW, int kT, int kSleep, bool kProbe, int kRings>
+template <bool kLog, int kW, int kT, int kSleep, bool kProbe, int kRings, bool kQueue = false>
 __global__ __launch_bounds__(kRings * kW * kWave) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void forces_ring_f32(const RingArgs args) {
     typedef float T;
@@ -836,6 +851,7 @@ void forces_ring_f32(const RingArgs args) {
     constexpr int kTilesPerRound = kW / kTurnsPerTile;
     constexpr int kWin = kWave + kT;                       // window entries a turn can touch (kWin - 1 used)
     static_assert(kRings == 1 || kRings == 2 || kRings == 4, "rings (64 bodies each) per workgroup");
+    static_assert(!kQueue || kW == kTurnsPerTile, "persistent form: an item is whole tiles and a wave keeps its part of every tile");
     // Per wave, double buffered, COMPONENT-MAJOR: x[kWin] y[kWin] m[kWin] r[kWin].  A lane's walk positions r, r + 1 are
     // then two consecutive words of each component: one ds_read2_b32 fills the register pair a packed fp32 instruction
     // takes, so two walk positions share EVERY instruction of the term (with records in LDS the differences and squares
@@ -843,6 +859,7 @@ void forces_ring_f32(const RingArgs args) {
     __shared__ float win_all[kRings][kW][2][4][kWin];
     __shared__ Int4 hand_all[kRings][kWave];               // {fx, fy, seq, flags = deleted} per lane
     __shared__ Float4 hand_m_all[kRings][kWave];           // {mnew, rnew, mi, -}: rewritten only when mnew / rnew change
+    __shared__ long long item_all[kQueue ? kRings : 1][2]; // persistent form: {claims of this slot so far << 32 | item}, twice
     const int N = meta->n, lo = meta->lo, cnt = meta->cnt;
     const bool all_bounded = (meta->summary & kSummaryUnbounded) == 0, any_radius = (meta->summary & kSummaryRadius) != 0;
     // every coordinate of the replica in [2^-16, 2^38), every radius +0, every mass finite: coincident bodies are the only
@@ -850,16 +867,11 @@ void forces_ring_f32(const RingArgs args) {
     const bool nan_screen = meta->summary == 0;
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid / kWave);
-    const int ring = wv / kW;                              // which 64 bodies of the block
+    const int ring = wv / kW;                              // which 64 bodies of the block (persistent form: which ring slot)
     const int w = wv % kW;                                 // place in the ring
     const int l = tid % kWave;
     const int wg = blockIdx.x;
-    const int ring_g = wg * kRings + ring;                 // ring of the launch: two per reference block
-    const int half = ring_g % 2;
-    const int b = lo / kTile + ring_g / 2;                 // reference block
-    const int t0 = half * kWave;
-    const int t = t0 + l;                                  // threadIdx.x of this lane's body in the reference
-    const long long blk0 = (long long)b * kTile;
+    const int slot = wg * kRings + ring;                   // ring slot of the launch
     float(&win)[kW][2][4][kWin] = win_all[ring];
     Int4(&hand)[kWave] = hand_all[ring];
     Float4(&hand_m)[kWave] = hand_m_all[ring];
@@ -867,554 +879,704 @@ void forces_ring_f32(const RingArgs args) {
     const bool lit = args.p.literal != 0;
     const int ntiles = lit ? nb : (N + kTile - 1) / kTile;
     const int nturns = ntiles * kTurnsPerTile;
-
-    const bool mine = blk0 + t >= lo && blk0 + t < (long long)lo + cnt;
-    const bool active = mine && blk0 + t < N && (!lit || blk0 + t < (long long)nb * kTile);
-    // The lane's body index, formed where it is needed (rare path, epilogue) from a lane number hipcc cannot see through:
-    // kept across the turn loop it is two vector registers the evaluation cannot spare.
-    auto body_index64 = [&]() -> long long {
-        int lane = l;
-        asm volatile("" : "+v"(lane));
-        return blk0 + t0 + lane;
-    };
-    // What a lane keeps in REGISTERS across the turns is its position and radius only: every fast turn needs them.  The
-    // rest of its state lives in LDS between turns - the running sum and `deleted` in the hand-off record, {mnew, rnew, mi}
-    // in the rare record - and is picked up where it is needed: by the general code and by the epilogue.
-    T xi = 0, yi = 0, ri = 0;
-    {
-        T mi = 0;
-        if (mine) {                                        // own start-of-step state, from the tile-planar copy like the windows
-            const long long i64 = blk0 + t;
-            const int i = (int)(i64 < 0x7fffffff ? i64 : 0x7fffffff);
-            const float* me = Jt + (size_t)(i / kTile) * (4 * kTile) + (i % kTile);
-            xi = me[0]; yi = me[kTile]; mi = me[2 * kTile]; ri = me[3 * kTile];
-        }
-        // the loads are waited for HERE: left to hipcc, the wait for `ri` lands at its first use - inside the turn loop,
-        // behind the next window's prefetch, which it would then wait for in every turn
-        asm volatile("" : "+v"(xi), "+v"(yi), "+v"(mi), "+v"(ri));
-        if (w == 0) {
-            *(LdsInt4Ptr)&hand[l] = Int4{0, 0, 0, 0};
-            *(LdsFloat4Ptr)&hand_m[l] = Float4{mi, ri, mi, 0.0f};            // mnew = mi, rnew = ri (:174-175)
-        }
-    }
-    const int spin_limit = __builtin_amdgcn_readfirstlane(args.p.spin_limit);   // (kept out of the poll loop's reach)
+    const int q_spin_limit = kQueue ? __builtin_amdgcn_readfirstlane(args.p.spin_limit) : 0;   // the persistent form's own waits
     bool dead = false;
     int timeouts = 0;
-    const bool lane_ok = !active || ((abs_(xi) < kCoordBound) && (abs_(yi) < kCoordBound));
-    const bool wave_ok = __ballot(!lane_ok) == 0ull;
-    int pairs_rare = 0;                                    // pairs of this lane's turns that left the common path
-    const LdsInt4Ptr hand_l = (LdsInt4Ptr)&hand[l];
-    const LdsFloat4Ptr hand_m_l = (LdsFloat4Ptr)&hand_m[l];
-    __syncthreads();                                       // the only workgroup barrier: seq = 0 everywhere
-    if (blk0 + t0 >= (long long)lo + cnt) return;          // a ring without own bodies (after the barrier)
-    // Two rings share a CU's SIMDs (two per workgroup here, or two workgroups per CU), and the instruction arbiter
-    // serves the OLDER wave first at equal priority: left alone, the older ring runs at full speed, the younger one
-    // on what is left, and the CU then spends a third of the kernel with one ring only (measured: workgroups ended at
-    // 3.2 and 4.8 ms of a 4.8 ms launch, profiles/r02_ring_fairness.txt).  With both rings in one workgroup each
-    // wave compares the two chains' progress at the start of a turn and evaluates at priority 1 when its own ring is
-    // behind, 0 otherwise: the rings stay level and finish together.
-    typedef const volatile __attribute__((address_space(3))) int* LdsSeqPtr;
-    const LdsSeqPtr seq_mine = (LdsSeqPtr)&hand_all[ring][0] + 2;
-    const LdsSeqPtr seq_o1 = (LdsSeqPtr)&hand_all[(ring + 1) % kRings][0] + 2;    // the other rings of the workgroup
-    const LdsSeqPtr seq_o2 = (LdsSeqPtr)&hand_all[(ring + 2) % kRings][0] + 2;
-    const LdsSeqPtr seq_o3 = (LdsSeqPtr)&hand_all[(ring + 3) % kRings][0] + 2;
-    unsigned long long pr_eval = 0, pr_wait = 0, pr_chain = 0, pr_check = 0, pr_polls = 0, pr_t0 = 0, pr_r0 = 0;
-    if (kProbe) { pr_t0 = __builtin_readcyclecounter(); pr_r0 = wall_clock64(); }
-
-    // First body of the tile of this wave's current turn (literal: cyclic tile b + kk), kept incrementally: a wave
-    // moves on by kW turns = kTilesPerRound tiles at a time, and a division here would cost as much as the turn's
-    // arithmetic.
-    auto tile_start_slow = [&](int kk) -> long long {
-        if (!lit) return (long long)kk * kTile;
-        return (blk0 % N + (long long)kk * kTile) % N;
-    };
-    auto round_on = [&](long long st) -> long long {
-        st += kTilesPerRound * kTile;
-        if (lit) while (st >= N) st -= N;                  // a next turn exists only when N > kTilesPerRound tiles: once
-        return st;
-    };
-    auto tile_len = [&](int kk, long long st) -> int {
-        if (lit) return (kk == nb - 1) ? N % (kTile + 1) : kTile;             // :194 (quirk Q1)
-        return (N - st) < kTile ? (int)(N - st) : kTile;
-    };
-    // Every turn reads its tile entries from the wave's LDS window, never from the replica.  Kind of a turn's window:
-    // 0 none (past the walk), 1 the standard window of a full tile, 2 a truncated tile (literal: the last one, of
-    // N mod 129 entries; clean: the partial last one), held whole.
-    auto turn_kind = [&](int tau, long long st) -> int {
-        if (tau >= nturns) return 0;
-        return tile_len(tau / kTurnsPerTile, st) == kTile ? 1 : 2;
-    };
-    // may a full tile take the fast path?  literal: yes (the self position, tile 0 / walk position 0, is masked in the
-    // first turn); clean: not the tile that holds the workgroup's own bodies (the self position differs per lane)
-    auto fast_tile = [&](int kk) -> bool { return lit || kk != b; };
-    // The standard window: entry j of the window is tile entry (wbase0 + off0 + j) mod 128, and off0 is the same
-    // for every turn of a wave (kW is a multiple of the turns per tile): the tile entries this lane fetches are two
-    // per-lane constants, the body index is that plus the tile's first body, wrapped at most once (st < N, e < 128 <= N).
-    const int wbase0 = lit ? t0 : 0;                       // literal: lane l reads window[l + r]; clean: window[r]
-    const int nwin = lit ? (kWave + kT - 1) : kT;          // entries of the window that are used
-    // (recomputed per window from the lane number - two instructions - instead of living in two registers)
-    auto first_entry = [&]() -> unsigned {
-        int lane = l;
-        asm volatile("" : "+v"(lane));
-        return (unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane) & (kTile - 1);
-    };
-    auto window_offset = [&](long long st, unsigned e) -> unsigned {   // byte offset of the body's x in the tiled copy Jt
-        const unsigned src = (unsigned)st + e;
-        const unsigned wrapped = src - (unsigned)N;        // huge when src < N
-        const unsigned idx = src < wrapped ? src : wrapped;
-        return ((idx / kTile) * (4u * kTile) + (idx % kTile)) * (unsigned)sizeof(T);
-    };
-    // Loaded from the replica STRAIGHT INTO LDS, one component of 64 bodies per instruction (lane l's word lands at
-    // base + 4 l; the per-lane source address does the transposition): the prefetch holds no registers and stays in
-    // flight for a whole turn.  The radii are only fetched when some radius of the replica is not +0 (Meta::summary).
-    auto issue_entries = [&](unsigned tile_byte, unsigned byte_offset, unsigned base, unsigned comp_bytes) {
-        // Source: Jt, the replica once more, tile by tile component-major (x[128] y[128] m[128] r[128] per aligned
-        // 128-body tile, written next to J by unpack_slots): a wave's 64 entries of one component are 256 contiguous
-        // bytes - two or three cache lines per instruction where the 16-byte records took eight or nine -, and the
-        // radius lines are never touched while every radius is +0: 3 of the 4 MiB, which an XCD's 4 MiB L2 keeps from one
-        // round of workgroups to the next (fabric-side reads halved, profiles/r02_traffic_pmc.json).
-        // The planes of a tile are 512 bytes apart.  Their base pointers are formed HERE, from an offset hipcc cannot see
-        // through: hoisted out of the turn loop they are three more scalar register pairs the kernel does not have
-        // (spilled pairs cost v_readlanes per turn).
-        unsigned long long plane = kTile * sizeof(T);
-        asm volatile("" : "+s"(plane));
-        if (kLog) {                                        // the four words this lane fetches lie inside Jt
-            const unsigned long long last = (unsigned long long)tile_byte + byte_offset + 3 * kTile * sizeof(T) + sizeof(T);
-            if (last > (unsigned long long)NB_RING_LATE(n_tiles) * (4 * kTile * sizeof(T))) {
-                atomicAdd(&NB_RING_LATE(ctr)->errors, kIndexError);
-                return;
-            }
+    unsigned long long pr_eval = 0, pr_wait = 0, pr_chain = 0, pr_check = 0, pr_polls = 0, pr_turns = 0, pr_t0 = 0, pr_r0 = 0;
+    // PERSISTENT FORM (kQueue).  The launch is one workgroup per CU and every ring of it is a SLOT that pulls ITEMS from a
+    // queue until none is left: an item is a whole walk (the first q_whole rings of the launch) or, for the other rings, one
+    // segment of q_seg_tiles tiles of a walk.  Item q_whole + k is (segment k / F, ring q_whole + k % F) with F the rings
+    // that are cut: every ring's segment s is drawn before anybody's segment s + 1, so the item a segment needs was drawn
+    // earlier, by a slot that is running - no item ever waits for one that has not started, whatever else is on the GPU.
+    // Between the segments of a walk the chain state is the two LDS records of the 64 lanes: the wave that took the
+    // segment's last turn stores them (write-through stores, then one flag word per ring) and wave 0 of the slot that drew
+    // the next segment loads them before the chain's first add - the other waves evaluate meanwhile.  Sequence numbers run
+    // on from item to item within a slot (one more per item: the closing turn, below), so the hand-off test and the
+    // priority rule are the ones of the one-shot form.
+    int seq_base = 0;                                      // sequence number of the current item's first turn
+    int claims = 0;                                        // items this slot has drawn
+    if (kQueue) {
+        if (w == 0) {
+            *(LdsInt4Ptr)&hand[l] = Int4{0, 0, 0, 0};
+            if (l < 2) *(LdsI64Ptr)&item_all[ring][l] = 0ll;
         }
-        const char* const src = (const char*)Jt + tile_byte;
-        load_to_lds_b32(src, byte_offset, base);
-        load_to_lds_b32(src + plane, byte_offset, base + comp_bytes);
-        load_to_lds_b32(src + 2 * plane, byte_offset, base + 2 * comp_bytes);
-        if (any_radius) load_to_lds_b32(src + 3 * plane, byte_offset, base + 3 * comp_bytes);
-    };
-    auto issue_window = [&](long long st, int buf) {
-        const unsigned base = __builtin_amdgcn_readfirstlane(lds_offset_of(&win[w][buf][0][0]));
-        const unsigned e0 = first_entry();
-        const unsigned e1 = e0 ^ kWave;                    // the entry 64 further on
-        if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= N) {
-            // the common case - the window's tile is an aligned tile of Jt -: the tile goes into the scalar base address,
-            // the lanes' offsets are the two per-lane constants, no vector arithmetic at all
-            const unsigned tile_byte = ((unsigned)st / kTile) * (4u * kTile * (unsigned)sizeof(T));
-            if (l < nwin) issue_entries(tile_byte, e0 * (unsigned)sizeof(T), base, kWin * (unsigned)sizeof(T));
-            if (l + kWave < nwin) issue_entries(tile_byte, e1 * (unsigned)sizeof(T), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
-        } else {
-            if (l < nwin) issue_entries(0u, window_offset(st, e0), base, kWin * (unsigned)sizeof(T));
-            if (l + kWave < nwin) issue_entries(0u, window_offset(st, e1), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
-        }
-    };
-    // A truncated tile: its L <= 128 entries in order, component-major x[128] y[128] m[128] r[128] across BOTH window
-    // buffers (2 * 4 * kWin >= 4 * 128 words), so it can only be issued when the wave is done with its current window:
-    // after the hand-off of the turn before.
-    static_assert(2 * kWin >= kTile, "a whole tile fits the two window buffers");
-    float* const whole = &win[w][0][0][0];
-    auto issue_truncated = [&](long long st, int L) {
-        const unsigned base = __builtin_amdgcn_readfirstlane(lds_offset_of(whole));
-        if (l < L) issue_entries(0u, window_offset(st, (unsigned)l), base, kTile * (unsigned)sizeof(T));
-        if (l + kWave < L) issue_entries(0u, window_offset(st, (unsigned)(l + kWave)), base + kWave * (unsigned)sizeof(T), kTile * (unsigned)sizeof(T));
-    };
-    // one entry of a window / of the whole truncated tile, as a record (general code only)
-    auto window_record = [&](const float* comp0, int stride, int idx) -> Rec<T> {
-        return Rec<T>{comp0[idx], comp0[stride + idx], comp0[2 * stride + idx], any_radius ? comp0[3 * stride + idx] : 0.0f};
-    };
-    // after the loads have landed: are all coordinates of the window bounded, is some radius not +0.0f
-    // The collision screen of a fast turn needs an upper bound of the radii the window holds.  The window's bodies are
-    // J[st .. st + 127] (wrapped at N): they lie in the aligned tiles st / 128 and st / 128 + 1 and, when wrapped, tile 0;
-    // unpack_slots keeps max |radius| per aligned tile.  Scalar loads, issued with the window a turn ahead.
-    auto window_rmax = [&](long long st) -> float {
-        if (!any_radius) return 0.0f;
-        const int ta = __builtin_amdgcn_readfirstlane((int)(st / kTile));
-        if (kLog && (ta < 0 || ta + 1 >= NB_RING_LATE(n_tiles))) {
-            if (l == 0) atomicAdd(&NB_RING_LATE(ctr)->errors, kIndexError);
-            return __builtin_inff();                       // every lane is flagged: the general code decides
-        }
-        const float ra = tile_rmax[ta], rb = tile_rmax[ta + 1];
-        const float rw = (st + kTile > N) ? tile_rmax[0] : 0.0f;
-        const float rab = ra > rb ? ra : rb;
-        return rab > rw ? rab : rw;
-    };
-    struct WindowState { bool fast; float rmax; };
-    auto check_window = [&](int kind, int kk, int buf, long long st_w) -> WindowState {
-        if (kind != 1) return WindowState{false, 0.0f};    // (a truncated tile is waited for where it is read)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // issued a whole turn ago
-        __builtin_amdgcn_wave_barrier();
-        // the whole replica is bounded (Meta::summary): no scan of the window; all its radii are +0 or not, globally
-        if (all_bounded) return WindowState{wave_ok && fast_tile(kk), window_rmax(st_w)};
-        Rec<T> r0{0, 0, 0, 0}, r1{0, 0, 0, 0};
-        if (l < nwin) r0 = window_record(&win[w][buf][0][0], kWin, l);
-        if (l + kWave < nwin) r1 = window_record(&win[w][buf][0][0], kWin, l + kWave);
-        const bool bad0 = !((abs_(r0.x) < kCoordBound) && (abs_(r0.y) < kCoordBound));
-        const bool bad1 = !((abs_(r1.x) < kCoordBound) && (abs_(r1.y) < kCoordBound));
-        WindowState ws;
-        ws.fast = __ballot(bad0 || bad1) == 0ull && wave_ok && fast_tile(kk);
-        ws.rmax = window_rmax(st_w);
-        return ws;
-    };
-    // the general code on this turn's walk positions, records from the window (kind 1) / the whole tile (kind 2)
-    // `bounded`: the window passed the coordinate check (a fast turn redone for a flagged lane): a pair that is no
-    // collision and not closer than 2^-40 then takes the scalar form of the fast chain - the same bits as the general
-    // code's IEEE square root and reciprocal (nbody_selftest_ieee_f32) at a quarter of the instructions; a flagged
-    // lane holds up its whole ring, so this path is worth keeping short.
-    auto general_turn = [&](BodyAcc<T>& a, int kind, int kk, long long st, int L, int off0, int buf, bool bounded) {
-        const long long i64 = body_index64();
-        const int i = (int)(i64 < 0x7fffffff ? i64 : 0x7fffffff);
-        const T growth = NB_RING_LATE(p.growth);
-        Event* const ev = kLog ? NB_RING_LATE(ev) : nullptr;
-        const int ev_cap = kLog ? NB_RING_LATE(ev_cap) : 0;
-        Counters* const ctr = kLog ? NB_RING_LATE(ctr) : nullptr;
-        const int step = kLog ? meta->step : 0;
-        if (kind == 2) {                                   // issued after the previous own turn's hand-off
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-        }
-        const int hi = off0 + kT < L ? off0 + kT : L;
-        int lane_entry = lit ? l : 0;                      // this lane's first window entry.  Computed HERE: hoisted out of
-        asm volatile("" : "+v"(lane_entry));               // the turn loop it is one more register the fast path cannot spare
-        const int t = (int)(i64 - blk0);                   // threadIdx.x of the body in the reference
-#pragma unroll 1
-        for (int off = off0; off < hi; ++off) {
-            int sidx;
-            long long j;
-            if (lit) {
-                if (kk == 0 && off == 0) continue;                                 // :200-204
-                sidx = (L == kTile) ? ((t + off) & (kTile - 1)) : ((t + off) % L); // :207
-                j = st + sidx;
-                if (j >= N) j %= N;
-            } else {
-                sidx = off;
-                j = st + off;
-                if (j == i64) continue;
-            }
-            const Rec<T> rec = kind == 1 ? window_record(&win[w][buf][0][0], kWin, lane_entry + (off - off0))
-                                         : window_record(whole, kTile, sidx);
-            if (bounded) {
-                const T dx = rec.x - a.xi, dy = rec.y - a.yi;
-                const T d2 = (dx * dx) + (dy * dy);
-                const T rs = a.ri + rec.r;
-                if (!(d2 <= fma_(rs, rs, kFastLo))) {      // no collision, inside the proved domain
-                    const T inv = fast_chain(d2).inv;
-                    a.fx = a.fx + (dx * rec.m) * inv;
-                    a.fy = a.fy + (dy * rec.m) * inv;
-                    continue;
-                }
-            }
-            interact<T, kLog>(a, rec, growth, i, (int)j, ev, ev_cap, ctr, step);
-        }
-    };
-
-    long long st = tile_start_slow(w / kTurnsPerTile);
-    int buf = 0;
-    int plain_turns = 0;                                   // turns of this wave that took the common path
-    bool first_plain = false;                              // ... the first turn of the walk among them (one pair less)
-    int kind = turn_kind(w, st);
-    if (kind == 1) issue_window(st, buf);
-    if (kind == 2) issue_truncated(st, tile_len(w / kTurnsPerTile, st));
-    WindowState cur = check_window(kind, w / kTurnsPerTile, buf, st);
-    for (int tau = w; tau < nturns; tau += kW) {
-        unsigned long long pt0 = 0, pt1 = 0, pt2 = 0, pt3 = 0;
-        if (kProbe) pt0 = __builtin_readcyclecounter();
-        const int kk = tau / kTurnsPerTile;
-        const int off0 = (tau % kTurnsPerTile) * kT;
-        const int L = tile_len(kk, st);
-        const bool fast = cur.fast;
-        const long long st_next = round_on(st);
-        const int kind_next = turn_kind(tau + kW, st_next);
-        if (kind_next == 1) issue_window(st_next, buf ^ 1);                  // in flight for the whole turn
-        const bool first = lit && tau == 0;                // walk position 0 is the body itself (:200-204)
-        if (kRings > 1) {                                  // behind the furthest ring of the workgroup: evaluate first
-            int ahead = *seq_o1;
-            if (kRings == 4) {
-                const int o2 = *seq_o2, o3 = *seq_o3;
-                ahead = ahead > o2 ? ahead : o2;
-                ahead = ahead > o3 ? ahead : o3;
-            }
-            if (*seq_mine < ahead) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-        }
-        // (2) the kT terms of this turn: walk positions 2v, 2v + 1 in the two halves of termx[v] / termy[v]
-        V2 termx[kT / 2], termy[kT / 2];
-        auto term_x = [&](int r) -> float { return (r & 1) ? termx[r / 2].y : termx[r / 2].x; };
-        auto term_y = [&](int r) -> float { return (r & 1) ? termy[r / 2].y : termy[r / 2].x; };
-        unsigned long long flag = 0;
-        auto evaluate = [&](auto screen_tag) {
-            constexpr bool kScreen = decltype(screen_tag)::value;     // false: no screen per pair (nan_screen)
-            const float* wx = &win[w][buf][0][lit ? l : 0];
-            const float* wy = wx + kWin;
-            const float* wm = wx + 2 * kWin;
-            const V2 ownx = {xi, xi}, owny = {yi, yi};
-            // Collision / tiny-distance screen, half an instruction per pair: a pair may only take the fast chain if it is
-            // no collision, d2 > (ri + rj)^2, and d2 > 2^-80 (the proved domain).  With R = |ri| + (largest |radius| the
-            // window can hold) every such pair has d2 > fma(R, R, 2^-80), a per-LANE constant of the turn, so the
-            // SMALLEST d2 of the lane's kT pairs decides for all of them (d2 is finite here - the coordinates are
-            // bounded - so no NaN can hide in the minimum; a NaN radius never collides and is not in the bound).  A
-            // lane below the threshold is redone by the general code, which applies the exact predicate.
-            const float reach = abs_(ri) + cur.rmax;
-            const float threshold = __builtin_fmaf(reach, reach, kFastLo);
-            float closest = kFastHi;
-            // the reads of a batch are issued one batch ahead (NB_RING_PREFETCH): their latency then runs under the arithmetic
-            // of the batch before instead of being exposed at every batch's start
-            V2 pxa = {wx[0], wx[1]}, pxb = {wx[2], wx[3]}, pya = {wy[0], wy[1]}, pyb = {wy[2], wy[3]};
-            V2 pma = {wm[0], wm[1]}, pmb = {wm[2], wm[3]};
-#pragma unroll
-            for (int r0 = 0; r0 < kT; r0 += 4) {           // four walk positions per batch of reads: a, a, b, b
-                const V2 xa = pxa, xb = pxb, ya = pya, yb = pyb, ma = pma, mb = pmb;
-                if (r0 + 4 < kT) {
-                    pxa = V2{wx[r0 + 4], wx[r0 + 5]}; pxb = V2{wx[r0 + 6], wx[r0 + 7]};
-                    pya = V2{wy[r0 + 4], wy[r0 + 5]}; pyb = V2{wy[r0 + 6], wy[r0 + 7]};
-                    pma = V2{wm[r0 + 4], wm[r0 + 5]}; pmb = V2{wm[r0 + 6], wm[r0 + 7]};
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const V2 dxa = xa - ownx, dxb = xb - ownx;
-                const V2 dya = ya - owny, dyb = yb - owny;
-                const V2 sxa = dxa * dxa, sxb = dxb * dxb;
-                const V2 sya = dya * dya, syb = dyb * dyb;
-                const V2 d2a = sxa + sya, d2b = sxb + syb; // three roundings per element (no contraction in this file)
-                if (kScreen) {
-                    const float first_d2 = (r0 == 0 && first) ? kFastHi : d2a.x;   // the self position is no pair
-                    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(closest) : "v"(closest), "v"(first_d2), "v"(d2a.y));
-                    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(closest) : "v"(closest), "v"(d2b.x), "v"(d2b.y));
-                }
-                V2 inva, invb;
-                fast_inv_cube2x2(d2a, d2b, inva, invb);
-                const V2 txa = dxa * ma, txb = dxb * mb;
-                const V2 tya = dya * ma, tyb = dyb * mb;
-                termx[r0 / 2] = txa * inva; termx[r0 / 2 + 1] = txb * invb;
-                termy[r0 / 2] = tya * inva; termy[r0 / 2 + 1] = tyb * invb;
-                // the terms are finished HERE (hipcc otherwise sinks the last multiply into the blocks that add them up
-                // and keeps both factors alive until then: twice the registers, spills)
-                asm volatile("" : "+v"(termx[r0 / 2]), "+v"(termx[r0 / 2 + 1]), "+v"(termy[r0 / 2]), "+v"(termy[r0 / 2 + 1]));
-            }
-            if (kScreen) flag = le_mask(closest, threshold);
-            // the reference skips the self position; the sum starts at +0.0f and +0 + +0 = +0: adding a zero term is
-            // the same bits (whatever the self "pair" evaluated to - NaN: d2 = 0 - is dropped here)
-            if (first) { termx[0].x = 0.0f; termy[0].x = 0.0f; }
-        };
-        if (fast) {
-            if (nan_screen) evaluate(std::false_type{});
-            else evaluate(std::true_type{});
-        }
-        if (kProbe) pt1 = __builtin_readcyclecounter();
-        // (3) the state after turn tau - 1.  Polled at raised priority: a poll is one LDS read plus scalar work, it
-        // takes next to nothing from the vector pipelines of the waves that are evaluating, and the chain moves on
-        // within one LDS round trip of the record being written.
-        Int4 h = Int4{0, 0, 0, 0};
-        bool timed_out = false;
-        __builtin_amdgcn_s_setprio(3);
-        if (tau > 0) {
-            int spins = 0;
-            for (;;) {
-                h = *hand_l;                               // one ds_read_b128
-                if (__ballot(h.z < tau) == 0ull) break;
-                if (++spins > spin_limit) { timed_out = true; break; }
-                if (kSleep > 0) __builtin_amdgcn_s_sleep(kSleep);
-            }
-            if (kProbe) pr_polls += spins + 1;
-        }
-        if (kProbe) pt2 = __builtin_readcyclecounter();
-        // (4) + (5).  The common case - a fast turn, no flagged lane, the sequence number the expected one - is kept as
-        // short as the arithmetic allows, because it is the serial part of the whole workgroup: 2 kT dependent adds
-        // (x and y chains interleaved: scalar adds need no wait states between dependent instructions, packed ones
-        // do), then one LDS write; `flags` passes through untouched.  The last turn publishes too: the epilogue takes the
-        // final state from the records.
-        bool plain = fast && flag == 0ull && !dead && !timed_out && __ballot(h.z != tau) == 0ull;
-        if (__builtin_expect(plain, 1)) {
-            float fx = __int_as_float(h.x), fy = __int_as_float(h.y);
-#pragma unroll
-            for (int r = 0; r < kT; ++r) {
-                fx = fx + term_x(r);
-                asm("" : "+v"(fx));                        // keeps hipcc from pairing the two adds into one v_pk_add_f32
-                fy = fy + term_y(r);
-            }
-            // nan_screen: a coincident pair (d2 = 0: a collision, :215-226) made its term NaN, and a NaN among the kT terms
-            // is a NaN sum.  ONE comparison per turn instead of a v_min3 per two pairs; a lane whose sum was NaN already is
-            // flagged in every turn (slow, and right: its collisions still have to be found).
-            if (nan_screen) flag = __builtin_amdgcn_fcmpf(fx, fy, 8 /* llvm::CmpInst::FCMP_UNO */);
-            if (__builtin_expect(flag == 0ull, 1)) {
-                *hand_l = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), tau + 1, h.w};
-                __builtin_amdgcn_s_setprio(0);
-                plain_turns += 1;                          // a scalar: kT pairs per active lane, added up at the end
-                first_plain = first_plain || first;
-            } else {
-                plain = false;                             // the sums are dropped: the turn is redone below from `h`
-            }
-        }
-        if (__builtin_expect(!plain, 0)) {
-            // the lane's whole state, for the general code: position and radius from the registers, the running sum and
-            // `deleted` from the record just received, {mnew, rnew, mi} from the rare record (its last writer published
-            // it before the sequence number this wave has seen)
-            BodyAcc<T> a;
-            a.xi = xi; a.yi = yi; a.ri = ri;
-            a.fx = __int_as_float(h.x); a.fy = __int_as_float(h.y);
-            a.deleted = h.w & 1;
-            const Float4 hm = *hand_m_l;
-            a.mnew = hm.x; a.rnew = hm.y; a.mi = hm.z;
-            timeouts += timed_out ? 1 : 0;
-            dead = dead || timed_out || __ballot(h.z >= kRingDeadSeq) != 0ull;
-            const unsigned m_before = __float_as_uint(a.mnew), r_before = __float_as_uint(a.rnew);
-            if (fast && nan_screen) {                      // (a turn that came here without its sums: every NaN term flags its lane)
-#pragma unroll
-                for (int r = 0; r < kT; ++r) flag |= __builtin_amdgcn_fcmpf(term_x(r), term_y(r), 8);
-            }
-            if (fast) {
-                // The flagged lanes (a SUPERSET of the lanes with a collision or a tiny distance in this turn) get the exact
-                // status of each of their kT pairs, and they get it in parallel: lane r of the wave evaluates walk position r
-                // of flagged lane fl's body from the same window.  `hits`: positions that are collisions the reference
-                // handles and moves on from (:215-226: no force term); `odd`: some pair inside the guard that is not
-                // such a collision (tiny distance, the 2^-80 margin, a NaN mass) - that lane is redone by the general code.
-                unsigned hits = 0;
-                bool odd = false;
-                unsigned long long todo = flag & __ballot(active);
-                while (todo != 0ull) {
-                    const int fl = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
-                    todo &= todo - 1ull;
-                    const T xf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.xi), fl));
-                    const T yf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.yi), fl));
-                    const T mf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.mi), fl));
-                    const T rf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.ri), fl));
-                    int r = l & (kT - 1);                                       // formed HERE (see general_turn's lane_entry)
-                    asm volatile("" : "+v"(r));
-                    const Rec<T> rec = window_record(&win[w][buf][0][0], kWin, (lit ? fl : 0) + r);
-                    const T dx = rec.x - xf, dy = rec.y - yf;
-                    const T d2 = (dx * dx) + (dy * dy);
-                    const T rs = rf + rec.r;
-                    const bool is_pair = l < kT && !(first && r == 0);          // walk position 0 of tile 0 is the body itself
-                    const bool hit = d2 <= rs * rs && (mf >= rec.m || mf < rec.m); // interact(): `hit && (ge || lt)`
-                    const bool guarded = d2 <= fma_(rs, rs, kFastLo);              // what the fast chain must not see
-                    const unsigned long long hm = __ballot(is_pair && hit);
-                    const unsigned long long om = __ballot(is_pair && guarded && !hit);
-                    if (l == fl) { hits = (unsigned)hm; odd = om != 0ull; }
-                }
-                if (active) {
-                    if (odd) {
-                        general_turn(a, 1, kk, st, L, off0, buf, true);
-                    } else {
-                        float fx = a.fx, fy = a.fy;
-#pragma unroll
-                        for (int r = 0; r < kT; ++r) {
-                            const float nx = add_unmerged(fx, term_x(r));
-                            const float ny = add_unmerged(fy, term_y(r));
-                            const bool skip = ((hits >> r) & 1u) != 0u;            // a collision adds no force term (not even +0)
-                            fx = skip ? fx : nx;
-                            fy = skip ? fy : ny;
-                        }
-                        a.fx = fx; a.fy = fy;
-                        unsigned rest = hits;                                      // the collisions themselves, in walk order
-                        int lane_entry = lit ? l : 0;
-                        asm volatile("" : "+v"(lane_entry));                       // (see general_turn)
-                        const T growth = NB_RING_LATE(p.growth);
-                        while (rest != 0u) {
-                            const int r = __builtin_ctz(rest);
-                            rest &= rest - 1u;
-                            const Rec<T> rec = window_record(&win[w][buf][0][0], kWin, lane_entry + r);
-                            const bool ge = a.mi >= rec.m;
-                            if (ge) {                                              // :215-221
-                                a.mnew = a.mnew + rec.m;
-                                a.rnew = a.rnew + rec.r * growth;
-                            } else {                                               // :222-226
-                                a.deleted = 1;
-                            }
-                            if (kLog) {
-                                const long long i64 = body_index64();
-                                const int i = (int)(i64 < 0x7fffffff ? i64 : 0x7fffffff);
-                                long long j = lit ? st + (((int)(i64 - blk0) + off0 + r) & (kTile - 1)) : st + off0 + r;
-                                if (j >= N) j %= N;
-                                Counters* const ctr = NB_RING_LATE(ctr);
-                                const unsigned long long slot = atomicAdd(&ctr->events, 1ull);
-                                if (slot < (unsigned long long)NB_RING_LATE(ev_cap))
-                                    NB_RING_LATE(ev)[slot] = Event{meta->step, i, (int)j, ge ? 0 : 1};
-                            }
-                        }
-                    }
-                    pairs_rare += kT - (first ? 1 : 0);
-                }
-            } else if (active) {
-                general_turn(a, kind, kk, st, L, off0, buf, false);
-                const int hi = off0 + kT < L ? off0 + kT : L;
-                if (lit) {
-                    if (hi > off0) pairs_rare += (hi - off0) - ((kk == 0 && off0 == 0) ? 1 : 0);
-                } else {
-                    const long long i64 = body_index64();
-                    for (int off = off0; off < hi; ++off) pairs_rare += (st + off != i64) ? 1 : 0;
-                }
-            }
-            if (dead) {                                    // a hand-off wait gave up somewhere before: poison, never a result
-                a.fx = a.fy = a.mnew = a.rnew = __builtin_nanf("");
-                a.deleted = 0;
-            }
-            // publish: the rare record first, then the one the next wave polls (a wave's LDS operations execute in order)
-            if (__float_as_uint(a.mnew) != m_before || __float_as_uint(a.rnew) != r_before)
-                *hand_m_l = Float4{a.mnew, a.rnew, a.mi, 0.0f};
-            *hand_l = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : tau + 1,
-                           a.deleted & 1};
-            __builtin_amdgcn_s_setprio(0);
-        }
-        if (kProbe) pt3 = __builtin_readcyclecounter();
-        // the prefetched window of this wave's next turn
-        if (kind_next == 2) issue_truncated(st_next, tile_len((tau + kW) / kTurnsPerTile, st_next));   // both buffers are free now
-        buf ^= 1;
-        st = st_next;
-        kind = kind_next;
-        cur = check_window(kind, (tau + kW) / kTurnsPerTile, buf, st);
-        if (kProbe) {
-            pr_eval += pt1 - pt0; pr_wait += pt2 - pt1; pr_chain += pt3 - pt2;
-            pr_check += __builtin_readcyclecounter() - pt3;
-        }
+        __syncthreads();                                   // the only workgroup barrier of the persistent form
+        if (kProbe) { pr_t0 = __builtin_readcyclecounter(); pr_r0 = wall_clock64(); }
     }
-    // Nothing above this line in the loop is a memory access the compiler tracks in vmcnt (the window loads and the
-    // general code's record loads are inline assembly with their own waits): hipcc therefore places no vmcnt wait in
-    // the loop, and the only one there is check_window's, for a prefetch issued a whole turn earlier.
-    if (mine && (nturns - 1) % kW == w) {                  // the wave that took the last turn: epilogue, from the records it
-        const long long i64 = body_index64();              // has just written (a wave's LDS operations execute in order)
-        const int q = (int)(i64 - lo);
-        const Int4 hf = *hand_l;
-        const Float4 hm = *hand_m_l;
-        BodyAcc<T> a;
-        a.xi = xi; a.yi = yi; a.ri = ri; a.mi = hm.z;
-        a.fx = __int_as_float(hf.x); a.fy = __int_as_float(hf.y);
-        a.mnew = hm.x; a.rnew = hm.y; a.deleted = hf.w & 1;
-        Rec<T>* const S_J = NB_RING_LATE(S_J);
-        Vec2<T>* const S_V = NB_RING_LATE(S_V);
-        const bool q_ok = q >= 0 && q < NB_RING_LATE(cap_own);
-        const Vec2<T> v = q_ok ? NB_RING_LATE(Vown)[q] : Vec2<T>{0, 0};
-        if (!q_ok) {
-            atomicAdd(&NB_RING_LATE(ctr)->errors, kIndexError);
-        } else if (active) {
-            const StepParams<T> p = NB_RING_LATE(p);
-            Rec<T> out; Vec2<T> vout;
-            finish_body<T>(a, v, p, out, vout);
-            S_J[q] = out;
-            S_V[q] = vout;
-        } else {   // frozen body: no thread exists for it in the reference, state carried over unchanged
-            S_J[q] = Rec<T>{a.xi, a.yi, a.mi, a.ri};
-            S_V[q] = v;
+    for (;;) {                                             // one pass per item (one-shot forms: one pass)
+        int ring_g = slot;                                     // ring of the launch: two per reference block
+        int tau_lo = 0, tau_hi = nturns, seg = 0;              // the item's turns [tau_lo, tau_hi) of the ring's walk
+        if (kQueue) {
+            // wave 0 draws the number, the ring's other waves read it from LDS when they get here.  Two entries: wave 0 cannot
+            // publish item i + 2 before its last turn of item i + 1, which follows the closing turn of item i - and every
+            // wave has read entry i by then.  That needs every published item to have a turn for every wave: an item of a
+            // ring WITHOUT own bodies (the launch is sized for an upper bound of the own count) is dropped by wave 0
+            // before it publishes anything, or it would run ahead and write over entries the others have not read.
+            const LdsI64Ptr entry = (LdsI64Ptr)&item_all[ring][claims & 1];
+            claims += 1;
+            const int q_whole = NB_RING_LATE(q_whole), q_cut = NB_RING_LATE(q_rings) - q_whole;
+            const int seg_tiles = NB_RING_LATE(q_seg_tiles);
+            const int nseg = (ntiles + seg_tiles - 1) / seg_tiles;
+            auto decode = [&](int k) -> int {              // 0: the queue is empty, 1: a ring without own bodies, 2: an item
+                if ((long long)k >= q_whole + (long long)q_cut * nseg) return 0;
+                ring_g = k; seg = 0; tau_lo = 0; tau_hi = nturns;
+                if (k >= q_whole) {
+                    seg = (k - q_whole) / q_cut;
+                    ring_g = q_whole + (k - q_whole) % q_cut;
+                    tau_lo = seg * seg_tiles * kTurnsPerTile;
+                    tau_hi = tau_lo + seg_tiles * kTurnsPerTile < nturns ? tau_lo + seg_tiles * kTurnsPerTile : nturns;
+                }
+                const long long first = (long long)(lo / kTile + ring_g / 2) * kTile + (ring_g % 2) * kWave;
+                return first >= (long long)lo + cnt ? 1 : 2;
+            };
+            int k = 0x7fffffff, what = 0;
+            if (w == 0) {
+                do {
+                    unsigned drawn = 0;
+                    if (l == 0) drawn = __hip_atomic_fetch_add((GlobalU32Ptr)NB_RING_LATE(q_head), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    k = __builtin_amdgcn_readfirstlane((int)(drawn < 0x7fffffffu ? drawn : 0x7fffffffu));
+                    what = decode(k);
+                } while (what == 1);
+                if (l == 0) *entry = ((long long)claims << 32) | (long long)k;
+            } else {
+                for (int spins = 0;;) {
+                    const long long e = *entry;
+                    if (__builtin_amdgcn_readfirstlane((int)(e >> 32)) == claims) { k = __builtin_amdgcn_readfirstlane((int)e); break; }
+                    if (++spins > q_spin_limit) { timeouts += 1; break; }      // wave 0 is stuck: reported; nothing is left to do here
+                    if (kSleep > 0) __builtin_amdgcn_s_sleep(kSleep);
+                }
+                what = decode(k);
+            }
+            if (what != 2) break;                          // the queue is empty
         }
+        const int half = ring_g % 2;
+        const int b = lo / kTile + ring_g / 2;                 // reference block
+        const int t0 = half * kWave;
+        const int t = t0 + l;                                  // threadIdx.x of this lane's body in the reference
+        const long long blk0 = (long long)b * kTile;
+
+        const bool mine = blk0 + t >= lo && blk0 + t < (long long)lo + cnt;
+        const bool active = mine && blk0 + t < N && (!lit || blk0 + t < (long long)nb * kTile);
+        // The lane's body index, formed where it is needed (rare path, epilogue) from a lane number hipcc cannot see through:
+        // kept across the turn loop it is two vector registers the evaluation cannot spare.
+        auto body_index64 = [&]() -> long long {
+            int lane = l;
+            asm volatile("" : "+v"(lane));
+            return blk0 + t0 + lane;
+        };
+        // What a lane keeps in REGISTERS across the turns is its position and radius only: every fast turn needs them.  The
+        // rest of its state lives in LDS between turns - the running sum and `deleted` in the hand-off record, {mnew, rnew, mi}
+        // in the rare record - and is picked up where it is needed: by the general code and by the epilogue.
+        T xi = 0, yi = 0, ri = 0;
+        {
+            T mi = 0;
+            if (mine) {                                        // own start-of-step state, from the tile-planar copy like the windows
+                const long long i64 = blk0 + t;
+                const int i = (int)(i64 < 0x7fffffff ? i64 : 0x7fffffff);
+                const float* me = Jt + (size_t)(i / kTile) * (4 * kTile) + (i % kTile);
+                xi = me[0]; yi = me[kTile]; mi = me[2 * kTile]; ri = me[3 * kTile];
+            }
+            // the loads are waited for HERE: left to hipcc, the wait for `ri` lands at its first use - inside the turn loop,
+            // behind the next window's prefetch, which it would then wait for in every turn
+            asm volatile("" : "+v"(xi), "+v"(yi), "+v"(mi), "+v"(ri));
+            if (kQueue) {
+                if (w == 0) {                                  // the chain's state at the item's first turn, sequence number seq_base
+                    Int4 h0 = Int4{0, 0, seq_base, 0};
+                    Float4 m0 = Float4{mi, ri, mi, 0.0f};
+                    bool late = false;
+                    // the records are free: the slot's previous item has been read back (its closing turn, see the epilogue)
+                    for (int spins = 0;;) {
+                        const Int4 h = *(LdsInt4Ptr)&hand[l];
+                        if (__ballot(h.z < seq_base) == 0ull) break;
+                        if (++spins > q_spin_limit) { late = true; break; }
+                        if (kSleep > 0) __builtin_amdgcn_s_sleep(kSleep);
+                    }
+                    if (tau_lo > 0) {                          // a later segment of a walk: the state its predecessor left
+                        const GlobalU64Ptr done = (GlobalU64Ptr)NB_RING_LATE(q_done) + ring_g;
+                        const unsigned long long want = ((unsigned long long)NB_RING_LATE(q_launch) << 32) | (unsigned)seg;
+                        for (int spins = 0; !late;) {
+                            const unsigned long long have = __hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (__ballot(have < want) == 0ull) break;
+                            if (++spins > q_spin_limit) { late = true; break; }
+                            if (kSleep > 0) __builtin_amdgcn_s_sleep(kSleep);
+                        }
+                        // every load of the handed-over bytes bypasses this CU's L1, like every store of them wrote through
+                        const GlobalU64Ptr rs = (GlobalU64Ptr)NB_RING_LATE(q_state) + (size_t)ring_g * (4 * kWave) + l;
+                        const unsigned long long s0 = __hip_atomic_load(rs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const unsigned long long s1 = __hip_atomic_load(rs + kWave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const unsigned long long s2 = __hip_atomic_load(rs + 2 * kWave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const unsigned long long s3 = __hip_atomic_load(rs + 3 * kWave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        h0 = Int4{(int)(unsigned)s0, (int)(unsigned)(s0 >> 32),
+                                  (int)(unsigned)s1 >= kRingDeadSeq ? kRingDeadSeq : seq_base, (int)(unsigned)(s1 >> 32)};
+                        m0 = Float4{__uint_as_float((unsigned)s2), __uint_as_float((unsigned)(s2 >> 32)), __uint_as_float((unsigned)s3), 0.0f};
+                    }
+                    if (late) { timeouts += 1; dead = true; }  // reported and poisoned like a hand-off wait that gave up
+                    if (dead) {
+                        h0 = Int4{(int)0x7fc00000, (int)0x7fc00000, kRingDeadSeq, 0};
+                        m0.x = m0.y = __builtin_nanf("");
+                    }
+                    *(LdsFloat4Ptr)&hand_m[l] = m0;
+                    *(LdsInt4Ptr)&hand[l] = h0;
+                }
+            } else if (w == 0) {
+                *(LdsInt4Ptr)&hand[l] = Int4{0, 0, 0, 0};
+                *(LdsFloat4Ptr)&hand_m[l] = Float4{mi, ri, mi, 0.0f};            // mnew = mi, rnew = ri (:174-175)
+            }
+        }
+        const int spin_limit = __builtin_amdgcn_readfirstlane(args.p.spin_limit);   // (kept out of the poll loop's reach)
+        const bool lane_ok = !active || ((abs_(xi) < kCoordBound) && (abs_(yi) < kCoordBound));
+        const bool wave_ok = __ballot(!lane_ok) == 0ull;
+        int pairs_rare = 0;                                    // pairs of this lane's turns that left the common path
+        const LdsInt4Ptr hand_l = (LdsInt4Ptr)&hand[l];
+        const LdsFloat4Ptr hand_m_l = (LdsFloat4Ptr)&hand_m[l];
+        if (!kQueue) {
+            __syncthreads();                                   // the only workgroup barrier: seq = 0 everywhere
+            if (blk0 + t0 >= (long long)lo + cnt) return;      // a ring without own bodies (after the barrier)
+        }
+        // Two rings share a CU's SIMDs (two per workgroup here, or two workgroups per CU), and the instruction arbiter
+        // serves the OLDER wave first at equal priority: left alone, the older ring runs at full speed, the younger one
+        // on what is left, and the CU then spends a third of the kernel with one ring only (measured: workgroups ended at
+        // 3.2 and 4.8 ms of a 4.8 ms launch, profiles/r02_ring_fairness.txt).  With both rings in one workgroup each
+        // wave compares the two chains' progress at the start of a turn and evaluates at priority 1 when its own ring is
+        // behind, 0 otherwise: the rings stay level and finish together.
+        typedef const volatile __attribute__((address_space(3))) int* LdsSeqPtr;
+        const LdsSeqPtr seq_mine = (LdsSeqPtr)&hand_all[ring][0] + 2;
+        const LdsSeqPtr seq_o1 = (LdsSeqPtr)&hand_all[(ring + 1) % kRings][0] + 2;    // the other rings of the workgroup
+        const LdsSeqPtr seq_o2 = (LdsSeqPtr)&hand_all[(ring + 2) % kRings][0] + 2;
+        const LdsSeqPtr seq_o3 = (LdsSeqPtr)&hand_all[(ring + 3) % kRings][0] + 2;
+        if (kProbe && !kQueue) { pr_t0 = __builtin_readcyclecounter(); pr_r0 = wall_clock64(); }
+
+        // First body of the tile of this wave's current turn (literal: cyclic tile b + kk), kept incrementally: a wave
+        // moves on by kW turns = kTilesPerRound tiles at a time, and a division here would cost as much as the turn's
+        // arithmetic.
+        auto tile_start_slow = [&](int kk) -> long long {
+            if (!lit) return (long long)kk * kTile;
+            return (blk0 % N + (long long)kk * kTile) % N;
+        };
+        auto round_on = [&](long long st) -> long long {
+            st += kTilesPerRound * kTile;
+            if (lit) while (st >= N) st -= N;                  // a next turn exists only when N > kTilesPerRound tiles: once
+            return st;
+        };
+        auto tile_len = [&](int kk, long long st) -> int {
+            if (lit) return (kk == nb - 1) ? N % (kTile + 1) : kTile;             // :194 (quirk Q1)
+            return (N - st) < kTile ? (int)(N - st) : kTile;
+        };
+        // Every turn reads its tile entries from the wave's LDS window, never from the replica.  Kind of a turn's window:
+        // 0 none (past the walk), 1 the standard window of a full tile, 2 a truncated tile (literal: the last one, of
+        // N mod 129 entries; clean: the partial last one), held whole.
+        auto turn_kind = [&](int tau, long long st) -> int {
+            if (tau >= tau_hi) return 0;
+            return tile_len(tau / kTurnsPerTile, st) == kTile ? 1 : 2;
+        };
+        // may a full tile take the fast path?  literal: yes (the self position, tile 0 / walk position 0, is masked in the
+        // first turn); clean: not the tile that holds the workgroup's own bodies (the self position differs per lane)
+        auto fast_tile = [&](int kk) -> bool { return lit || kk != b; };
+        // The standard window: entry j of the window is tile entry (wbase0 + off0 + j) mod 128, and off0 is the same
+        // for every turn of a wave (kW is a multiple of the turns per tile): the tile entries this lane fetches are two
+        // per-lane constants, the body index is that plus the tile's first body, wrapped at most once (st < N, e < 128 <= N).
+        const int wbase0 = lit ? t0 : 0;                       // literal: lane l reads window[l + r]; clean: window[r]
+        const int nwin = lit ? (kWave + kT - 1) : kT;          // entries of the window that are used
+        // (recomputed per window from the lane number - two instructions - instead of living in two registers)
+        auto first_entry = [&]() -> unsigned {
+            int lane = l;
+            asm volatile("" : "+v"(lane));
+            return (unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane) & (kTile - 1);
+        };
+        auto window_offset = [&](long long st, unsigned e) -> unsigned {   // byte offset of the body's x in the tiled copy Jt
+            const unsigned src = (unsigned)st + e;
+            const unsigned wrapped = src - (unsigned)N;        // huge when src < N
+            const unsigned idx = src < wrapped ? src : wrapped;
+            return ((idx / kTile) * (4u * kTile) + (idx % kTile)) * (unsigned)sizeof(T);
+        };
+        // Loaded from the replica STRAIGHT INTO LDS, one component of 64 bodies per instruction (lane l's word lands at
+        // base + 4 l; the per-lane source address does the transposition): the prefetch holds no registers and stays in
+        // flight for a whole turn.  The radii are only fetched when some radius of the replica is not +0 (Meta::summary).
+        auto issue_entries = [&](unsigned tile_byte, unsigned byte_offset, unsigned base, unsigned comp_bytes) {
+            // Source: Jt, the replica once more, tile by tile component-major (x[128] y[128] m[128] r[128] per aligned
+            // 128-body tile, written next to J by unpack_slots): a wave's 64 entries of one component are 256 contiguous
+            // bytes - two or three cache lines per instruction where the 16-byte records took eight or nine -, and the
+            // radius lines are never touched while every radius is +0: 3 of the 4 MiB, which an XCD's 4 MiB L2 keeps from one
+            // round of workgroups to the next (fabric-side reads halved, profiles/r02_traffic_pmc.json).
+            // The planes of a tile are 512 bytes apart.  Their base pointers are formed HERE, from an offset hipcc cannot see
+            // through: hoisted out of the turn loop they are three more scalar register pairs the kernel does not have
+            // (spilled pairs cost v_readlanes per turn).
+            unsigned long long plane = kTile * sizeof(T);
+            asm volatile("" : "+s"(plane));
+            if (kLog) {                                        // the four words this lane fetches lie inside Jt
+                const unsigned long long last = (unsigned long long)tile_byte + byte_offset + 3 * kTile * sizeof(T) + sizeof(T);
+                if (last > (unsigned long long)NB_RING_LATE(n_tiles) * (4 * kTile * sizeof(T))) {
+                    atomicAdd(&NB_RING_LATE(ctr)->errors, kIndexError);
+                    return;
+                }
+            }
+            const char* const src = (const char*)Jt + tile_byte;
+            load_to_lds_b32(src, byte_offset, base);
+            load_to_lds_b32(src + plane, byte_offset, base + comp_bytes);
+            load_to_lds_b32(src + 2 * plane, byte_offset, base + 2 * comp_bytes);
+            if (any_radius) load_to_lds_b32(src + 3 * plane, byte_offset, base + 3 * comp_bytes);
+        };
+        auto issue_window = [&](long long st, int buf) {
+            const unsigned base = __builtin_amdgcn_readfirstlane(lds_offset_of(&win[w][buf][0][0]));
+            const unsigned e0 = first_entry();
+            const unsigned e1 = e0 ^ kWave;                    // the entry 64 further on
+            if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= N) {
+                // the common case - the window's tile is an aligned tile of Jt -: the tile goes into the scalar base address,
+                // the lanes' offsets are the two per-lane constants, no vector arithmetic at all
+                const unsigned tile_byte = ((unsigned)st / kTile) * (4u * kTile * (unsigned)sizeof(T));
+                if (l < nwin) issue_entries(tile_byte, e0 * (unsigned)sizeof(T), base, kWin * (unsigned)sizeof(T));
+                if (l + kWave < nwin) issue_entries(tile_byte, e1 * (unsigned)sizeof(T), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+            } else {
+                if (l < nwin) issue_entries(0u, window_offset(st, e0), base, kWin * (unsigned)sizeof(T));
+                if (l + kWave < nwin) issue_entries(0u, window_offset(st, e1), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+            }
+        };
+        // A truncated tile: its L <= 128 entries in order, component-major x[128] y[128] m[128] r[128] across BOTH window
+        // buffers (2 * 4 * kWin >= 4 * 128 words), so it can only be issued when the wave is done with its current window:
+        // after the hand-off of the turn before.
+        static_assert(2 * kWin >= kTile, "a whole tile fits the two window buffers");
+        float* const whole = &win[w][0][0][0];
+        auto issue_truncated = [&](long long st, int L) {
+            const unsigned base = __builtin_amdgcn_readfirstlane(lds_offset_of(whole));
+            if (l < L) issue_entries(0u, window_offset(st, (unsigned)l), base, kTile * (unsigned)sizeof(T));
+            if (l + kWave < L) issue_entries(0u, window_offset(st, (unsigned)(l + kWave)), base + kWave * (unsigned)sizeof(T), kTile * (unsigned)sizeof(T));
+        };
+        // one entry of a window / of the whole truncated tile, as a record (general code only)
+        auto window_record = [&](const float* comp0, int stride, int idx) -> Rec<T> {
+            return Rec<T>{comp0[idx], comp0[stride + idx], comp0[2 * stride + idx], any_radius ? comp0[3 * stride + idx] : 0.0f};
+        };
+        // after the loads have landed: are all coordinates of the window bounded, is some radius not +0.0f
+        // The collision screen of a fast turn needs an upper bound of the radii the window holds.  The window's bodies are
+        // J[st .. st + 127] (wrapped at N): they lie in the aligned tiles st / 128 and st / 128 + 1 and, when wrapped, tile 0;
+        // unpack_slots keeps max |radius| per aligned tile.  Scalar loads, issued with the window a turn ahead.
+        auto window_rmax = [&](long long st) -> float {
+            if (!any_radius) return 0.0f;
+            const int ta = __builtin_amdgcn_readfirstlane((int)(st / kTile));
+            if (kLog && (ta < 0 || ta + 1 >= NB_RING_LATE(n_tiles))) {
+                if (l == 0) atomicAdd(&NB_RING_LATE(ctr)->errors, kIndexError);
+                return __builtin_inff();                       // every lane is flagged: the general code decides
+            }
+            const float ra = tile_rmax[ta], rb = tile_rmax[ta + 1];
+            const float rw = (st + kTile > N) ? tile_rmax[0] : 0.0f;
+            const float rab = ra > rb ? ra : rb;
+            return rab > rw ? rab : rw;
+        };
+        struct WindowState { bool fast; float rmax; };
+        auto check_window = [&](int kind, int kk, int buf, long long st_w) -> WindowState {
+            if (kind != 1) return WindowState{false, 0.0f};    // (a truncated tile is waited for where it is read)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // issued a whole turn ago
+            __builtin_amdgcn_wave_barrier();
+            // the whole replica is bounded (Meta::summary): no scan of the window; all its radii are +0 or not, globally
+            if (all_bounded) return WindowState{wave_ok && fast_tile(kk), window_rmax(st_w)};
+            Rec<T> r0{0, 0, 0, 0}, r1{0, 0, 0, 0};
+            if (l < nwin) r0 = window_record(&win[w][buf][0][0], kWin, l);
+            if (l + kWave < nwin) r1 = window_record(&win[w][buf][0][0], kWin, l + kWave);
+            const bool bad0 = !((abs_(r0.x) < kCoordBound) && (abs_(r0.y) < kCoordBound));
+            const bool bad1 = !((abs_(r1.x) < kCoordBound) && (abs_(r1.y) < kCoordBound));
+            WindowState ws;
+            ws.fast = __ballot(bad0 || bad1) == 0ull && wave_ok && fast_tile(kk);
+            ws.rmax = window_rmax(st_w);
+            return ws;
+        };
+        // the general code on this turn's walk positions, records from the window (kind 1) / the whole tile (kind 2)
+        // `bounded`: the window passed the coordinate check (a fast turn redone for a flagged lane): a pair that is no
+        // collision and not closer than 2^-40 then takes the scalar form of the fast chain - the same bits as the general
+        // code's IEEE square root and reciprocal (nbody_selftest_ieee_f32) at a quarter of the instructions; a flagged
+        // lane holds up its whole ring, so this path is worth keeping short.
+        auto general_turn = [&](BodyAcc<T>& a, int kind, int kk, long long st, int L, int off0, int buf, bool bounded) {
+            const long long i64 = body_index64();
+            const int i = (int)(i64 < 0x7fffffff ? i64 : 0x7fffffff);
+            const T growth = NB_RING_LATE(p.growth);
+            Event* const ev = kLog ? NB_RING_LATE(ev) : nullptr;
+            const int ev_cap = kLog ? NB_RING_LATE(ev_cap) : 0;
+            Counters* const ctr = kLog ? NB_RING_LATE(ctr) : nullptr;
+            const int step = kLog ? meta->step : 0;
+            if (kind == 2) {                                   // issued after the previous own turn's hand-off
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_wave_barrier();
+            }
+            const int hi = off0 + kT < L ? off0 + kT : L;
+            int lane_entry = lit ? l : 0;                      // this lane's first window entry.  Computed HERE: hoisted out of
+            asm volatile("" : "+v"(lane_entry));               // the turn loop it is one more register the fast path cannot spare
+            const int t = (int)(i64 - blk0);                   // threadIdx.x of the body in the reference
+    #pragma unroll 1
+            for (int off = off0; off < hi; ++off) {
+                int sidx;
+                long long j;
+                if (lit) {
+                    if (kk == 0 && off == 0) continue;                                 // :200-204
+                    sidx = (L == kTile) ? ((t + off) & (kTile - 1)) : ((t + off) % L); // :207
+                    j = st + sidx;
+                    if (j >= N) j %= N;
+                } else {
+                    sidx = off;
+                    j = st + off;
+                    if (j == i64) continue;
+                }
+                const Rec<T> rec = kind == 1 ? window_record(&win[w][buf][0][0], kWin, lane_entry + (off - off0))
+                                             : window_record(whole, kTile, sidx);
+                if (bounded) {
+                    const T dx = rec.x - a.xi, dy = rec.y - a.yi;
+                    const T d2 = (dx * dx) + (dy * dy);
+                    const T rs = a.ri + rec.r;
+                    if (!(d2 <= fma_(rs, rs, kFastLo))) {      // no collision, inside the proved domain
+                        const T inv = fast_chain(d2).inv;
+                        a.fx = a.fx + (dx * rec.m) * inv;
+                        a.fy = a.fy + (dy * rec.m) * inv;
+                        continue;
+                    }
+                }
+                interact<T, kLog>(a, rec, growth, i, (int)j, ev, ev_cap, ctr, step);
+            }
+        };
+
+        const int tau0 = tau_lo + w;                           // this wave's first turn of the item
+        const int dseq = kQueue ? seq_base - tau_lo : 0;       // turn tau of the walk has sequence number tau + dseq
+        long long st = tile_start_slow(tau0 / kTurnsPerTile);
+        int buf = 0;
+        int plain_turns = 0;                                   // turns of this wave that took the common path
+        bool first_plain = false;                              // ... the first turn of the walk among them (one pair less)
+        int kind = turn_kind(tau0, st);
+        if (kind == 1) issue_window(st, buf);
+        if (kind == 2) issue_truncated(st, tile_len(tau0 / kTurnsPerTile, st));
+        WindowState cur = check_window(kind, tau0 / kTurnsPerTile, buf, st);
+        for (int tau = tau0; tau < tau_hi; tau += kW) {
+            unsigned long long pt0 = 0, pt1 = 0, pt2 = 0, pt3 = 0;
+            if (kProbe) pt0 = __builtin_readcyclecounter();
+            const int kk = tau / kTurnsPerTile;
+            const int off0 = (tau % kTurnsPerTile) * kT;
+            const int L = tile_len(kk, st);
+            const bool fast = cur.fast;
+            const long long st_next = round_on(st);
+            const int kind_next = turn_kind(tau + kW, st_next);
+            if (kind_next == 1) issue_window(st_next, buf ^ 1);                  // in flight for the whole turn
+            const bool first = lit && tau == 0;                // walk position 0 is the body itself (:200-204)
+            if (kRings > 1) {                                  // behind the furthest ring of the workgroup: evaluate first
+                int ahead = *seq_o1;
+                if (kRings == 4) {
+                    const int o2 = *seq_o2, o3 = *seq_o3;
+                    ahead = ahead > o2 ? ahead : o2;
+                    ahead = ahead > o3 ? ahead : o3;
+                }
+                if (*seq_mine < ahead) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            }
+            // (2) the kT terms of this turn: walk positions 2v, 2v + 1 in the two halves of termx[v] / termy[v]
+            V2 termx[kT / 2], termy[kT / 2];
+            auto term_x = [&](int r) -> float { return (r & 1) ? termx[r / 2].y : termx[r / 2].x; };
+            auto term_y = [&](int r) -> float { return (r & 1) ? termy[r / 2].y : termy[r / 2].x; };
+            unsigned long long flag = 0;
+            auto evaluate = [&](auto screen_tag) {
+                constexpr bool kScreen = decltype(screen_tag)::value;     // false: no screen per pair (nan_screen)
+                const float* wx = &win[w][buf][0][lit ? l : 0];
+                const float* wy = wx + kWin;
+                const float* wm = wx + 2 * kWin;
+                const V2 ownx = {xi, xi}, owny = {yi, yi};
+                // Collision / tiny-distance screen, half an instruction per pair: a pair may only take the fast chain if it is
+                // no collision, d2 > (ri + rj)^2, and d2 > 2^-80 (the proved domain).  With R = |ri| + (largest |radius| the
+                // window can hold) every such pair has d2 > fma(R, R, 2^-80), a per-LANE constant of the turn, so the
+                // SMALLEST d2 of the lane's kT pairs decides for all of them (d2 is finite here - the coordinates are
+                // bounded - so no NaN can hide in the minimum; a NaN radius never collides and is not in the bound).  A
+                // lane below the threshold is redone by the general code, which applies the exact predicate.
+                const float reach = abs_(ri) + cur.rmax;
+                const float threshold = __builtin_fmaf(reach, reach, kFastLo);
+                float closest = kFastHi;
+                // the reads of a batch are issued one batch ahead (NB_RING_PREFETCH): their latency then runs under the arithmetic
+                // of the batch before instead of being exposed at every batch's start
+                V2 pxa = {wx[0], wx[1]}, pxb = {wx[2], wx[3]}, pya = {wy[0], wy[1]}, pyb = {wy[2], wy[3]};
+                V2 pma = {wm[0], wm[1]}, pmb = {wm[2], wm[3]};
+    #pragma unroll
+                for (int r0 = 0; r0 < kT; r0 += 4) {           // four walk positions per batch of reads: a, a, b, b
+                    const V2 xa = pxa, xb = pxb, ya = pya, yb = pyb, ma = pma, mb = pmb;
+                    if (r0 + 4 < kT) {
+                        pxa = V2{wx[r0 + 4], wx[r0 + 5]}; pxb = V2{wx[r0 + 6], wx[r0 + 7]};
+                        pya = V2{wy[r0 + 4], wy[r0 + 5]}; pyb = V2{wy[r0 + 6], wy[r0 + 7]};
+                        pma = V2{wm[r0 + 4], wm[r0 + 5]}; pmb = V2{wm[r0 + 6], wm[r0 + 7]};
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    const V2 dxa = xa - ownx, dxb = xb - ownx;
+                    const V2 dya = ya - owny, dyb = yb - owny;
+                    const V2 sxa = dxa * dxa, sxb = dxb * dxb;
+                    const V2 sya = dya * dya, syb = dyb * dyb;
+                    const V2 d2a = sxa + sya, d2b = sxb + syb; // three roundings per element (no contraction in this file)
+                    if (kScreen) {
+                        const float first_d2 = (r0 == 0 && first) ? kFastHi : d2a.x;   // the self position is no pair
+                        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(closest) : "v"(closest), "v"(first_d2), "v"(d2a.y));
+                        asm("v_min3_f32 %0, %1, %2, %3" : "=v"(closest) : "v"(closest), "v"(d2b.x), "v"(d2b.y));
+                    }
+                    V2 inva, invb;
+                    fast_inv_cube2x2(d2a, d2b, inva, invb);
+                    const V2 txa = dxa * ma, txb = dxb * mb;
+                    const V2 tya = dya * ma, tyb = dyb * mb;
+                    termx[r0 / 2] = txa * inva; termx[r0 / 2 + 1] = txb * invb;
+                    termy[r0 / 2] = tya * inva; termy[r0 / 2 + 1] = tyb * invb;
+                    // the terms are finished HERE (hipcc otherwise sinks the last multiply into the blocks that add them up
+                    // and keeps both factors alive until then: twice the registers, spills)
+                    asm volatile("" : "+v"(termx[r0 / 2]), "+v"(termx[r0 / 2 + 1]), "+v"(termy[r0 / 2]), "+v"(termy[r0 / 2 + 1]));
+                }
+                if (kScreen) flag = le_mask(closest, threshold);
+                // the reference skips the self position; the sum starts at +0.0f and +0 + +0 = +0: adding a zero term is
+                // the same bits (whatever the self "pair" evaluated to - NaN: d2 = 0 - is dropped here)
+                if (first) { termx[0].x = 0.0f; termy[0].x = 0.0f; }
+            };
+            if (fast) {
+                if (nan_screen) evaluate(std::false_type{});
+                else evaluate(std::true_type{});
+            }
+            if (kProbe) pt1 = __builtin_readcyclecounter();
+            // (3) the state after turn tau - 1.  Polled at raised priority: a poll is one LDS read plus scalar work, it
+            // takes next to nothing from the vector pipelines of the waves that are evaluating, and the chain moves on
+            // within one LDS round trip of the record being written.
+            Int4 h = Int4{0, 0, 0, 0};
+            bool timed_out = false;
+            __builtin_amdgcn_s_setprio(3);
+            const int sq = tau + dseq;
+            if (kQueue || tau > 0) {
+                int spins = 0;
+                for (;;) {
+                    h = *hand_l;                               // one ds_read_b128
+                    if (__ballot(h.z < sq) == 0ull) break;
+                    if (++spins > spin_limit) { timed_out = true; break; }
+                    if (kSleep > 0) __builtin_amdgcn_s_sleep(kSleep);
+                }
+                if (kProbe) pr_polls += spins + 1;
+            }
+            if (kProbe) pt2 = __builtin_readcyclecounter();
+            // (4) + (5).  The common case - a fast turn, no flagged lane, the sequence number the expected one - is kept as
+            // short as the arithmetic allows, because it is the serial part of the whole workgroup: 2 kT dependent adds
+            // (x and y chains interleaved: scalar adds need no wait states between dependent instructions, packed ones
+            // do), then one LDS write; `flags` passes through untouched.  The last turn publishes too: the epilogue takes the
+            // final state from the records.
+            bool plain = fast && flag == 0ull && !dead && !timed_out && __ballot(h.z != sq) == 0ull;
+            if (__builtin_expect(plain, 1)) {
+                float fx = __int_as_float(h.x), fy = __int_as_float(h.y);
+    #pragma unroll
+                for (int r = 0; r < kT; ++r) {
+                    fx = fx + term_x(r);
+                    asm("" : "+v"(fx));                        // keeps hipcc from pairing the two adds into one v_pk_add_f32
+                    fy = fy + term_y(r);
+                }
+                // nan_screen: a coincident pair (d2 = 0: a collision, :215-226) made its term NaN, and a NaN among the kT terms
+                // is a NaN sum.  ONE comparison per turn instead of a v_min3 per two pairs; a lane whose sum was NaN already is
+                // flagged in every turn (slow, and right: its collisions still have to be found).
+                if (nan_screen) flag = __builtin_amdgcn_fcmpf(fx, fy, 8 /* llvm::CmpInst::FCMP_UNO */);
+                if (__builtin_expect(flag == 0ull, 1)) {
+                    *hand_l = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), sq + 1, h.w};
+                    __builtin_amdgcn_s_setprio(0);
+                    plain_turns += 1;                          // a scalar: kT pairs per active lane, added up at the end
+                    first_plain = first_plain || first;
+                } else {
+                    plain = false;                             // the sums are dropped: the turn is redone below from `h`
+                }
+            }
+            if (__builtin_expect(!plain, 0)) {
+                // the lane's whole state, for the general code: position and radius from the registers, the running sum and
+                // `deleted` from the record just received, {mnew, rnew, mi} from the rare record (its last writer published
+                // it before the sequence number this wave has seen)
+                BodyAcc<T> a;
+                a.xi = xi; a.yi = yi; a.ri = ri;
+                a.fx = __int_as_float(h.x); a.fy = __int_as_float(h.y);
+                a.deleted = h.w & 1;
+                const Float4 hm = *hand_m_l;
+                a.mnew = hm.x; a.rnew = hm.y; a.mi = hm.z;
+                timeouts += timed_out ? 1 : 0;
+                dead = dead || timed_out || __ballot(h.z >= kRingDeadSeq) != 0ull;
+                const unsigned m_before = __float_as_uint(a.mnew), r_before = __float_as_uint(a.rnew);
+                if (fast && nan_screen) {                      // (a turn that came here without its sums: every NaN term flags its lane)
+    #pragma unroll
+                    for (int r = 0; r < kT; ++r) flag |= __builtin_amdgcn_fcmpf(term_x(r), term_y(r), 8);
+                }
+                if (fast) {
+                    // The flagged lanes (a SUPERSET of the lanes with a collision or a tiny distance in this turn) get the exact
+                    // status of each of their kT pairs, and they get it in parallel: lane r of the wave evaluates walk position r
+                    // of flagged lane fl's body from the same window.  `hits`: positions that are collisions the reference
+                    // handles and moves on from (:215-226: no force term); `odd`: some pair inside the guard that is not
+                    // such a collision (tiny distance, the 2^-80 margin, a NaN mass) - that lane is redone by the general code.
+                    unsigned hits = 0;
+                    bool odd = false;
+                    unsigned long long todo = flag & __ballot(active);
+                    while (todo != 0ull) {
+                        const int fl = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
+                        todo &= todo - 1ull;
+                        const T xf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.xi), fl));
+                        const T yf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.yi), fl));
+                        const T mf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.mi), fl));
+                        const T rf = __int_as_float(__builtin_amdgcn_readlane((int)__float_as_uint(a.ri), fl));
+                        int r = l & (kT - 1);                                       // formed HERE (see general_turn's lane_entry)
+                        asm volatile("" : "+v"(r));
+                        const Rec<T> rec = window_record(&win[w][buf][0][0], kWin, (lit ? fl : 0) + r);
+                        const T dx = rec.x - xf, dy = rec.y - yf;
+                        const T d2 = (dx * dx) + (dy * dy);
+                        const T rs = rf + rec.r;
+                        const bool is_pair = l < kT && !(first && r == 0);          // walk position 0 of tile 0 is the body itself
+                        const bool hit = d2 <= rs * rs && (mf >= rec.m || mf < rec.m); // interact(): `hit && (ge || lt)`
+                        const bool guarded = d2 <= fma_(rs, rs, kFastLo);              // what the fast chain must not see
+                        const unsigned long long hm = __ballot(is_pair && hit);
+                        const unsigned long long om = __ballot(is_pair && guarded && !hit);
+                        if (l == fl) { hits = (unsigned)hm; odd = om != 0ull; }
+                    }
+                    if (active) {
+                        if (odd) {
+                            general_turn(a, 1, kk, st, L, off0, buf, true);
+                        } else {
+                            float fx = a.fx, fy = a.fy;
+    #pragma unroll
+                            for (int r = 0; r < kT; ++r) {
+                                const float nx = add_unmerged(fx, term_x(r));
+                                const float ny = add_unmerged(fy, term_y(r));
+                                const bool skip = ((hits >> r) & 1u) != 0u;            // a collision adds no force term (not even +0)
+                                fx = skip ? fx : nx;
+                                fy = skip ? fy : ny;
+                            }
+                            a.fx = fx; a.fy = fy;
+                            unsigned rest = hits;                                      // the collisions themselves, in walk order
+                            int lane_entry = lit ? l : 0;
+                            asm volatile("" : "+v"(lane_entry));                       // (see general_turn)
+                            const T growth = NB_RING_LATE(p.growth);
+                            while (rest != 0u) {
+                                const int r = __builtin_ctz(rest);
+                                rest &= rest - 1u;
+                                const Rec<T> rec = window_record(&win[w][buf][0][0], kWin, lane_entry + r);
+                                const bool ge = a.mi >= rec.m;
+                                if (ge) {                                              // :215-221
+                                    a.mnew = a.mnew + rec.m;
+                                    a.rnew = a.rnew + rec.r * growth;
+                                } else {                                               // :222-226
+                                    a.deleted = 1;
+                                }
+                                if (kLog) {
+                                    const long long i64 = body_index64();
+                                    const int i = (int)(i64 < 0x7fffffff ? i64 : 0x7fffffff);
+                                    long long j = lit ? st + (((int)(i64 - blk0) + off0 + r) & (kTile - 1)) : st + off0 + r;
+                                    if (j >= N) j %= N;
+                                    Counters* const ctr = NB_RING_LATE(ctr);
+                                    const unsigned long long slot = atomicAdd(&ctr->events, 1ull);
+                                    if (slot < (unsigned long long)NB_RING_LATE(ev_cap))
+                                        NB_RING_LATE(ev)[slot] = Event{meta->step, i, (int)j, ge ? 0 : 1};
+                                }
+                            }
+                        }
+                        pairs_rare += kT - (first ? 1 : 0);
+                    }
+                } else if (active) {
+                    general_turn(a, kind, kk, st, L, off0, buf, false);
+                    const int hi = off0 + kT < L ? off0 + kT : L;
+                    if (lit) {
+                        if (hi > off0) pairs_rare += (hi - off0) - ((kk == 0 && off0 == 0) ? 1 : 0);
+                    } else {
+                        const long long i64 = body_index64();
+                        for (int off = off0; off < hi; ++off) pairs_rare += (st + off != i64) ? 1 : 0;
+                    }
+                }
+                if (dead) {                                    // a hand-off wait gave up somewhere before: poison, never a result
+                    a.fx = a.fy = a.mnew = a.rnew = __builtin_nanf("");
+                    a.deleted = 0;
+                }
+                // publish: the rare record first, then the one the next wave polls (a wave's LDS operations execute in order)
+                if (__float_as_uint(a.mnew) != m_before || __float_as_uint(a.rnew) != r_before)
+                    *hand_m_l = Float4{a.mnew, a.rnew, a.mi, 0.0f};
+                *hand_l = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : sq + 1,
+                               a.deleted & 1};
+                __builtin_amdgcn_s_setprio(0);
+            }
+            if (kProbe) pt3 = __builtin_readcyclecounter();
+            // the prefetched window of this wave's next turn
+            if (kind_next == 2) issue_truncated(st_next, tile_len((tau + kW) / kTurnsPerTile, st_next));   // both buffers are free now
+            buf ^= 1;
+            st = st_next;
+            kind = kind_next;
+            cur = check_window(kind, (tau + kW) / kTurnsPerTile, buf, st);
+            if (kProbe) {
+                pr_eval += pt1 - pt0; pr_wait += pt2 - pt1; pr_chain += pt3 - pt2;
+                pr_check += __builtin_readcyclecounter() - pt3;
+            }
+        }
+        // Nothing above this line in the loop is a memory access the compiler tracks in vmcnt (the window loads and the
+        // general code's record loads are inline assembly with their own waits): hipcc therefore places no vmcnt wait in
+        // the loop, and the only one there is check_window's, for a prefetch issued a whole turn earlier.
+        if ((kQueue || mine) && (tau_hi - 1) % kW == w) {      // the wave that took the item's last turn, from the records it has
+            const Int4 hf = *hand_l;                           // just written (a wave's LDS operations execute in order)
+            const Float4 hm = *hand_m_l;
+            if (kQueue && tau_hi < nturns) {
+                // not the walk's last segment: the two records of every lane go to the ring's state, write-through (each store
+                // leaves the XCD's L2), and when all of them have left, ONE lane raises the ring's done word
+                const GlobalU64Ptr rs = (GlobalU64Ptr)NB_RING_LATE(q_state) + (size_t)ring_g * (4 * kWave) + l;
+                __hip_atomic_store(rs, ((unsigned long long)(unsigned)hf.y << 32) | (unsigned)hf.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(rs + kWave, ((unsigned long long)(unsigned)hf.w << 32) | (unsigned)hf.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(rs + 2 * kWave, ((unsigned long long)__float_as_uint(hm.y) << 32) | __float_as_uint(hm.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(rs + 3 * kWave, (unsigned long long)__float_as_uint(hm.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (l == 0)
+                    __hip_atomic_store((GlobalU64Ptr)NB_RING_LATE(q_done) + ring_g,
+                                       ((unsigned long long)NB_RING_LATE(q_launch) << 32) | (unsigned)(seg + 1),
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (mine) {                                 // the walk's last turn: epilogue
+                const long long i64 = body_index64();
+                const int q = (int)(i64 - lo);
+                BodyAcc<T> a;
+                a.xi = xi; a.yi = yi; a.ri = ri; a.mi = hm.z;
+                a.fx = __int_as_float(hf.x); a.fy = __int_as_float(hf.y);
+                a.mnew = hm.x; a.rnew = hm.y; a.deleted = hf.w & 1;
+                Rec<T>* const S_J = NB_RING_LATE(S_J);
+                Vec2<T>* const S_V = NB_RING_LATE(S_V);
+                const bool q_ok = q >= 0 && q < NB_RING_LATE(cap_own);
+                const Vec2<T> v = q_ok ? NB_RING_LATE(Vown)[q] : Vec2<T>{0, 0};
+                if (!q_ok) {
+                    atomicAdd(&NB_RING_LATE(ctr)->errors, kIndexError);
+                } else if (active) {
+                    const StepParams<T> p = NB_RING_LATE(p);
+                    Rec<T> out; Vec2<T> vout;
+                    finish_body<T>(a, v, p, out, vout);
+                    S_J[q] = out;
+                    S_V[q] = vout;
+                } else {   // frozen body: no thread exists for it in the reference, state carried over unchanged
+                    S_J[q] = Rec<T>{a.xi, a.yi, a.mi, a.ri};
+                    S_V[q] = v;
+                }
+            }
+            // the item's CLOSING TURN: one more sequence number, published when the records have been read back - wave 0 of
+            // the slot's next item waits for it before it writes that item's starting state over them
+            if (kQueue) *hand_l = Int4{hf.x, hf.y, hf.z >= kRingDeadSeq ? kRingDeadSeq : seq_base + (tau_hi - tau_lo) + 1, hf.w};
+        }
+        {
+            unsigned long long pairs = 0;
+            if (active) pairs = (unsigned long long)((long long)plain_turns * kT - (first_plain ? 1 : 0) + pairs_rare);
+            for (int sh = kWave / 2; sh > 0; sh >>= 1) pairs += __shfl_down(pairs, sh, kWave);
+            if (l == 0 && pairs) atomicAdd(&NB_RING_LATE(ctr)->pairs, pairs);
+        }
+        if (kProbe) pr_turns += (unsigned long long)((tau_hi - tau0 + kW - 1) / kW);
+        if (!kQueue) break;
+        seq_base += tau_hi - tau_lo + 1;
     }
     Counters* const ctr = NB_RING_LATE(ctr);
-    unsigned long long pairs = 0;
-    if (active) pairs = (unsigned long long)((long long)plain_turns * kT - (first_plain ? 1 : 0) + pairs_rare);
+    if (kQueue && w == 0 && l == 0) {                      // the last slot to leave clears the queue for the next launch
+        const GlobalU32Ptr head = (GlobalU32Ptr)NB_RING_LATE(q_head);
+        if (__hip_atomic_fetch_add(head + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * kRings - 1u) {
+            __hip_atomic_store(head, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(head + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
     if (timeouts != 0 && l == 0) atomicAdd(&ctr->errors, (unsigned long long)timeouts);
-    for (int sh = kWave / 2; sh > 0; sh >>= 1) pairs += __shfl_down(pairs, sh, kWave);
-    if (l == 0 && pairs) atomicAdd(&ctr->pairs, pairs);
     if (kProbe && l == 0) {
         Event* const ev = NB_RING_LATE(ev);
         const int ev_cap = NB_RING_LATE(ev_cap);
         atomicAdd(&ctr->probe[0], pr_eval); atomicAdd(&ctr->probe[1], pr_wait);
         atomicAdd(&ctr->probe[2], pr_chain); atomicAdd(&ctr->probe[3], pr_check);
         atomicAdd(&ctr->probe[4], pr_polls);
-        atomicAdd(&ctr->probe[5], (unsigned long long)((nturns - w + kW - 1) / kW));
+        atomicAdd(&ctr->probe[5], pr_turns);
         if (wg == 0 && w == 0) {
             ctr->probe[6] = __builtin_readcyclecounter() - pr_t0;   // shader clocks of one wave's life
             ctr->probe[7] = wall_clock64() - pr_r0;                 // the same in 100 MHz ticks
         }
-        if (w == 0) {   // where and when this workgroup ran: {start, end (constant-rate ticks), HW_ID, XCC_ID << 20 | wg}
-            const unsigned long long slot = atomicAdd(&ctr->events, 1ull);
-            if (slot < (unsigned long long)ev_cap)
-                ev[slot] = Event{(int)(unsigned)pr_r0, (int)(unsigned)wall_clock64(),
-                                 (int)__builtin_amdgcn_s_getreg((31 << 11) | 4),
-                                 (int)((__builtin_amdgcn_s_getreg((31 << 11) | 20) << 20) | (unsigned)wg)};
+        // where and when this ring (persistent form: ring slot) ran, one record each, from its wave 0 (whose last turn is at
+        // most kW - 1 turns before the ring's): {first turn, end (constant-rate ticks), HW_ID, XCC_ID << 20 | ring of the
+        // launch}; the workgroup is ring / kRings
+        if (w == 0) {
+            const unsigned long long at = atomicAdd(&ctr->events, 1ull);
+            if (at < (unsigned long long)ev_cap)
+                ev[at] = Event{(int)(unsigned)pr_r0, (int)(unsigned)wall_clock64(),
+                               (int)__builtin_amdgcn_s_getreg((31 << 11) | 4),
+                               (int)((__builtin_amdgcn_s_getreg((31 << 11) | 20) << 20) | (unsigned)slot)};
         }
     }
 }
