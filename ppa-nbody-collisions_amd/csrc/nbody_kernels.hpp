@@ -1039,11 +1039,31 @@ void forces_ring_f32(const RingArgs args) {
         // 3.2 and 4.8 ms of a 4.8 ms launch, profiles/r02_ring_fairness.txt).  With both rings in one workgroup each
         // wave compares the two chains' progress at the start of a turn and evaluates at priority 1 when its own ring is
         // behind, 0 otherwise: the rings stay level and finish together.
+        // The look costs ONE vector instruction: lane l reads the sequence number of ring l % kRings (lane 0's record) and
+        // compares its own record's with it, so the wave's compare mask says whether ANY ring is ahead of this one.  The
+        // lanes that look at their own ring read it first and their own record after it; should a publish of 64 records
+        // land between the two reads, lane 0's new number meets the lane's old one: at worst one spurious turn at priority
+        // 1 - the look steers priority only, never a result.  The address is
+        // a per-lane constant of the launch, kept in a register like the window's first entry.  (One uniform address per
+        // ring was four v_mov, a v_max3 and the compare: the event-logging builds, which have no register for it, keep that.)
         typedef const volatile __attribute__((address_space(3))) int* LdsSeqPtr;
-        const LdsSeqPtr seq_mine = (LdsSeqPtr)&hand_all[ring][0] + 2;
-        const LdsSeqPtr seq_o1 = (LdsSeqPtr)&hand_all[(ring + 1) % kRings][0] + 2;    // the other rings of the workgroup
-        const LdsSeqPtr seq_o2 = (LdsSeqPtr)&hand_all[(ring + 2) % kRings][0] + 2;
-        const LdsSeqPtr seq_o3 = (LdsSeqPtr)&hand_all[(ring + 3) % kRings][0] + 2;
+        auto seq_of_ring_of = [&](int lane) -> LdsSeqPtr { return (LdsSeqPtr)&hand_all[lane % kRings][0] + 2; };
+        LdsSeqPtr seq_look_kept = seq_of_ring_of(kLog ? 0 : l);
+        if (!kLog && kRings > 1) asm volatile("" : "+v"(seq_look_kept));
+        auto any_ring_ahead = [&]() -> bool {
+            if (kLog) {                                        // as before: one uniform address per ring
+                int ahead = *seq_of_ring_of(ring + 1);
+                if (kRings == 4) {
+                    const int o2 = *seq_of_ring_of(ring + 2), o3 = *seq_of_ring_of(ring + 3);
+                    ahead = ahead > o2 ? ahead : o2;
+                    ahead = ahead > o3 ? ahead : o3;
+                }
+                return *seq_of_ring_of(ring) < ahead;
+            }
+            const int theirs = *seq_look_kept;
+            const int ours = ((LdsSeqPtr)hand_l)[2];
+            return __ballot(ours < theirs) != 0ull;
+        };
         if (kProbe && !kQueue) { pr_t0 = __builtin_readcyclecounter(); pr_r0 = wall_clock64(); }
 
         // First body of the tile of this wave's current turn (literal: cyclic tile b + kk), kept incrementally: a wave
@@ -1053,19 +1073,29 @@ void forces_ring_f32(const RingArgs args) {
             if (!lit) return (long long)kk * kTile;
             return (blk0 % N + (long long)kk * kTile) % N;
         };
-        auto round_on = [&](long long st) -> long long {
+        // `st`, N and st + kTilesPerRound * kTile are below 2^31: the turn loop keeps them as 32-bit unsigned numbers, which
+        // the scalar unit compares (it has no ordered 64-bit compare: as long long every one of these tests was a v_mov_b64
+        // and a v_cmp_*_i64 on the vector ALU, three per turn).  The rare code takes st as the long long it was.
+        // The event-logging builds keep the long long arithmetic, the per-window entry and the four-address look of before:
+        // their code is instruction for instruction what it was (they have no register for the kept values, and the one
+        // line that runs them at a chain-bound size, N = 1024 with the log on, measured 2 us per step slower with the trims).
+        typedef typename std::conditional<kLog, long long, unsigned>::type Idx;
+        const Idx Nu = (Idx)N;
+        auto round_on = [&](Idx st) -> Idx {
             st += kTilesPerRound * kTile;
-            if (lit) while (st >= N) st -= N;                  // a next turn exists only when N > kTilesPerRound tiles: once
+            if (lit) while (st >= Nu) st -= Nu;                // a next turn exists only when N > kTilesPerRound tiles: once
             return st;
         };
-        auto tile_len = [&](int kk, long long st) -> int {
+        auto tile_len = [&](int kk, Idx st) -> int {
             if (lit) return (kk == nb - 1) ? N % (kTile + 1) : kTile;             // :194 (quirk Q1)
-            return (N - st) < kTile ? (int)(N - st) : kTile;
+            if (kLog) return (Nu - st) < kTile ? (int)(Nu - st) : kTile;
+            const int rest = (int)(Nu - st);
+            return rest < kTile ? rest : kTile;
         };
         // Every turn reads its tile entries from the wave's LDS window, never from the replica.  Kind of a turn's window:
         // 0 none (past the walk), 1 the standard window of a full tile, 2 a truncated tile (literal: the last one, of
         // N mod 129 entries; clean: the partial last one), held whole.
-        auto turn_kind = [&](int tau, long long st) -> int {
+        auto turn_kind = [&](int tau, Idx st) -> int {
             if (tau >= tau_hi) return 0;
             return tile_len(tau / kTurnsPerTile, st) == kTile ? 1 : 2;
         };
@@ -1077,15 +1107,19 @@ void forces_ring_f32(const RingArgs args) {
         // per-lane constants, the body index is that plus the tile's first body, wrapped at most once (st < N, e < 128 <= N).
         const int wbase0 = lit ? t0 : 0;                       // literal: lane l reads window[l + r]; clean: window[r]
         const int nwin = lit ? (kWave + kT - 1) : kT;          // entries of the window that are used
-        // (recomputed per window from the lane number - two instructions - instead of living in two registers)
-        auto first_entry = [&]() -> unsigned {
-            int lane = l;
-            asm volatile("" : "+v"(lane));
-            return (unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane) & (kTile - 1);
+        // The first of the two lives in ONE register for the whole item, as the byte offset the aligned window's loads take
+        // (entry * 4; an opaque value, or hipcc forms it again from the lane number for every window: six vector
+        // instructions per turn); the entry 64 further on is that xor 256, because the entry is taken mod 128.  The
+        // event-logging builds have no register to spare (127 of 128; with this one they spill to scratch): they form it
+        // per window from a lane number hipcc cannot see through, as every build did before (issue_window).
+        auto entry_bytes_of = [&](int lane) -> unsigned {
+            return ((unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane) & (kTile - 1)) * (unsigned)sizeof(T);
         };
-        auto window_offset = [&](long long st, unsigned e) -> unsigned {   // byte offset of the body's x in the tiled copy Jt
+        unsigned entry0_kept = kLog ? 0u : entry_bytes_of(l);
+        if (!kLog) asm volatile("" : "+v"(entry0_kept));
+        auto window_offset = [&](Idx st, unsigned e) -> unsigned {   // byte offset of the body's x in the tiled copy Jt
             const unsigned src = (unsigned)st + e;
-            const unsigned wrapped = src - (unsigned)N;        // huge when src < N
+            const unsigned wrapped = src - (unsigned)N;                // huge when src < N
             const unsigned idx = src < wrapped ? src : wrapped;
             return ((idx / kTile) * (4u * kTile) + (idx % kTile)) * (unsigned)sizeof(T);
         };
@@ -1116,19 +1150,34 @@ void forces_ring_f32(const RingArgs args) {
             load_to_lds_b32(src + 2 * plane, byte_offset, base + 2 * comp_bytes);
             if (any_radius) load_to_lds_b32(src + 3 * plane, byte_offset, base + 3 * comp_bytes);
         };
-        auto issue_window = [&](long long st, int buf) {
+        auto issue_window = [&](Idx st, int buf) {
             const unsigned base = __builtin_amdgcn_readfirstlane(lds_offset_of(&win[w][buf][0][0]));
-            const unsigned e0 = first_entry();
-            const unsigned e1 = e0 ^ kWave;                    // the entry 64 further on
-            if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= N) {
+            if (kLog) {                                        // as before: entries, not bytes; 64-bit compare
+                int lane = l;
+                asm volatile("" : "+v"(lane));
+                const unsigned e0 = (unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane) & (kTile - 1);
+                const unsigned e1 = e0 ^ kWave;
+                if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= Nu) {
+                    const unsigned tile_byte = ((unsigned)st / kTile) * (4u * kTile * (unsigned)sizeof(T));
+                    if (l < nwin) issue_entries(tile_byte, e0 * (unsigned)sizeof(T), base, kWin * (unsigned)sizeof(T));
+                    if (l + kWave < nwin) issue_entries(tile_byte, e1 * (unsigned)sizeof(T), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+                } else {
+                    if (l < nwin) issue_entries(0u, window_offset(st, e0), base, kWin * (unsigned)sizeof(T));
+                    if (l + kWave < nwin) issue_entries(0u, window_offset(st, e1), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+                }
+                return;
+            }
+            const unsigned entry0_bytes = entry0_kept;
+            const unsigned entry1_bytes = entry0_bytes ^ (kWave * (unsigned)sizeof(T));   // the entry 64 further on
+            if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= Nu) {
                 // the common case - the window's tile is an aligned tile of Jt -: the tile goes into the scalar base address,
-                // the lanes' offsets are the two per-lane constants, no vector arithmetic at all
+                // the lanes' offsets are the two per-lane constants, no vector arithmetic in the loop (hipcc hoists the xor)
                 const unsigned tile_byte = ((unsigned)st / kTile) * (4u * kTile * (unsigned)sizeof(T));
-                if (l < nwin) issue_entries(tile_byte, e0 * (unsigned)sizeof(T), base, kWin * (unsigned)sizeof(T));
-                if (l + kWave < nwin) issue_entries(tile_byte, e1 * (unsigned)sizeof(T), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+                if (l < nwin) issue_entries(tile_byte, entry0_bytes, base, kWin * (unsigned)sizeof(T));
+                if (l + kWave < nwin) issue_entries(tile_byte, entry1_bytes, base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
             } else {
-                if (l < nwin) issue_entries(0u, window_offset(st, e0), base, kWin * (unsigned)sizeof(T));
-                if (l + kWave < nwin) issue_entries(0u, window_offset(st, e1), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+                if (l < nwin) issue_entries(0u, window_offset(st, entry0_bytes / (unsigned)sizeof(T)), base, kWin * (unsigned)sizeof(T));
+                if (l + kWave < nwin) issue_entries(0u, window_offset(st, entry1_bytes / (unsigned)sizeof(T)), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
             }
         };
         // A truncated tile: its L <= 128 entries in order, component-major x[128] y[128] m[128] r[128] across BOTH window
@@ -1136,7 +1185,7 @@ void forces_ring_f32(const RingArgs args) {
         // after the hand-off of the turn before.
         static_assert(2 * kWin >= kTile, "a whole tile fits the two window buffers");
         float* const whole = &win[w][0][0][0];
-        auto issue_truncated = [&](long long st, int L) {
+        auto issue_truncated = [&](Idx st, int L) {
             const unsigned base = __builtin_amdgcn_readfirstlane(lds_offset_of(whole));
             if (l < L) issue_entries(0u, window_offset(st, (unsigned)l), base, kTile * (unsigned)sizeof(T));
             if (l + kWave < L) issue_entries(0u, window_offset(st, (unsigned)(l + kWave)), base + kWave * (unsigned)sizeof(T), kTile * (unsigned)sizeof(T));
@@ -1149,7 +1198,7 @@ void forces_ring_f32(const RingArgs args) {
         // The collision screen of a fast turn needs an upper bound of the radii the window holds.  The window's bodies are
         // J[st .. st + 127] (wrapped at N): they lie in the aligned tiles st / 128 and st / 128 + 1 and, when wrapped, tile 0;
         // unpack_slots keeps max |radius| per aligned tile.  Scalar loads, issued with the window a turn ahead.
-        auto window_rmax = [&](long long st) -> float {
+        auto window_rmax = [&](Idx st) -> float {
             if (!any_radius) return 0.0f;
             const int ta = __builtin_amdgcn_readfirstlane((int)(st / kTile));
             if (kLog && (ta < 0 || ta + 1 >= NB_RING_LATE(n_tiles))) {
@@ -1157,12 +1206,12 @@ void forces_ring_f32(const RingArgs args) {
                 return __builtin_inff();                       // every lane is flagged: the general code decides
             }
             const float ra = tile_rmax[ta], rb = tile_rmax[ta + 1];
-            const float rw = (st + kTile > N) ? tile_rmax[0] : 0.0f;
+            const float rw = (st + kTile > Nu) ? tile_rmax[0] : 0.0f;
             const float rab = ra > rb ? ra : rb;
             return rab > rw ? rab : rw;
         };
         struct WindowState { bool fast; float rmax; };
-        auto check_window = [&](int kind, int kk, int buf, long long st_w) -> WindowState {
+        auto check_window = [&](int kind, int kk, int buf, Idx st_w) -> WindowState {
             if (kind != 1) return WindowState{false, 0.0f};    // (a truncated tile is waited for where it is read)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // issued a whole turn ago
             __builtin_amdgcn_wave_barrier();
@@ -1232,7 +1281,7 @@ void forces_ring_f32(const RingArgs args) {
 
         const int tau0 = tau_lo + w;                           // this wave's first turn of the item
         const int dseq = kQueue ? seq_base - tau_lo : 0;       // turn tau of the walk has sequence number tau + dseq
-        long long st = tile_start_slow(tau0 / kTurnsPerTile);
+        Idx st = (Idx)tile_start_slow(tau0 / kTurnsPerTile);        // in [0, N)
         int buf = 0;
         int plain_turns = 0;                                   // turns of this wave that took the common path
         bool first_plain = false;                              // ... the first turn of the walk among them (one pair less)
@@ -1247,18 +1296,12 @@ void forces_ring_f32(const RingArgs args) {
             const int off0 = (tau % kTurnsPerTile) * kT;
             const int L = tile_len(kk, st);
             const bool fast = cur.fast;
-            const long long st_next = round_on(st);
+            const Idx st_next = round_on(st);
             const int kind_next = turn_kind(tau + kW, st_next);
             if (kind_next == 1) issue_window(st_next, buf ^ 1);                  // in flight for the whole turn
             const bool first = lit && tau == 0;                // walk position 0 is the body itself (:200-204)
             if (kRings > 1) {                                  // behind the furthest ring of the workgroup: evaluate first
-                int ahead = *seq_o1;
-                if (kRings == 4) {
-                    const int o2 = *seq_o2, o3 = *seq_o3;
-                    ahead = ahead > o2 ? ahead : o2;
-                    ahead = ahead > o3 ? ahead : o3;
-                }
-                if (*seq_mine < ahead) __builtin_amdgcn_s_setprio(1);
+                if (any_ring_ahead()) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
             // (2) the kT terms of this turn: walk positions 2v, 2v + 1 in the two halves of termx[v] / termy[v]
@@ -1447,7 +1490,7 @@ void forces_ring_f32(const RingArgs args) {
                                 if (kLog) {
                                     const long long i64 = body_index64();
                                     const int i = (int)(i64 < 0x7fffffff ? i64 : 0x7fffffff);
-                                    long long j = lit ? st + (((int)(i64 - blk0) + off0 + r) & (kTile - 1)) : st + off0 + r;
+                                    long long j = lit ? (long long)st + (((int)(i64 - blk0) + off0 + r) & (kTile - 1)) : (long long)st + off0 + r;
                                     if (j >= N) j %= N;
                                     Counters* const ctr = NB_RING_LATE(ctr);
                                     const unsigned long long slot = atomicAdd(&ctr->events, 1ull);
@@ -1465,7 +1508,7 @@ void forces_ring_f32(const RingArgs args) {
                         if (hi > off0) pairs_rare += (hi - off0) - ((kk == 0 && off0 == 0) ? 1 : 0);
                     } else {
                         const long long i64 = body_index64();
-                        for (int off = off0; off < hi; ++off) pairs_rare += (st + off != i64) ? 1 : 0;
+                        for (int off = off0; off < hi; ++off) pairs_rare += ((long long)st + off != i64) ? 1 : 0;
                     }
                 }
                 if (dead) {                                    // a hand-off wait gave up somewhere before: poison, never a result
