@@ -348,6 +348,49 @@ int nbody_get_diagnostics(nbody_ctx* ctx, nbody_diag* out, double* phi);
 int nbody_group_diagnostics(nbody_ctx** ctxs, int world, nbody_diag* out, double* phi);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Field evaluation (the reference has none): acceleration and potential at the bodies' own positions or at
+ * arbitrary probe points.  Over the n current bodies, in IEEE fp64 (fp32 states are widened exactly), G = (double)6.67408e-11f,
+ * independent of the semantics like the diagnostics (a literal context's frozen tail is a source like any other body).  With
+ * x_j a source position, m_j its mass and r_j = |x - x_j|:
+ *     phi(x) = -G sum_j m_j / r_j                    a(x) = -G sum_j m_j (x - x_j) / r_j^3
+ * over the sources with r_j > 0; a source at distance exactly 0 is left out of all three sums and counted in *coincident.
+ * Explicit points (points != NULL): m probe points, always nbody_vec2 (double) whatever the context's precision; out[p] is the
+ * field at points[p]; *n_out = m; m == 0 is legal and launches nothing.
+ * Own positions (points == NULL): the probe points are the current bodies' own positions, taken on the device with no
+ * download; body i's self term is excluded by index and not counted, so *coincident equals nbody_diag.coincident_pairs; m is
+ * the room in out, *n_out the current count n; m < n is NBODY_ERR_CAPACITY with nothing written.
+ * Order contract (the one of the diagnostics).  ax, ay and phi of a point are each one running sum over j = 0 .. n-1 ascending:
+ * the bits depend on the state and the point only, not on rank, world, transport, force kernel, m or the point's position in
+ * points.  With points == NULL, out[i].phi has the bits nbody_get_diagnostics puts in phi[i], for every state.  A sum whose fast
+ * chain is not finite is redone by general code (IEEE sqrt and divide, hypot outside the normal range, distance-0 sources
+ * skipped and counted) in which a term overflows only where m_j / r_j^2 itself does; a finite sum is never replaced.  Each
+ * term of a component is within 13 ulps of its exact value (m_j / r_j within 3): |error| <= (n + 14) 2^-53 sum_j |term|.
+ * Non-finite inputs may give non-finite outputs.
+ * nbody_get_field synchronises, reads the replica only and never changes what later steps compute.  It is NOT collective:
+ * every rank's replica holds every position and mass (as nbody_render_image relies on), so any context may call it on its own
+ * - world > 1, a rank of a NBODY_FLAG_GROUP_EXCHANGE group, a NBODY_FLAG_FORCE_COMM context - and each gives the same bits.
+ * The device points, the device results and their pinned staging are allocated on the first call and grown to the largest m
+ * seen; a context that never calls it allocates nothing and launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: NULL ctx, out, n_out or coincident; m < 0; m x 24 bytes above 2^31.
+ * NBODY_ERR_STATE: before an upload.  A device-side failure is reported as by every synchronising call.
+ * Cost (one MI355X, fp32; profiles/field_probe.txt): a whole call at N = 262144 with points == NULL 42.5 ms (the kernel 40.8 ms:
+ * 1.35 times the time per pair of the diagnostics' potential kernel, 1.38 expected from the 15 + 1 against 10 + 1 fp64
+ * instructions per pair), against 29.4 ms for nbody_get_diagnostics with phi and 28.7 ms for a step; 65536 explicit points on
+ * that state 13.9 ms (1.79 times: 256 workgroups are one wave per SIMD); a batch of 256 x 1024 with points == NULL 1.42 ms per
+ * call, 0.18 ms of it the kernel.
+ * nbody_batch_get_field: the same evaluation for every system of a batch in ONE launch, whatever S is, with the one set of
+ * points for all of them.  Explicit points: system s's results at out[s * m + p] (systems x m x 24 bytes at most 2^31).
+ * points == NULL: system s's results go to out + s * capacity, one entry per current body, the rest of the slice is left
+ * unchanged (the layout of nbody_batch_diagnostics' phi).  coincident: one int64_t per system.  System s gives the bits an
+ * nbody_ctx holding that system's state gives; an empty system gives +0 in every field of every point and 0 coincident.  A
+ * count outside [0, capacity] is treated as 0 and reported for that system, as by nbody_batch_diagnostics.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_field { double ax, ay, phi; } nbody_field;   /* 24 bytes */
+int nbody_get_field(nbody_ctx* ctx, const nbody_vec2* points, int m, nbody_field* out, int* n_out, int64_t* coincident);
+struct nbody_batch;   /* the batched stepper, below */
+int nbody_batch_get_field(struct nbody_batch* b, const nbody_vec2* points, int m, nbody_field* out, int64_t* coincident);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

@@ -95,6 +95,11 @@ class Diag(ctypes.Structure):
                 "angular_momentum": self.angular_momentum, "kinetic": self.kinetic, "potential": self.potential}
 
 
+class Field(ctypes.Structure):
+    """struct nbody_field (include/nbody.h): acceleration and potential at one point, fp64."""
+    _fields_ = [("ax", ctypes.c_double), ("ay", ctypes.c_double), ("phi", ctypes.c_double)]
+
+
 class Rng(ctypes.Structure):
     _fields_ = [("u", ctypes.c_uint64), ("v", ctypes.c_uint64), ("w", ctypes.c_uint64)]
 
@@ -106,6 +111,9 @@ LINEAGE_DTYPE = np.dtype([("step", np.int32), ("id_i", np.int32), ("id_j", np.in
 DIAG_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64), ("coincident_pairs", np.int64), ("mass", np.float64),
                        ("momentum", np.float64, (2,)), ("center_of_mass", np.float64, (2,)),
                        ("angular_momentum", np.float64), ("kinetic", np.float64), ("potential", np.float64)])
+
+# struct nbody_field as a numpy record (Stepper.field, StepperBatch.field)
+FIELD_DTYPE = np.dtype([("acc", np.float64, (2,)), ("phi", np.float64)])
 
 # struct nbody_track_row, nbody_track_f32 / nbody_track_f64: the planes of the track log (Stepper.tracks, StepperBatch.tracks)
 TRACK_ROW_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64)])
@@ -168,6 +176,7 @@ SYMBOLS = {
     "nbody_ctx_stream": (_vp, [_vp]),
     "nbody_get_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_group_diagnostics": (_i, [_pp, _i, ctypes.POINTER(Diag), _vp]),
+    "nbody_get_field": (_i, [_vp, _vp, _i, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_create": (_i, [_pp, ctypes.POINTER(_BatchDesc), ctypes.POINTER(_BatchParams)]),
     "nbody_batch_destroy": (_i, [_vp]),
     "nbody_batch_upload": (_i, [_vp, _pp, _ip]),
@@ -181,6 +190,7 @@ SYMBOLS = {
     "nbody_batch_get_stats": (_i, [_vp, _i, ctypes.POINTER(Stats)]),
     "nbody_batch_kernel_name": (ctypes.c_char_p, [_vp]),
     "nbody_batch_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
+    "nbody_batch_get_field": (_i, [_vp, _vp, _i, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_diag_reserve": (_i, [_vp, _i]),
     "nbody_batch_diag_record": (_i, [_vp]),
     "nbody_batch_diag_read": (_i, [_vp, _vp, _i, _ip]),
@@ -380,6 +390,28 @@ def _diagnostics(call, capacity, potential):
     if potential:
         out["phi"] = phi[:d.n_bodies].copy()
     return out
+
+
+def _field_points(points):
+    """The probe points of field(): None (the bodies' own positions), or anything np.asarray(..., float64) turns into
+    shape (m, 2).  Checked here, before the library is called."""
+    if points is None:
+        return None
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64))
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError("points must have shape (m, 2), got %r" % (pts.shape,))
+    return pts
+
+
+def _field(call, points, capacity):
+    """nbody_get_field through `call(points, m, out, n_out, coincident)` -> {"acc", "phi", "coincident"}."""
+    pts = _field_points(points)
+    m = capacity if pts is None else len(pts)
+    buf = np.zeros(max(m, 1), dtype=FIELD_DTYPE)
+    n, coin = ctypes.c_int(0), ctypes.c_int64(0)
+    _check(call(None if pts is None else pts.ctypes.data, m, buf.ctypes.data, ctypes.byref(n), ctypes.byref(coin)))
+    return {"acc": np.ascontiguousarray(buf["acc"][:n.value]), "phi": np.ascontiguousarray(buf["phi"][:n.value]),
+            "coincident": coin.value}
 
 
 def _reserve_tracks(call, samples, ids, potential):
@@ -582,6 +614,13 @@ class Stepper:
         coincident_pairs of the current state; with potential=True also "phi", the per-body potential (n float64)."""
         return _diagnostics(lambda d, phi: lib.nbody_get_diagnostics(self._ctx, d, phi), self.capacity, potential)
 
+    def field(self, points=None):
+        """nbody_get_field: acceleration and potential (fp64) of the current bodies at `points` (m, 2), or with
+        points=None at the bodies' own positions (self term left out): {"acc": (m, 2), "phi": (m,), "coincident": sources
+        at distance 0, left out and counted}; m is the current body count for points=None, where "phi" has the bits of
+        diagnostics(potential=True)["phi"].  Not collective: any rank of any world may call it on its own."""
+        return _field(lambda *a: lib.nbody_get_field(self._ctx, *a), points, self.capacity)
+
     def stats(self):
         s = Stats()
         _check(lib.nbody_get_stats(self._ctx, ctypes.byref(s)))
@@ -619,6 +658,10 @@ class StepperGroup:
         """nbody_group_diagnostics: as Stepper.diagnostics, for the whole group."""
         return _diagnostics(lambda d, phi: lib.nbody_group_diagnostics(self._arr, self.world, d, phi), self.capacity,
                             potential)
+
+    def field(self, points=None, rank=0):
+        """Stepper.field through one rank: every rank's replica holds every position and mass, each gives the same bits."""
+        return self.ranks[rank].field(points)
 
     def close(self):
         for r in self.ranks:
@@ -728,6 +771,19 @@ class StepperBatch:
                 d["phi"] = phi[s * self.capacity:s * self.capacity + d["n_bodies"]].copy()
             res.append(d)
         return res
+
+    def field(self, points=None):
+        """nbody_batch_get_field: Stepper.field for every system in one launch, with the one set of points for all of
+        them: {"acc": (S, m, 2), "phi": (S, m), "coincident": (S,) int64}, system s having the bits a Stepper holding its
+        state gives.  points=None: m is `capacity`, and the entries past a system's count are zero."""
+        pts = _field_points(points)
+        m = self.capacity if pts is None else len(pts)
+        buf = np.zeros((self.systems, max(m, 1)), dtype=FIELD_DTYPE)
+        coin = np.zeros(self.systems, dtype=np.int64)
+        _check(lib.nbody_batch_get_field(self._b, None if pts is None else pts.ctypes.data, m, buf.ctypes.data,
+                                         coin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return {"acc": np.ascontiguousarray(buf["acc"][:, :m]), "phi": np.ascontiguousarray(buf["phi"][:, :m]),
+                "coincident": coin}
 
     def reserve_diagnostics(self, samples):
         """Room for `samples` recorded samples of every system on the device (0 frees it); empties the series."""

@@ -19,6 +19,7 @@
 #include "nbody_error.h"
 #include "nbody_batch_kernels.hpp"
 #include "nbody_batch_diag.hpp"
+#include "nbody_field.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
 
@@ -71,6 +72,8 @@ struct nbody_batch {
     IdsState ids;                       // the map [S * cap] twice, the lineage [S * ev_cap], [S] translated-up-to counters
     // track log (nbody_batch_track_*, nbody_tracks.hpp): nothing is allocated without a reservation
     TrackState trk;
+    // field evaluation (nbody_batch_get_field, nbody_field.hpp): nothing is allocated before the first call
+    FieldState fld;
 };
 
 namespace {
@@ -89,6 +92,7 @@ void free_all(nbody_batch* b) {
     (void)hipFree(b->blk_counts);
     (void)hipFree(b->ids.map[0]); (void)hipFree(b->ids.map[1]); (void)hipFree(b->ids.lineage); (void)hipFree(b->ids.done);
     (void)hipFree(b->trk.buf); (void)hipFree(b->trk.sel);
+    field_free(b->fld);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -674,6 +678,63 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
     int rc = read_meta(b);                                 // synchronises: every enqueued record has been written
     if (rc != NBODY_OK) return rc;
     return track_read(b->trk, "nbody_batch_track_read", rows, rec, index, phi, cap_samples, n_samples, columns);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Field evaluation (nbody_batch_get_field; kernel and the shared host code in nbody_field.hpp): one launch for every
+// system, system = blockIdx.y, one set of points for all of them.  At the end of the file for the reason the identities are.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+struct FieldBatchCount {
+    static constexpr bool kBatch = true;
+    static __device__ __forceinline__ int checked(const Meta* meta_all, int sys, int stride, int) {
+        return batch_checked_count(meta_all[sys].n, stride);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int nbody_batch_get_field(nbody_batch* b, const nbody_vec2* points, int m, nbody_field* out, int64_t* coincident) {
+    int rc = field_check_args("nbody_batch_get_field", b, m, out, b, coincident, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK) return rc;
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_field before nbody_batch_upload");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    const bool own = points == nullptr;
+    const int rows = own ? b->n_upper : m;                 // what the grid covers
+    const size_t per_sys = own ? (size_t)b->cap : (size_t)m;   // results of one system on the device
+    const size_t total = per_sys * (size_t)b->S;
+    for (int s = 0; s < b->S; ++s) coincident[s] = 0;
+    if (rows > 0) {
+        rc = field_reserve(b->fld, own ? 0 : (size_t)m, total, "nbody_batch_get_field");
+        if (rc != NBODY_OK) return rc;
+        if (!own) HIP_TRY(field_stage_points(b->fld, b->stream, points, m));
+        const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock, b->S);
+        if (own)
+            hipLaunchKernelGGL((field_at<float, true, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
+                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
+                               (const FieldPoint*)nullptr, 0, (double)kG, b->fld.out);
+        else
+            hipLaunchKernelGGL((field_at<float, false, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
+                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
+                               (const FieldPoint*)b->fld.pts, m, (double)kG, b->fld.out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(b->fld.h, b->fld.out, total * sizeof(FieldOut), hipMemcpyDeviceToHost, b->stream));
+    }
+    rc = read_meta(b);                                     // synchronises; a system whose count failed its check ends here
+    if (rc != NBODY_OK) return rc;
+    if (rows == 0) return NBODY_OK;
+    const FieldOut* h = reinterpret_cast<const FieldOut*>(b->fld.h);
+    for (int s = 0; s < b->S; ++s) {
+        const int n = b->h_meta[s].n;                      // 0 .. cap: read_meta has passed
+        const size_t cnt = own ? (size_t)(n < 0 || n > b->cap ? 0 : n) : (size_t)m;
+        coincident[s] = (int64_t)field_unpack(h + (size_t)s * per_sys, cnt, out + (size_t)s * per_sys);
+    }
+    return NBODY_OK;
 }
 
 }  // extern "C"

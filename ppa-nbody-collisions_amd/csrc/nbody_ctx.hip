@@ -22,6 +22,7 @@
 #include "nbody_error.h"
 #include "nbody_kernels.hpp"
 #include "nbody_diag.hpp"
+#include "nbody_field.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
 
@@ -177,6 +178,8 @@ struct nbody_ctx {
     IdsState ids;                          // the map [cap_own] twice, the lineage [ev_cap], the translated-up-to counter
     // track log (nbody_track_*, nbody_tracks.hpp): nothing is allocated without a reservation
     TrackState trk;
+    // field evaluation (nbody_get_field, nbody_field.hpp): nothing is allocated before the first call
+    FieldState fld;
 };
 
 namespace {
@@ -572,6 +575,7 @@ void free_all(nbody_ctx* c) {
     hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
     hipFree(c->ids.map[0]); hipFree(c->ids.map[1]); hipFree(c->ids.lineage); hipFree(c->ids.done);
     hipFree(c->trk.buf); hipFree(c->trk.sel);
+    field_free(c->fld);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -1614,6 +1618,61 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return track_read(c->trk, "nbody_track_read", rows, rec, index, phi, cap_samples, n_samples, columns);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Field evaluation (nbody_get_field; kernel and the shared host code in nbody_field.hpp).  At the end of the file for the
+// reason the identities are.  Reads the replica J only - every rank holds every position and mass - so any context may
+// call it on its own, whatever its world or transport.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+template <typename T>
+void field_launch(nbody_ctx* c, int n, bool own, int m) {
+    const int rows = own ? n : m;
+    const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock);
+    if (own)
+        hipLaunchKernelGGL((field_at<T, true, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
+                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)nullptr, 0, (double)kG, c->fld.out);
+    else
+        hipLaunchKernelGGL((field_at<T, false, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
+                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)c->fld.pts, m, (double)kG,
+                           c->fld.out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbody_get_field(nbody_ctx* c, const nbody_vec2* points, int m, nbody_field* out, int* n_out, int64_t* coincident) {
+    int rc = field_check_args("nbody_get_field", c, m, out, n_out, coincident, 1);
+    if (rc != NBODY_OK) return rc;
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_get_field before nbody_upload");
+    HIP_TRY(hipSetDevice(c->desc.device));
+    rc = read_meta(c);
+    if (rc != NBODY_OK) return rc;
+    const int n = c->h_meta->n;
+    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "nbody_get_field: %d bodies, capacity %d", n, c->cap);
+    const bool own = points == nullptr;
+    if (own && m < n)
+        return nbody_fail(NBODY_ERR_CAPACITY, "nbody_get_field: room for %d results, the context holds %d bodies", m, n);
+    const int rows = own ? n : m;
+    *n_out = rows;
+    *coincident = 0;
+    if (rows == 0) return NBODY_OK;
+    rc = field_reserve(c->fld, own ? 0 : (size_t)m, (size_t)rows, "nbody_get_field");
+    if (rc != NBODY_OK) return rc;
+    if (!own) HIP_TRY(field_stage_points(c->fld, c->stream, points, m));
+    if (c->desc.precision == NBODY_F64) field_launch<double>(c, n, own, m);
+    else field_launch<float>(c, n, own, m);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->fld.h, c->fld.out, (size_t)rows * sizeof(FieldOut), hipMemcpyDeviceToHost, c->stream));
+    rc = read_meta(c);                                     // synchronises; a device-side failure is reported here
+    if (rc != NBODY_OK) return rc;
+    *coincident = (int64_t)field_unpack(reinterpret_cast<const FieldOut*>(c->fld.h), (size_t)rows, out);
+    return NBODY_OK;
 }
 
 }  // extern "C"

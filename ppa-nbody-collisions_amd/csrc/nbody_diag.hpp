@@ -1,7 +1,8 @@
 // csrc/nbody_diag.hpp -- physical diagnostics of the resident state (nbody_get_diagnostics, include/nbody.h): the
 // per-body potential phi_i = -G sum_{j != i, r_ij > 0} m_j / r_ij and the O(N) moments, all in fp64 (fp32 inputs are
 // widened exactly).  Included after nbody_kernels.hpp.  What every potential kernel and every finish of the totals must
-// agree on bit for bit lives here once: diag_walk (the sum over j; also batch_diag_potential's and track_potential's),
+// agree on bit for bit lives here once: diag_walk (the sum over j; also batch_diag_potential's, track_potential's and, as
+// diag_walk_sums, field_at's),
 // diag_row_general, and diag_add / diag_finish (host and device: diag_collect in nbody_ctx.hip, batch_diag_reduce).
 //
 // Order contract.  phi_i is ONE running sum over j = 0, 1, ..., n-1 in ascending order, whatever the
@@ -101,6 +102,26 @@ __device__ __forceinline__ double diag_rinv(double d2) {
     return __builtin_fma(y * e, p, y);
 }
 
+// What a row carries along the j stream: the potential's running sum `s`, and for kMore whatever else is summed over
+// the same pairs (FieldSums, nbody_field.hpp: the two acceleration components).  The per-pair expressions - dx, dy, d2,
+// diag_rinv and the fma into s - are written here and in diag_walk_sums' checked loop, nowhere else: every kernel that
+// sums over j calls the one walk.
+struct DiagPhiSum {
+    static constexpr bool kMore = false;
+    double s = 0.0;
+    __device__ __forceinline__ void more(double, double, double, double) {}
+};
+
+// One pair of the fast chain: source j at (xj, yj) with mass mj - references into the LDS tile, read where the expressions
+// use them - and the row at (xi, yi).
+template <typename Sums>
+__device__ __forceinline__ void diag_pair(Sums& a, const double& xj, const double& yj, const double& mj, double xi, double yi) {
+    const double dx = xj - xi, dy = yj - yi;
+    const double d2 = __builtin_fma(dx, dx, dy * dy);
+    a.s = __builtin_fma(mj, diag_rinv(d2), a.s);
+    if constexpr (Sums::kMore) a.more(mj, dx, dy, diag_rinv(d2));   // the same d2, mj and diag_rinv: evaluated once
+}
+
 // The general code of a flagged row: exact on the whole range, coincident pairs counted and skipped.
 struct DiagRow { double s; long long coincident; };
 template <typename T>
@@ -119,21 +140,22 @@ __device__ __forceinline__ DiagRow diag_row_general(const Rec<T>* __restrict__ J
     return DiagRow{s, c};
 }
 
-// The sum over j of row i at (xi, yi), j = 0 .. n-1 ascending: every potential kernel's inner walk.  Called by all
-// kDiagBlock lanes of the workgroup (it owns the tile buffers and the barriers), lanes without a row included.
+// The sum over j of row i at (xi, yi), j = 0 .. n-1 ascending: every potential kernel's inner walk, and field_at's.  Called
+// by all kDiagBlock lanes of the workgroup (it owns the tile buffers and the barriers), lanes without a row included.
 // self_tile: the j tile that holds the lane's self term j == i.
 // kGatheredRows = false: the rows of a wave are contiguous and within one tile; self_tile is that tile, wave-uniform
 //                        (lanes past the last row carry it too: they compute and are not stored).
-// kGatheredRows = true : any row per lane, -1 for a lane without one; the wave votes per tile, and a wave without any row
-//                        only loads tiles.
-template <bool kGatheredRows, typename T>
-__device__ __forceinline__ double diag_walk(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi,
-                                            int self_tile) {
-    __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
+// kGatheredRows = true : any row per lane, -1 for a lane without one; the wave votes per tile.
+// kSelfTerms = false   : no row is a body (probe points): there is no checked loop at all.
+// wave_works (wave-uniform): a wave without any row only loads tiles.
+// sx, sy, sm: the caller's LDS planes - diag_walk's for the potential kernels, so that their LDS layout stays what it was.
+typedef double DiagPlanes[2][kTile];          // one component of the double-buffered j tile, in LDS
+template <bool kGatheredRows, bool kSelfTerms, typename T, typename Sums>
+__device__ __forceinline__ void diag_walk_sums(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi,
+                                               int self_tile, bool wave_works, Sums& a, DiagPlanes& sx, DiagPlanes& sy,
+                                               DiagPlanes& sm) {
     const int tid = threadIdx.x;
-    const bool wave_works = !kGatheredRows || __any(self_tile >= 0);
     const int jtiles = (n + kTile - 1) / kTile;
-    double acc = 0.0;
     for (int t = 0; t < jtiles; ++t) {
         const int b = t & 1;
         const int j0 = t * kTile;
@@ -145,31 +167,33 @@ __device__ __forceinline__ double diag_walk(const Rec<T>* __restrict__ J, int n,
         // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
         __syncthreads();
         if (!wave_works) continue;
-        if (kGatheredRows ? !__any(self_tile == t) : t != self_tile) {
+        if (!kSelfTerms || (kGatheredRows ? !__any(self_tile == t) : t != self_tile)) {
             int q = 0;
             for (; q + 4 <= jn; q += 4) {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double dx = sx[b][q + u] - xi, dy = sy[b][q + u] - yi;
-                    const double d2 = __builtin_fma(dx, dx, dy * dy);
-                    acc = __builtin_fma(sm[b][q + u], diag_rinv(d2), acc);
-                }
+                for (int u = 0; u < 4; ++u) diag_pair(a, sx[b][q + u], sy[b][q + u], sm[b][q + u], xi, yi);
             }
-            for (; q < jn; ++q) {
-                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
-                const double d2 = __builtin_fma(dx, dx, dy * dy);
-                acc = __builtin_fma(sm[b][q], diag_rinv(d2), acc);
-            }
+            for (; q < jn; ++q) diag_pair(a, sx[b][q], sy[b][q], sm[b][q], xi, yi);
         } else {
+            // diag_pair with the self term masked (m = 0 at d2 = 1: an exact +0).  Written out: a function boundary around
+            // the conditional LDS read changes the code of every kernel that has this loop.
             for (int q = 0; q < jn; ++q) {
                 const bool self = j0 + q == i;
                 const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
                 const double d2 = self ? 1.0 : __builtin_fma(dx, dx, dy * dy);
-                acc = __builtin_fma(self ? 0.0 : sm[b][q], diag_rinv(d2), acc);
+                a.s = __builtin_fma(self ? 0.0 : sm[b][q], diag_rinv(d2), a.s);
+                if constexpr (Sums::kMore) a.more(self ? 0.0 : sm[b][q], dx, dy, diag_rinv(d2));
             }
         }
     }
-    return acc;
+}
+template <bool kGatheredRows, typename T>
+__device__ __forceinline__ double diag_walk(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi,
+                                            int self_tile) {
+    __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
+    DiagPhiSum a;
+    diag_walk_sums<kGatheredRows, true, T>(J, n, i, xi, yi, self_tile, !kGatheredRows || __any(self_tile >= 0), a, sx, sy, sm);
+    return a.s;
 }
 
 template <typename T>
