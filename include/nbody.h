@@ -391,6 +391,58 @@ struct nbody_batch;   /* the batched stepper, below */
 int nbody_batch_get_field(struct nbody_batch* b, const nbody_vec2* points, int m, nbody_field* out, int64_t* coincident);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Neighbour queries (the reference has none): for every row - a current body, or an arbitrary probe point -
+ * the nearest of the n current bodies, its squared distance, and how many of them satisfy the reference's collision
+ * predicate d^2 <= (r_i + r_j)^2 (src/nbody.cu:126-134) with the row right now.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma.  A row has
+ * a position (x, y) and a radius r: for an explicit point r = +0; for a body x, y and r are the body's record widened
+ * exactly.  A source j has the record (X_j, Y_j, R_j), widened exactly from fp32 or taken as it is from fp64.  Then
+ *     dx = X_j - x;  dy = Y_j - y;  d2_j = (dx*dx) + (dy*dy);              three roundings after the two subtractions
+ *     nearest:  best = +inf, index = -1;  for j ascending:  if (d2_j < best) { best = d2_j; index = j; }
+ *     overlaps: the number of j with  d2_j <= s*s,  s = r + R_j            the reference's predicate read in fp64
+ * and out.d2 = best, out.index = index, out.overlaps = that number.  What follows from it:
+ *   - ties go to the lowest j;
+ *   - a source whose d2 is NaN or +inf is never the nearest; a source whose d2 is NaN is never an overlap (one whose d2 is
+ *     +inf is an overlap exactly where s*s is +inf too);
+ *   - a row with no eligible source gives {+inf, -1, 0};
+ *   - the result is a function of the set of sources only, so an implementation may walk j in any order and with any number
+ *     of lanes per row, as long as it returns exactly this;
+ *   - it is independent of the semantics, like the diagnostics: a literal context's frozen tail is a source like any other
+ *     body; the masses play no part;
+ *   - with the bodies' own positions d2_ij and d2_ji have the same bits (dx only changes sign, s is the same sum), so
+ *     overlaps are symmetric: j counts for i exactly where i counts for j;
+ *   - accuracy: the inputs are exact, dx is within 1 u of the exact difference, its square within 3 u, the sum within 4 u
+ *     (first order, u = 2^-53): d2 is within 4 u of the exact squared distance as long as no square underflows.
+ * Explicit points (points != NULL): m probe points, always nbody_vec2 (double) whatever the context's precision; out[p]
+ * belongs to points[p]; *n_out = m; m == 0 is legal and launches nothing.
+ * Own positions (points == NULL): the rows are the current bodies, taken on the device with no download; body i's self term
+ * is excluded by index (a second body at the same place is a source at d2 = +0); m is the room in out, *n_out the current
+ * count n; m < n is NBODY_ERR_CAPACITY with nothing written.
+ * nbody_get_neighbors synchronises, reads the replica only and never changes what later steps compute.  It is NOT
+ * collective: every rank's replica holds every {x, y, m, r}, so any context may call it on its own - world > 1, a rank of a
+ * NBODY_FLAG_GROUP_EXCHANGE group, a NBODY_FLAG_FORCE_COMM context - and each gives the same bits.  The device points, the
+ * device results and their pinned staging are allocated on the first call and grown to the largest m seen; a context that
+ * never calls it allocates nothing and launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: NULL ctx, out or n_out; m < 0; m x 16 bytes above 2^31.
+ * NBODY_ERR_STATE: before an upload.  A device-side failure is reported as by every synchronising call.
+ * Cost (one MI355X, fp32, stock radii; profiles/neighbor_probe.txt): a whole call at N = 262144 with points == NULL 31.6 ms (the
+ * kernel 29.5 ms: 2.33e12 ordered pairs per second, 0.95 times the time per pair of the diagnostics' potential kernel and 0.71
+ * times field_at's, measured in the same run); 65536 explicit points on that state 13.0 ms (1.60 times the potential's time
+ * per pair: 256 workgroups are one wave per SIMD); a batch of 256 x 1024 with points == NULL 0.13 ms of kernel, 1.9 ms for
+ * StepperBatch.neighbors() with its 4 MiB of results.  The route without the call, nbody_download plus the numpy model on the
+ * host, took 1.28 s at N = 16384 against 0.93 ms for the call.
+ * nbody_batch_get_neighbors: the same query for every system of a batch in ONE launch, whatever S is, with the one set of
+ * points for all of them.  Explicit points: system s's results at out[s * m + p] (systems x m x 16 bytes at most 2^31).
+ * points == NULL: system s's results go to out + s * capacity, one entry per current body, the rest of the slice is left
+ * unchanged (the layout of nbody_batch_get_field).  System s gives the bits an nbody_ctx holding that system's state gives;
+ * an empty system gives {+inf, -1, 0} for every explicit point and writes nothing in the own form.  A count outside
+ * [0, capacity] is treated as 0 and reported for that system, as by nbody_batch_get_field.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_neighbor { double d2; int32_t index; int32_t overlaps; } nbody_neighbor;   /* 16 bytes */
+int nbody_get_neighbors(nbody_ctx* ctx, const nbody_vec2* points, int m, nbody_neighbor* out, int* n_out);
+int nbody_batch_get_neighbors(struct nbody_batch* b, const nbody_vec2* points, int m, nbody_neighbor* out);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

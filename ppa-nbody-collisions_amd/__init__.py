@@ -100,6 +100,11 @@ class Field(ctypes.Structure):
     _fields_ = [("ax", ctypes.c_double), ("ay", ctypes.c_double), ("phi", ctypes.c_double)]
 
 
+class Neighbor(ctypes.Structure):
+    """struct nbody_neighbor (include/nbody.h): the nearest source of one row and the row's overlap count."""
+    _fields_ = [("d2", ctypes.c_double), ("index", ctypes.c_int32), ("overlaps", ctypes.c_int32)]
+
+
 class Rng(ctypes.Structure):
     _fields_ = [("u", ctypes.c_uint64), ("v", ctypes.c_uint64), ("w", ctypes.c_uint64)]
 
@@ -114,6 +119,9 @@ DIAG_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64), ("coincident_
 
 # struct nbody_field as a numpy record (Stepper.field, StepperBatch.field)
 FIELD_DTYPE = np.dtype([("acc", np.float64, (2,)), ("phi", np.float64)])
+
+# struct nbody_neighbor as a numpy record (Stepper.neighbors, StepperBatch.neighbors)
+NEIGHBOR_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("overlaps", np.int32)])
 
 # struct nbody_track_row, nbody_track_f32 / nbody_track_f64: the planes of the track log (Stepper.tracks, StepperBatch.tracks)
 TRACK_ROW_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64)])
@@ -177,6 +185,7 @@ SYMBOLS = {
     "nbody_get_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_group_diagnostics": (_i, [_pp, _i, ctypes.POINTER(Diag), _vp]),
     "nbody_get_field": (_i, [_vp, _vp, _i, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
+    "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
     "nbody_batch_create": (_i, [_pp, ctypes.POINTER(_BatchDesc), ctypes.POINTER(_BatchParams)]),
     "nbody_batch_destroy": (_i, [_vp]),
     "nbody_batch_upload": (_i, [_vp, _pp, _ip]),
@@ -191,6 +200,7 @@ SYMBOLS = {
     "nbody_batch_kernel_name": (ctypes.c_char_p, [_vp]),
     "nbody_batch_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_batch_get_field": (_i, [_vp, _vp, _i, _vp, ctypes.POINTER(ctypes.c_int64)]),
+    "nbody_batch_get_neighbors": (_i, [_vp, _vp, _i, _vp]),
     "nbody_batch_diag_reserve": (_i, [_vp, _i]),
     "nbody_batch_diag_record": (_i, [_vp]),
     "nbody_batch_diag_read": (_i, [_vp, _vp, _i, _ip]),
@@ -414,6 +424,16 @@ def _field(call, points, capacity):
             "coincident": coin.value}
 
 
+def _neighbors(call, points, capacity):
+    """nbody_get_neighbors through `call(points, m, out, n_out)` -> a NEIGHBOR_DTYPE array, one record per row."""
+    pts = _field_points(points)
+    m = capacity if pts is None else len(pts)
+    buf = np.zeros(max(m, 1), dtype=NEIGHBOR_DTYPE)
+    n = ctypes.c_int(0)
+    _check(call(None if pts is None else pts.ctypes.data, m, buf.ctypes.data, ctypes.byref(n)))
+    return buf[:n.value].copy()
+
+
 def _reserve_tracks(call, samples, ids, potential):
     """-> (samples, has_phi): what tracks() needs to size its buffers."""
     k = 0 if ids is None else len(ids)
@@ -621,6 +641,13 @@ class Stepper:
         diagnostics(potential=True)["phi"].  Not collective: any rank of any world may call it on its own."""
         return _field(lambda *a: lib.nbody_get_field(self._ctx, *a), points, self.capacity)
 
+    def neighbors(self, points=None):
+        """nbody_get_neighbors: for every row - each of `points` (m, 2), or with points=None each current body (self term
+        left out) - a record {"d2": squared distance to the nearest current body (fp64; +inf if there is none), "index":
+        that body (-1), "overlaps": how many bodies satisfy d2 <= (r + r_j)^2 with the row (r = 0 for a point)}, as a
+        NEIGHBOR_DTYPE array.  Not collective: any rank of any world may call it on its own."""
+        return _neighbors(lambda *a: lib.nbody_get_neighbors(self._ctx, *a), points, self.capacity)
+
     def stats(self):
         s = Stats()
         _check(lib.nbody_get_stats(self._ctx, ctypes.byref(s)))
@@ -662,6 +689,10 @@ class StepperGroup:
     def field(self, points=None, rank=0):
         """Stepper.field through one rank: every rank's replica holds every position and mass, each gives the same bits."""
         return self.ranks[rank].field(points)
+
+    def neighbors(self, points=None, rank=0):
+        """Stepper.neighbors through one rank: every rank's replica holds every body, each gives the same bits."""
+        return self.ranks[rank].neighbors(points)
 
     def close(self):
         for r in self.ranks:
@@ -784,6 +815,18 @@ class StepperBatch:
                                          coin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return {"acc": np.ascontiguousarray(buf["acc"][:, :m]), "phi": np.ascontiguousarray(buf["phi"][:, :m]),
                 "coincident": coin}
+
+    def neighbors(self, points=None):
+        """nbody_batch_get_neighbors: Stepper.neighbors for every system in one launch, with the one set of points for all
+        of them, system s having the bits a Stepper holding its state gives.  points=None: a list of S NEIGHBOR_DTYPE
+        arrays, one record per current body of the system; otherwise one array of shape (S, m)."""
+        pts = _field_points(points)
+        m = self.capacity if pts is None else len(pts)
+        buf = np.zeros((self.systems, max(m, 1)), dtype=NEIGHBOR_DTYPE)
+        _check(lib.nbody_batch_get_neighbors(self._b, None if pts is None else pts.ctypes.data, m, buf.ctypes.data))
+        if pts is None:
+            return [buf[s, :int(k)].copy() for s, k in enumerate(self.counts())]
+        return np.ascontiguousarray(buf[:, :m])
 
     def reserve_diagnostics(self, samples):
         """Room for `samples` recorded samples of every system on the device (0 frees it); empties the series."""

@@ -22,6 +22,7 @@
 #include "nbody_field.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
+#include "nbody_neighbors.hpp"
 
 using namespace nbk;
 
@@ -74,6 +75,8 @@ struct nbody_batch {
     TrackState trk;
     // field evaluation (nbody_batch_get_field, nbody_field.hpp): nothing is allocated before the first call
     FieldState fld;
+    // neighbour queries (nbody_batch_get_neighbors, nbody_neighbors.hpp): nothing is allocated before the first call
+    NeighborState nbr;
 };
 
 namespace {
@@ -93,6 +96,7 @@ void free_all(nbody_batch* b) {
     (void)hipFree(b->ids.map[0]); (void)hipFree(b->ids.map[1]); (void)hipFree(b->ids.lineage); (void)hipFree(b->ids.done);
     (void)hipFree(b->trk.buf); (void)hipFree(b->trk.sel);
     field_free(b->fld);
+    field_free(b->nbr);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -733,6 +737,52 @@ int nbody_batch_get_field(nbody_batch* b, const nbody_vec2* points, int m, nbody
         const int n = b->h_meta[s].n;                      // 0 .. cap: read_meta has passed
         const size_t cnt = own ? (size_t)(n < 0 || n > b->cap ? 0 : n) : (size_t)m;
         coincident[s] = (int64_t)field_unpack(h + (size_t)s * per_sys, cnt, out + (size_t)s * per_sys);
+    }
+    return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Neighbour queries (nbody_batch_get_neighbors; kernel and the shared host code in nbody_neighbors.hpp): one launch for
+// every system, system = blockIdx.y, one set of points for all of them; the count comes through FieldBatchCount, above.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int nbody_batch_get_neighbors(nbody_batch* b, const nbody_vec2* points, int m, nbody_neighbor* out) {
+    int rc = field_check_args("nbody_batch_get_neighbors", b, m, out, b, out, b ? (unsigned long long)b->S : 1,
+                              sizeof(nbody_neighbor));
+    if (rc != NBODY_OK) return rc;
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_neighbors before nbody_batch_upload");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    const bool own = points == nullptr;
+    const int rows = own ? b->n_upper : m;                 // what the grid covers
+    const size_t per_sys = own ? (size_t)b->cap : (size_t)m;   // results of one system on the device
+    const size_t total = per_sys * (size_t)b->S;
+    if (rows > 0) {
+        rc = field_reserve(b->nbr, own ? 0 : (size_t)m, total, "nbody_batch_get_neighbors");
+        if (rc != NBODY_OK) return rc;
+        if (!own) HIP_TRY(field_stage_points(b->nbr, b->stream, points, m));
+        const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock, b->S);
+        if (own)
+            hipLaunchKernelGGL((neighbors_at<float, true, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
+                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
+                               (const FieldPoint*)nullptr, 0, b->nbr.out);
+        else
+            hipLaunchKernelGGL((neighbors_at<float, false, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
+                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
+                               (const FieldPoint*)b->nbr.pts, m, b->nbr.out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(b->nbr.h, b->nbr.out, total * sizeof(NeighborOut), hipMemcpyDeviceToHost, b->stream));
+    }
+    rc = read_meta(b);                                     // synchronises; a system whose count failed its check ends here
+    if (rc != NBODY_OK) return rc;
+    if (rows == 0) return NBODY_OK;
+    const NeighborOut* h = reinterpret_cast<const NeighborOut*>(b->nbr.h);
+    for (int s = 0; s < b->S; ++s) {
+        const int n = b->h_meta[s].n;                      // 0 .. cap: read_meta has passed
+        const size_t cnt = own ? (size_t)(n < 0 || n > b->cap ? 0 : n) : (size_t)m;
+        memcpy(out + (size_t)s * per_sys, h + (size_t)s * per_sys, cnt * sizeof(NeighborOut));
     }
     return NBODY_OK;
 }

@@ -25,6 +25,7 @@
 #include "nbody_field.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
+#include "nbody_neighbors.hpp"
 
 using namespace nbk;
 
@@ -180,6 +181,8 @@ struct nbody_ctx {
     TrackState trk;
     // field evaluation (nbody_get_field, nbody_field.hpp): nothing is allocated before the first call
     FieldState fld;
+    // neighbour queries (nbody_get_neighbors, nbody_neighbors.hpp): nothing is allocated before the first call
+    NeighborState nbr;
 };
 
 namespace {
@@ -576,6 +579,7 @@ void free_all(nbody_ctx* c) {
     hipFree(c->ids.map[0]); hipFree(c->ids.map[1]); hipFree(c->ids.lineage); hipFree(c->ids.done);
     hipFree(c->trk.buf); hipFree(c->trk.sel);
     field_free(c->fld);
+    field_free(c->nbr);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -1672,6 +1676,59 @@ int nbody_get_field(nbody_ctx* c, const nbody_vec2* points, int m, nbody_field* 
     rc = read_meta(c);                                     // synchronises; a device-side failure is reported here
     if (rc != NBODY_OK) return rc;
     *coincident = (int64_t)field_unpack(reinterpret_cast<const FieldOut*>(c->fld.h), (size_t)rows, out);
+    return NBODY_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Neighbour queries (nbody_get_neighbors; kernel and the shared host code in nbody_neighbors.hpp).  At the end of the file
+// for the reason the identities are.  Reads the replica J only - every rank holds every {x, y, m, r} - so any context may
+// call it on its own, whatever its world or transport.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+template <typename T>
+void neighbors_launch(nbody_ctx* c, int n, bool own, int m) {
+    const int rows = own ? n : m;
+    const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock);
+    if (own)
+        hipLaunchKernelGGL((neighbors_at<T, true, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
+                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)nullptr, 0, c->nbr.out);
+    else
+        hipLaunchKernelGGL((neighbors_at<T, false, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
+                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)c->nbr.pts, m, c->nbr.out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nbody_get_neighbors(nbody_ctx* c, const nbody_vec2* points, int m, nbody_neighbor* out, int* n_out) {
+    int rc = field_check_args("nbody_get_neighbors", c, m, out, n_out, out, 1, sizeof(nbody_neighbor));
+    if (rc != NBODY_OK) return rc;
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_get_neighbors before nbody_upload");
+    HIP_TRY(hipSetDevice(c->desc.device));
+    rc = read_meta(c);
+    if (rc != NBODY_OK) return rc;
+    const int n = c->h_meta->n;
+    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "nbody_get_neighbors: %d bodies, capacity %d", n, c->cap);
+    const bool own = points == nullptr;
+    if (own && m < n)
+        return nbody_fail(NBODY_ERR_CAPACITY, "nbody_get_neighbors: room for %d results, the context holds %d bodies", m, n);
+    const int rows = own ? n : m;
+    *n_out = rows;
+    if (rows == 0) return NBODY_OK;
+    rc = field_reserve(c->nbr, own ? 0 : (size_t)m, (size_t)rows, "nbody_get_neighbors");
+    if (rc != NBODY_OK) return rc;
+    if (!own) HIP_TRY(field_stage_points(c->nbr, c->stream, points, m));
+    if (c->desc.precision == NBODY_F64) neighbors_launch<double>(c, n, own, m);
+    else neighbors_launch<float>(c, n, own, m);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->nbr.h, c->nbr.out, (size_t)rows * sizeof(NeighborOut), hipMemcpyDeviceToHost, c->stream));
+    rc = read_meta(c);                                     // synchronises; a device-side failure is reported here
+    if (rc != NBODY_OK) return rc;
+    memcpy(out, c->nbr.h, (size_t)rows * sizeof(NeighborOut));
     return NBODY_OK;
 }
 

@@ -141,24 +141,29 @@ __global__ __launch_bounds__(kDiagBlock) void field_at(const Rec<T>* __restrict_
 
 // ---------------------------------------------------------------------------------------------------------
 // Host side shared by the two steppers: the buffers of one context or batch, allocated on the first call and grown to the
-// largest request seen - the device points, the device results, and one pinned staging area for both directions.
+// largest request seen - the device points, the device results, and one pinned staging area for both directions.  A
+// template over the device result record: FieldOut here, NeighborOut for the neighbour queries (nbody_neighbors.hpp).
 // ---------------------------------------------------------------------------------------------------------
 constexpr unsigned long long kFieldMaxBytes = 1ull << 31;   // of the caller's `out`
 
-struct FieldState {
+template <typename Out>
+struct PointBuffers {
     FieldPoint* pts = nullptr;      // [cap_pts]
-    FieldOut* out = nullptr;        // [cap_out]
-    unsigned char* h = nullptr;     // pinned: max(cap_pts * sizeof(FieldPoint), cap_out * sizeof(FieldOut)) bytes
+    Out* out = nullptr;             // [cap_out]
+    unsigned char* h = nullptr;     // pinned: max(cap_pts * sizeof(FieldPoint), cap_out * sizeof(Out)) bytes
     size_t cap_pts = 0, cap_out = 0, h_bytes = 0;
 };
+using FieldState = PointBuffers<FieldOut>;
 
-inline void field_free(FieldState& f) {
+template <typename Out>
+inline void field_free(PointBuffers<Out>& f) {
     (void)hipFree(f.pts); (void)hipFree(f.out);
     if (f.h) (void)hipHostFree(f.h);
-    f = FieldState{};
+    f = PointBuffers<Out>{};
 }
 
-inline int field_reserve(FieldState& f, size_t n_pts, size_t n_out, const char* who) {
+template <typename Out>
+inline int field_reserve(PointBuffers<Out>& f, size_t n_pts, size_t n_out, const char* who) {
     hipError_t e = hipSuccess;
     if (n_pts > f.cap_pts) {
         (void)hipFree(f.pts);
@@ -169,11 +174,11 @@ inline int field_reserve(FieldState& f, size_t n_pts, size_t n_out, const char* 
     if (e == hipSuccess && n_out > f.cap_out) {
         (void)hipFree(f.out);
         f.out = nullptr; f.cap_out = 0;
-        e = hipMalloc((void**)&f.out, n_out * sizeof(FieldOut));
+        e = hipMalloc((void**)&f.out, n_out * sizeof(Out));
         if (e == hipSuccess) f.cap_out = n_out; else f.out = nullptr;
     }
-    const size_t hb = f.cap_pts * sizeof(FieldPoint) > f.cap_out * sizeof(FieldOut) ? f.cap_pts * sizeof(FieldPoint)
-                                                                                    : f.cap_out * sizeof(FieldOut);
+    const size_t hb = f.cap_pts * sizeof(FieldPoint) > f.cap_out * sizeof(Out) ? f.cap_pts * sizeof(FieldPoint)
+                                                                               : f.cap_out * sizeof(Out);
     if (e == hipSuccess && hb > f.h_bytes) {
         if (f.h) (void)hipHostFree(f.h);
         f.h = nullptr; f.h_bytes = 0;
@@ -182,24 +187,26 @@ inline int field_reserve(FieldState& f, size_t n_pts, size_t n_out, const char* 
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, field buffers: %s", who,
+        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point and result buffers: %s", who,
                           hipGetErrorString(e));
     }
     return NBODY_OK;
 }
 
-// The argument checks both entry points make before any device call.
+// The argument checks the entry points make before any device call.  `more`: a further output that must not be NULL (the
+// field's coincident count), or `out` again; `record`: the size of one of the caller's result records.
 inline int field_check_args(const char* who, const void* handle, int m, const void* out, const void* n_out_or_handle,
-                            const void* coincident, unsigned long long systems) {
-    if (!handle || !out || !n_out_or_handle || !coincident) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
+                            const void* more, unsigned long long systems, size_t record = sizeof(nbody_field)) {
+    if (!handle || !out || !n_out_or_handle || !more) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
     if (m < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: m = %d", who, m);
-    if ((unsigned long long)m * systems * sizeof(nbody_field) > kFieldMaxBytes)
+    if ((unsigned long long)m * systems * record > kFieldMaxBytes)
         return nbody_fail(NBODY_ERR_INVALID, "%s: %d points are more than 2^31 bytes of results", who, m);
     return NBODY_OK;
 }
 
 // Stages the explicit points and enqueues their copy to the device.
-inline hipError_t field_stage_points(FieldState& f, hipStream_t stream, const nbody_vec2* points, int m) {
+template <typename Out>
+inline hipError_t field_stage_points(PointBuffers<Out>& f, hipStream_t stream, const nbody_vec2* points, int m) {
     memcpy(f.h, points, (size_t)m * sizeof(FieldPoint));
     return hipMemcpyAsync(f.pts, f.h, (size_t)m * sizeof(FieldPoint), hipMemcpyHostToDevice, stream);
 }

@@ -1,0 +1,188 @@
+#!/usr/bin/env python3
+"""Cost of the neighbour queries (nbody_get_neighbors, nbody_batch_get_neighbors) next to the two kernels that
+walk the same j stream, diag_potential<float> and field_at<float, own>, measured in the same run.
+
+    python3 csrc/tune/neighbor_probe.py kernels [rounds]   the launches alone: target of `rocprofv3 --kernel-trace --stats`
+                                                           (a run of its own; nothing else is traced with it)
+    python3 csrc/tune/neighbor_probe.py host [reps]        whole Stepper.neighbors() / StepperBatch.neighbors() calls under the
+                                                           host clock, and the route without the call: download() plus the
+                                                           numpy model of tests/neighbor_cases.py at N = 16384
+    python3 csrc/tune/neighbor_probe.py report TRACE_DIR [HOST_LOG]
+                                                           reads the kernel trace (csv), counts the instructions per pair of
+                                                           the inner loops in build/csrc/nbody_ctx.s (make asm) and prints the
+                                                           text of profiles/neighbor_probe.txt
+
+Shapes: N = 262144 fp32, stock radii, with points=None; the same state with 65536 explicit points; a batch of 256 x 1024.
+Every result is checked bit-equal to the model (sampled rows at N = 262144, whole systems of the batch) before a time is taken."""
+import collections
+import csv
+import glob
+import json
+import os
+import re
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+N_ONE, M_POINTS, BATCH_S, BATCH_N, N_HOST = 262144, 65536, 256, 1024, 16384
+ROUNDS = 3                                                   # what `report` expects of `kernels`
+
+
+def workloads():
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import torch  # noqa: F401  (one ROCm runtime per process: tests/conftest.py)
+    import numpy as np
+    import ppa_nbody_collisions_amd as nb
+    import neighbor_cases as nc
+    cfg = nb.stock_config(particleCount=N_ONE)
+    b = nb.init_bodies(cfg)
+    st = nb.Stepper(cfg)
+    st.upload(b)
+    pts = np.random.default_rng(2).uniform(0, 1, size=(M_POINTS, 2)) * [cfg.fieldWidth, cfg.fieldHeight]
+    bcfg = nb.stock_config(particleCount=BATCH_N)
+    bodies = [nb.init_bodies(bcfg, seed=100 + s) for s in range(BATCH_S)]
+    batch = nb.StepperBatch(BATCH_S, BATCH_N, cfg=bcfg)
+    batch.upload(bodies)
+    # bit-equal to the model before any time is taken
+    P, R = nc.widen(b)
+    rows = np.sort(np.random.default_rng(3).choice(N_ONE, 256, replace=False))
+    rows[0], rows[-1] = 0, N_ONE - 1
+    own = st.neighbors()
+    nc.assert_same(own[rows], nc.model_neighbors(P, R, rows=rows), "N=%d, 256 sampled rows" % N_ONE)
+    sel = np.arange(0, M_POINTS, 257)
+    nc.assert_same(st.neighbors(pts)[sel], nc.model_neighbors(P, R, points=pts[sel]), "%d points, every 257th" % M_POINTS)
+    bown = batch.neighbors()
+    for s in (0, 1, 127, 255):
+        nc.assert_same(bown[s], nc.model_neighbors(*nc.widen(bodies[s])), "batch system %d" % s)
+    print("# checked bit-equal to the model: 256 sampled rows and 256 sampled points at N=%d, 4 whole systems of the batch; "
+          "%d overlapping ordered pairs among the sampled rows" % (N_ONE, int(own["overlaps"][rows].sum())), flush=True)
+    return np, nb, nc, st, pts, batch
+
+
+def run_kernels(rounds):
+    np, nb, nc, st, pts, batch = workloads()
+    for _ in range(rounds + 1):                             # the first round warms up (code objects, lazy buffers)
+        st.diagnostics(potential=True)
+        st.field()
+        st.neighbors()
+        st.neighbors(pts)
+        batch.diagnostics(potential=True)
+        batch.neighbors()
+    st.close()
+    batch.close()
+
+
+def timed(np, name, call, reps):
+    call()
+    ms = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        call()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    r = {"call": name, "reps": reps, "ms_median": float(np.median(ms)), "ms_min": min(ms), "ms_max": max(ms)}
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def run_host(reps):
+    np, nb, nc, st, pts, batch = workloads()
+    timed(np, "Stepper.neighbors() N=%d" % N_ONE, st.neighbors, reps)
+    timed(np, "Stepper.neighbors(%d points) N=%d" % (M_POINTS, N_ONE), lambda: st.neighbors(pts), reps)
+    timed(np, "Stepper.field() N=%d" % N_ONE, st.field, reps)
+    timed(np, "Stepper.diagnostics(potential=True) N=%d" % N_ONE, lambda: st.diagnostics(potential=True), reps)
+    timed(np, "StepperBatch.neighbors() %d x %d" % (BATCH_S, BATCH_N), batch.neighbors, reps)
+    st.close()
+    batch.close()
+    # the route without the call, against the call, on one state
+    cfg = nb.stock_config(particleCount=N_HOST)
+    small = nb.Stepper(cfg)
+    small.upload(nb.init_bodies(cfg))
+    nc.assert_same(small.neighbors(), nc.model_neighbors(*nc.widen(small.download())), "N=%d" % N_HOST)
+    a = timed(np, "Stepper.neighbors() N=%d" % N_HOST, small.neighbors, reps)
+    h = timed(np, "download() + numpy model on the host N=%d" % N_HOST,
+              lambda: nc.model_neighbors(*nc.widen(small.download())), 3)
+    print("# the host route takes %.0f times the call at N=%d; numpy's elementwise float64 arithmetic ran on 1 thread "
+          "(%d CPUs available to the process)" % (h["ms_median"] / a["ms_median"], N_HOST, len(os.sched_getaffinity(0))))
+    small.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def hot_loop(asm, sub, mark):
+    """Opcode classes per pair of the kernel's hottest block: the one with the most `mark` instructions (one per pair)."""
+    lines = asm.split("\n")
+    k0 = next(k for k, l in enumerate(lines) if re.match(r"_ZN\w*" + sub + r"\w*:", l))
+    k1 = next(k for k in range(k0, len(lines)) if lines[k].startswith(".Lfunc_end"))
+    blocks = re.split(r"\n(?=\.LBB)", "\n".join(lines[k0:k1]))
+    best = max(blocks, key=lambda b: b.count(mark))
+    pairs = best.count(mark)
+    ops = collections.Counter(l.split()[0] for l in best.split("\n") if l.startswith("\t") and not l.strip().startswith((".", ";")))
+    cls = collections.Counter()
+    for op, k in ops.items():
+        if op.startswith("v_rsq_f64"):
+            cls["v_rsq_f64"] += k
+        elif op.startswith(("v_fma_f64", "v_fmac_f64", "v_mul_f64", "v_add_f64")):
+            cls["fp64 arithmetic"] += k
+        elif op.startswith("v_cmp") and "f64" in op:
+            cls["fp64 compare"] += k
+        elif op.startswith("v_"):
+            cls["32-bit VALU"] += k
+        elif op.startswith("ds_"):
+            cls["ds_read"] += k
+    return {k: v / pairs for k, v in cls.items()}
+
+
+def report(trace_dir, host_log):
+    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
+    assert files, "no *kernel_trace.csv under %s" % trace_dir
+    dur = collections.defaultdict(list)
+    for row in csv.DictReader(open(files[0])):
+        dur[row["Kernel_Name"]].append((int(row["Start_Timestamp"]), (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-6))
+
+    def ms_of(*alternatives):                                # the name as the trace has it: demangled, or mangled
+        names = [k for k in dur if any(all(s in k for s in subs) for subs in alternatives)]
+        assert len(names) == 1, (alternatives, names)
+        d = [t for _, t in sorted(dur[names[0]])][-ROUNDS:]  # without the checks and the warm-up round
+        d.sort()
+        return d[len(d) // 2], d[-1] - d[0], len(d)
+
+    asm = open(os.path.join(ROOT, "build", "csrc", "nbody_ctx.s")).read()
+    print("# csrc/tune/neighbor_probe.py on one MI355X: neighbors_at next to diag_potential and field_at, fp32, stock radii")
+    print("# inner loops (build/csrc/nbody_ctx.s, the unchecked 4-pair block), instructions per pair:")
+    for name, sub, mark in (("diag_potential<float>", "diag_potentialIfEE", "v_rsq_f64"), ("field_at<float, own>", "field_atIfLb1E", "v_rsq_f64"),
+                            ("neighbors_at<float, own>", "neighbors_atIfLb1E", "v_cmp_lt_f64"),
+                            ("neighbors_at<float, points>", "neighbors_atIfLb0E", "v_cmp_lt_f64")):
+        per = hot_loop(asm, sub, mark)
+        print("#   %-28s %s" % (name, "  ".join("%s %.2f" % (k, per[k]) for k in sorted(per))))
+    pairs_one, pairs_pts, pairs_batch = float(N_ONE) * N_ONE, float(M_POINTS) * N_ONE, float(BATCH_S) * BATCH_N * BATCH_N
+    rows = (("own", "neighbors_at N=%d points=None" % N_ONE, (("neighbors_at<float, true", "FieldOneCount"), ("neighbors_atIfLb1E", "FieldOneCount")), pairs_one),
+            ("points", "neighbors_at N=%d, %d points" % (N_ONE, M_POINTS), (("neighbors_at<float, false", "FieldOneCount"), ("neighbors_atIfLb0E", "FieldOneCount")), pairs_pts),
+            ("batch", "neighbors_at batch %d x %d points=None" % (BATCH_S, BATCH_N), (("neighbors_at<float, true", "FieldBatchCount"), ("neighbors_atIfLb1E", "FieldBatchCount")), pairs_batch),
+            ("potential", "diag_potential<float> N=%d" % N_ONE, (("nbk::diag_potential<float>",), ("3nbk14diag_potentialIfEE",)), pairs_one),
+            ("field", "field_at<float, own> N=%d" % N_ONE, (("field_at<float, true", "FieldOneCount"), ("field_atIfLb1E", "FieldOneCount")), pairs_one),
+            ("batch potential", "batch_diag_potential %d x %d" % (BATCH_S, BATCH_N), (("batch_diag_potential<true>",), ("batch_diag_potentialILb1E",)), pairs_batch))
+    print("# kernel trace: rocprofv3 --kernel-trace --stats -- python neighbor_probe.py kernels 3 (a run of its own); ms, median of the rounds (spread)")
+    got = {}
+    for key, what, subs, pairs in rows:
+        t, spread, k = ms_of(*subs)
+        got[key] = t / pairs
+        print("%-46s %9.3f ms (%.3f)  %d rounds  %.3f ps per ordered pair  %.3e pairs/s" % (what, t, spread, k, t / pairs * 1e9, pairs / t * 1e3))
+    print("# time per pair, neighbors_at over diag_potential: own %.3f, points %.3f, batch %.3f (over batch_diag_potential); over field_at, own: %.3f"
+          % (got["own"] / got["potential"], got["points"] / got["potential"], got["batch"] / got["batch potential"],
+             got["own"] / got["field"]))
+    if host_log:
+        print("# whole calls under the host clock (neighbor_probe.py host 5; median of 5 after a warm-up):")
+        for line in open(host_log):
+            if line.startswith(("{", "#")):
+                print(line.rstrip())
+
+
+if __name__ == "__main__":
+    mode = sys.argv[1] if len(sys.argv) > 1 else "host"
+    if mode == "kernels":
+        run_kernels(int(sys.argv[2]) if len(sys.argv) > 2 else ROUNDS)
+    elif mode == "host":
+        run_host(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
+    elif mode == "report":
+        report(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
+    else:
+        sys.exit(__doc__)
