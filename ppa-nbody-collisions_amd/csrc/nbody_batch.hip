@@ -19,6 +19,7 @@
 #include "nbody_error.h"
 #include "nbody_batch_kernels.hpp"
 #include "nbody_batch_diag.hpp"
+#include "nbody_rows.hpp"
 #include "nbody_field.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
@@ -95,8 +96,8 @@ void free_all(nbody_batch* b) {
     (void)hipFree(b->blk_counts);
     (void)hipFree(b->ids.map[0]); (void)hipFree(b->ids.map[1]); (void)hipFree(b->ids.lineage); (void)hipFree(b->ids.done);
     (void)hipFree(b->trk.buf); (void)hipFree(b->trk.sel);
-    field_free(b->fld);
-    field_free(b->nbr);
+    rows_free(b->fld);
+    rows_free(b->nbr);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -687,104 +688,38 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Field evaluation (nbody_batch_get_field; kernel and the shared host code in nbody_field.hpp): one launch for every
-// system, system = blockIdx.y, one set of points for all of them.  At the end of the file for the reason the identities are.
+// Row queries (nbody_batch_get_field, nbody_batch_get_neighbors; nbody_rows.hpp and the two query headers): one launch for
+// every system, system = blockIdx.y, one set of points for all of them.  At the end of the file for the reason the
+// identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
-struct FieldBatchCount {
-    static constexpr bool kBatch = true;
-    static __device__ __forceinline__ int checked(const Meta* meta_all, int sys, int stride, int) {
-        return batch_checked_count(meta_all[sys].n, stride);
-    }
-};
+// A batch makes no read before the launch: the grid covers the largest uploaded count, each system's count comes from Meta.
+template <typename Q>
+int batch_rows(nbody_batch* b, const char* who, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points,
+               int m, typename Q::Result* out) {
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_batch_upload", who);
+    HIP_TRY(hipSetDevice(b->desc.device));
+    const RowsSite site{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
+    return rows_run<float, RowsBatchCount>(who, site, buf, q, points, m, out, [b] { return read_meta(b); });
+}
 
 }  // namespace
 
 extern "C" {
 
 int nbody_batch_get_field(nbody_batch* b, const nbody_vec2* points, int m, nbody_field* out, int64_t* coincident) {
-    int rc = field_check_args("nbody_batch_get_field", b, m, out, b, coincident, b ? (unsigned long long)b->S : 1);
+    const int rc = rows_check_args("nbody_batch_get_field", {b, out, coincident}, m, b ? (unsigned long long)b->S : 1,
+                                   sizeof(nbody_field));
     if (rc != NBODY_OK) return rc;
-    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_field before nbody_batch_upload");
-    HIP_TRY(hipSetDevice(b->desc.device));
-    const bool own = points == nullptr;
-    const int rows = own ? b->n_upper : m;                 // what the grid covers
-    const size_t per_sys = own ? (size_t)b->cap : (size_t)m;   // results of one system on the device
-    const size_t total = per_sys * (size_t)b->S;
-    for (int s = 0; s < b->S; ++s) coincident[s] = 0;
-    if (rows > 0) {
-        rc = field_reserve(b->fld, own ? 0 : (size_t)m, total, "nbody_batch_get_field");
-        if (rc != NBODY_OK) return rc;
-        if (!own) HIP_TRY(field_stage_points(b->fld, b->stream, points, m));
-        const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock, b->S);
-        if (own)
-            hipLaunchKernelGGL((field_at<float, true, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
-                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
-                               (const FieldPoint*)nullptr, 0, (double)kG, b->fld.out);
-        else
-            hipLaunchKernelGGL((field_at<float, false, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
-                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
-                               (const FieldPoint*)b->fld.pts, m, (double)kG, b->fld.out);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(b->fld.h, b->fld.out, total * sizeof(FieldOut), hipMemcpyDeviceToHost, b->stream));
-    }
-    rc = read_meta(b);                                     // synchronises; a system whose count failed its check ends here
-    if (rc != NBODY_OK) return rc;
-    if (rows == 0) return NBODY_OK;
-    const FieldOut* h = reinterpret_cast<const FieldOut*>(b->fld.h);
-    for (int s = 0; s < b->S; ++s) {
-        const int n = b->h_meta[s].n;                      // 0 .. cap: read_meta has passed
-        const size_t cnt = own ? (size_t)(n < 0 || n > b->cap ? 0 : n) : (size_t)m;
-        coincident[s] = (int64_t)field_unpack(h + (size_t)s * per_sys, cnt, out + (size_t)s * per_sys);
-    }
-    return NBODY_OK;
+    return batch_rows(b, "nbody_batch_get_field", b->fld, FieldQuery{(double)kG, coincident}, points, m, out);
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------
-// Neighbour queries (nbody_batch_get_neighbors; kernel and the shared host code in nbody_neighbors.hpp): one launch for
-// every system, system = blockIdx.y, one set of points for all of them; the count comes through FieldBatchCount, above.
-// ---------------------------------------------------------------------------------------------------------
-extern "C" {
-
 int nbody_batch_get_neighbors(nbody_batch* b, const nbody_vec2* points, int m, nbody_neighbor* out) {
-    int rc = field_check_args("nbody_batch_get_neighbors", b, m, out, b, out, b ? (unsigned long long)b->S : 1,
-                              sizeof(nbody_neighbor));
+    const int rc = rows_check_args("nbody_batch_get_neighbors", {b, out}, m, b ? (unsigned long long)b->S : 1,
+                                   sizeof(nbody_neighbor));
     if (rc != NBODY_OK) return rc;
-    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_get_neighbors before nbody_batch_upload");
-    HIP_TRY(hipSetDevice(b->desc.device));
-    const bool own = points == nullptr;
-    const int rows = own ? b->n_upper : m;                 // what the grid covers
-    const size_t per_sys = own ? (size_t)b->cap : (size_t)m;   // results of one system on the device
-    const size_t total = per_sys * (size_t)b->S;
-    if (rows > 0) {
-        rc = field_reserve(b->nbr, own ? 0 : (size_t)m, total, "nbody_batch_get_neighbors");
-        if (rc != NBODY_OK) return rc;
-        if (!own) HIP_TRY(field_stage_points(b->nbr, b->stream, points, m));
-        const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock, b->S);
-        if (own)
-            hipLaunchKernelGGL((neighbors_at<float, true, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
-                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
-                               (const FieldPoint*)nullptr, 0, b->nbr.out);
-        else
-            hipLaunchKernelGGL((neighbors_at<float, false, FieldBatchCount>), grid, dim3(kDiagBlock), 0, b->stream,
-                               (const Rec<float>*)b->J, (const Meta*)b->meta, b->counters, b->cap, 0,
-                               (const FieldPoint*)b->nbr.pts, m, b->nbr.out);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(b->nbr.h, b->nbr.out, total * sizeof(NeighborOut), hipMemcpyDeviceToHost, b->stream));
-    }
-    rc = read_meta(b);                                     // synchronises; a system whose count failed its check ends here
-    if (rc != NBODY_OK) return rc;
-    if (rows == 0) return NBODY_OK;
-    const NeighborOut* h = reinterpret_cast<const NeighborOut*>(b->nbr.h);
-    for (int s = 0; s < b->S; ++s) {
-        const int n = b->h_meta[s].n;                      // 0 .. cap: read_meta has passed
-        const size_t cnt = own ? (size_t)(n < 0 || n > b->cap ? 0 : n) : (size_t)m;
-        memcpy(out + (size_t)s * per_sys, h + (size_t)s * per_sys, cnt * sizeof(NeighborOut));
-    }
-    return NBODY_OK;
+    return batch_rows(b, "nbody_batch_get_neighbors", b->nbr, NeighborQuery{}, points, m, out);
 }
 
 }  // extern "C"

@@ -92,8 +92,8 @@ constexpr int kBatchMaxSystems = 65535;                    // gridDim.y
 // Meta::summary is not kept (0): the one-lane kernel builds its screens from the tiles it stages and never reads it.
 // A count outside [0, stride] cannot come from these kernels; if one is found the system is emptied instead of
 // indexed with, and Counters::errors of that system says so (kIndexError, as the ring kernel's index checks do).
+// The check is batch_checked_count (nbody_kernels.hpp).
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int batch_checked_count(int n, int stride) { return (n < 0 || n > stride) ? -1 : n; }
 
 template <int B>
 __global__ __launch_bounds__(B) void batch_count(const Rec<float>* __restrict__ S_J_all, Meta* __restrict__ meta_all,

@@ -22,6 +22,7 @@
 #include "nbody_error.h"
 #include "nbody_kernels.hpp"
 #include "nbody_diag.hpp"
+#include "nbody_rows.hpp"
 #include "nbody_field.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
@@ -578,8 +579,8 @@ void free_all(nbody_ctx* c) {
     hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
     hipFree(c->ids.map[0]); hipFree(c->ids.map[1]); hipFree(c->ids.lineage); hipFree(c->ids.done);
     hipFree(c->trk.buf); hipFree(c->trk.sel);
-    field_free(c->fld);
-    field_free(c->nbr);
+    rows_free(c->fld);
+    rows_free(c->nbr);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -1627,23 +1628,29 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Field evaluation (nbody_get_field; kernel and the shared host code in nbody_field.hpp).  At the end of the file for the
-// reason the identities are.  Reads the replica J only - every rank holds every position and mass - so any context may
-// call it on its own, whatever its world or transport.
+// Row queries (nbody_get_field, nbody_get_neighbors; nbody_rows.hpp and the two query headers).  At the end of the file
+// for the reason the identities are.  They read the replica J only - every rank holds every {x, y, m, r} - so any context
+// may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
-template <typename T>
-void field_launch(nbody_ctx* c, int n, bool own, int m) {
-    const int rows = own ? n : m;
-    const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock);
-    if (own)
-        hipLaunchKernelGGL((field_at<T, true, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
-                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)nullptr, 0, (double)kG, c->fld.out);
-    else
-        hipLaunchKernelGGL((field_at<T, false, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
-                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)c->fld.pts, m, (double)kG,
-                           c->fld.out);
+// A context reads Meta first and hands the kernel the exact count.
+template <typename Q>
+int ctx_rows(nbody_ctx* c, const char* who, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points, int m,
+             typename Q::Result* out, int* n_out) {
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_upload", who);
+    HIP_TRY(hipSetDevice(c->desc.device));
+    const int rc = read_meta(c);
+    if (rc != NBODY_OK) return rc;
+    const int n = c->h_meta->n;
+    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "%s: %d bodies, capacity %d", who, n, c->cap);
+    if (!points && m < n)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, n);
+    *n_out = points ? m : n;
+    const RowsSite site{c->stream, c->J, (const Meta*)c->meta, c->counters, c->h_meta, c->cap, 1, n};
+    const auto sync = [c] { return read_meta(c); };
+    return c->desc.precision == NBODY_F64 ? rows_run<double, RowsOneCount>(who, site, buf, q, points, m, out, sync)
+                                          : rows_run<float, RowsOneCount>(who, site, buf, q, points, m, out, sync);
 }
 
 }  // namespace
@@ -1651,85 +1658,15 @@ void field_launch(nbody_ctx* c, int n, bool own, int m) {
 extern "C" {
 
 int nbody_get_field(nbody_ctx* c, const nbody_vec2* points, int m, nbody_field* out, int* n_out, int64_t* coincident) {
-    int rc = field_check_args("nbody_get_field", c, m, out, n_out, coincident, 1);
+    const int rc = rows_check_args("nbody_get_field", {c, out, n_out, coincident}, m, 1, sizeof(nbody_field));
     if (rc != NBODY_OK) return rc;
-    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_get_field before nbody_upload");
-    HIP_TRY(hipSetDevice(c->desc.device));
-    rc = read_meta(c);
-    if (rc != NBODY_OK) return rc;
-    const int n = c->h_meta->n;
-    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "nbody_get_field: %d bodies, capacity %d", n, c->cap);
-    const bool own = points == nullptr;
-    if (own && m < n)
-        return nbody_fail(NBODY_ERR_CAPACITY, "nbody_get_field: room for %d results, the context holds %d bodies", m, n);
-    const int rows = own ? n : m;
-    *n_out = rows;
-    *coincident = 0;
-    if (rows == 0) return NBODY_OK;
-    rc = field_reserve(c->fld, own ? 0 : (size_t)m, (size_t)rows, "nbody_get_field");
-    if (rc != NBODY_OK) return rc;
-    if (!own) HIP_TRY(field_stage_points(c->fld, c->stream, points, m));
-    if (c->desc.precision == NBODY_F64) field_launch<double>(c, n, own, m);
-    else field_launch<float>(c, n, own, m);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->fld.h, c->fld.out, (size_t)rows * sizeof(FieldOut), hipMemcpyDeviceToHost, c->stream));
-    rc = read_meta(c);                                     // synchronises; a device-side failure is reported here
-    if (rc != NBODY_OK) return rc;
-    *coincident = (int64_t)field_unpack(reinterpret_cast<const FieldOut*>(c->fld.h), (size_t)rows, out);
-    return NBODY_OK;
+    return ctx_rows(c, "nbody_get_field", c->fld, FieldQuery{(double)kG, coincident}, points, m, out, n_out);
 }
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------
-// Neighbour queries (nbody_get_neighbors; kernel and the shared host code in nbody_neighbors.hpp).  At the end of the file
-// for the reason the identities are.  Reads the replica J only - every rank holds every {x, y, m, r} - so any context may
-// call it on its own, whatever its world or transport.
-// ---------------------------------------------------------------------------------------------------------
-namespace {
-
-template <typename T>
-void neighbors_launch(nbody_ctx* c, int n, bool own, int m) {
-    const int rows = own ? n : m;
-    const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock);
-    if (own)
-        hipLaunchKernelGGL((neighbors_at<T, true, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
-                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)nullptr, 0, c->nbr.out);
-    else
-        hipLaunchKernelGGL((neighbors_at<T, false, FieldOneCount>), grid, dim3(kDiagBlock), 0, c->stream, (const Rec<T>*)c->J,
-                           (const Meta*)c->meta, c->counters, c->cap, n, (const FieldPoint*)c->nbr.pts, m, c->nbr.out);
-}
-
-}  // namespace
-
-extern "C" {
 
 int nbody_get_neighbors(nbody_ctx* c, const nbody_vec2* points, int m, nbody_neighbor* out, int* n_out) {
-    int rc = field_check_args("nbody_get_neighbors", c, m, out, n_out, out, 1, sizeof(nbody_neighbor));
+    const int rc = rows_check_args("nbody_get_neighbors", {c, out, n_out}, m, 1, sizeof(nbody_neighbor));
     if (rc != NBODY_OK) return rc;
-    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_get_neighbors before nbody_upload");
-    HIP_TRY(hipSetDevice(c->desc.device));
-    rc = read_meta(c);
-    if (rc != NBODY_OK) return rc;
-    const int n = c->h_meta->n;
-    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "nbody_get_neighbors: %d bodies, capacity %d", n, c->cap);
-    const bool own = points == nullptr;
-    if (own && m < n)
-        return nbody_fail(NBODY_ERR_CAPACITY, "nbody_get_neighbors: room for %d results, the context holds %d bodies", m, n);
-    const int rows = own ? n : m;
-    *n_out = rows;
-    if (rows == 0) return NBODY_OK;
-    rc = field_reserve(c->nbr, own ? 0 : (size_t)m, (size_t)rows, "nbody_get_neighbors");
-    if (rc != NBODY_OK) return rc;
-    if (!own) HIP_TRY(field_stage_points(c->nbr, c->stream, points, m));
-    if (c->desc.precision == NBODY_F64) neighbors_launch<double>(c, n, own, m);
-    else neighbors_launch<float>(c, n, own, m);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->nbr.h, c->nbr.out, (size_t)rows * sizeof(NeighborOut), hipMemcpyDeviceToHost, c->stream));
-    rc = read_meta(c);                                     // synchronises; a device-side failure is reported here
-    if (rc != NBODY_OK) return rc;
-    memcpy(out, c->nbr.h, (size_t)rows * sizeof(NeighborOut));
-    return NBODY_OK;
+    return ctx_rows(c, "nbody_get_neighbors", c->nbr, NeighborQuery{}, points, m, out, n_out);
 }
 
 }  // extern "C"

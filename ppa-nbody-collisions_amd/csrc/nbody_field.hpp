@@ -2,9 +2,8 @@
 // DESIGN.md 4.8): acceleration and potential at the bodies' own positions or at arbitrary probe points, in fp64 over the
 // n current bodies (fp32 states are widened exactly),
 //     phi(x) = -G sum_j m_j / r_j          a(x) = -G sum_j m_j (x - x_j) / r_j^3          r_j = |x - x_j| > 0,
-// a source at distance exactly 0 left out of all three sums and counted.  Included after nbody_diag.hpp by both
-// translation units; one system (nbody_ctx.hip) and a batch (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride`
-// apart, one set of points for every system) share the one kernel.
+// a source at distance exactly 0 left out of all three sums and counted.  The launch geometry, the count and the early
+// exits are those of every row query (nbody_rows.hpp); this file has the pair, the walk's use and the result record.
 //
 // Order contract.  ax, ay and phi of a point are each ONE running sum over j = 0, 1, ..., n-1 in
 // ascending order: the bits depend on the state and the point only.  The walk is diag_walk_sums and the pair is diag_pair
@@ -24,11 +23,8 @@
 // moderate size - every pair of an fp32 state, whose d2 lies within [2^-298, 2^257].  Above that range a term's weight
 // underflows gradually instead of being flagged (below it, it overflows and the sum is redone).
 //
-// field_at: one lane per point, kDiagBlock lanes per workgroup.  kOwn: the points are the bodies themselves (read from J on
-// the device), the self term is left out by index through diag_walk's checked self tile; otherwise there is no checked
-// loop at all.  Workgroups past the last point leave before the first barrier; a wave past the last point only loads
-// tiles.  An empty system gives +0 in every field.  The result record carries the point's coincident count; the host adds
-// them up.
+// field_at: kOwn leaves the self term out by index through diag_walk's checked self tile.  The result record carries the
+// point's coincident count; the host adds them up.
 #pragma once
 #include <float.h>
 #include <stddef.h>
@@ -36,7 +32,7 @@
 
 #include "nbody.h"
 #include "nbody_error.h"
-#include "nbody_diag.hpp"
+#include "nbody_rows.hpp"
 
 #pragma clang fp contract(off)
 
@@ -46,8 +42,6 @@ struct FieldOut { double ax, ay, phi; long long coincident; };   // device resul
 static_assert(sizeof(FieldOut) == 32, "FieldOut layout");
 static_assert(sizeof(nbody_field) == 24 && offsetof(nbody_field, ax) == 0 && offsetof(nbody_field, ay) == 8 &&
               offsetof(nbody_field, phi) == 16, "nbody_field layout");
-struct FieldPoint { double x, y; };                               // nbody_vec2
-static_assert(sizeof(FieldPoint) == sizeof(nbody_vec2), "nbody_vec2 layout");
 
 struct FieldSums {
     static constexpr bool kMore = true;
@@ -82,38 +76,18 @@ __device__ __forceinline__ FieldAcc field_acc_general(const Rec<T>* __restrict__
     return FieldAcc{ax, ay};
 }
 
-// Where the count comes from.  One system: the exact count is an argument (the host has just read Meta) and blockIdx.y is 0.
-// A batch (FieldBatchCount, nbody_batch.hip): from the system's Meta through batch_checked_count.
-struct FieldOneCount {
-    static constexpr bool kBatch = false;
-    static __device__ __forceinline__ int checked(const Meta*, int, int, int n_one) { return n_one; }
-};
-
-// grid = (ceil(points / kDiagBlock), systems).  Count::checked < 0: a count outside [0, stride], treated as 0 and reported
-// once as kIndexError.  A batch's J and - for kOwn - out are `stride` apart per system; explicit points: out[sys * m + p].
+// grid and early exits: rows_prologue (nbody_rows.hpp).  An empty system gives +0 in every field.
 template <typename T, bool kOwn, typename Count>
 __global__ __launch_bounds__(kDiagBlock) void field_at(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
                                                        Counters* __restrict__ ctr_all, int stride, int n_one,
                                                        const FieldPoint* __restrict__ points, int m, double G,
                                                        FieldOut* __restrict__ out_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int tid = threadIdx.x;
-    const int chk = Count::checked(meta_all, sys, stride, n_one);
-    const int n = chk < 0 ? 0 : chk;
-    if (chk < 0 && blockIdx.x == 0 && tid == 0) atomicAdd(&ctr_all[sys].errors, kIndexError);
-    const int rows = kOwn ? n : m;
-    const int row0 = blockIdx.x * kDiagBlock;                    // first point of the workgroup
-    if (row0 >= rows) return;                                    // the whole workgroup, before any barrier
-    const int p = row0 + tid;                                    // point of this lane
-    const bool valid = p < rows;
-    const Rec<T>* __restrict__ J = J_all + (size_t)sys * (size_t)stride;
-    FieldOut* __restrict__ out = out_all + (size_t)sys * (size_t)(kOwn ? stride : m);
-    if (n == 0) {                                                // explicit points over an empty system: +0 everywhere
-        if (valid) out[p] = FieldOut{0.0, 0.0, 0.0, 0};
-        return;
-    }
+    RowsLane<T, FieldOut> L;
+    if (rows_prologue<T, kOwn, Count>(L, J_all, meta_all, ctr_all, stride, n_one, m, out_all, FieldOut{0.0, 0.0, 0.0, 0})) return;
+    const Rec<T>* __restrict__ J = L.J;
+    const int n = L.n, p = L.p;
     double xi = 0.0, yi = 0.0;
-    if (valid) {
+    if (L.valid) {
         if (kOwn) {
             const Rec<T> r = J[p];
             xi = (double)r.x; yi = (double)r.y;
@@ -122,11 +96,10 @@ __global__ __launch_bounds__(kDiagBlock) void field_at(const Rec<T>* __restrict_
             xi = q.x; yi = q.y;
         }
     }
-    const int wave0 = row0 + (tid & ~(kWave - 1));               // first point of this wave
     __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
     FieldSums a;
-    diag_walk_sums<false, kOwn, T>(J, n, kOwn ? p : -1, xi, yi, kOwn ? wave0 / kTile : -1, wave0 < rows, a, sx, sy, sm);
-    if (!valid) return;
+    diag_walk_sums<false, kOwn, T>(J, n, kOwn ? p : -1, xi, yi, L.self_tile, L.wave_works, a, sx, sy, sm);
+    if (!L.valid) return;
     long long coin = 0;
     if (!(__builtin_isfinite(a.s) && __builtin_isfinite(a.ax) && __builtin_isfinite(a.ay))) {
         const DiagRow g = diag_row_general<T>(J, n, kOwn ? p : -1, xi, yi);      // the potential's, and the count
@@ -136,89 +109,31 @@ __global__ __launch_bounds__(kDiagBlock) void field_at(const Rec<T>* __restrict_
         if (!__builtin_isfinite(a.ax)) a.ax = ga.ax;
         if (!__builtin_isfinite(a.ay)) a.ay = ga.ay;
     }
-    out[p] = FieldOut{G * a.ax, G * a.ay, -G * a.s, coin};
+    L.out[p] = FieldOut{G * a.ax, G * a.ay, -G * a.s, coin};
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Host side shared by the two steppers: the buffers of one context or batch, allocated on the first call and grown to the
-// largest request seen - the device points, the device results, and one pinned staging area for both directions.  A
-// template over the device result record: FieldOut here, NeighborOut for the neighbour queries (nbody_neighbors.hpp).
-// ---------------------------------------------------------------------------------------------------------
-constexpr unsigned long long kFieldMaxBytes = 1ull << 31;   // of the caller's `out`
-
-template <typename Out>
-struct PointBuffers {
-    FieldPoint* pts = nullptr;      // [cap_pts]
-    Out* out = nullptr;             // [cap_out]
-    unsigned char* h = nullptr;     // pinned: max(cap_pts * sizeof(FieldPoint), cap_out * sizeof(Out)) bytes
-    size_t cap_pts = 0, cap_out = 0, h_bytes = 0;
-};
+// The query's traits for rows_run (nbody_rows.hpp): the caller gets 24-byte records and, per system, the sum of their
+// coincident sources.
 using FieldState = PointBuffers<FieldOut>;
 
-template <typename Out>
-inline void field_free(PointBuffers<Out>& f) {
-    (void)hipFree(f.pts); (void)hipFree(f.out);
-    if (f.h) (void)hipHostFree(f.h);
-    f = PointBuffers<Out>{};
-}
-
-template <typename Out>
-inline int field_reserve(PointBuffers<Out>& f, size_t n_pts, size_t n_out, const char* who) {
-    hipError_t e = hipSuccess;
-    if (n_pts > f.cap_pts) {
-        (void)hipFree(f.pts);
-        f.pts = nullptr; f.cap_pts = 0;
-        e = hipMalloc((void**)&f.pts, n_pts * sizeof(FieldPoint));
-        if (e == hipSuccess) f.cap_pts = n_pts; else f.pts = nullptr;
+struct FieldQuery {
+    using Device = FieldOut;
+    using Result = nbody_field;
+    double G;
+    int64_t* coincident;            // [systems]
+    template <typename T, bool kOwn, typename Count, typename... Common>
+    void launch(dim3 grid, hipStream_t stream, FieldOut* out, Common... common) const {
+        hipLaunchKernelGGL((field_at<T, kOwn, Count>), grid, dim3(kDiagBlock), 0, stream, common..., G, out);
     }
-    if (e == hipSuccess && n_out > f.cap_out) {
-        (void)hipFree(f.out);
-        f.out = nullptr; f.cap_out = 0;
-        e = hipMalloc((void**)&f.out, n_out * sizeof(Out));
-        if (e == hipSuccess) f.cap_out = n_out; else f.out = nullptr;
+    void empty(int sys) const { coincident[sys] = 0; }
+    void unpack(int sys, const FieldOut* h, size_t cnt, nbody_field* out) const {
+        long long coin = 0;
+        for (size_t p = 0; p < cnt; ++p) {
+            out[p].ax = h[p].ax; out[p].ay = h[p].ay; out[p].phi = h[p].phi;
+            coin += h[p].coincident;
+        }
+        coincident[sys] = (int64_t)coin;
     }
-    const size_t hb = f.cap_pts * sizeof(FieldPoint) > f.cap_out * sizeof(Out) ? f.cap_pts * sizeof(FieldPoint)
-                                                                               : f.cap_out * sizeof(Out);
-    if (e == hipSuccess && hb > f.h_bytes) {
-        if (f.h) (void)hipHostFree(f.h);
-        f.h = nullptr; f.h_bytes = 0;
-        e = hipHostMalloc((void**)&f.h, hb, hipHostMallocDefault);
-        if (e == hipSuccess) f.h_bytes = hb; else f.h = nullptr;
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point and result buffers: %s", who,
-                          hipGetErrorString(e));
-    }
-    return NBODY_OK;
-}
-
-// The argument checks the entry points make before any device call.  `more`: a further output that must not be NULL (the
-// field's coincident count), or `out` again; `record`: the size of one of the caller's result records.
-inline int field_check_args(const char* who, const void* handle, int m, const void* out, const void* n_out_or_handle,
-                            const void* more, unsigned long long systems, size_t record = sizeof(nbody_field)) {
-    if (!handle || !out || !n_out_or_handle || !more) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
-    if (m < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: m = %d", who, m);
-    if ((unsigned long long)m * systems * record > kFieldMaxBytes)
-        return nbody_fail(NBODY_ERR_INVALID, "%s: %d points are more than 2^31 bytes of results", who, m);
-    return NBODY_OK;
-}
-
-// Stages the explicit points and enqueues their copy to the device.
-template <typename Out>
-inline hipError_t field_stage_points(PointBuffers<Out>& f, hipStream_t stream, const nbody_vec2* points, int m) {
-    memcpy(f.h, points, (size_t)m * sizeof(FieldPoint));
-    return hipMemcpyAsync(f.pts, f.h, (size_t)m * sizeof(FieldPoint), hipMemcpyHostToDevice, stream);
-}
-
-// Unpacks `cnt` staged device records into the caller's 24-byte records; returns their coincident sources.
-inline long long field_unpack(const FieldOut* h, size_t cnt, nbody_field* out) {
-    long long coin = 0;
-    for (size_t p = 0; p < cnt; ++p) {
-        out[p].ax = h[p].ax; out[p].ay = h[p].ay; out[p].phi = h[p].phi;
-        coin += h[p].coincident;
-    }
-    return coin;
-}
+};
 
 }  // namespace nbk

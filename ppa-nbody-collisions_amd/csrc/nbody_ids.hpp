@@ -25,8 +25,11 @@ struct IdPair { int32_t id_i, id_j; };                     // one lineage record
 
 constexpr int kIdsBlock = 256;                             // threads of ids_fill / ids_translate workgroups
 
-// A count outside [0, stride] never becomes an index (batch_checked_count's rule): the system is treated as empty.
-__device__ __forceinline__ int ids_checked_count(int n, int stride) { return (n < 0 || n > stride) ? 0 : n; }
+// batch_checked_count (nbody_kernels.hpp) for the kernels that leave the report to others: the system is treated as empty.
+__device__ __forceinline__ int ids_checked_count(int n, int stride) {
+    const int chk = batch_checked_count(n, stride);
+    return chk < 0 ? 0 : chk;
+}
 
 // Events of a log that are stored: the counter runs on past the capacity (overflow is counted, not stored).
 __host__ __device__ inline unsigned long long log_stored(unsigned long long logged, int ev_cap) {

@@ -773,6 +773,9 @@ constexpr int kRingDeadSeq = 0x40000000;                   // sequence number of
 // unexplained fault) also check the source range of every window gather and the radius-bound lookups.  A
 // failed check SKIPS the access and adds kIndexError to Counters::errors: the host then fails like after a time-out.
 constexpr unsigned long long kIndexError = 1ull << 32;
+// A body count read back from Meta goes through this before it becomes an index or a loop bound: -1 for one outside
+// [0, stride] - the caller treats the system as empty and, where it reports, adds kIndexError.
+__device__ __forceinline__ int batch_checked_count(int n, int stride) { return (n < 0 || n > stride) ? -1 : n; }
 
 // Global memory straight into LDS (gfx950 LDS-DMA).  Inline assembly on purpose: hipcc tracks the builtin form as a writer
 // of all LDS and waits vmcnt(0) before the next LDS read.  M0 is written by nothing else in these kernels (gfx9 DS

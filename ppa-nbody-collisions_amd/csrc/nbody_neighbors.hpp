@@ -1,9 +1,8 @@
 // csrc/nbody_neighbors.hpp -- neighbour queries on the resident state (nbody_get_neighbors, nbody_batch_get_neighbors,
 // include/nbody.h): for every row - a current body, or an arbitrary probe point - the nearest source, its
-// squared distance, and the number of sources that satisfy the reference's collision predicate with the row.  Included
-// last by both translation units, after nbody_field.hpp, whose one-system / batch count policies (FieldOneCount,
-// FieldBatchCount), point type and host-side buffers it uses: one system (nbody_ctx.hip) and a batch (nbody_batch.hip: system = blockIdx.y,
-// per-body arrays `stride` apart, one set of points for every system) share the one kernel.
+// squared distance, and the number of sources that satisfy the reference's collision predicate with the row.  The launch
+// geometry, the count and the early exits are those of every row query (nbody_rows.hpp); this file has the pair, the tile
+// loop and the result record.
 //
 // The definition (include/nbody.h has it in full).  IEEE fp64, every operation rounded on its own, no fma.  A row at (x, y)
 // with radius r (+0 for a probe point; the body's own, widened exactly, for a body) and a source j at (X_j, Y_j) with
@@ -15,16 +14,13 @@
 // overlap.  The result is a function of the set of sources only; this kernel happens to walk j ascending with one lane per
 // row, so `d2 < best` IS the tie rule (the lowest j among equal distances).
 //
-// neighbors_at: one lane per row, kDiagBlock lanes per workgroup, grid = (ceil(rows / kDiagBlock), systems).  Every
-// workgroup walks the replica in kTile-body tiles; a tile's {x, y, r} are widened to fp64 ONCE into double-buffered LDS
-// planes (6 KiB, one barrier per tile) and read back as wave-uniform broadcasts, the way diag_walk_sums reads {x, y, m}.
+// neighbors_at: every workgroup walks the replica in kTile-body tiles; a tile's {x, y, r} are widened to fp64 ONCE into
+// double-buffered LDS planes (6 KiB, one barrier per tile) and read back as wave-uniform broadcasts, the way
+// diag_walk_sums reads {x, y, m}.
 //   * The ragged last tile is padded with x = NaN (y = r = +0): a padding entry has d2 = NaN and can be neither nearest nor
 //     overlap, so the pair loop carries no bound test and no remainder loop - it runs in fours up to the tile's count
 //     rounded up to 4.  (Not to kTile: a 64-body system of a batch would pay 128 pairs per row for 64.)
-//   * kOwn: the rows are the bodies themselves, read from J on the device; j == i can only occur in the tile that holds the
-//     wave's own rows (64 contiguous rows, inside one 128-body tile: wave-uniform), and only that tile runs the loop with the
-//     index test.  Probe points have no checked loop at all.
-//   * Workgroups past the last row leave before the first barrier; a wave past the last row only loads tiles.
+//   * kOwn: only the wave's self tile (nbody_rows.hpp) runs the loop with the index test.
 // Per pair: 2 subtractions, 2 multiplies, 1 add, 1 compare and the selects of best (2 halves) and index; for the count
 // 1 add, 1 multiply, 1 compare and the add of the compare's bit.  No transcendental, no divide.
 // The device record is the caller's nbody_neighbor: the host copies it out of the pinned staging as it stands.
@@ -34,7 +30,7 @@
 
 #include "nbody.h"
 #include "nbody_error.h"
-#include "nbody_field.hpp"
+#include "nbody_rows.hpp"
 
 #pragma clang fp contract(off)
 
@@ -69,31 +65,19 @@ __device__ __forceinline__ void neighbor_pair(NeighborBest& a, const double& xj,
     asm("" : "+v"(a.overlaps));
 }
 
-// grid = (ceil(rows / kDiagBlock), systems).  Count::checked < 0: a count outside [0, stride], treated as 0 and reported
-// once as kIndexError.  A batch's J and - for kOwn - out are `stride` apart per system; explicit points: out[sys * m + p].
+// grid and early exits: rows_prologue (nbody_rows.hpp).  An empty system gives {+inf, -1, 0}.
 template <typename T, bool kOwn, typename Count>
 __global__ __launch_bounds__(kDiagBlock) void neighbors_at(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
                                                            Counters* __restrict__ ctr_all, int stride, int n_one,
                                                            const FieldPoint* __restrict__ points, int m,
                                                            NeighborOut* __restrict__ out_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int tid = threadIdx.x;
-    const int chk = Count::checked(meta_all, sys, stride, n_one);
-    const int n = chk < 0 ? 0 : chk;
-    if (chk < 0 && blockIdx.x == 0 && tid == 0) atomicAdd(&ctr_all[sys].errors, kIndexError);
-    const int rows = kOwn ? n : m;
-    const int row0 = blockIdx.x * kDiagBlock;                    // first row of the workgroup
-    if (row0 >= rows) return;                                    // the whole workgroup, before any barrier
-    const int p = row0 + tid;                                    // row of this lane
-    const bool valid = p < rows;
-    const Rec<T>* __restrict__ J = J_all + (size_t)sys * (size_t)stride;
-    NeighborOut* __restrict__ out = out_all + (size_t)sys * (size_t)(kOwn ? stride : m);
-    if (n == 0) {                                                // explicit points over an empty system
-        if (valid) out[p] = NeighborOut{__builtin_inf(), -1, 0};
+    RowsLane<T, NeighborOut> L;
+    if (rows_prologue<T, kOwn, Count>(L, J_all, meta_all, ctr_all, stride, n_one, m, out_all, NeighborOut{__builtin_inf(), -1, 0}))
         return;
-    }
+    const Rec<T>* __restrict__ J = L.J;
+    const int n = L.n, p = L.p, tid = threadIdx.x;
     double xi = 0.0, yi = 0.0, ri = 0.0;
-    if (valid) {
+    if (L.valid) {
         if (kOwn) {
             const Rec<T> r = J[p];
             xi = (double)r.x; yi = (double)r.y; ri = (double)r.r;
@@ -102,9 +86,6 @@ __global__ __launch_bounds__(kDiagBlock) void neighbors_at(const Rec<T>* __restr
             xi = q.x; yi = q.y;
         }
     }
-    const int wave0 = row0 + (tid & ~(kWave - 1));               // first row of this wave
-    const bool wave_works = wave0 < rows;
-    const int self_tile = kOwn ? wave0 / kTile : -1;             // the one j tile that holds this wave's self terms
     __shared__ double sx[2][kTile], sy[2][kTile], sr[2][kTile];
     NeighborBest a;
     const int jtiles = (n + kTile - 1) / kTile;
@@ -122,9 +103,9 @@ __global__ __launch_bounds__(kDiagBlock) void neighbors_at(const Rec<T>* __restr
         }
         // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
         __syncthreads();
-        if (!wave_works) continue;
+        if (!L.wave_works) continue;
         const int jn4 = (jn + 3) & ~3;                           // <= kTile: the padding is there
-        if (!kOwn || t != self_tile) {
+        if (!kOwn || t != L.self_tile) {
             for (int q = 0; q < jn4; q += 4) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -138,11 +119,21 @@ __global__ __launch_bounds__(kDiagBlock) void neighbors_at(const Rec<T>* __restr
             }
         }
     }
-    if (valid) out[p] = NeighborOut{a.best, a.index, a.overlaps};
+    if (L.valid) L.out[p] = NeighborOut{a.best, a.index, a.overlaps};
 }
 
-// Host side: the buffers and the argument check are the field's (PointBuffers, field_reserve, field_stage_points,
-// field_check_args with this record's size; nbody_field.hpp).
+// The query's traits for rows_run (nbody_rows.hpp): the device record is the caller's, copied as it stands.
 using NeighborState = PointBuffers<NeighborOut>;
+
+struct NeighborQuery {
+    using Device = NeighborOut;
+    using Result = nbody_neighbor;
+    template <typename T, bool kOwn, typename Count, typename... Common>
+    void launch(dim3 grid, hipStream_t stream, NeighborOut* out, Common... common) const {
+        hipLaunchKernelGGL((neighbors_at<T, kOwn, Count>), grid, dim3(kDiagBlock), 0, stream, common..., out);
+    }
+    void empty(int) const {}
+    void unpack(int, const NeighborOut* h, size_t cnt, nbody_neighbor* out) const { memcpy(out, h, cnt * sizeof(NeighborOut)); }
+};
 
 }  // namespace nbk

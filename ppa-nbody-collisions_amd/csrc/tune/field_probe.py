@@ -137,9 +137,9 @@ def report(trace_dir, host_log, bench_json):
     print("# expected ratio of time per pair: own %.3f, points %.3f"
           % (ns["field_at<float, own>"] / ns["diag_potential<float>"], ns["field_at<float, points>"] / ns["diag_potential<float>"]))
     pairs_one, pairs_pts, pairs_batch = float(N_ONE) * N_ONE, float(M_POINTS) * N_ONE, float(BATCH_S) * BATCH_N * BATCH_N
-    one_own = (("field_at<float, true", "FieldOneCount"), ("field_atIfLb1E", "FieldOneCount"))
-    one_pts = (("field_at<float, false", "FieldOneCount"), ("field_atIfLb0E", "FieldOneCount"))
-    batch_own = (("field_at<float, true", "FieldBatchCount"), ("field_atIfLb1E", "FieldBatchCount"))
+    one_own = (("field_at<float, true", "RowsOneCount"), ("field_atIfLb1E", "RowsOneCount"))
+    one_pts = (("field_at<float, false", "RowsOneCount"), ("field_atIfLb0E", "RowsOneCount"))
+    batch_own = (("field_at<float, true", "RowsBatchCount"), ("field_atIfLb1E", "RowsBatchCount"))
     diag_one = (("nbk::diag_potential<float>",), ("3nbk14diag_potentialIfEE",))
     diag_batch = (("batch_diag_potential<true>",), ("batch_diag_potentialILb1E",))
     shapes = (("N=%d points=None" % N_ONE, one_own, diag_one, pairs_one, pairs_one, "own"),

@@ -154,11 +154,11 @@ def report(trace_dir, host_log):
         per = hot_loop(asm, sub, mark)
         print("#   %-28s %s" % (name, "  ".join("%s %.2f" % (k, per[k]) for k in sorted(per))))
     pairs_one, pairs_pts, pairs_batch = float(N_ONE) * N_ONE, float(M_POINTS) * N_ONE, float(BATCH_S) * BATCH_N * BATCH_N
-    rows = (("own", "neighbors_at N=%d points=None" % N_ONE, (("neighbors_at<float, true", "FieldOneCount"), ("neighbors_atIfLb1E", "FieldOneCount")), pairs_one),
-            ("points", "neighbors_at N=%d, %d points" % (N_ONE, M_POINTS), (("neighbors_at<float, false", "FieldOneCount"), ("neighbors_atIfLb0E", "FieldOneCount")), pairs_pts),
-            ("batch", "neighbors_at batch %d x %d points=None" % (BATCH_S, BATCH_N), (("neighbors_at<float, true", "FieldBatchCount"), ("neighbors_atIfLb1E", "FieldBatchCount")), pairs_batch),
+    rows = (("own", "neighbors_at N=%d points=None" % N_ONE, (("neighbors_at<float, true", "RowsOneCount"), ("neighbors_atIfLb1E", "RowsOneCount")), pairs_one),
+            ("points", "neighbors_at N=%d, %d points" % (N_ONE, M_POINTS), (("neighbors_at<float, false", "RowsOneCount"), ("neighbors_atIfLb0E", "RowsOneCount")), pairs_pts),
+            ("batch", "neighbors_at batch %d x %d points=None" % (BATCH_S, BATCH_N), (("neighbors_at<float, true", "RowsBatchCount"), ("neighbors_atIfLb1E", "RowsBatchCount")), pairs_batch),
             ("potential", "diag_potential<float> N=%d" % N_ONE, (("nbk::diag_potential<float>",), ("3nbk14diag_potentialIfEE",)), pairs_one),
-            ("field", "field_at<float, own> N=%d" % N_ONE, (("field_at<float, true", "FieldOneCount"), ("field_atIfLb1E", "FieldOneCount")), pairs_one),
+            ("field", "field_at<float, own> N=%d" % N_ONE, (("field_at<float, true", "RowsOneCount"), ("field_atIfLb1E", "RowsOneCount")), pairs_one),
             ("batch potential", "batch_diag_potential %d x %d" % (BATCH_S, BATCH_N), (("batch_diag_potential<true>",), ("batch_diag_potentialILb1E",)), pairs_batch))
     print("# kernel trace: rocprofv3 --kernel-trace --stats -- python neighbor_probe.py kernels 3 (a run of its own); ms, median of the rounds (spread)")
     got = {}

@@ -5,11 +5,13 @@ Product against oracle: the long-double oracle and the derived bounds of field_c
 acceleration component, (n + 4) u |phi|; nothing fitted to runs).  Product against product - the same state through
 another route: other points beside it, another partition, a batch - zero tolerance, bit for bit."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
 
 import field_cases as fc
+import test_gpu_diagnostics as dg
 from field_cases import G, LD, U
 from test_gpu_batch import FIELD_OF, params_of
 from test_gpu_diagnostics import bodies_with_velocities, state_arrays
@@ -420,3 +422,85 @@ def test_errors(nb):
     assert bcall(batch._b, None, 300, bout.ctypes.data, c2) == 0
     assert np.array_equal(bits(bout["phi"][:300]), bits(out["phi"])) and (bout["phi"][300:] == 7.0).all()
     batch.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 12. the bits, pinned.  The bounds above leave room for a changed summation order and the routes compared bit for bit all
+# go through one kernel; tests/golden/field_pins.npz holds what the library gave for the states of diag_pins.npz when the
+# fixture was recorded (tests/golden/make_field_pins.py): the bits may not move.  The states: n = 1, 129, 256, 300, bodies 5
+# and 200 of the last at one position.  The 257 points (two workgroups, the second ragged) are part of the fixture, one
+# set per precision, point 100 exactly on body 5 of that precision's n = 300 state: its chains are NaN, the general code
+# answers and counts both bodies.
+# ---------------------------------------------------------------------------------------------------------------------
+FIELD_PINS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "field_pins.npz")
+FIELD_PIN_POINTS = 257
+FIELD_PIN_ON_BODY = (100, 5)                                    # (point, body of the n = 300 state)
+FIELD_PIN_BATCH_CAPACITY = 300
+
+
+def pin_field_points(nb, states, precision):
+    """The fixture's point set of one precision, made once by the generator."""
+    pts = probe_points(nb.stock_config(particleCount=dg.PIN_SIZES[-1]), FIELD_PIN_POINTS, 31 + precision)
+    point, body = FIELD_PIN_ON_BODY
+    pts[point] = dg.pin_bodies(nb, states, precision, dg.PIN_SIZES[-1]).Positions[body].astype(np.float64)
+    return {"points_" + dg.pin_tag(nb, precision): dg.pin_bits(pts)}
+
+
+def pin_field_result(tag, f):
+    return {tag + "_acc": dg.pin_bits(f["acc"]), tag + "_phi": dg.pin_bits(f["phi"]),
+            tag + "_coincident": np.asarray(f["coincident"], dtype=np.int64).reshape(-1)}
+
+
+def pin_field_stepper(nb, states, pins, precision, n):
+    """-> {key: bits} of field() and field(points) straight after the upload."""
+    tag = "ctx_%s_n%d" % (dg.pin_tag(nb, precision), n)
+    pts = pins["points_" + dg.pin_tag(nb, precision)].view(np.float64)
+    with nb.Stepper(nb.stock_config(particleCount=n), precision=precision) as st:
+        st.upload(dg.pin_bodies(nb, states, precision, n))
+        return {**pin_field_result(tag + "_own", st.field()), **pin_field_result(tag + "_points", st.field(pts))}
+
+
+def pin_field_batch(nb, states, pins):
+    """One fp32 batch of the systems n = 0, 1, 129, 256, 300 at capacity 300."""
+    pts = pins["points_f32"].view(np.float64)
+    cfg = nb.stock_config(particleCount=FIELD_PIN_BATCH_CAPACITY)
+    with nb.StepperBatch(len(dg.PIN_BATCH_SIZES), FIELD_PIN_BATCH_CAPACITY, cfg=cfg) as b:
+        b.upload([dg.pin_bodies(nb, states, nb.F32, n) for n in dg.PIN_BATCH_SIZES])
+        return {**pin_field_result("batch_own", b.field()), **pin_field_result("batch_points", b.field(pts))}
+
+
+@pytest.fixture(scope="module")
+def field_pins():
+    with np.load(FIELD_PINS) as z:
+        return {k: z[k] for k in z.files}
+
+
+def test_pinned_bits(nb, field_pins):
+    with np.load(dg.PINS) as z:
+        states = {k: z[k] for k in z.files if k.startswith("in_")}
+    got = {}
+    for precision in (nb.F32, nb.F64):
+        for n in dg.PIN_SIZES:
+            got.update(pin_field_stepper(nb, states, field_pins, precision, n))
+    got.update(pin_field_batch(nb, states, field_pins))
+    assert set(got) | {"points_f32", "points_f64"} == set(field_pins)
+    dg.check_pins(field_pins, got)
+    # what the inputs were built to reach: the shared position counted from both sides, and the point placed on it counting
+    # every body that lies there (the states share their first bodies, so it meets body 5 of the smaller ones too)
+    def bodies_at_the_point(precision, n):
+        at = field_pins["points_" + dg.pin_tag(nb, precision)].view(np.float64)[FIELD_PIN_ON_BODY[0]]
+        return int((dg.pin_bodies(nb, states, precision, n).Positions.astype(np.float64) == at).all(axis=1).sum()) if n else 0
+
+    for precision in (nb.F32, nb.F64):
+        tag = "ctx_%s_n300" % dg.pin_tag(nb, precision)
+        assert bodies_at_the_point(precision, 300) == 2
+        assert got[tag + "_own_coincident"].tolist() == [2], tag
+        assert np.isfinite(got[tag + "_points_phi"].view(np.float64)[FIELD_PIN_ON_BODY[0]]), tag
+        for n in dg.PIN_SIZES:
+            tag = "ctx_%s_n%d" % (dg.pin_tag(nb, precision), n)
+            assert got[tag + "_points_coincident"].tolist() == [bodies_at_the_point(precision, n)], tag
+    assert got["batch_own_coincident"].tolist() == [0, 0, 0, 0, 2]
+    assert got["batch_points_coincident"].tolist() == [bodies_at_the_point(nb.F32, n) for n in dg.PIN_BATCH_SIZES]
+    # the batch's n = 300 system is the fp32 context's state: the same bits through the other count policy
+    assert np.array_equal(got["batch_points_acc"][4], got["ctx_f32_n300_points_acc"])
+    assert np.array_equal(got["batch_own_phi"][4], got["ctx_f32_n300_own_phi"])
