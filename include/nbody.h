@@ -443,6 +443,61 @@ int nbody_get_neighbors(nbody_ctx* ctx, const nbody_vec2* points, int m, nbody_n
 int nbody_batch_get_neighbors(struct nbody_batch* b, const nbody_vec2* points, int m, nbody_neighbor* out);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Group finding (the reference has none): friends-of-friends.  Which of the n current bodies hang together,
+ * and how many clumps there are: the connected components of the graph of linked pairs.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the
+ * records of nbody_get_neighbors: (X, Y, R) of every current body, widened exactly from fp32 or taken as it is from fp64.
+ * For two bodies i != j
+ *     dx = X_j - X_i;  dy = Y_j - Y_i;  d2 = (dx*dx) + (dy*dy)
+ *     s  = (radius_scale * (R_i + R_j)) + link
+ *     linked(i, j)  <=>  d2 <= s*s
+ * link is a length: link >= 0, +inf allowed; radius_scale is finite and >= 0.  A group is a connected component of the
+ * undirected graph of links, and label[i] is the LOWEST INDEX in body i's group.  What follows from it:
+ *   - linked is symmetric bit for bit (dx only changes sign, R_i + R_j is commutative);
+ *   - a NaN d2 or a NaN s*s links nothing: a body with a NaN coordinate is a group of its own;
+ *   - with radius_scale = 1 and link = 0 the predicate is exactly the overlap predicate of nbody_get_neighbors (1*x and
+ *     x + 0 are exact where it matters: s*s has the same bits), so body i's number of links equals its `overlaps`;
+ *   - with radius_scale = 0 it is classical friends-of-friends on the centres with linking length `link`;
+ *   - label[label[i]] == label[i] and label[i] <= i; n_groups is the number of i with label[i] == i;
+ *   - the result is a function of the state and the two parameters only: an implementation may find it any way it likes as
+ *     long as it returns exactly this;
+ *   - it is independent of the semantics: a literal context's frozen tail is a body like any other; the masses play no part.
+ * info: n_bodies = n; n_groups; largest = the size of the biggest group (0 for no bodies); sweeps = the pair-walk launches
+ * the call made, informational (for a batch the one number of the whole call, repeated in every record).
+ * nbody_get_groups follows nbody_get_neighbors with points == NULL in every respect: it synchronises, reads the replica only
+ * and never changes what later steps compute; it is NOT collective - any rank of any world or transport may call it on its
+ * own and each gives the same labels; cap is the room in label, cap < n is NBODY_ERR_CAPACITY with nothing written; n == 0
+ * launches nothing and gives {0, 0, 0, 0}.  The device arrays and their pinned staging are allocated on the first call; a
+ * context that never calls it allocates nothing and launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: a NaN or negative link; a NaN, negative or infinite radius_scale; NULL
+ * ctx, label or info; cap < 0.  NBODY_ERR_STATE: before an upload.  A device-side failure is reported as by every
+ * synchronising call.
+ * How (csrc/nbody_groups.hpp): hook and repeat over a parent array in device memory - a triangular pair walk (j < i) that on
+ * a linked pair with different roots lowers the larger root's parent to the smaller with one atomicMin, repeated until a
+ * walk changes nothing (at most n + 1 walks; 4 bytes per system come back after each), then label[i] = root of i.  No
+ * device-side waiting, no retry loop.
+ * Cost (one MI355X, fp32; profiles/groups_probe.txt): the stock state of N = 262144, n = 130965 bodies after 3 steps.  A whole
+ * call with (link, radius_scale) = (0, 1) 14.7 ms, with a centre-only link that gives many small groups (381.8: 77493 groups,
+ * the largest 21) 14.8 ms, with one that percolates (824.8: 21 groups, the largest 130937) 16.9 ms, each 2 sweeps, against 9.6
+ * ms for nbody_get_neighbors with points == NULL on that state.  A sweep's kernel 7.1 / 7.2 / 8.3 ms: 0.76 / 0.79 / 0.92 of
+ * neighbors_at's own-form kernel timed in the same run (9.1 - 9.4 ms), not the 0.5 its pair count suggests - the workgroup
+ * with the last rows walks the whole replica, and with every workgroup resident at once the busiest CU has 1.5 times the mean
+ * work; the percolating link adds two finds per linked pair.  A batch of 256 x 1024: 0.91 ms per call with (0, 1) (2 sweeps of
+ * 0.124 ms against neighbors_at's 0.136 ms) and 1.17 ms on a many-small-groups link (3 sweeps of 0.19 / 0.16 / 0.13 ms: the
+ * hooks of a system's four workgroups sit on the critical path, so a sweep can cost more than neighbors_at), against 1.94 ms
+ * for nbody_batch_get_neighbors.
+ * nbody_batch_get_groups: the same for every system of a batch, every sweep ONE launch for the whole batch, whatever S is;
+ * the batch sweeps until no system changed, systems that have converged leave at once.  System s's labels go to
+ * label + s * capacity, one per current body, the rest of the slice is left unchanged (the layout of
+ * nbody_batch_get_neighbors); info: one record per system.  System s gives exactly what an nbody_ctx holding that system's
+ * state gives; an empty system gives {0, 0, 0, sweeps}.  A count outside [0, capacity] is treated as 0 and reported for that
+ * system, as by nbody_batch_get_neighbors.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_groups_info { int32_t n_bodies, n_groups, largest, sweeps; } nbody_groups_info;   /* 16 bytes */
+int nbody_get_groups(nbody_ctx* ctx, double link, double radius_scale, int32_t* label, int cap, nbody_groups_info* info);
+int nbody_batch_get_groups(struct nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

@@ -123,6 +123,9 @@ FIELD_DTYPE = np.dtype([("acc", np.float64, (2,)), ("phi", np.float64)])
 # struct nbody_neighbor as a numpy record (Stepper.neighbors, StepperBatch.neighbors)
 NEIGHBOR_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("overlaps", np.int32)])
 
+# struct nbody_groups_info as a numpy record (Stepper.groups, StepperBatch.groups)
+GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
+
 # struct nbody_track_row, nbody_track_f32 / nbody_track_f64: the planes of the track log (Stepper.tracks, StepperBatch.tracks)
 TRACK_ROW_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64)])
 TRACK_FIELDS = ("x", "y", "vx", "vy", "m", "r")
@@ -186,6 +189,7 @@ SYMBOLS = {
     "nbody_group_diagnostics": (_i, [_pp, _i, ctypes.POINTER(Diag), _vp]),
     "nbody_get_field": (_i, [_vp, _vp, _i, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
+    "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
     "nbody_batch_create": (_i, [_pp, ctypes.POINTER(_BatchDesc), ctypes.POINTER(_BatchParams)]),
     "nbody_batch_destroy": (_i, [_vp]),
     "nbody_batch_upload": (_i, [_vp, _pp, _ip]),
@@ -201,6 +205,7 @@ SYMBOLS = {
     "nbody_batch_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_batch_get_field": (_i, [_vp, _vp, _i, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_get_neighbors": (_i, [_vp, _vp, _i, _vp]),
+    "nbody_batch_get_groups": (_i, [_vp, _d, _d, _vp, _vp]),
     "nbody_batch_diag_reserve": (_i, [_vp, _i]),
     "nbody_batch_diag_record": (_i, [_vp]),
     "nbody_batch_diag_read": (_i, [_vp, _vp, _i, _ip]),
@@ -434,6 +439,10 @@ def _neighbors(call, points, capacity):
     return buf[:n.value].copy()
 
 
+def _groups_dict(label, info):
+    return {"label": label, "n_groups": int(info["n_groups"]), "largest": int(info["largest"]), "sweeps": int(info["sweeps"])}
+
+
 def _reserve_tracks(call, samples, ids, potential):
     """-> (samples, has_phi): what tracks() needs to size its buffers."""
     k = 0 if ids is None else len(ids)
@@ -648,6 +657,16 @@ class Stepper:
         NEIGHBOR_DTYPE array.  Not collective: any rank of any world may call it on its own."""
         return _neighbors(lambda *a: lib.nbody_get_neighbors(self._ctx, *a), points, self.capacity)
 
+    def groups(self, link, radius_scale=1.0):
+        """nbody_get_groups: friends-of-friends groups of the current bodies, i and j linked where d2 <= s*s with
+        s = radius_scale * (r_i + r_j) + link (fp64): {"label": int32 (n,), label[i] the lowest index of body i's group,
+        "n_groups", "largest": the size of the biggest group, "sweeps": pair walks the call took}.  (0, 1) links the
+        overlapping bodies of neighbors(); radius_scale=0 is friends-of-friends on the centres.  Not collective."""
+        label = np.zeros(max(self.capacity, 1), dtype=np.int32)
+        info = np.zeros(1, dtype=GROUPS_INFO_DTYPE)
+        _check(lib.nbody_get_groups(self._ctx, link, radius_scale, label.ctypes.data, self.capacity, info.ctypes.data))
+        return _groups_dict(label[:int(info["n_bodies"][0])].copy(), info[0])
+
     def stats(self):
         s = Stats()
         _check(lib.nbody_get_stats(self._ctx, ctypes.byref(s)))
@@ -693,6 +712,10 @@ class StepperGroup:
     def neighbors(self, points=None, rank=0):
         """Stepper.neighbors through one rank: every rank's replica holds every body, each gives the same bits."""
         return self.ranks[rank].neighbors(points)
+
+    def groups(self, link, radius_scale=1.0, rank=0):
+        """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
+        return self.ranks[rank].groups(link, radius_scale)
 
     def close(self):
         for r in self.ranks:
@@ -827,6 +850,14 @@ class StepperBatch:
         if pts is None:
             return [buf[s, :int(k)].copy() for s, k in enumerate(self.counts())]
         return np.ascontiguousarray(buf[:, :m])
+
+    def groups(self, link, radius_scale=1.0):
+        """nbody_batch_get_groups: Stepper.groups for every system, every pair walk one launch for the whole batch: a list
+        of S dicts in the form (and with the labels) a Stepper holding the system's state gives."""
+        label = np.zeros((self.systems, max(self.capacity, 1)), dtype=np.int32)
+        info = np.zeros(max(self.systems, 1), dtype=GROUPS_INFO_DTYPE)
+        _check(lib.nbody_batch_get_groups(self._b, link, radius_scale, label.ctypes.data, info.ctypes.data))
+        return [_groups_dict(label[s, :int(info["n_bodies"][s])].copy(), info[s]) for s in range(self.systems)]
 
     def reserve_diagnostics(self, samples):
         """Room for `samples` recorded samples of every system on the device (0 frees it); empties the series."""

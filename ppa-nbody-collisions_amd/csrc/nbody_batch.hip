@@ -24,6 +24,7 @@
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
+#include "nbody_groups.hpp"
 
 using namespace nbk;
 
@@ -78,6 +79,8 @@ struct nbody_batch {
     FieldState fld;
     // neighbour queries (nbody_batch_get_neighbors, nbody_neighbors.hpp): nothing is allocated before the first call
     NeighborState nbr;
+    // group finding (nbody_batch_get_groups, nbody_groups.hpp): nothing is allocated before the first call
+    GroupsState grp;
 };
 
 namespace {
@@ -98,6 +101,7 @@ void free_all(nbody_batch* b) {
     (void)hipFree(b->trk.buf); (void)hipFree(b->trk.sel);
     rows_free(b->fld);
     rows_free(b->nbr);
+    groups_free(b->grp);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -720,6 +724,17 @@ int nbody_batch_get_neighbors(nbody_batch* b, const nbody_vec2* points, int m, n
                                    sizeof(nbody_neighbor));
     if (rc != NBODY_OK) return rc;
     return batch_rows(b, "nbody_batch_get_neighbors", b->nbr, NeighborQuery{}, points, m, out);
+}
+
+// Group finding (nbody_groups.hpp): every sweep one launch for all systems, the counts from Meta on the device.
+int nbody_batch_get_groups(nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info) {
+    const char* who = "nbody_batch_get_groups";
+    const int rc = groups_check_args(who, link, radius_scale, {b, label, info});
+    if (rc != NBODY_OK) return rc;
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_batch_upload", who);
+    HIP_TRY(hipSetDevice(b->desc.device));
+    const RowsSite site{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
+    return groups_run<float, RowsBatchCount>(who, site, b->grp, link, radius_scale, label, info, [b] { return read_meta(b); });
 }
 
 }  // extern "C"

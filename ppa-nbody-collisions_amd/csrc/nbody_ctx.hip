@@ -27,6 +27,7 @@
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
+#include "nbody_groups.hpp"
 
 using namespace nbk;
 
@@ -184,6 +185,8 @@ struct nbody_ctx {
     FieldState fld;
     // neighbour queries (nbody_get_neighbors, nbody_neighbors.hpp): nothing is allocated before the first call
     NeighborState nbr;
+    // group finding (nbody_get_groups, nbody_groups.hpp): nothing is allocated before the first call
+    GroupsState grp;
 };
 
 namespace {
@@ -581,6 +584,7 @@ void free_all(nbody_ctx* c) {
     hipFree(c->trk.buf); hipFree(c->trk.sel);
     rows_free(c->fld);
     rows_free(c->nbr);
+    groups_free(c->grp);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -1667,6 +1671,25 @@ int nbody_get_neighbors(nbody_ctx* c, const nbody_vec2* points, int m, nbody_nei
     const int rc = rows_check_args("nbody_get_neighbors", {c, out, n_out}, m, 1, sizeof(nbody_neighbor));
     if (rc != NBODY_OK) return rc;
     return ctx_rows(c, "nbody_get_neighbors", c->nbr, NeighborQuery{}, points, m, out, n_out);
+}
+
+// Group finding (nbody_groups.hpp): as the own form of the row queries - Meta first, the exact count to the kernels.
+int nbody_get_groups(nbody_ctx* c, double link, double radius_scale, int32_t* label, int cap, nbody_groups_info* info) {
+    const char* who = "nbody_get_groups";
+    int rc = groups_check_args(who, link, radius_scale, {c, label, info});
+    if (rc != NBODY_OK) return rc;
+    if (cap < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: cap = %d", who, cap);
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_upload", who);
+    HIP_TRY(hipSetDevice(c->desc.device));
+    rc = read_meta(c);
+    if (rc != NBODY_OK) return rc;
+    const int n = c->h_meta->n;
+    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "%s: %d bodies, capacity %d", who, n, c->cap);
+    if (cap < n) return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d labels, the context holds %d bodies", who, cap, n);
+    const RowsSite site{c->stream, c->J, (const Meta*)c->meta, c->counters, c->h_meta, c->cap, 1, n};
+    const auto sync = [c] { return read_meta(c); };
+    return c->desc.precision == NBODY_F64 ? groups_run<double, RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync)
+                                          : groups_run<float, RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync);
 }
 
 }  // extern "C"
