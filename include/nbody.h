@@ -296,8 +296,12 @@ int nbody_write_pgm(const char* path, const unsigned char* img, int width, int h
  * body count, steps since upload, timestep, growthRate, field} followed by the [P|V|M|R] block of the current
  * survivors, i.e. exactly what nbody_download returns.  nbody_state_load uploads the block into ctx (which must
  * have the same precision and enough capacity) and restores the step counter; parameters in the file are
- * informational, the context keeps its own. */
+ * informational, the context keeps its own.  A rank of a NBODY_FLAG_GROUP_EXCHANGE group holds its own velocities only:
+ * nbody_state_save on it is NBODY_ERR_STATE and no file is opened.  nbody_group_state_save writes the block of
+ * nbody_group_download under the header of rank 0 (the same file a plain context in that state writes); every rank of a
+ * group loads such a file with nbody_state_load. */
 int nbody_state_save(nbody_ctx* ctx, const char* path);
+int nbody_group_state_save(nbody_ctx** ctxs, int world, const char* path);
 int nbody_state_load(nbody_ctx* ctx, const char* path);
 /* Reads only the header of a state file. Any output pointer may be NULL. */
 int nbody_state_peek(const char* path, int* precision, int* n, int64_t* steps);

@@ -177,6 +177,7 @@ SYMBOLS = {
     "nbody_ctx_info": (_i, [_vp, ctypes.POINTER(_CtxDesc), ctypes.POINTER(ctypes.c_int64)]),
     "nbody_ctx_set_steps": (_i, [_vp, ctypes.c_int64]),
     "nbody_state_save": (_i, [_vp, ctypes.c_char_p]),
+    "nbody_group_state_save": (_i, [_pp, _i, ctypes.c_char_p]),
     "nbody_state_load": (_i, [_vp, ctypes.c_char_p]),
     "nbody_state_peek": (_i, [ctypes.c_char_p, _ip, _ip, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_comm_unique_id": (_i, [_vp]),
@@ -716,6 +717,15 @@ class StepperGroup:
     def groups(self, link, radius_scale=1.0, rank=0):
         """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
         return self.ranks[rank].groups(link, radius_scale)
+
+    def save_state(self, path):
+        """nbody_group_state_save: the group's download under the header of rank 0, the file a plain Stepper writes."""
+        _check(lib.nbody_group_state_save(self._arr, self.world, os.fsencode(path)))
+
+    def load_state(self, path):
+        """Every rank loads the file (a load is an upload, and a group is uploaded rank by rank)."""
+        for r in self.ranks:
+            r.load_state(path)
 
     def close(self):
         for r in self.ranks:

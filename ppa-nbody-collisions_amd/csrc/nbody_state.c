@@ -22,31 +22,60 @@ typedef struct state_header {
 
 _Static_assert(sizeof(state_header) == 64, "state header is 64 bytes");
 
+/* The writing half of both save calls: the header of context `d` at `steps`, then the n survivors of `block`. */
+static int write_state(const char* path, const nbody_ctx_desc* d, int64_t steps, const void* block, int n) {
+    state_header h;
+    memset(&h, 0, sizeof(h));
+    memcpy(h.magic, "NBODYST1", 8);
+    h.precision = d->precision; h.n = n; h.steps = steps;
+    h.timestep = d->timestep; h.growthRate = d->growthRate;
+    h.fieldWidth = d->fieldWidth; h.fieldHeight = d->fieldHeight; h.semantics = d->semantics;
+    FILE* f = fopen(path, "wb");
+    if (!f) return nbody_fail(NBODY_ERR_IO, "cannot open %s for writing", path);
+    const size_t bytes = nbody_block_bytes(n, d->precision);
+    const int okw = fwrite(&h, sizeof(h), 1, f) == 1 && (bytes == 0 || fwrite(block, bytes, 1, f) == 1);
+    const int okc = fclose(f) == 0;
+    if (!okw || !okc) return nbody_fail(NBODY_ERR_IO, "short write to %s", path);
+    return NBODY_OK;
+}
+
 int nbody_state_save(nbody_ctx* ctx, const char* path) {
     if (!ctx || !path) return nbody_fail(NBODY_ERR_INVALID, "nbody_state_save: NULL argument");
     nbody_ctx_desc d;
     int64_t steps = 0;
     int rc = nbody_ctx_info(ctx, &d, &steps);
     if (rc != NBODY_OK) return rc;
+    /* a rank of a group holds its own velocities only (nbody_download zeroes the rest): that is not the state */
+    if (d.world > 1 && (d.flags & NBODY_FLAG_GROUP_EXCHANGE))
+        return nbody_fail(NBODY_ERR_STATE, "group context: its state needs the whole group (nbody_group_state_save)");
     void* block = nbody_block_alloc(d.capacity, d.precision);
     if (!block) return NBODY_ERR_NOMEM;
     int n = 0;
     rc = nbody_download(ctx, block, &n);
-    if (rc != NBODY_OK) { nbody_block_free(block); return rc; }
-    state_header h;
-    memset(&h, 0, sizeof(h));
-    memcpy(h.magic, "NBODYST1", 8);
-    h.precision = d.precision; h.n = n; h.steps = steps;
-    h.timestep = d.timestep; h.growthRate = d.growthRate;
-    h.fieldWidth = d.fieldWidth; h.fieldHeight = d.fieldHeight; h.semantics = d.semantics;
-    FILE* f = fopen(path, "wb");
-    if (!f) { nbody_block_free(block); return nbody_fail(NBODY_ERR_IO, "cannot open %s for writing", path); }
-    const size_t bytes = nbody_block_bytes(n, d.precision);
-    const int okw = fwrite(&h, sizeof(h), 1, f) == 1 && (bytes == 0 || fwrite(block, bytes, 1, f) == 1);
-    const int okc = fclose(f) == 0;
+    if (rc == NBODY_OK) rc = write_state(path, &d, steps, block, n);
     nbody_block_free(block);
-    if (!okw || !okc) return nbody_fail(NBODY_ERR_IO, "short write to %s", path);
-    return NBODY_OK;
+    return rc;
+}
+
+/* This file is also built on its own with the host code (tests/host_asan: stand-ins for the context calls, no device
+ * code), where nothing need define the group download: a weak reference, resolved inside the library. */
+extern int nbody_group_download(nbody_ctx** ctxs, int world, void* block, int* n) __attribute__((weak));
+
+/* The state of a single-process group: the block of nbody_group_download under the header of rank 0. */
+int nbody_group_state_save(nbody_ctx** ctxs, int world, const char* path) {
+    if (!ctxs || world < 1 || !ctxs[0] || !path) return nbody_fail(NBODY_ERR_INVALID, "nbody_group_state_save: bad argument");
+    if (!nbody_group_download) return nbody_fail(NBODY_ERR_STATE, "nbody_group_state_save: built without nbody_group_download");
+    nbody_ctx_desc d;
+    int64_t steps = 0;
+    int rc = nbody_ctx_info(ctxs[0], &d, &steps);
+    if (rc != NBODY_OK) return rc;
+    void* block = nbody_block_alloc(d.capacity, d.precision);
+    if (!block) return NBODY_ERR_NOMEM;
+    int n = 0;
+    rc = nbody_group_download(ctxs, world, block, &n);
+    if (rc == NBODY_OK) rc = write_state(path, &d, steps, block, n);
+    nbody_block_free(block);
+    return rc;
 }
 
 static int read_header(FILE* f, const char* path, state_header* h) {

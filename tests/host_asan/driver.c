@@ -34,6 +34,9 @@ int nbody_upload(nbody_ctx* c, const void* block, int n) {
     return NBODY_OK;
 }
 int nbody_ctx_set_steps(nbody_ctx* c, int64_t steps) { c->steps = steps; return NBODY_OK; }
+int nbody_group_download(nbody_ctx** ctxs, int world, void* block, int* n_out) {
+    return world == 1 ? nbody_download(ctxs[0], block, n_out) : NBODY_ERR_STATE;
+}
 
 static int do_state(const char* path, int prec) {
     nbody_config cfg;
@@ -51,6 +54,11 @@ static int do_state(const char* path, int prec) {
     if (nbody_state_save(&a, path) != NBODY_OK) { printf("save: %s\n", nbody_last_error_string()); return 1; }
     int p2 = -1, n2 = -1; int64_t s2 = -1;
     if (nbody_state_peek(path, &p2, &n2, &s2) != NBODY_OK || p2 != prec || n2 != 777 || s2 != 41) return 1;
+    nbody_ctx* group[1] = {&a};                            /* the group form writes the same file: the load below reads it */
+    if (nbody_group_state_save(group, 1, path) != NBODY_OK) { printf("group save: %s\n", nbody_last_error_string()); return 1; }
+    a.d.world = 2; a.d.flags = NBODY_FLAG_GROUP_EXCHANGE;  /* a rank of a group on its own: refused */
+    if (nbody_state_save(&a, path) != NBODY_ERR_STATE) return 1;
+    a.d.world = b.d.world; a.d.flags = b.d.flags;
     if (nbody_state_load(&b, path) != NBODY_OK) { printf("load: %s\n", nbody_last_error_string()); return 1; }
     const int same = b.n == 777 && b.steps == 41 && !memcmp(a.block, b.block, nbody_block_bytes(777, prec));
     b.d.capacity = 100;                                    /* too small a context: must be refused, not overrun */
