@@ -502,6 +502,63 @@ int nbody_get_groups(nbody_ctx* ctx, double link, double radius_scale, int32_t* 
 int nbody_batch_get_groups(struct nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Pair-separation counts (the reference has none): how many pairs lie in each bin of separation - the DD
+ * (bodies with bodies) and DR (probe points with bodies) counts from which a two-point correlation function, a radial
+ * distribution function g(r) or a Landy-Szalay estimate is made.  The one read-out that says how the bodies lie relative to
+ * each other; it has no per-body result.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the
+ * records (X, Y) of the n current bodies, widened exactly from fp32 or taken as they are from fp64; radii and masses play
+ * no part.  For a row at (x, y) and a source j
+ *     dx = X_j - x;  dy = Y_j - y;  d2 = (dx*dx) + (dy*dy)                  the d2 of nbody_get_neighbors
+ * edges2[0 .. bins] are bins + 1 SQUARED edges, 1 <= bins <= 256: strictly increasing, no NaN, edges2[0] >= 0, and
+ * edges2[bins] may be +inf.  Then
+ *     counts[k] = the number of counted pairs with  edges2[k] <= d2 && d2 < edges2[k+1]      k = 0 .. bins-1
+ *     below     = the number with  d2 < edges2[0]
+ *     rest      = pairs - below - (the sum of counts)
+ * rest is DERIVED, on the host, not counted: it holds every counted pair whose d2 is >= edges2[bins] or NaN (a +inf d2 - a
+ * coordinate near 1e200 - is in rest even where edges2[bins] is +inf, since +inf < +inf fails).
+ * Own form (points == NULL): the counted pairs are the unordered pairs i < j of the n current bodies, each once:
+ * pairs = n (n - 1) / 2, rows = n; m is not used beyond its check.  d2_ij and d2_ji have the same bits (dx and dy only change sign), so one orientation
+ * suffices and the result does not depend on which.  Two distinct bodies at the same place are a pair at d2 = +0: in
+ * counts[0] where edges2[0] == 0, else in below.
+ * Points form (points != NULL): m probe points, always nbody_vec2 (double); the counted pairs are ALL (point, body) pairs:
+ * pairs = m n, rows = m, no self exclusion (a point on a body is a pair at d2 = +0).  m == 0 is legal and launches nothing.
+ * info: n_bodies = n, rows, pairs, below, rest as above.  What follows from the definition:
+ *   - the counts are integers, so they are exact whatever order an implementation adds them in;
+ *   - they are a function of the state and the edges only;
+ *   - they are independent of the semantics: a literal context's frozen tail counts like any other body.
+ * nbody_get_pair_counts follows nbody_get_groups: it synchronises, reads the replica only and never changes what later
+ * steps compute; it is NOT collective - any rank of any world or transport may call it on its own and each gives the same
+ * numbers.  The device edges, histogram and points and their pinned staging are allocated on the first call; a context that
+ * never calls it allocates nothing and launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: NULL ctx, edges2, counts or info; bins outside [1, 256]; an edge that is
+ * NaN, negative or not above its predecessor; m < 0; m x 16 bytes above 2^31 (the limit nbody_get_neighbors sets on its
+ * points).  NBODY_ERR_STATE: before an upload.  A device-side failure is reported as by every synchronising call.
+ * How (csrc/nbody_pairs.hpp): one lane per row over the tile walk of the row queries - triangular (j < i) in the own form,
+ * full in the points form.  A pair costs 2 subtractions, 2 multiplies, 1 add and ONE compare, d2 < edges2[bins]; only a pair
+ * below the top edge goes on to a binary search over the edges in LDS and one 64-bit LDS atomic add; a workgroup adds its
+ * non-zero counters to the system's histogram in device memory once, at its end.  Cheap where the top edge is small against
+ * the system (the clustering use), correct but slower where the edges cover every separation.
+ * Cost (one MI355X, fp32; profiles/pairs_probe.txt): the stock state of N = 262144, n = 130965 bodies after 3 steps (8.58e9
+ * pairs), points == NULL, 32 logarithmic bins.  Top edge at the sparse centre link of the group probe (381.8; 6.8e-6 of the
+ * pairs below it): the kernel 5.49 ms, the whole call 5.47 ms under the host clock; top edge at the percolating link (824.8;
+ * 4.9e-5 of the pairs): 5.72 and 5.73 ms.  groups_sweep at (0, 1), which walks the same triangle, took 7.27 ms in the same run:
+ * 0.755 and 0.787 of it (2 LDS reads per pair against 3, 6 fp64 instructions against 10), and a call is one walk where
+ * nbody_get_groups makes two (14.6 ms).  With a last bin up to +inf every pair takes the search and the LDS atomic: 81.1 ms,
+ * 11.1 times a sweep - correct, not the use this shape is for.  A batch of 256 x 1024: 0.12 ms of kernel and 0.48 ms per
+ * call on the sparse edges of its density (1.4e-3 of the pairs in range), 1.08 ms and 1.45 ms with a last bin up to +inf.
+ * nbody_batch_get_pair_counts: the same for every system of a batch in ONE launch, whatever S is, with the one set of
+ * points and edges for all of them: system s's counts at counts[s * bins + k], its record at info[s].  System s gives
+ * exactly what an nbody_ctx holding that system's state gives; an empty system gives all zeros (rows = m in the points
+ * form).  A count outside [0, capacity] is treated as 0 and reported for that system, as by nbody_batch_get_neighbors.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_pair_info { int64_t n_bodies, rows, pairs, below, rest; } nbody_pair_info;   /* 40 bytes */
+int nbody_get_pair_counts(nbody_ctx* ctx, const nbody_vec2* points, int m, const double* edges2, int bins, uint64_t* counts,
+                          nbody_pair_info* info);
+int nbody_batch_get_pair_counts(struct nbody_batch* b, const nbody_vec2* points, int m, const double* edges2, int bins,
+                                uint64_t* counts /* [systems * bins] */, nbody_pair_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

@@ -126,6 +126,10 @@ NEIGHBOR_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("overlaps",
 # struct nbody_groups_info as a numpy record (Stepper.groups, StepperBatch.groups)
 GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
 
+# struct nbody_pair_info as a numpy record (Stepper.pair_counts, StepperBatch.pair_counts)
+PAIR_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("rows", np.int64), ("pairs", np.int64), ("below", np.int64),
+                            ("rest", np.int64)])
+
 # struct nbody_track_row, nbody_track_f32 / nbody_track_f64: the planes of the track log (Stepper.tracks, StepperBatch.tracks)
 TRACK_ROW_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64)])
 TRACK_FIELDS = ("x", "y", "vx", "vy", "m", "r")
@@ -191,6 +195,7 @@ SYMBOLS = {
     "nbody_get_field": (_i, [_vp, _vp, _i, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
+    "nbody_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_batch_create": (_i, [_pp, ctypes.POINTER(_BatchDesc), ctypes.POINTER(_BatchParams)]),
     "nbody_batch_destroy": (_i, [_vp]),
     "nbody_batch_upload": (_i, [_vp, _pp, _ip]),
@@ -207,6 +212,7 @@ SYMBOLS = {
     "nbody_batch_get_field": (_i, [_vp, _vp, _i, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_get_neighbors": (_i, [_vp, _vp, _i, _vp]),
     "nbody_batch_get_groups": (_i, [_vp, _d, _d, _vp, _vp]),
+    "nbody_batch_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_batch_diag_reserve": (_i, [_vp, _i]),
     "nbody_batch_diag_record": (_i, [_vp]),
     "nbody_batch_diag_read": (_i, [_vp, _vp, _i, _ip]),
@@ -444,6 +450,38 @@ def _groups_dict(label, info):
     return {"label": label, "n_groups": int(info["n_groups"]), "largest": int(info["largest"]), "sweeps": int(info["sweeps"])}
 
 
+def pair_edges2(edges, squared=False):
+    """The squared edges pair_counts() sends: `edges` as float64 (B + 1,), each multiplied by itself - one rounding - unless
+    they are squared already.  Negative lengths are refused here; everything else (order, NaN, the number of bins) by the
+    library."""
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim != 1 or len(e) < 2:
+        raise ValueError("edges must have shape (bins + 1,) with bins >= 1, got %r" % (e.shape,))
+    if not squared:
+        if (e < 0).any():
+            raise ValueError("edges are lengths: none may be negative (pass squared=True for squared edges)")
+        with np.errstate(over="ignore"):                        # a length above 1.3e154 squares to +inf, a legal top edge
+            e = e * e
+    return np.ascontiguousarray(e, dtype=np.float64).copy()
+
+
+def _pair_dict(counts, info, edges2):
+    return {"counts": counts, "below": int(info["below"]), "rest": int(info["rest"]), "pairs": int(info["pairs"]),
+            "n_bodies": int(info["n_bodies"]), "edges2": edges2}
+
+
+def _pair_counts(call, systems, edges, points, squared):
+    """nbody_get_pair_counts through `call(points, m, edges2, bins, counts, info)` -> one dict per system."""
+    e2 = pair_edges2(edges, squared)
+    pts = _field_points(points)
+    bins = len(e2) - 1
+    counts = np.zeros((max(systems, 1), bins), dtype=np.uint64)
+    info = np.zeros(max(systems, 1), dtype=PAIR_INFO_DTYPE)
+    _check(call(None if pts is None else pts.ctypes.data, 0 if pts is None else len(pts), e2.ctypes.data, bins,
+                counts.ctypes.data, info.ctypes.data))
+    return [_pair_dict(counts[s].copy(), info[s], e2) for s in range(systems)]
+
+
 def _reserve_tracks(call, samples, ids, potential):
     """-> (samples, has_phi): what tracks() needs to size its buffers."""
     k = 0 if ids is None else len(ids)
@@ -668,6 +706,13 @@ class Stepper:
         _check(lib.nbody_get_groups(self._ctx, link, radius_scale, label.ctypes.data, self.capacity, info.ctypes.data))
         return _groups_dict(label[:int(info["n_bodies"][0])].copy(), info[0])
 
+    def pair_counts(self, edges, points=None, squared=False):
+        """nbody_get_pair_counts: the number of pairs in each bin of separation between the B + 1 `edges` (lengths; squared
+        lengths with squared=True) - the unordered pairs of current bodies, or with `points` (m, 2) every (point, body)
+        pair -> {"counts": uint64 (B,), "below": pairs under the first edge, "rest": pairs at or above the last (or NaN),
+        "pairs": all of them, "n_bodies", "edges2": the squared edges that were sent}.  Not collective."""
+        return _pair_counts(lambda *a: lib.nbody_get_pair_counts(self._ctx, *a), 1, edges, points, squared)[0]
+
     def stats(self):
         s = Stats()
         _check(lib.nbody_get_stats(self._ctx, ctypes.byref(s)))
@@ -717,6 +762,10 @@ class StepperGroup:
     def groups(self, link, radius_scale=1.0, rank=0):
         """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
         return self.ranks[rank].groups(link, radius_scale)
+
+    def pair_counts(self, edges, points=None, squared=False, rank=0):
+        """Stepper.pair_counts through one rank: every rank's replica holds every body, each gives the same numbers."""
+        return self.ranks[rank].pair_counts(edges, points, squared)
 
     def save_state(self, path):
         """nbody_group_state_save: the group's download under the header of rank 0, the file a plain Stepper writes."""
@@ -868,6 +917,12 @@ class StepperBatch:
         info = np.zeros(max(self.systems, 1), dtype=GROUPS_INFO_DTYPE)
         _check(lib.nbody_batch_get_groups(self._b, link, radius_scale, label.ctypes.data, info.ctypes.data))
         return [_groups_dict(label[s, :int(info["n_bodies"][s])].copy(), info[s]) for s in range(self.systems)]
+
+    def pair_counts(self, edges, points=None, squared=False):
+        """nbody_batch_get_pair_counts: Stepper.pair_counts for every system in one launch, with the one set of edges and
+        points for all of them: a list of S dicts in the form (and with the numbers) a Stepper holding the system's state
+        gives."""
+        return _pair_counts(lambda *a: lib.nbody_batch_get_pair_counts(self._b, *a), self.systems, edges, points, squared)
 
     def reserve_diagnostics(self, samples):
         """Room for `samples` recorded samples of every system on the device (0 frees it); empties the series."""

@@ -25,6 +25,7 @@
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
 #include "nbody_groups.hpp"
+#include "nbody_pairs.hpp"
 
 using namespace nbk;
 
@@ -81,6 +82,8 @@ struct nbody_batch {
     NeighborState nbr;
     // group finding (nbody_batch_get_groups, nbody_groups.hpp): nothing is allocated before the first call
     GroupsState grp;
+    // pair-separation counts (nbody_batch_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
+    PairsState prs;
 };
 
 namespace {
@@ -102,6 +105,7 @@ void free_all(nbody_batch* b) {
     rows_free(b->fld);
     rows_free(b->nbr);
     groups_free(b->grp);
+    pairs_free(b->prs);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -735,6 +739,18 @@ int nbody_batch_get_groups(nbody_batch* b, double link, double radius_scale, int
     HIP_TRY(hipSetDevice(b->desc.device));
     const RowsSite site{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
     return groups_run<float, RowsBatchCount>(who, site, b->grp, link, radius_scale, label, info, [b] { return read_meta(b); });
+}
+
+// Pair-separation counts (nbody_pairs.hpp): one launch for all systems, one set of points and edges, the counts from Meta.
+int nbody_batch_get_pair_counts(nbody_batch* b, const nbody_vec2* points, int m, const double* edges2, int bins, uint64_t* counts,
+                                nbody_pair_info* info) {
+    const char* who = "nbody_batch_get_pair_counts";
+    const int rc = pairs_check_args(who, {b, edges2, counts, info}, m, edges2, bins);
+    if (rc != NBODY_OK) return rc;
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_batch_upload", who);
+    HIP_TRY(hipSetDevice(b->desc.device));
+    const RowsSite site{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
+    return pairs_run<float, RowsBatchCount>(who, site, b->prs, points, m, edges2, bins, counts, info, [b] { return read_meta(b); });
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
 #include "nbody_groups.hpp"
+#include "nbody_pairs.hpp"
 
 using namespace nbk;
 
@@ -187,6 +188,8 @@ struct nbody_ctx {
     NeighborState nbr;
     // group finding (nbody_get_groups, nbody_groups.hpp): nothing is allocated before the first call
     GroupsState grp;
+    // pair-separation counts (nbody_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
+    PairsState prs;
 };
 
 namespace {
@@ -585,6 +588,7 @@ void free_all(nbody_ctx* c) {
     rows_free(c->fld);
     rows_free(c->nbr);
     groups_free(c->grp);
+    pairs_free(c->prs);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -1690,6 +1694,24 @@ int nbody_get_groups(nbody_ctx* c, double link, double radius_scale, int32_t* la
     const auto sync = [c] { return read_meta(c); };
     return c->desc.precision == NBODY_F64 ? groups_run<double, RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync)
                                           : groups_run<float, RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync);
+}
+
+// Pair-separation counts (nbody_pairs.hpp): Meta first, the exact count to the kernel.
+int nbody_get_pair_counts(nbody_ctx* c, const nbody_vec2* points, int m, const double* edges2, int bins, uint64_t* counts,
+                          nbody_pair_info* info) {
+    const char* who = "nbody_get_pair_counts";
+    int rc = pairs_check_args(who, {c, edges2, counts, info}, m, edges2, bins);
+    if (rc != NBODY_OK) return rc;
+    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_upload", who);
+    HIP_TRY(hipSetDevice(c->desc.device));
+    rc = read_meta(c);
+    if (rc != NBODY_OK) return rc;
+    const int n = c->h_meta->n;
+    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "%s: %d bodies, capacity %d", who, n, c->cap);
+    const RowsSite site{c->stream, c->J, (const Meta*)c->meta, c->counters, c->h_meta, c->cap, 1, n};
+    const auto sync = [c] { return read_meta(c); };
+    return c->desc.precision == NBODY_F64 ? pairs_run<double, RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync)
+                                          : pairs_run<float, RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync);
 }
 
 }  // extern "C"
