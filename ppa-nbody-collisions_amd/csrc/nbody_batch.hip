@@ -696,20 +696,35 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_batch_get_field, nbody_batch_get_neighbors; nbody_rows.hpp and the two query headers): one launch for
-// every system, system = blockIdx.y, one set of points for all of them.  At the end of the file for the reason the
-// identities are.
+// Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_groups, nbody_batch_get_pair_counts;
+// nbody_rows.hpp and the four query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
+// of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
-// A batch makes no read before the launch: the grid covers the largest uploaded count, each system's count comes from Meta.
+// What every row query of a batch begins with.  It makes no read before the launch: the grid covers the largest uploaded
+// count (site.n_bound), each system's count comes from Meta on the device.
+int batch_rows_site(nbody_batch* b, const char* who, RowsSite& site) {
+    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_batch_upload", who);
+    HIP_TRY(hipSetDevice(b->desc.device));
+    site = RowsSite{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
+    return NBODY_OK;
+}
+
+// run(T(), read_meta): run is the query's host driver <T, RowsBatchCount>; a batch is fp32.
+template <typename Run>
+int batch_rows_run(nbody_batch* b, Run run) { return run(float(), [b] { return read_meta(b); }); }
+
+// A query with a record per row (rows_run).
 template <typename Q>
 int batch_rows(nbody_batch* b, const char* who, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points,
                int m, typename Q::Result* out) {
-    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_batch_upload", who);
-    HIP_TRY(hipSetDevice(b->desc.device));
-    const RowsSite site{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
-    return rows_run<float, RowsBatchCount>(who, site, buf, q, points, m, out, [b] { return read_meta(b); });
+    RowsSite site;
+    const int rc = batch_rows_site(b, who, site);
+    if (rc != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return rows_run<decltype(t), RowsBatchCount>(who, site, buf, q, points, m, out, sync);
+    });
 }
 
 }  // namespace
@@ -717,40 +732,38 @@ int batch_rows(nbody_batch* b, const char* who, PointBuffers<typename Q::Device>
 extern "C" {
 
 int nbody_batch_get_field(nbody_batch* b, const nbody_vec2* points, int m, nbody_field* out, int64_t* coincident) {
-    const int rc = rows_check_args("nbody_batch_get_field", {b, out, coincident}, m, b ? (unsigned long long)b->S : 1,
-                                   sizeof(nbody_field));
+    const int rc = rows_check_args("nbody_batch_get_field", {b, out, coincident}, m,
+                                   (b ? (unsigned long long)b->S : 1) * sizeof(nbody_field), " of results");
     if (rc != NBODY_OK) return rc;
     return batch_rows(b, "nbody_batch_get_field", b->fld, FieldQuery{(double)kG, coincident}, points, m, out);
 }
 
 int nbody_batch_get_neighbors(nbody_batch* b, const nbody_vec2* points, int m, nbody_neighbor* out) {
-    const int rc = rows_check_args("nbody_batch_get_neighbors", {b, out}, m, b ? (unsigned long long)b->S : 1,
-                                   sizeof(nbody_neighbor));
+    const int rc = rows_check_args("nbody_batch_get_neighbors", {b, out}, m,
+                                   (b ? (unsigned long long)b->S : 1) * sizeof(nbody_neighbor), " of results");
     if (rc != NBODY_OK) return rc;
     return batch_rows(b, "nbody_batch_get_neighbors", b->nbr, NeighborQuery{}, points, m, out);
 }
 
-// Group finding (nbody_groups.hpp): every sweep one launch for all systems, the counts from Meta on the device.
 int nbody_batch_get_groups(nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info) {
     const char* who = "nbody_batch_get_groups";
-    const int rc = groups_check_args(who, link, radius_scale, {b, label, info});
-    if (rc != NBODY_OK) return rc;
-    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_batch_upload", who);
-    HIP_TRY(hipSetDevice(b->desc.device));
-    const RowsSite site{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
-    return groups_run<float, RowsBatchCount>(who, site, b->grp, link, radius_scale, label, info, [b] { return read_meta(b); });
+    RowsSite site;
+    int rc = groups_check_args(who, link, radius_scale, {b, label, info});
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return groups_run<decltype(t), RowsBatchCount>(who, site, b->grp, link, radius_scale, label, info, sync);
+    });
 }
 
-// Pair-separation counts (nbody_pairs.hpp): one launch for all systems, one set of points and edges, the counts from Meta.
 int nbody_batch_get_pair_counts(nbody_batch* b, const nbody_vec2* points, int m, const double* edges2, int bins, uint64_t* counts,
                                 nbody_pair_info* info) {
     const char* who = "nbody_batch_get_pair_counts";
-    const int rc = pairs_check_args(who, {b, edges2, counts, info}, m, edges2, bins);
-    if (rc != NBODY_OK) return rc;
-    if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_batch_upload", who);
-    HIP_TRY(hipSetDevice(b->desc.device));
-    const RowsSite site{b->stream, b->J, (const Meta*)b->meta, b->counters, b->h_meta, b->cap, b->S, b->n_upper};
-    return pairs_run<float, RowsBatchCount>(who, site, b->prs, points, m, edges2, bins, counts, info, [b] { return read_meta(b); });
+    RowsSite site;
+    int rc = pairs_check_args(who, {b, edges2, counts, info}, m, edges2, bins);
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return pairs_run<decltype(t), RowsBatchCount>(who, site, b->prs, points, m, edges2, bins, counts, info, sync);
+    });
 }
 
 }  // extern "C"

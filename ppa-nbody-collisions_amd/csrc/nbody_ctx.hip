@@ -1636,29 +1636,45 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_get_field, nbody_get_neighbors; nbody_rows.hpp and the two query headers).  At the end of the file
-// for the reason the identities are.  They read the replica J only - every rank holds every {x, y, m, r} - so any context
-// may call them on its own, whatever its world or transport.
+// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_groups, nbody_get_pair_counts; nbody_rows.hpp and the four
+// query headers).  At the end of the file for the reason the identities are.  They read the replica J only - every rank
+// holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
-// A context reads Meta first and hands the kernel the exact count.
-template <typename Q>
-int ctx_rows(nbody_ctx* c, const char* who, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points, int m,
-             typename Q::Result* out, int* n_out) {
+// What every row query of a context begins with: it reads Meta first, so that the kernels get the exact count
+// (site.n_bound).
+int ctx_rows_site(nbody_ctx* c, const char* who, RowsSite& site) {
     if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_upload", who);
     HIP_TRY(hipSetDevice(c->desc.device));
     const int rc = read_meta(c);
     if (rc != NBODY_OK) return rc;
     const int n = c->h_meta->n;
     if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "%s: %d bodies, capacity %d", who, n, c->cap);
-    if (!points && m < n)
-        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, n);
-    *n_out = points ? m : n;
-    const RowsSite site{c->stream, c->J, (const Meta*)c->meta, c->counters, c->h_meta, c->cap, 1, n};
+    site = RowsSite{c->stream, c->J, (const Meta*)c->meta, c->counters, c->h_meta, c->cap, 1, n};
+    return NBODY_OK;
+}
+
+// run(T(), read_meta) at the context's precision: run is the query's host driver <T, RowsOneCount>.
+template <typename Run>
+int ctx_rows_run(nbody_ctx* c, Run run) {
     const auto sync = [c] { return read_meta(c); };
-    return c->desc.precision == NBODY_F64 ? rows_run<double, RowsOneCount>(who, site, buf, q, points, m, out, sync)
-                                          : rows_run<float, RowsOneCount>(who, site, buf, q, points, m, out, sync);
+    return c->desc.precision == NBODY_F64 ? run(double(), sync) : run(float(), sync);
+}
+
+// A query with a record per row (rows_run): own rows need room for every body.
+template <typename Q>
+int ctx_rows(nbody_ctx* c, const char* who, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points, int m,
+             typename Q::Result* out, int* n_out) {
+    RowsSite site;
+    const int rc = ctx_rows_site(c, who, site);
+    if (rc != NBODY_OK) return rc;
+    if (!points && m < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, site.n_bound);
+    *n_out = points ? m : site.n_bound;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return rows_run<decltype(t), RowsOneCount>(who, site, buf, q, points, m, out, sync);
+    });
 }
 
 }  // namespace
@@ -1666,52 +1682,40 @@ int ctx_rows(nbody_ctx* c, const char* who, PointBuffers<typename Q::Device>& bu
 extern "C" {
 
 int nbody_get_field(nbody_ctx* c, const nbody_vec2* points, int m, nbody_field* out, int* n_out, int64_t* coincident) {
-    const int rc = rows_check_args("nbody_get_field", {c, out, n_out, coincident}, m, 1, sizeof(nbody_field));
+    const int rc = rows_check_args("nbody_get_field", {c, out, n_out, coincident}, m, sizeof(nbody_field), " of results");
     if (rc != NBODY_OK) return rc;
     return ctx_rows(c, "nbody_get_field", c->fld, FieldQuery{(double)kG, coincident}, points, m, out, n_out);
 }
 
 int nbody_get_neighbors(nbody_ctx* c, const nbody_vec2* points, int m, nbody_neighbor* out, int* n_out) {
-    const int rc = rows_check_args("nbody_get_neighbors", {c, out, n_out}, m, 1, sizeof(nbody_neighbor));
+    const int rc = rows_check_args("nbody_get_neighbors", {c, out, n_out}, m, sizeof(nbody_neighbor), " of results");
     if (rc != NBODY_OK) return rc;
     return ctx_rows(c, "nbody_get_neighbors", c->nbr, NeighborQuery{}, points, m, out, n_out);
 }
 
-// Group finding (nbody_groups.hpp): as the own form of the row queries - Meta first, the exact count to the kernels.
 int nbody_get_groups(nbody_ctx* c, double link, double radius_scale, int32_t* label, int cap, nbody_groups_info* info) {
     const char* who = "nbody_get_groups";
+    RowsSite site;
     int rc = groups_check_args(who, link, radius_scale, {c, label, info});
     if (rc != NBODY_OK) return rc;
     if (cap < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: cap = %d", who, cap);
-    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_upload", who);
-    HIP_TRY(hipSetDevice(c->desc.device));
-    rc = read_meta(c);
-    if (rc != NBODY_OK) return rc;
-    const int n = c->h_meta->n;
-    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "%s: %d bodies, capacity %d", who, n, c->cap);
-    if (cap < n) return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d labels, the context holds %d bodies", who, cap, n);
-    const RowsSite site{c->stream, c->J, (const Meta*)c->meta, c->counters, c->h_meta, c->cap, 1, n};
-    const auto sync = [c] { return read_meta(c); };
-    return c->desc.precision == NBODY_F64 ? groups_run<double, RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync)
-                                          : groups_run<float, RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync);
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if (cap < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d labels, the context holds %d bodies", who, cap, site.n_bound);
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return groups_run<decltype(t), RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync);
+    });
 }
 
-// Pair-separation counts (nbody_pairs.hpp): Meta first, the exact count to the kernel.
 int nbody_get_pair_counts(nbody_ctx* c, const nbody_vec2* points, int m, const double* edges2, int bins, uint64_t* counts,
                           nbody_pair_info* info) {
     const char* who = "nbody_get_pair_counts";
+    RowsSite site;
     int rc = pairs_check_args(who, {c, edges2, counts, info}, m, edges2, bins);
-    if (rc != NBODY_OK) return rc;
-    if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "%s before nbody_upload", who);
-    HIP_TRY(hipSetDevice(c->desc.device));
-    rc = read_meta(c);
-    if (rc != NBODY_OK) return rc;
-    const int n = c->h_meta->n;
-    if (n < 0 || n > c->cap) return nbody_fail(NBODY_ERR_STATE, "%s: %d bodies, capacity %d", who, n, c->cap);
-    const RowsSite site{c->stream, c->J, (const Meta*)c->meta, c->counters, c->h_meta, c->cap, 1, n};
-    const auto sync = [c] { return read_meta(c); };
-    return c->desc.precision == NBODY_F64 ? pairs_run<double, RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync)
-                                          : pairs_run<float, RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync);
+    if (rc != NBODY_OK || (rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return pairs_run<decltype(t), RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync);
+    });
 }
 
 }  // extern "C"

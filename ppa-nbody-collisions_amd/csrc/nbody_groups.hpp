@@ -1,7 +1,8 @@
 // csrc/nbody_groups.hpp -- group finding on the resident state (nbody_get_groups, nbody_batch_get_groups, include/nbody.h;
 // DESIGN.md 4.10): friends-of-friends, the connected components of the graph of linked pairs, label[i] = the lowest index
 // of body i's component.  The launch geometry, the count and the early exits are those of every row query
-// (nbody_rows.hpp); this file has the pair, the triangular tile walk, the parent array and the host loop.
+// (nbody_rows.hpp), and so is the tile walk (rows_walk, triangular shape); this file has the pair, the parent array and the
+// host loop.
 //
 // The definition (include/nbody.h has it in full).  IEEE fp64, every operation rounded on its own, no fma.  Bodies i != j
 // with records (X, Y, R) widened exactly:
@@ -27,12 +28,8 @@
 //   * find reads with relaxed device-scope atomic loads - not needed for any of the above, which holds for arbitrarily
 //     stale reads, but a fresher view hooks more in one sweep, and the read is on the rare path only.
 //
-// groups_sweep: one lane per body i, kDiagBlock lanes per workgroup.  A tile's {x, y, r} are widened to fp64 once into
-// double-buffered LDS planes, as neighbors_at does, the ragged tile padded with x = NaN (d2 = NaN links nothing; a lane
-// without a row carries x = NaN for the same reason).  The walk is triangular: a workgroup stages only the tiles up to the
-// one that holds its last row (a workgroup-uniform bound: the barriers need it); a wave computes on the tiles below its own
-// rows without an index test, on its own tile (nbody_rows.hpp: self_tile) with the test j < i and only up to its last row,
-// and on none above.
+// groups_sweep: one lane per body i, rows_walk's triangular shape over {x, y, r} planes: a padding entry or a lane without a
+// row has d2 = NaN and links nothing; on the wave's own tile the test is j < i.
 // Per pair: 2 subtractions, 2 multiplies, 1 add for d2; 1 add, 1 multiply, 1 add for s; 1 multiply, 1 compare.
 // A batch: the system's `changed` word of the previous sweep is read at the prologue and a system that had converged
 // leaves there (nothing writes its parents any more); the words of this sweep are another array, cleared by the host before
@@ -90,8 +87,32 @@ __global__ __launch_bounds__(kDiagBlock) void groups_init(int32_t* __restrict__ 
     if (i < n_bound && i < stride) parent_all[(size_t)blockIdx.y * (size_t)stride + i] = i;
 }
 
-// grid and early exits: rows_prologue (nbody_rows.hpp).  prev / cur: the systems' `changed` words of the last sweep and of
-// this one.
+// The four pairs of one trip of rows_walk: the hooks wait behind one branch, which is rarely taken.
+struct GroupsFour {
+    const DiagPlanes *sx, *sy, *sr;
+    int i; RowsRow w;               // the row
+    double link, scale;
+    int32_t* parent; int* changed;  // the system's
+    template <bool kChecked>
+    __device__ __forceinline__ void four(int b, int q, int j) {
+        bool hit[4];
+        int any = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            hit[u] = groups_linked<kChecked>((*sx)[b][q + u], (*sy)[b][q + u], (*sr)[b][q + u], j + u, i, w.x, w.y, w.r, link, scale);
+            any += hit[u] ? 1 : 0;
+            asm("" : "+v"(any));                                 // as neighbor_pair: one add-with-carry per compare mask
+        }
+        if (any) {                                               // rare
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (hit[u]) groups_hook(parent, changed, i, j + u);
+        }
+    }
+};
+
+// grid and early exits: rows_prologue; the triangular walk: rows_walk (nbody_rows.hpp).  prev / cur: the systems' `changed`
+// words of the last sweep and of this one.
 template <typename T, typename Count>
 __global__ __launch_bounds__(kDiagBlock) void groups_sweep(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
                                                            Counters* __restrict__ ctr_all, int stride, int n_one, double link,
@@ -101,72 +122,9 @@ __global__ __launch_bounds__(kDiagBlock) void groups_sweep(const Rec<T>* __restr
     if (rows_prologue<T, true, Count>(L, J_all, meta_all, ctr_all, stride, n_one, 0, parent_all, (int32_t)0)) return;
     const int sys = Count::kBatch ? (int)blockIdx.y : 0;
     if (prev[sys] == 0) return;                                  // converged in an earlier sweep: the whole workgroup
-    const Rec<T>* __restrict__ J = L.J;
-    int32_t* parent = L.out;
-    int* changed = cur + sys;
-    const int n = L.n, p = L.p, tid = threadIdx.x;
-    double xi = __builtin_nan(""), yi = 0.0, ri = 0.0;           // a lane without a row links nothing
-    if (L.valid) {
-        const Rec<T> r = J[p];
-        xi = (double)r.x; yi = (double)r.y; ri = (double)r.r;
-    }
     __shared__ double sx[2][kTile], sy[2][kTile], sr[2][kTile];
-    const int row0 = blockIdx.x * kDiagBlock;
-    const int last = (row0 + kDiagBlock < n ? row0 + kDiagBlock : n) - 1;   // the workgroup's last row
-    const int jtiles = last / kTile + 1;                         // workgroup-uniform
-    const int wave_end = row0 + (tid & ~(kWave - 1)) + kWave;    // one past the wave's last row
-    for (int t = 0; t < jtiles; ++t) {
-        const int b = t & 1;
-        const int j0 = t * kTile;
-        const int jn = n - j0 < kTile ? n - j0 : kTile;
-        if (tid < kTile) {
-            double x = __builtin_nan(""), y = 0.0, r = 0.0;      // padding: d2 = NaN
-            if (tid < jn) {
-                const Rec<T> s = J[j0 + tid];
-                x = (double)s.x; y = (double)s.y; r = (double)s.r;
-            }
-            sx[b][tid] = x; sy[b][tid] = y; sr[b][tid] = r;
-        }
-        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
-        __syncthreads();
-        if (!L.wave_works || t > L.self_tile) continue;
-        if (t != L.self_tile) {
-            const int jn4 = (jn + 3) & ~3;                       // <= kTile: the padding is there
-            for (int q = 0; q < jn4; q += 4) {
-                bool hit[4];
-                int any = 0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    hit[u] = groups_linked<false>(sx[b][q + u], sy[b][q + u], sr[b][q + u], j0 + q + u, p, xi, yi, ri, link, scale);
-                    any += hit[u] ? 1 : 0;
-                    asm("" : "+v"(any));                         // as neighbor_pair: one add-with-carry per compare mask
-                }
-                if (any) {                                       // rare
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (hit[u]) groups_hook(parent, changed, p, j0 + q + u);
-                }
-            }
-        } else {
-            const int je = wave_end - j0 < jn ? wave_end - j0 : jn;   // no row of this wave is above wave_end - 1
-            const int jn4 = (je + 3) & ~3;
-            for (int q = 0; q < jn4; q += 4) {
-                bool hit[4];
-                int any = 0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    hit[u] = groups_linked<true>(sx[b][q + u], sy[b][q + u], sr[b][q + u], j0 + q + u, p, xi, yi, ri, link, scale);
-                    any += hit[u] ? 1 : 0;
-                    asm("" : "+v"(any));                         // as neighbor_pair: one add-with-carry per compare mask
-                }
-                if (any) {                                       // rare
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (hit[u]) groups_hook(parent, changed, p, j0 + q + u);
-                }
-            }
-        }
-    }
+    GroupsFour f{&sx, &sy, &sr, L.p, rows_row<T, true>(L, nullptr), link, scale, L.out, cur + sys};
+    rows_walk<true, true, true>(L, sx, sy, &sr, f);
 }
 
 // label[i] = find(i), after the sweep that changed nothing: the lowest index of i's component.
@@ -212,14 +170,12 @@ inline int groups_reserve(GroupsState& g, size_t total, size_t systems, const ch
     return NBODY_OK;
 }
 
-// The argument checks an entry point makes before any device call.
+// The argument checks an entry point makes before any device call: the query's values, then the pointers.
 inline int groups_check_args(const char* who, double link, double radius_scale, std::initializer_list<const void*> required) {
     if (!(link >= 0.0)) return nbody_fail(NBODY_ERR_INVALID, "%s: link = %g (a length: >= 0, +inf allowed)", who, link);
     if (!(radius_scale >= 0.0) || radius_scale == __builtin_inf())
         return nbody_fail(NBODY_ERR_INVALID, "%s: radius_scale = %g (finite and >= 0)", who, radius_scale);
-    for (const void* p : required)
-        if (!p) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
-    return NBODY_OK;
+    return rows_check_args(who, required, 0, 0, "");
 }
 
 // n_groups and largest of one system's n labels.
@@ -234,9 +190,7 @@ inline void groups_summarise(const int32_t* label, int n, int sweeps, std::vecto
     *info = nbody_groups_info{n, groups, largest, sweeps};
 }
 
-// One call, from the reservation to the caller's labels.  Count says whose, as for rows_run: a context hands over the exact
-// count it has just read (s.n_bound), a batch an upper bound, and the kernels take each count from Meta.  read_meta
-// synchronises the stream and reports a device-side failure.
+// One call, from the reservation to the caller's labels; the site, Count and read_meta as for rows_run (nbody_rows.hpp).
 template <typename T, typename Count, typename ReadMeta>
 int groups_run(const char* who, const RowsSite& s, GroupsState& g, double link, double radius_scale, int32_t* label,
                nbody_groups_info* info, ReadMeta read_meta) {
@@ -245,9 +199,9 @@ int groups_run(const char* who, const RowsSite& s, GroupsState& g, double link, 
     if (s.n_bound > 0) {
         int rc = groups_reserve(g, total, S, who);
         if (rc != NBODY_OK) return rc;
-        const dim3 grid((s.n_bound + kDiagBlock - 1) / kDiagBlock, s.systems), block(kDiagBlock);
+        const dim3 grid = s.grid(s.n_bound), block(kDiagBlock);
         const Rec<T>* J = (const Rec<T>*)s.J;
-        const int n_one = Count::kBatch ? 0 : s.n_bound;
+        const int n_one = s.n_one<Count>();
         int* h_changed = reinterpret_cast<int*>(g.h + total * sizeof(int32_t));
         hipLaunchKernelGGL((groups_init<Count>), grid, block, 0, s.stream, g.parent, s.stride, s.n_bound);
         NBK_ROWS_TRY(hipGetLastError());
@@ -275,14 +229,11 @@ int groups_run(const char* who, const RowsSite& s, GroupsState& g, double link, 
         const size_t copied = Count::kBatch ? total : (size_t)s.n_bound;
         NBK_ROWS_TRY(hipMemcpyAsync(g.h, g.label, copied * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
     }
-    if (Count::kBatch || s.n_bound > 0) {
-        const int rc = read_meta();                            // synchronises; a system whose count failed its check ends here
-        if (rc != NBODY_OK) return rc;
-    }
+    const int rc = s.sync<Count>(s.n_bound > 0, read_meta);
+    if (rc != NBODY_OK) return rc;
     std::vector<int32_t> size;
     for (int sys = 0; sys < s.systems; ++sys) {
-        const int m = s.h_meta[sys].n;
-        const int n = m < 0 || m > s.stride || m > s.n_bound ? 0 : m;
+        const int n = s.count(sys);
         const int32_t* h = n ? reinterpret_cast<const int32_t*>(g.h) + (size_t)sys * (size_t)s.stride : nullptr;   // no staging yet
         if (n) memcpy(label + (size_t)sys * (size_t)s.stride, h, (size_t)n * sizeof(int32_t));
         groups_summarise(h, n, sweeps, size, info + sys);

@@ -14,13 +14,8 @@
 // overlap.  The result is a function of the set of sources only; this kernel happens to walk j ascending with one lane per
 // row, so `d2 < best` IS the tie rule (the lowest j among equal distances).
 //
-// neighbors_at: every workgroup walks the replica in kTile-body tiles; a tile's {x, y, r} are widened to fp64 ONCE into
-// double-buffered LDS planes (6 KiB, one barrier per tile) and read back as wave-uniform broadcasts, the way
-// diag_walk_sums reads {x, y, m}.
-//   * The ragged last tile is padded with x = NaN (y = r = +0): a padding entry has d2 = NaN and can be neither nearest nor
-//     overlap, so the pair loop carries no bound test and no remainder loop - it runs in fours up to the tile's count
-//     rounded up to 4.  (Not to kTile: a 64-body system of a batch would pay 128 pairs per row for 64.)
-//   * kOwn: only the wave's self tile (nbody_rows.hpp) runs the loop with the index test.
+// neighbors_at: rows_walk's full shape over {x, y, r} planes (6 KiB of LDS).  A padding entry's d2 = NaN can be neither
+// nearest nor overlap; kOwn: only the wave's self tile runs the pairs with the index test j != i.
 // Per pair: 2 subtractions, 2 multiplies, 1 add, 1 compare and the selects of best (2 halves) and index; for the count
 // 1 add, 1 multiply, 1 compare and the add of the compare's bit.  No transcendental, no divide.
 // The device record is the caller's nbody_neighbor: the host copies it out of the pinned staging as it stands.
@@ -65,7 +60,21 @@ __device__ __forceinline__ void neighbor_pair(NeighborBest& a, const double& xj,
     asm("" : "+v"(a.overlaps));
 }
 
-// grid and early exits: rows_prologue (nbody_rows.hpp).  An empty system gives {+inf, -1, 0}.
+// The four pairs of one trip of rows_walk, and what the row carries along the j stream.
+template <bool kOwn>
+struct NeighborFour {
+    const DiagPlanes *sx, *sy, *sr;
+    int i; RowsRow w;               // the row
+    NeighborBest a;
+    template <bool kChecked>
+    __device__ __forceinline__ void four(int b, int q, int j) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            neighbor_pair<kChecked, !kOwn>(a, (*sx)[b][q + u], (*sy)[b][q + u], (*sr)[b][q + u], j + u, i, w.x, w.y, w.r);
+    }
+};
+
+// grid and early exits: rows_prologue; the full walk: rows_walk (nbody_rows.hpp).  An empty system gives {+inf, -1, 0}.
 template <typename T, bool kOwn, typename Count>
 __global__ __launch_bounds__(kDiagBlock) void neighbors_at(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
                                                            Counters* __restrict__ ctr_all, int stride, int n_one,
@@ -74,52 +83,10 @@ __global__ __launch_bounds__(kDiagBlock) void neighbors_at(const Rec<T>* __restr
     RowsLane<T, NeighborOut> L;
     if (rows_prologue<T, kOwn, Count>(L, J_all, meta_all, ctr_all, stride, n_one, m, out_all, NeighborOut{__builtin_inf(), -1, 0}))
         return;
-    const Rec<T>* __restrict__ J = L.J;
-    const int n = L.n, p = L.p, tid = threadIdx.x;
-    double xi = 0.0, yi = 0.0, ri = 0.0;
-    if (L.valid) {
-        if (kOwn) {
-            const Rec<T> r = J[p];
-            xi = (double)r.x; yi = (double)r.y; ri = (double)r.r;
-        } else {
-            const FieldPoint q = points[p];
-            xi = q.x; yi = q.y;
-        }
-    }
     __shared__ double sx[2][kTile], sy[2][kTile], sr[2][kTile];
-    NeighborBest a;
-    const int jtiles = (n + kTile - 1) / kTile;
-    for (int t = 0; t < jtiles; ++t) {
-        const int b = t & 1;
-        const int j0 = t * kTile;
-        const int jn = n - j0 < kTile ? n - j0 : kTile;
-        if (tid < kTile) {
-            double x = __builtin_nan(""), y = 0.0, r = 0.0;      // padding: d2 = NaN, neither nearest nor overlap
-            if (tid < jn) {
-                const Rec<T> s = J[j0 + tid];
-                x = (double)s.x; y = (double)s.y; r = (double)s.r;
-            }
-            sx[b][tid] = x; sy[b][tid] = y; sr[b][tid] = r;
-        }
-        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
-        __syncthreads();
-        if (!L.wave_works) continue;
-        const int jn4 = (jn + 3) & ~3;                           // <= kTile: the padding is there
-        if (!kOwn || t != L.self_tile) {
-            for (int q = 0; q < jn4; q += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    neighbor_pair<false, !kOwn>(a, sx[b][q + u], sy[b][q + u], sr[b][q + u], j0 + q + u, p, xi, yi, ri);
-            }
-        } else {
-            for (int q = 0; q < jn4; q += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    neighbor_pair<true, false>(a, sx[b][q + u], sy[b][q + u], sr[b][q + u], j0 + q + u, p, xi, yi, ri);
-            }
-        }
-    }
-    if (L.valid) L.out[p] = NeighborOut{a.best, a.index, a.overlaps};
+    NeighborFour<kOwn> f{&sx, &sy, &sr, L.p, rows_row<T, kOwn>(L, points), NeighborBest{}};
+    rows_walk<kOwn, false, true>(L, sx, sy, &sr, f);
+    if (L.valid) L.out[L.p] = NeighborOut{f.a.best, f.a.index, f.a.overlaps};
 }
 
 // The query's traits for rows_run (nbody_rows.hpp): the device record is the caller's, copied as it stands.

@@ -1,12 +1,12 @@
 // csrc/nbody_rows.hpp -- a row per lane over the resident state: what the row queries (field evaluation, nbody_field.hpp;
-// neighbour queries, nbody_neighbors.hpp) have in common, on the device and on the host.  Included
-// after nbody_diag.hpp and before the query headers by both translation units: one system (nbody_ctx.hip) and a batch
-// (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride` apart, one set of points for every system) share each
-// query's one kernel.
+// neighbour queries, nbody_neighbors.hpp; group finding, nbody_groups.hpp; pair counts, nbody_pairs.hpp; DESIGN.md 4.8 to
+// 4.11) have in common, on the device and on the host.  Included after nbody_diag.hpp and before the query headers by both
+// translation units: one system (nbody_ctx.hip) and a batch (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride`
+// apart, one set of points for every system) share each query's one kernel.
 //
 // A row is a current body (kOwn: read from J on the device, results `stride` apart per system) or an explicit point
 // (results m apart per system).  One lane per row, kDiagBlock lanes per workgroup, grid = (ceil(rows / kDiagBlock),
-// systems); every workgroup walks all n sources of its system in kTile-body tiles.
+// systems); every workgroup walks the sources of its system in kTile-body tiles.
 //   * The count.  One system: the exact count is an argument (the host has just read Meta).  A batch: from the system's
 //     Meta; a count outside [0, stride] never becomes an index - the system is treated as empty and reported once (block 0,
 //     lane 0) as kIndexError in its Counters::errors, which fails the host's next read_meta.
@@ -15,9 +15,11 @@
 //   * kOwn: the self term j == i can only occur in the tile that holds the wave's own rows (64 contiguous rows, inside one
 //     128-body tile: wave-uniform), so only that tile runs a checked loop.  Points have no checked loop at all.
 //
-// Adding a row query takes a kernel `<T, kOwn, Count>` that opens with rows_prologue and walks with its own pair functor,
-// and a traits struct (FieldQuery, NeighborQuery) that names the records, launches that kernel and unpacks a system's
-// results; rows_run and the per-handle wrappers in the two .hip files do the rest.
+// Adding a row query takes a kernel `<T, kOwn, Count>` that opens with rows_prologue, loads its row with rows_row and hands
+// rows_walk (the tile loop, below) a functor with the query's four pairs of one trip; and a host side built from rows_run
+// (a result record per row: a traits struct such as FieldQuery or NeighborQuery is all it takes) or, for another shape of
+// result, from the pieces of rows_run - RowsSite's grid, count and sync, RowPoints, rows_check_args.  The per-handle
+// preamble and the precision dispatch are in the two .hip files.  field_at walks with diag_walk_sums instead (see rows_walk).
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -82,69 +84,82 @@ __device__ __forceinline__ bool rows_prologue(RowsLane<T, Out>& L, const Rec<T>*
     return false;
 }
 
+// The lane's own row widened to fp64: the body {x, y, r} or the point (r = +0).  A lane without a row carries x = NaN: every
+// d2 it forms is NaN, which passes no comparison of any query.
+struct RowsRow { double x, y, r; };
+template <typename T, bool kOwn, typename Out>
+__device__ __forceinline__ RowsRow rows_row(const RowsLane<T, Out>& L, const FieldPoint* __restrict__ points) {
+    RowsRow w{__builtin_nan(""), 0.0, 0.0};
+    if (L.valid) {
+        if (kOwn) {
+            const Rec<T> r = L.J[L.p];
+            w = RowsRow{(double)r.x, (double)r.y, (double)r.r};
+        } else {
+            const FieldPoint q = points[L.p];
+            w = RowsRow{q.x, q.y, 0.0};
+        }
+    }
+    return w;
+}
+
+// The tile walk of a row query whose pairs need no order: all kDiagBlock lanes call it after rows_prologue.  A tile's
+// {x, y[, r]} are widened to fp64 ONCE into the caller's double-buffered LDS planes (one barrier per tile; sr is staged only
+// for kRadius and may be NULL otherwise) and read back by the functor as wave-uniform broadcasts.  The ragged tile is padded
+// with x = NaN (y = r = +0): a padding entry has d2 = NaN and passes no comparison, so the pair loop carries no bound test
+// and no remainder loop - it runs in fours up to the tile's count rounded up to 4 (not to kTile: a 64-body system of a batch
+// would pay 128 pairs per row).  The functor is called as f.template four<kChecked>(b, q, j): the sources j .. j + 3 are
+// entries q .. q + 3 of buffer b; kChecked: the tile holds the wave's own rows, the functor applies its index test.  It is
+// walked in a copy and handed back at the end: what it carries from pair to pair (NeighborFour's best), carried through the
+// reference, is promoted from memory twice and every pair pays two more selects.
+//   * kTri = false, the full walk: every tile; kOwn runs the whole self tile checked, points have no checked loop.
+//   * kTri = true (kOwn only), the triangular walk for symmetric pairs, each counted at the higher row: only the tiles up
+//     to the one that holds the workgroup's last row are staged (a workgroup-uniform bound: the barriers need it); a wave
+//     computes on the tiles below its own rows unchecked, on its own tile checked and only up to its last row, on none above.
+// Not one walk with diag_walk_sums (nbody_diag.hpp), which field_at calls: that one sums in ascending order under an order
+// contract with fma-contracted arithmetic, so it cannot pad with NaN, keeps a remainder loop, votes per tile for gathered
+// rows, and its comment records that a function boundary inside it changes the code of every potential kernel.
+template <bool kOwn, bool kTri, bool kRadius, typename T, typename Out, typename Four>
+__device__ __forceinline__ void rows_walk(const RowsLane<T, Out>& L, DiagPlanes& sx, DiagPlanes& sy, DiagPlanes* sr, Four& carried) {
+    static_assert(kOwn || !kTri, "the triangular walk is over own rows");
+    Four f = carried;                                            // see above: a local of the function that has the loops
+    const Rec<T>* __restrict__ J = L.J;
+    const int n = L.n, tid = threadIdx.x;
+    const int row0 = blockIdx.x * kDiagBlock;
+    const int last = (row0 + kDiagBlock < n ? row0 + kDiagBlock : n) - 1;   // kTri: the workgroup's last row
+    const int jtiles = kTri ? last / kTile + 1 : (n + kTile - 1) / kTile;   // workgroup-uniform
+    const int wave_end = row0 + (tid & ~(kWave - 1)) + kWave;    // one past the wave's last row
+    for (int t = 0; t < jtiles; ++t) {
+        const int b = t & 1;
+        const int j0 = t * kTile;
+        const int jn = n - j0 < kTile ? n - j0 : kTile;
+        if (tid < kTile) {
+            double x = __builtin_nan(""), y = 0.0, r = 0.0;      // padding: d2 = NaN
+            if (tid < jn) {
+                const Rec<T> s = J[j0 + tid];
+                x = (double)s.x; y = (double)s.y; r = (double)s.r;
+            }
+            sx[b][tid] = x; sy[b][tid] = y;
+            if constexpr (kRadius) (*sr)[b][tid] = r;
+        }
+        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
+        __syncthreads();
+        if (!L.wave_works || (kTri && t > L.self_tile)) continue;
+        if (!kOwn || t != L.self_tile) {
+            const int jn4 = (jn + 3) & ~3;                       // <= kTile: the padding is there
+            for (int q = 0; q < jn4; q += 4) f.template four<false>(b, q, j0 + q);
+        } else {
+            const int je = kTri && wave_end - j0 < jn ? wave_end - j0 : jn;   // no row of this wave is above wave_end - 1
+            const int jn4 = (je + 3) & ~3;
+            for (int q = 0; q < jn4; q += 4) f.template four<true>(b, q, j0 + q);
+        }
+    }
+    carried = f;
+}
+
 // ---------------------------------------------------------------------------------------------------------
-// Host side.  The buffers of one query of one context or batch, allocated on the first call and grown to the largest
-// request seen - the device points, the device results, and one pinned staging area for both directions.
+// Host side.
 // ---------------------------------------------------------------------------------------------------------
 constexpr unsigned long long kFieldMaxBytes = 1ull << 31;   // of the caller's `out`
-
-template <typename Out>
-struct PointBuffers {
-    FieldPoint* pts = nullptr;      // [cap_pts]
-    Out* out = nullptr;             // [cap_out]
-    unsigned char* h = nullptr;     // pinned: max(cap_pts * sizeof(FieldPoint), cap_out * sizeof(Out)) bytes
-    size_t cap_pts = 0, cap_out = 0, h_bytes = 0;
-};
-
-template <typename Out>
-inline void rows_free(PointBuffers<Out>& f) {
-    (void)hipFree(f.pts); (void)hipFree(f.out);
-    if (f.h) (void)hipHostFree(f.h);
-    f = PointBuffers<Out>{};
-}
-
-template <typename Out>
-inline int rows_reserve(PointBuffers<Out>& f, size_t n_pts, size_t n_out, const char* who) {
-    hipError_t e = hipSuccess;
-    if (n_pts > f.cap_pts) {
-        (void)hipFree(f.pts);
-        f.pts = nullptr; f.cap_pts = 0;
-        e = hipMalloc((void**)&f.pts, n_pts * sizeof(FieldPoint));
-        if (e == hipSuccess) f.cap_pts = n_pts; else f.pts = nullptr;
-    }
-    if (e == hipSuccess && n_out > f.cap_out) {
-        (void)hipFree(f.out);
-        f.out = nullptr; f.cap_out = 0;
-        e = hipMalloc((void**)&f.out, n_out * sizeof(Out));
-        if (e == hipSuccess) f.cap_out = n_out; else f.out = nullptr;
-    }
-    const size_t hb = f.cap_pts * sizeof(FieldPoint) > f.cap_out * sizeof(Out) ? f.cap_pts * sizeof(FieldPoint)
-                                                                               : f.cap_out * sizeof(Out);
-    if (e == hipSuccess && hb > f.h_bytes) {
-        if (f.h) (void)hipHostFree(f.h);
-        f.h = nullptr; f.h_bytes = 0;
-        e = hipHostMalloc((void**)&f.h, hb, hipHostMallocDefault);
-        if (e == hipSuccess) f.h_bytes = hb; else f.h = nullptr;
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point and result buffers: %s", who,
-                          hipGetErrorString(e));
-    }
-    return NBODY_OK;
-}
-
-// The argument checks an entry point makes before any device call.  `required`: every pointer that must not be NULL;
-// `record`: the size of one of the caller's result records, of which there are m per system.
-inline int rows_check_args(const char* who, std::initializer_list<const void*> required, int m, unsigned long long systems,
-                           size_t record) {
-    for (const void* p : required)
-        if (!p) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
-    if (m < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: m = %d", who, m);
-    if ((unsigned long long)m * systems * record > kFieldMaxBytes)
-        return nbody_fail(NBODY_ERR_INVALID, "%s: %d points are more than 2^31 bytes of results", who, m);
-    return NBODY_OK;
-}
 
 #define NBK_ROWS_TRY(expr)                                                                                \
     do {                                                                                                  \
@@ -154,7 +169,75 @@ inline int rows_check_args(const char* who, std::initializer_list<const void*> r
                               __FILE__, __LINE__);                                                        \
     } while (0)
 
-// What a context or a batch lends rows_run.
+// A device array and the pinned memory it is sent from or read back into, allocated on the first use and grown to the
+// largest request seen.  RowPoints: the explicit points of one query of one context or batch.
+template <typename E>
+struct RowsArray {
+    E* d = nullptr;                 // [cap]
+    unsigned char* h = nullptr;     // pinned: cap elements
+    size_t cap = 0;
+};
+using RowPoints = RowsArray<FieldPoint>;
+
+template <typename E>
+inline void rows_free(RowsArray<E>& f) {
+    (void)hipFree(f.d);
+    if (f.h) (void)hipHostFree(f.h);
+    f = RowsArray<E>{};
+}
+
+template <typename E>
+inline hipError_t rows_reserve(RowsArray<E>& f, size_t n) {
+    if (n <= f.cap) return hipSuccess;
+    rows_free(f);
+    hipError_t e = hipMalloc((void**)&f.d, n * sizeof(E));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f.h, n * sizeof(E), hipHostMallocDefault);
+    if (e == hipSuccess) f.cap = n; else f.h = nullptr;
+    return e;
+}
+
+// Enqueues the copy of the caller's m points (reserved before) to the device.
+inline hipError_t rows_upload(RowPoints& f, const nbody_vec2* points, int m, hipStream_t stream) {
+    memcpy(f.h, points, (size_t)m * sizeof(FieldPoint));
+    return hipMemcpyAsync(f.d, f.h, (size_t)m * sizeof(FieldPoint), hipMemcpyHostToDevice, stream);
+}
+
+// The buffers of one query with a record per row: the points and the results.
+template <typename Out>
+struct PointBuffers {
+    RowPoints pts;
+    RowsArray<Out> out;
+};
+
+template <typename Out>
+inline void rows_free(PointBuffers<Out>& f) { rows_free(f.pts); rows_free(f.out); }
+
+template <typename Out>
+inline int rows_reserve(PointBuffers<Out>& f, size_t n_pts, size_t n_out, const char* who) {
+    hipError_t e = rows_reserve(f.pts, n_pts);
+    if (e == hipSuccess) e = rows_reserve(f.out, n_out);
+    if (e == hipSuccess) return NBODY_OK;
+    (void)hipGetLastError();
+    return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point and result buffers: %s", who,
+                      hipGetErrorString(e));
+}
+
+// The argument checks every entry point makes before any device call; a query's own value checks stay next to the query.
+// `required`: every pointer that must not be NULL; `bytes_per_point`: the caller's result records of all systems per point
+// (`of` = " of results") or the point itself (`of` = ""); a query without points passes m = 0.
+inline int rows_check_args(const char* who, std::initializer_list<const void*> required, int m, unsigned long long bytes_per_point,
+                           const char* of) {
+    for (const void* p : required)
+        if (!p) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
+    if (m < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: m = %d", who, m);
+    if ((unsigned long long)m * bytes_per_point > kFieldMaxBytes)
+        return nbody_fail(NBODY_ERR_INVALID, "%s: %d points are more than 2^31 bytes%s", who, m, of);
+    return NBODY_OK;
+}
+
+// What a context or a batch lends a row query, and what every host driver derives from it.  Count says whose: a context
+// (RowsOneCount: the exact count, read by the caller just before, goes to the kernel) or a batch (RowsBatchCount: the grid
+// covers n_bound rows of every system and the kernel takes each count from Meta).
 struct RowsSite {
     hipStream_t stream;
     const void* J;              // device Rec<T> [systems * stride]
@@ -163,14 +246,25 @@ struct RowsSite {
     const Meta* h_meta;         // the host's copy [systems], current once read_meta has returned
     int stride, systems;
     int n_bound;                // own rows the grid covers: a context's exact count, a batch's upper bound
+
+    dim3 grid(int rows) const { return dim3((rows + kDiagBlock - 1) / kDiagBlock, systems); }
+    template <typename Count>
+    int n_one() const { return Count::kBatch ? 0 : n_bound; }
+    // The bodies of system sys as the host counts them after read_meta: 0 for a count that failed its check.  A count
+    // above n_bound cannot occur - bodies only merge - and its rows past n_bound were never covered by the grid.
+    int count(int sys) const {
+        const int c = h_meta[sys].n;
+        return c < 0 || c > stride || c > n_bound ? 0 : c;
+    }
+    // read_meta synchronises the stream and reports a device-side failure (a count that failed its check ends there).  A
+    // batch calls it even when nothing was launched; a context has read Meta just before.
+    template <typename Count, typename ReadMeta>
+    int sync(bool launched, ReadMeta read_meta) const { return Count::kBatch || launched ? read_meta() : NBODY_OK; }
 };
 
-// One query, from the reservation to the caller's records.  Count says whose: a context (RowsOneCount: the exact count,
-// read by the caller just before, goes to the kernel; nothing to do for no rows) or a batch (RowsBatchCount: the grid
-// covers n_bound rows of every system, the kernel takes each count from Meta, and read_meta is called even for no rows).
+// One query with a record per row, from the reservation to the caller's records.
 // Q: the query's traits - Device and Result records, launch<T, kOwn, Count>(grid, stream, out, common kernel arguments...),
-// empty(s) and unpack(s, staged records, how many, the caller's) for system s.  read_meta synchronises the stream and
-// reports a device-side failure.
+// empty(s) and unpack(s, staged records, how many, the caller's) for system s.
 template <typename T, typename Count, typename Q, typename ReadMeta>
 int rows_run(const char* who, const RowsSite& s, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points,
              int m, typename Q::Result* out, ReadMeta read_meta) {
@@ -180,31 +274,26 @@ int rows_run(const char* who, const RowsSite& s, PointBuffers<typename Q::Device
     const size_t per_sys = own ? (size_t)s.stride : (size_t)m;             // results of one system on the device
     const size_t total = Count::kBatch ? per_sys * (size_t)s.systems : (size_t)rows;
     for (int sys = 0; sys < s.systems; ++sys) q.empty(sys);
-    if (rows == 0) return Count::kBatch ? read_meta() : NBODY_OK;
-    int rc = rows_reserve(buf, own ? 0 : (size_t)m, total, who);
-    if (rc != NBODY_OK) return rc;
-    const dim3 grid((rows + kDiagBlock - 1) / kDiagBlock, s.systems);
-    const Rec<T>* J = (const Rec<T>*)s.J;
-    const int n_one = Count::kBatch ? 0 : s.n_bound;
-    if (own) {
-        q.template launch<T, true, Count>(grid, s.stream, buf.out, J, s.meta, s.counters, s.stride, n_one,
-                                          (const FieldPoint*)nullptr, 0);
-    } else {
-        memcpy(buf.h, points, (size_t)m * sizeof(FieldPoint));
-        NBK_ROWS_TRY(hipMemcpyAsync(buf.pts, buf.h, (size_t)m * sizeof(FieldPoint), hipMemcpyHostToDevice, s.stream));
-        q.template launch<T, false, Count>(grid, s.stream, buf.out, J, s.meta, s.counters, s.stride, n_one,
-                                           (const FieldPoint*)buf.pts, m);
+    if (rows > 0) {
+        const int rc = rows_reserve(buf, own ? 0 : (size_t)m, total, who);
+        if (rc != NBODY_OK) return rc;
+        const Rec<T>* J = (const Rec<T>*)s.J;
+        if (own) {
+            q.template launch<T, true, Count>(s.grid(rows), s.stream, buf.out.d, J, s.meta, s.counters, s.stride,
+                                              s.n_one<Count>(), (const FieldPoint*)nullptr, 0);
+        } else {
+            NBK_ROWS_TRY(rows_upload(buf.pts, points, m, s.stream));
+            q.template launch<T, false, Count>(s.grid(rows), s.stream, buf.out.d, J, s.meta, s.counters, s.stride,
+                                               s.n_one<Count>(), (const FieldPoint*)buf.pts.d, m);
+        }
+        NBK_ROWS_TRY(hipGetLastError());
+        NBK_ROWS_TRY(hipMemcpyAsync(buf.out.h, buf.out.d, total * sizeof(Device), hipMemcpyDeviceToHost, s.stream));
     }
-    NBK_ROWS_TRY(hipGetLastError());
-    NBK_ROWS_TRY(hipMemcpyAsync(buf.h, buf.out, total * sizeof(Device), hipMemcpyDeviceToHost, s.stream));
-    rc = read_meta();                                      // synchronises; a system whose count failed its check ends here
-    if (rc != NBODY_OK) return rc;
-    const Device* h = reinterpret_cast<const Device*>(buf.h);
-    for (int sys = 0; sys < s.systems; ++sys) {
-        const int n = s.h_meta[sys].n;
-        const size_t cnt = own ? (size_t)(n < 0 || n > s.stride ? 0 : n) : (size_t)m;
-        q.unpack(sys, h + (size_t)sys * per_sys, cnt, out + (size_t)sys * per_sys);
-    }
+    const int rc = s.sync<Count>(rows > 0, read_meta);
+    if (rc != NBODY_OK || rows == 0) return rc;
+    const Device* h = reinterpret_cast<const Device*>(buf.out.h);
+    for (int sys = 0; sys < s.systems; ++sys)
+        q.unpack(sys, h + (size_t)sys * per_sys, own ? (size_t)s.count(sys) : (size_t)m, out + (size_t)sys * per_sys);
     return NBODY_OK;
 }
 

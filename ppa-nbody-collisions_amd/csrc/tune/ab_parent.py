@@ -2,7 +2,7 @@
 """This library against the parent commit's, on the work of the kernels that share a rule with another kernel: the
 compaction's offsets (compact_count / compact_scatter, batch_count / batch_commit, ids_scatter), the potential's walk
 (diag_potential, batch_diag_potential, track_potential), the finish of the diagnostics (batch_diag_reduce) and the row
-queries' prologue and host driver (field_at, neighbors_at; nbody_rows.hpp).
+queries' prologue, tile walk and host driver (field_at, neighbors_at, groups_sweep, pair_counts; nbody_rows.hpp).
 
     python3 csrc/tune/ab_parent.py --baseline-root DIR [--lines a,b256,...] [--rounds 3] [--out FILE]
     python3 csrc/tune/ab_parent.py --trace [--root DIR]     (every line once, target of rocprofv3 --kernel-trace --stats)
@@ -27,6 +27,9 @@ Lines (fp32, literal, stock configuration with stock radii):
               (20 steps), dctx1024 (2000), d256x1024 (1000), d64x4096 (500)
     fld, nbr  Stepper N = 262144, field() / neighbors(); ...pts: the same state with 65536  ms per call
               explicit points; ...256: StepperBatch 256 x 1024 after 3 steps, points=None
+    grp, prs  the shapes of groups_probe.py and pairs_probe.py: Stepper N = 262144 after 3      ms per call
+              steps, groups(0, 1) / pair_counts() over the 32 "sparse" bins; prspts: the same
+              bins from 65536 explicit points; ...256: StepperBatch 256 x 1024 after 3 steps
 A line passes when the candidate's median is not above the parent's median by more than max(the parent's round spread
 (max - min), |control median - parent median|).  Exit status 1 if a line does not pass.
 """
@@ -44,10 +47,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", "..", ".."))
 REPLY_TIMEOUT_S = 240           # a side that does not answer within this is killed and the probe fails
 LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024", "d256x1024", "d64x4096",
-         "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256")
+         "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256")
 BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
 STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
 ROWS = {"": 3, "pts": 8, "256": 100}    # the row queries' shapes (field_probe.py, neighbor_probe.py): calls per window
+SCANS = {"grp": 8, "grp256": 100, "prs": 20, "prspts": 30, "prs256": 200}    # groups and pair counts: calls per window
 N_BIG = 262144
 M_POINTS = 65536
 
@@ -92,8 +96,8 @@ class Line:
             if name == "c":
                 self.st.step(8)
                 self.sel = [int(x) for x in np.unique(np.linspace(0, N_BIG - 1, 64).astype(np.int32))]
-        elif name[:3] in ("fld", "nbr"):
-            self.unit, self.reps = "ms per call", ROWS[name[3:]]
+        elif name[:3] in ("fld", "nbr", "grp", "prs"):
+            self.unit, self.reps = "ms per call", SCANS[name] if name in SCANS else ROWS[name[3:]]
             self.pts = None
             if name.endswith("256"):
                 cfg = nb.stock_config(particleCount=1024)
@@ -104,9 +108,19 @@ class Line:
                 cfg = nb.stock_config(particleCount=N_BIG)
                 self.st = nb.Stepper(cfg)
                 self.st.upload(nb.init_bodies(cfg, seed=1))
+                if name in SCANS:
+                    self.st.step(3)
                 if name.endswith("pts"):
                     self.pts = np.random.default_rng(2).uniform(0, 1, size=(M_POINTS, 2)) * [cfg.fieldWidth, cfg.fieldHeight]
-            self.call = self.st.field if name.startswith("fld") else self.st.neighbors
+            if name.startswith("grp"):
+                self.call = lambda pts: self.st.groups(0.0, 1.0)
+            elif name.startswith("prs"):                                    # pairs_probe.py's (a): 1.5 others within the top edge
+                P = np.asarray((self.st.download(0) if self.batch else self.st.download()).Positions, dtype=np.float64)
+                top = float(np.sqrt(1.5 * np.prod(P.max(axis=0) - P.min(axis=0)) / (np.pi * len(P))))
+                e2 = np.geomspace(top / 1000.0, top, 33) ** 2
+                self.call = lambda pts: self.st.pair_counts(e2, points=pts, squared=True)
+            else:
+                self.call = self.st.field if name.startswith("fld") else self.st.neighbors
         elif name in STEPS:
             shape = name[1:]
             self.steps = 200 if short else STEPS[name]
@@ -146,13 +160,15 @@ class Line:
                 o, ids = (st.download(s), st.ids(s)) if self.batch else (st.download(), st.ids())
                 parts += [b"%d:" % o.numBodies, o.block.tobytes(), ids.tobytes()]
             return seconds, digest_of(parts)
-        if name[:3] in ("fld", "nbr"):
+        if name[:3] in ("fld", "nbr", "grp", "prs"):
             t0 = time.perf_counter()
             for _ in range(self.reps):                                      # each call ends in a copy back and a synchronise
                 r = self.call(self.pts)
             seconds = time.perf_counter() - t0
             if isinstance(r, dict):
                 return seconds, digest_of(diag_parts(r))
+            if isinstance(r, list) and r and isinstance(r[0], dict):
+                return seconds, digest_of([p for e in r for p in diag_parts(e)])
             return seconds, digest_of([a.tobytes() for a in (r if isinstance(r, list) else [r])])
         if name == "c":
             st.reserve_tracks(self.reps, ids=self.sel, potential=True)      # empties the log; synchronises

@@ -64,7 +64,9 @@ def test_random_states(nb, precision):
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. tile and workgroup edges
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 2, 127, 128, 129, 257])
+# 63 .. 65: the cut at the wave's last row inside tile 0; 191 .. 193: the third wave, cut at 64 entries of tile 1; 385: a second
+# workgroup whose first wave has self tile 2
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 385])
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_tile_edges(nb, precision, n):
     P, R = gc.random_state(n, DTYPE_OF[precision], seed=n, field=5.0 * np.sqrt(n))
@@ -204,7 +206,7 @@ def test_errors(nb):
 # ---------------------------------------------------------------------------------------------------------------------
 # 7. batch
 # ---------------------------------------------------------------------------------------------------------------------
-BATCH_COUNTS = [0, 1, 127, 300, 129]
+BATCH_COUNTS = [0, 1, 127, 300, 129, 63, 64, 65, 193]
 
 
 @pytest.mark.parametrize("track_ids", [False, True], ids=["plain", "track_ids"])

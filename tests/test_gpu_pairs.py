@@ -43,7 +43,9 @@ def check(st, P, edges2, what, points=None):
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. tile and workgroup edges
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 2, 127, 128, 129, 257, 300])
+# 63 .. 65: the cut at the wave's last row inside tile 0; 191 .. 193: the third wave, cut at 64 entries of tile 1; 385: a second
+# workgroup whose first wave has self tile 2
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 300, 385])
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_tile_edges(nb, precision, n):
     field = 5.0 * np.sqrt(n)
@@ -130,7 +132,7 @@ def test_points_form(nb, precision):
     allpts = np.random.default_rng(4).uniform(-5.0, field + 5.0, size=(300, 2))
     with small_stepper(nb, precision, n) as st:
         st.upload(bodies_of(nb, P, precision))
-        for m in (0, 1, 255, 256, 300):
+        for m in (0, 1, 63, 65, 255, 256, 257, 300):               # 63, 65, 257: a wave past the last row only loads tiles
             got = check(st, P, e2, "m %d" % m, points=allpts[:m])
             assert m == 0 or got["counts"].sum() > 0
             check(st, P, np.array([0.0, np.inf]), "m %d, one bin" % m, points=allpts[:m])
@@ -176,34 +178,38 @@ def test_after_stepping_and_no_effect_on_stepping(nb, precision):
 # 6. batch
 # ---------------------------------------------------------------------------------------------------------------------
 def test_batch_equals_stepper_and_model(nb):
-    cap, counts = 512, (512, 130, 0)
+    cap, counts = 512, (512, 130, 0, 63, 64, 65, 193)
+    S = len(counts)
     cfg = nb.stock_config(particleCount=cap, fieldWidth=3000, fieldHeight=3000)
     bodies = [nb.init_bodies(nb.stock_config(particleCount=k, fieldWidth=3000, fieldHeight=3000), seed=40 + s) if k else nb.BodiesData(0)
               for s, k in enumerate(counts)]
     e2 = np.geomspace(4.0, 600.0 ** 2, 13)
     pts = np.random.default_rng(6).uniform(0.0, 3000.0, size=(200, 2))
-    with nb.StepperBatch(3, cap, cfg=cfg) as batch, nb.Stepper(cfg) as one:
+    with nb.StepperBatch(S, cap, cfg=cfg) as batch, nb.Stepper(cfg) as one:
         batch.upload(bodies)
-        batch.step(2)
-        for points in (None, pts):
-            got = batch.pair_counts(e2, points=points, squared=True)
-            assert len(got) == 3
-            for s in range(3):
-                d = batch.download(s)
-                P, _ = pc.widen(d)
-                n = d.numBodies
-                what = "system %d (n %d), %s form" % (s, n, "own" if points is None else "points")
-                pc.assert_same(got[s], pc.model_pair_counts(P[:n], e2, points), what + ": model")
-                pc.check_sum(got[s], n * (n - 1) // 2 if points is None else 200 * n, what)
-                one.upload(d)
-                pc.assert_same(got[s], one.pair_counts(e2, points=points, squared=True), what + ": Stepper")
-            assert 0 < batch.download(1).numBodies <= 130 and got[0]["counts"].sum() > 0 and got[1]["counts"].sum() > 0
-            empty = got[2]
-            assert (empty["counts"].sum(), empty["below"], empty["rest"], empty["pairs"], empty["n_bodies"]) == (0, 0, 0, 0, 0)
-        raw = np.full((3, 12), 77, dtype=np.uint64)               # the C call: every count and record is written
-        infos = np.full(3, -7, dtype=pc.INFO_DTYPE)
+        for steps in (0, 2):                                      # as uploaded: systems of exactly 63, 64, 65 and 193 bodies
+            if steps:
+                batch.step(steps)
+            assert steps or [batch.download(s).numBodies for s in range(S)] == list(counts)
+            for points in (None, pts):
+                got = batch.pair_counts(e2, points=points, squared=True)
+                assert len(got) == S
+                for s in range(S):
+                    d = batch.download(s)
+                    P, _ = pc.widen(d)
+                    n = d.numBodies
+                    what = "system %d (n %d), %s form" % (s, n, "own" if points is None else "points")
+                    pc.assert_same(got[s], pc.model_pair_counts(P[:n], e2, points), what + ": model")
+                    pc.check_sum(got[s], n * (n - 1) // 2 if points is None else 200 * n, what)
+                    one.upload(d)
+                    pc.assert_same(got[s], one.pair_counts(e2, points=points, squared=True), what + ": Stepper")
+                assert 0 < batch.download(1).numBodies <= 130 and got[0]["counts"].sum() > 0 and got[1]["counts"].sum() > 0
+                empty = got[2]
+                assert (empty["counts"].sum(), empty["below"], empty["rest"], empty["pairs"], empty["n_bodies"]) == (0, 0, 0, 0, 0)
+        raw = np.full((S, 12), 77, dtype=np.uint64)               # the C call: every count and record is written
+        infos = np.full(S, -7, dtype=pc.INFO_DTYPE)
         assert nb.lib.nbody_batch_get_pair_counts(batch._b, pts.ctypes.data, 200, e2.ctypes.data, 12, raw.ctypes.data, infos.ctypes.data) == 0
-        assert np.array_equal(raw, np.stack([g["counts"] for g in got])) and infos["rows"].tolist() == [200, 200, 200]
+        assert np.array_equal(raw, np.stack([g["counts"] for g in got])) and infos["rows"].tolist() == [200] * S
         assert infos["n_bodies"].tolist() == [g["n_bodies"] for g in got] and infos["pairs"].tolist() == [g["pairs"] for g in got]
 
 
