@@ -559,6 +559,67 @@ int nbody_batch_get_pair_counts(struct nbody_batch* b, const nbody_vec2* points,
                                 uint64_t* counts /* [systems * bins] */, nbody_pair_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Tracer particles (the reference has none): massless probes advected with every step.
+ * A tracer has a position and a velocity {x, y, vx, vy}, always fp64 whatever the context's precision.  It behaves like a
+ * body of mass 0 and radius 0 that nothing collides with: it is attracted by the bodies; it attracts nothing and is never a
+ * source; it is never deleted and never compacted - tracer k stays tracer k.
+ * A body step t turns state J_t (n_t bodies) into J_{t+1}.  That step advances every tracer once, from the field of J_t:
+ *     (ax, ay, phi, coincident) = what nbody_get_field returns for the one point (x, y) on the state J_t (same bits: the
+ *                                 running sums over j ascending, the same general-code replacement of a non-finite sum, a
+ *                                 source at distance exactly 0 left out and counted; n_t == 0 gives +0, +0, +0, 0)
+ *     dt  = the context's time step widened to double: (double)(float)desc.timestep for fp32, desc.timestep for fp64; per
+ *           system for a batch
+ *     dvx = dt * ax;  dvy = dt * ay
+ *     with NBODY_TRACER_WALLS only (a body's wall rule with r = 0, its quirk included: the test uses ax * dt, not v):
+ *           tx = x + (ax * dt);  if (tx > hi_x || tx < lo_x) vx = vx * -1.0       hi_x = fieldWidth, lo_x = -fieldWidth
+ *           ty likewise with fieldHeight
+ *     vx = vx + dvx;  vy = vy + dvy
+ *     x  = x + (dt * vx);  y = y + (dt * vy)
+ * Every operation is IEEE fp64 and rounded on its own; there is no fma outside the field sums.  The result for tracer k
+ * depends on J_t, the tracer and the parameters only: not on m, on k, on the semantics or on the force kernel.  Non-finite
+ * inputs may give non-finite outputs; they never disturb another tracer.  Next to the state the library keeps, per tracer,
+ * the {ax, ay, phi} of the most recent advance ("last", +0 until the first) and, per system, the number of advances since
+ * the tracers were set and the sum of `coincident` over those advances.
+ * Stepping: nbody_step and nbody_batch_step advance the tracers inside every step they enqueue, at the cost of one more
+ * launch per step (a batch: one launch for all systems, the same m per system), on the same stream, before the step's
+ * commit overwrites J_t; enqueue-only, no copy and no host wait.  The body count comes from the device; a count outside
+ * [0, capacity] never becomes an index: the system is treated as empty and the failure reported as by every synchronising
+ * call.  nbody_debug_force_only does not advance tracers.  A context or batch that never sets tracers allocates nothing
+ * and launches nothing more.
+ * nbody_tracers_set replaces the tracers by t[0 .. m-1] and zeroes the counters and "last"; m == 0 removes them and frees
+ * their memory.  It may be called before the first upload (stepping still needs one); it waits for the steps enqueued so
+ * far.  nbody_upload and nbody_state_load leave the tracers and their counters as they are.
+ * nbody_tracers_get synchronises, writes min(cap, m) records to out (and to last, unless NULL) and fills *info: steps,
+ * coincident, count = m, flags; out may be NULL with cap == 0.  With no tracers set it gives count = 0 and writes nothing else.
+ * nbody_batch_tracers_set: t holds systems x m records, system s's at t[s * m]; nbody_batch_tracers_get writes system s's m
+ * records at out[s * m] (out NULL: only info, e.g. to learn m) and info[s].  System s has the bits an nbody_ctx with the
+ * same state, parameters and tracers gives; the tracers of an empty system drift only.
+ * NBODY_ERR_INVALID, found before any device call: a NULL handle (or info); NULL t with m > 0; m < 0; unknown flag bits;
+ * m x 32 bytes (a batch: systems x m x 32) above 2^31; cap < 0; NULL out with cap > 0.
+ * NBODY_ERR_STATE: nbody_tracers_set on a context with world > 1, NBODY_FLAG_GROUP_EXCHANGE or NBODY_FLAG_FORCE_COMM: a
+ * rank's replica is a step behind for the other ranks' bodies until the exchange, and an advance against it has not been
+ * built.
+ * Cost (one MI355X, fp32, ms per step under the host clock, every round from a fresh upload; profiles/tracer_probe.txt): the
+ * advance is the walk of nbody_get_field over explicit points and costs what that costs.  N = 262144 with 65536 tracers: the
+ * first step 30.3 -> 43.2, +12.8 (one field call for those points on that state: 13.2; 0.42 of the step, 0.48 expected from
+ * 13.9 against 28.7 above); over 4 steps, while the stock state merges to half its bodies, 16.1 -> 24.0, +7.9.  1048576
+ * tracers: the first step +150.8 (the field call 162.0), over 4 steps +96.6.  A batch of 256 x 1024 with 1024 tracers per
+ * system: 0.234 -> 0.390, +0.157 over 20 steps.  The route this replaces - per step nbody_get_field, an update on the host,
+ * nbody_step(1) - adds 13.9 / 7.2 (M = 65536, first step / 4 steps), 168.9 / 108.9 (M = 1048576) and, with one set of
+ * points for all systems, 1.48 for the batch: its wait per step is what a batch step costs several times over, it is a
+ * tenth of a million tracers' walk, and at M = 65536 it is repaid because the wait tells the host the current body count
+ * for the next step's grids.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_tracer { double x, y, vx, vy; } nbody_tracer;                 /* 32 bytes */
+typedef struct nbody_tracer_info { int64_t steps, coincident; int32_t count; uint32_t flags; } nbody_tracer_info;
+enum { NBODY_TRACER_WALLS = 1u << 0 };
+int nbody_tracers_set(nbody_ctx* ctx, const nbody_tracer* t, int m, uint32_t flags);   /* m == 0 removes and frees */
+int nbody_tracers_get(nbody_ctx* ctx, nbody_tracer* out, nbody_field* last /* may be NULL */, int cap, nbody_tracer_info* info);
+int nbody_batch_tracers_set(struct nbody_batch* b, const nbody_tracer* t /* [systems * m] */, int m, uint32_t flags);
+int nbody_batch_tracers_get(struct nbody_batch* b, nbody_tracer* out /* [systems * m] */, nbody_field* last,
+                            nbody_tracer_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

@@ -23,6 +23,7 @@ FLAG_RECORD_EVENTS = 1
 FLAG_GROUP_EXCHANGE = 2
 FLAG_FORCE_COMM = 4
 FLAG_TRACK_IDS = 8
+TRACER_WALLS = 1
 TRACK_PHI = 1
 COMM_ID_BYTES = 128
 IMAGE_PATH_MAX = 1024
@@ -130,6 +131,10 @@ GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("
 PAIR_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("rows", np.int64), ("pairs", np.int64), ("below", np.int64),
                             ("rest", np.int64)])
 
+# struct nbody_tracer / nbody_tracer_info as numpy records (Stepper.set_tracers / tracers, StepperBatch likewise)
+TRACER_DTYPE = np.dtype([("pos", np.float64, (2,)), ("vel", np.float64, (2,))])
+TRACER_INFO_DTYPE = np.dtype([("steps", np.int64), ("coincident", np.int64), ("count", np.int32), ("flags", np.uint32)])
+
 # struct nbody_track_row, nbody_track_f32 / nbody_track_f64: the planes of the track log (Stepper.tracks, StepperBatch.tracks)
 TRACK_ROW_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64)])
 TRACK_FIELDS = ("x", "y", "vx", "vy", "m", "r")
@@ -196,6 +201,10 @@ SYMBOLS = {
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
     "nbody_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "nbody_tracers_set": (_i, [_vp, _vp, _i, ctypes.c_uint32]),
+    "nbody_tracers_get": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "nbody_batch_tracers_set": (_i, [_vp, _vp, _i, ctypes.c_uint32]),
+    "nbody_batch_tracers_get": (_i, [_vp, _vp, _vp, _vp]),
     "nbody_batch_create": (_i, [_pp, ctypes.POINTER(_BatchDesc), ctypes.POINTER(_BatchParams)]),
     "nbody_batch_destroy": (_i, [_vp]),
     "nbody_batch_upload": (_i, [_vp, _pp, _ip]),
@@ -434,6 +443,35 @@ def _field(call, points, capacity):
     _check(call(None if pts is None else pts.ctypes.data, m, buf.ctypes.data, ctypes.byref(n), ctypes.byref(coin)))
     return {"acc": np.ascontiguousarray(buf["acc"][:n.value]), "phi": np.ascontiguousarray(buf["phi"][:n.value]),
             "coincident": coin.value}
+
+
+def _tracer_records(pos, vel, systems=None):
+    """The tracers of set_tracers() as a TRACER_DTYPE array: pos and vel of shape (m, 2), vel=None meaning zeros; with
+    `systems` (a batch) of shape (systems, m, 2), a (m, 2) input being given to every system.  Checked here, before the
+    library is called."""
+    pos = np.asarray(pos, dtype=np.float64)
+    vel = np.zeros_like(pos) if vel is None else np.asarray(vel, dtype=np.float64)
+    want = "(m, 2)" if systems is None else "(%d, m, 2) or (m, 2)" % systems
+    for name, a in (("pos", pos), ("vel", vel)):
+        ok = a.ndim >= 2 and a.shape[-1] == 2 and (a.ndim == 2 or (systems is not None and a.ndim == 3 and a.shape[0] == systems))
+        if not ok:
+            raise ValueError("%s must have shape %s, got %r" % (name, want, a.shape))
+    if systems is not None:
+        m = pos.shape[-2]
+        pos, vel = (np.broadcast_to(a, (systems, a.shape[-2], 2)) for a in (pos, vel))
+        if vel.shape[1] != m:
+            raise ValueError("pos has %d tracers per system, vel %d" % (m, vel.shape[1]))
+    elif vel.shape != pos.shape:
+        raise ValueError("pos has shape %r, vel %r" % (pos.shape, vel.shape))
+    rec = np.zeros(pos.shape[:-1], dtype=TRACER_DTYPE)
+    rec["pos"], rec["vel"] = pos, vel
+    return rec
+
+
+def _tracer_dict(rec, last, info):
+    return {"pos": np.ascontiguousarray(rec["pos"]), "vel": np.ascontiguousarray(rec["vel"]),
+            "acc": np.ascontiguousarray(last["acc"]), "phi": np.ascontiguousarray(last["phi"]),
+            "steps": info["steps"], "coincident": info["coincident"]}
 
 
 def _neighbors(call, points, capacity):
@@ -689,6 +727,28 @@ class Stepper:
         diagnostics(potential=True)["phi"].  Not collective: any rank of any world may call it on its own."""
         return _field(lambda *a: lib.nbody_get_field(self._ctx, *a), points, self.capacity)
 
+    def set_tracers(self, pos, vel=None, walls=False):
+        """nbody_tracers_set: m massless tracers at `pos` (m, 2) with velocities `vel` (m, 2; None: zeros), fp64 whatever
+        the precision, advanced inside every later step from the field of the state the step starts from.  walls=True:
+        they reflect at the field's walls by the bodies' rule.  Replaces earlier tracers and zeroes their counters."""
+        rec = _tracer_records(pos, vel)
+        _check(lib.nbody_tracers_set(self._ctx, rec.ctypes.data, len(rec), TRACER_WALLS if walls else 0))
+
+    def clear_tracers(self):
+        """Removes the tracers and frees their memory."""
+        _check(lib.nbody_tracers_set(self._ctx, None, 0, 0))
+
+    def tracers(self):
+        """nbody_tracers_get: {"pos": (m, 2), "vel": (m, 2), "acc": (m, 2), "phi": (m,), "steps", "coincident"} - the
+        tracers, the field of their most recent advance, the advances since set_tracers and the sources at distance 0 left
+        out over them.  Synchronises."""
+        info = np.zeros(1, dtype=TRACER_INFO_DTYPE)
+        _check(lib.nbody_tracers_get(self._ctx, None, None, 0, info.ctypes.data))
+        m = int(info["count"][0])
+        rec, last = np.zeros(max(m, 1), dtype=TRACER_DTYPE), np.zeros(max(m, 1), dtype=FIELD_DTYPE)
+        _check(lib.nbody_tracers_get(self._ctx, rec.ctypes.data, last.ctypes.data, m, info.ctypes.data))
+        return _tracer_dict(rec[:m], last[:m], {k: int(info[k][0]) for k in ("steps", "coincident")})
+
     def neighbors(self, points=None):
         """nbody_get_neighbors: for every row - each of `points` (m, 2), or with points=None each current body (self term
         left out) - a record {"d2": squared distance to the nearest current body (fp64; +inf if there is none), "index":
@@ -897,6 +957,28 @@ class StepperBatch:
                                          coin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return {"acc": np.ascontiguousarray(buf["acc"][:, :m]), "phi": np.ascontiguousarray(buf["phi"][:, :m]),
                 "coincident": coin}
+
+    def set_tracers(self, pos, vel=None, walls=False):
+        """nbody_batch_tracers_set: Stepper.set_tracers for every system, the same m each: pos and vel of shape (S, m, 2);
+        a (m, 2) input is given to every system."""
+        rec = _tracer_records(pos, vel, self.systems)
+        _check(lib.nbody_batch_tracers_set(self._b, rec.ctypes.data, rec.shape[1], TRACER_WALLS if walls else 0))
+
+    def clear_tracers(self):
+        """Removes the tracers and frees their memory."""
+        _check(lib.nbody_batch_tracers_set(self._b, None, 0, 0))
+
+    def tracers(self):
+        """nbody_batch_tracers_get: Stepper.tracers with a leading system axis: "pos", "vel", "acc" (S, m, 2), "phi" (S, m),
+        "steps" and "coincident" (S,) int64; system s has the bits a Stepper with its state and tracers gives."""
+        info = np.zeros(max(self.systems, 1), dtype=TRACER_INFO_DTYPE)
+        _check(lib.nbody_batch_tracers_get(self._b, None, None, info.ctypes.data))
+        m = int(info["count"][0])
+        rec = np.zeros((self.systems, max(m, 1)), dtype=TRACER_DTYPE)
+        last = np.zeros((self.systems, max(m, 1)), dtype=FIELD_DTYPE)
+        if m:
+            _check(lib.nbody_batch_tracers_get(self._b, rec.ctypes.data, last.ctypes.data, info.ctypes.data))
+        return _tracer_dict(rec[:, :m], last[:, :m], {k: info[k].copy() for k in ("steps", "coincident")})
 
     def neighbors(self, points=None):
         """nbody_batch_get_neighbors: Stepper.neighbors for every system in one launch, with the one set of points for all

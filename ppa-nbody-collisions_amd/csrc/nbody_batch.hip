@@ -21,6 +21,7 @@
 #include "nbody_batch_diag.hpp"
 #include "nbody_rows.hpp"
 #include "nbody_field.hpp"
+#include "nbody_tracers.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
@@ -84,6 +85,8 @@ struct nbody_batch {
     GroupsState grp;
     // pair-separation counts (nbody_batch_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
     PairsState prs;
+    // tracer particles (nbody_batch_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
+    TracerState trc;
 };
 
 namespace {
@@ -106,6 +109,7 @@ void free_all(nbody_batch* b) {
     rows_free(b->nbr);
     groups_free(b->grp);
     pairs_free(b->prs);
+    tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
     if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
@@ -167,6 +171,11 @@ int enqueue_step(nbody_batch* b) {
         case 2: launch_forces_k<2>(b, nblocks, log); break;
         case 4: launch_forces_k<4>(b, nblocks, log); break;
         default: launch_forces_k<8>(b, nblocks, log); break;
+    }
+    if (b->trc.on()) {                                     // tracers: J still holds step t until the commit
+        const int rc = tracers_enqueue<float, TracersBatch>(b->trc, b->stream, b->S, (const Rec<float>*)b->J, (const Meta*)b->meta,
+                                                            b->counters, b->cap, TracerParams{}, (const StepParams<float>*)b->params);
+        if (rc != NBODY_OK) return rc;
     }
     if (n <= kCommitSmall) launch_commit_b<kCommitSmall>(b, 1);
     else launch_commit_b<kCommitLarge>(b, (n + kCommitLarge - 1) / kCommitLarge);
@@ -764,6 +773,21 @@ int nbody_batch_get_pair_counts(nbody_batch* b, const nbody_vec2* points, int m,
     return batch_rows_run(b, [&](auto t, auto sync) {
         return pairs_run<decltype(t), RowsBatchCount>(who, site, b->prs, points, m, edges2, bins, counts, info, sync);
     });
+}
+
+// Tracers (nbody_tracers.hpp): the same m for every system, one launch per ensemble step.
+int nbody_batch_tracers_set(nbody_batch* b, const nbody_tracer* t, int m, uint32_t flags) {
+    const char* who = "nbody_batch_tracers_set";
+    const int rc = tracers_check_set(who, b, t, m, flags, b ? b->S : 1);
+    if (rc != NBODY_OK) return rc;
+    HIP_TRY(hipSetDevice(b->desc.device));
+    return tracers_set(who, b->trc, b->stream, b->S, t, m, flags);
+}
+
+int nbody_batch_tracers_get(nbody_batch* b, nbody_tracer* out, nbody_field* last, nbody_tracer_info* info) {
+    if (!b || !info) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_tracers_get: NULL argument");
+    HIP_TRY(hipSetDevice(b->desc.device));
+    return tracers_get(b->trc, b->stream, b->S, out, last, out ? b->trc.m : 0, info, [b] { return read_meta(b); });
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 #include "nbody_diag.hpp"
 #include "nbody_rows.hpp"
 #include "nbody_field.hpp"
+#include "nbody_tracers.hpp"
 #include "nbody_ids.hpp"
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
@@ -190,6 +191,8 @@ struct nbody_ctx {
     GroupsState grp;
     // pair-separation counts (nbody_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
     PairsState prs;
+    // tracer particles (nbody_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
+    TracerState trc;
 };
 
 namespace {
@@ -554,6 +557,14 @@ int compute_phase(nbody_ctx* c) {
     if (rc != NBODY_OK || !c->ids.on()) return rc;
     return ids_step(c);
 }
+// Tracers (nbody_tracers.hpp): after the compute phase and before the commit, where J still holds step t.
+int tracer_phase(nbody_ctx* c) {
+    if (c->desc.precision == NBODY_F64)
+        return tracers_enqueue<double, TracersOne>(c->trc, c->stream, 1, (const Rec<double>*)c->J, (const Meta*)c->meta, c->counters,
+                                                   c->cap, tracer_params(make_params<double>(c->desc)), nullptr);
+    return tracers_enqueue<float, TracersOne>(c->trc, c->stream, 1, (const Rec<float>*)c->J, (const Meta*)c->meta, c->counters, c->cap,
+                                              tracer_params(make_params<float>(c->desc)), nullptr);
+}
 int commit_phase(nbody_ctx* c) {
     int rc = c->desc.precision == NBODY_F64 ? launch_commit<double>(c) : launch_commit<float>(c);
     if (rc != NBODY_OK) return rc;
@@ -589,6 +600,7 @@ void free_all(nbody_ctx* c) {
     rows_free(c->nbr);
     groups_free(c->grp);
     pairs_free(c->prs);
+    tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
     if (c->h_meta_async) hipHostFree(c->h_meta_async);
@@ -1084,6 +1096,7 @@ int nbody_step(nbody_ctx* c, int nsteps) {
     for (int s = 0; s < nsteps; ++s) {
         int rc = compute_phase(c);
         if (rc != NBODY_OK) return rc;
+        if (c->trc.on() && (rc = tracer_phase(c)) != NBODY_OK) return rc;
         rc = do_exchange(c);
         if (rc != NBODY_OK) return rc;
         rc = commit_phase(c);
@@ -1716,6 +1729,29 @@ int nbody_get_pair_counts(nbody_ctx* c, const nbody_vec2* points, int m, const d
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return pairs_run<decltype(t), RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync);
     });
+}
+
+// Tracers (nbody_tracers.hpp).  A context of more than one rank is refused: inside a group step a rank's replica is a step
+// behind for the other ranks' bodies until the exchange.
+int nbody_tracers_set(nbody_ctx* c, const nbody_tracer* t, int m, uint32_t flags) {
+    const char* who = "nbody_tracers_set";
+    const int rc = tracers_check_set(who, c, t, m, flags, 1);
+    if (rc != NBODY_OK) return rc;
+    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
+        return nbody_fail(NBODY_ERR_STATE, "%s: tracers need a single-rank context without an exchange (world %d, flags 0x%x): "
+                                           "an advance against a rank's lagging replica is not built", who, c->desc.world,
+                          c->desc.flags);
+    HIP_TRY(hipSetDevice(c->desc.device));
+    return tracers_set(who, c->trc, c->stream, 1, t, m, flags);
+}
+
+int nbody_tracers_get(nbody_ctx* c, nbody_tracer* out, nbody_field* last, int cap, nbody_tracer_info* info) {
+    const char* who = "nbody_tracers_get";
+    if (!c || !info) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
+    if (cap < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: cap = %d", who, cap);
+    if (!out && cap > 0) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL out with cap = %d", who, cap);
+    HIP_TRY(hipSetDevice(c->desc.device));
+    return tracers_get(c->trc, c->stream, 1, out, last, cap < c->trc.m ? cap : c->trc.m, info, [c] { return nbody_sync(c); });
 }
 
 }  // extern "C"

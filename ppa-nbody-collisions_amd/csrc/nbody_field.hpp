@@ -24,7 +24,8 @@
 // underflows gradually instead of being flagged (below it, it overflows and the sum is redone).
 //
 // field_at: kOwn leaves the self term out by index through diag_walk's checked self tile.  The result record carries the
-// point's coincident count; the host adds them up.
+// point's coincident count; the host adds them up.  What follows the walk is field_finish, which the tracers' advance
+// (tracers_advance, nbody_tracers.hpp) calls after the same walk: a tracer's field has the bits of a probe point's.
 #pragma once
 #include <float.h>
 #include <stddef.h>
@@ -76,6 +77,24 @@ __device__ __forceinline__ FieldAcc field_acc_general(const Rec<T>* __restrict__
     return FieldAcc{ax, ay};
 }
 
+// What follows the walk for a point that has a row, field_at's and tracers_advance's (nbody_tracers.hpp): the finite tests,
+// the general code for the sums that failed them, and the products with G.  n > 0.  The sums are repaired in place, through
+// the reference: handed over by value, field_at's replacement compiled to other code than it had.
+template <typename T>
+__device__ __forceinline__ FieldOut field_finish(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi, FieldSums& a,
+                                                 double G) {
+    long long coin = 0;
+    if (!(__builtin_isfinite(a.s) && __builtin_isfinite(a.ax) && __builtin_isfinite(a.ay))) {
+        const DiagRow g = diag_row_general<T>(J, n, i, xi, yi);                  // the potential's, and the count
+        const FieldAcc ga = field_acc_general<T>(J, n, i, xi, yi);
+        coin = g.coincident;
+        if (!__builtin_isfinite(a.s)) a.s = g.s;
+        if (!__builtin_isfinite(a.ax)) a.ax = ga.ax;
+        if (!__builtin_isfinite(a.ay)) a.ay = ga.ay;
+    }
+    return FieldOut{G * a.ax, G * a.ay, -G * a.s, coin};
+}
+
 // grid and early exits: rows_prologue (nbody_rows.hpp).  An empty system gives +0 in every field.
 template <typename T, bool kOwn, typename Count>
 __global__ __launch_bounds__(kDiagBlock) void field_at(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
@@ -100,16 +119,7 @@ __global__ __launch_bounds__(kDiagBlock) void field_at(const Rec<T>* __restrict_
     FieldSums a;
     diag_walk_sums<false, kOwn, T>(J, n, kOwn ? p : -1, xi, yi, L.self_tile, L.wave_works, a, sx, sy, sm);
     if (!L.valid) return;
-    long long coin = 0;
-    if (!(__builtin_isfinite(a.s) && __builtin_isfinite(a.ax) && __builtin_isfinite(a.ay))) {
-        const DiagRow g = diag_row_general<T>(J, n, kOwn ? p : -1, xi, yi);      // the potential's, and the count
-        const FieldAcc ga = field_acc_general<T>(J, n, kOwn ? p : -1, xi, yi);
-        coin = g.coincident;
-        if (!__builtin_isfinite(a.s)) a.s = g.s;
-        if (!__builtin_isfinite(a.ax)) a.ax = ga.ax;
-        if (!__builtin_isfinite(a.ay)) a.ay = ga.ay;
-    }
-    L.out[p] = FieldOut{G * a.ax, G * a.ay, -G * a.s, coin};
+    L.out[p] = field_finish<T>(J, n, kOwn ? p : -1, xi, yi, a, G);
 }
 
 // The query's traits for rows_run (nbody_rows.hpp): the caller gets 24-byte records and, per system, the sum of their
