@@ -285,7 +285,8 @@ int read_meta(nbody_ctx* c) {
 // kernel_variant: 0 automatic | 1 v1 (one body per lane, compiler IEEE sqrt/div) |
 //                 11,12,14,18 v3 with K = 1,2,4,8 lanes per body, 128-thread workgroups |
 //                 31,32 v3 K = 1 with 256-thread workgroups, registers sized for 4 / 2 waves per SIMD |
-//                 50,52,54 ring of waves with 2x8, 4x4, 1x8 (rings x waves) per workgroup; 53,55,56,58,59 its tuning forms
+//                 50,52,54 ring of waves with 2x8, 4x4, 1x8 (rings x waves) per workgroup; 53,55,56,58,59 its tuning forms |
+//                 60-63 the persistent 4x4 form | 70 solo waves, one-shot; 71 persistent; 72 with one-tile items
 // Where a force launch goes: the context's own stream and velocities, or - the reference-shaped launch through the
 // workspace context - the caller's stream and the velocities where they lie in the caller's block.
 struct LaunchTarget {
@@ -336,8 +337,10 @@ void launch_v3w(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log,
 }
 
 // seg_tiles > 0: the persistent form (kQueue) with the walks of the last `cut` rings in segments of seg_tiles tiles.
+// kW = 1 is the solo form (a ring is one wave); its persistent form cuts EVERY walk: lead_tiles tiles, then such segments.
 template <int kW, int kT, int kSleep, bool kProbe, int kRings, bool kQueue = false>
-void launch_ring(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to, int cut = 0, int seg_tiles = 0) {
+void launch_ring(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to, int cut = 0, int seg_tiles = 0,
+                 int lead_tiles = 0) {
     const int rings = nblocks * 2;                         // rings of 64 bodies, two per reference block
     int grid = (rings + kRings - 1) / kRings;              // a workgroup serves kRings rings
     RingArgs a{};
@@ -347,6 +350,7 @@ void launch_ring(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log
         if (c->q_launches == 0) c->q_launches = 1;
         a.q_head = c->q_head; a.q_done = c->q_done; a.q_state = c->q_state; a.q_launch = c->q_launches;
         a.q_rings = rings; a.q_whole = rings - (cut < rings ? cut : rings); a.q_seg_tiles = seg_tiles > 0 ? seg_tiles : 1;
+        if (kW == 1) a.q_whole = lead_tiles > 0 ? lead_tiles : 1;
     }
     a.Vown = (const Vec2<float>*)to.vown; a.S_J = (Rec<float>*)c->S_J; a.S_V = (Vec2<float>*)c->S_V;
     a.meta = c->meta; a.p = p; a.ev = c->events; a.ev_cap = c->ev_cap; a.ctr = c->counters;
@@ -380,6 +384,20 @@ bool launch_ring_queue(nbody_ctx* c, const StepParams<float>& p, int nblocks, bo
     launch_ring<4, 32, 8, kProbe, 4, true>(c, p, nblocks, log, to, slots, (tiles + kQueueSegments - 1) / kQueueSegments);
     return true;
 }
+// The SOLO form: one wave per 64 bodies takes every turn of its walk - no hand-off, no poll -, 16 such waves per workgroup.
+// Its persistent form cuts EVERY walk - all walks start together and last the whole launch -: the last eighth of the tiles
+// in 32 segments was the best cut measured (profiles/ring_solo.txt).
+// Selected where the own range is EXACTLY one wave per wave slot of the device (16 per CU: 262144 bodies on 256 CUs) and the
+// event log is off: there the ring's parallelism buys nothing, and the solo form measured 0.9 to 1.2 % faster than the
+// persistent 4 x 4 form in three visits and equal in a fourth.  With fewer walks slots stay empty; with more, the
+// walks of the second round would run on a chip that is mostly idle - the 4 x 4 form, whose rings need a quarter of the
+// bodies to fill a slot, levels those.
+bool ring_solo_applies(const nbody_ctx* c, bool log, int nblocks) {
+    return !log && nblocks * 2 == 16 * c->num_cus && nblocks * 2 <= c->q_rings_cap;
+}
+// The solo launches are DEFINED at the end of this file: their kernels are then instantiated last and the code object keeps
+// every other kernel where it was (form 70 one-shot, 71 persistent with the cut above, 72 persistent with one-tile items).
+void launch_ring_solo(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to, int form);
 template <>
 void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to) {
     switch (c->desc.kernel_variant) {
@@ -405,10 +423,12 @@ void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks,
         case 61: launch_ring<4, 32, 8, false, 4, true>(c, p, nblocks, log, to, nblocks * 2, 1); return;   // ... every walk in segments of 1 tile
         case 62: launch_ring<4, 32, 8, false, 4, true>(c, p, nblocks, log, to, nblocks * 2, 3); return;   // ... of 3 tiles
         case 63: if (launch_ring_queue<true>(c, p, nblocks, log, to)) return; break;   // tuning: stamps of the persistent form
+        case 70: case 71: case 72: launch_ring_solo(c, p, nblocks, log, to, c->desc.kernel_variant); return;   // the solo form
         default: break;
     }
     // default: chosen by how many bodies this rank owns, i.e. how many ordered chains there are to fill the chip with
     // (measured on MI355X with csrc/tune/ring_probe.py, profiles/r02_ring_*):
+    //   one wave per wave slot, exactly, and no event log: the solo form (ring_solo_applies)
     //   >= 48k bodies : ring kernel, workgroups of 4 rings x 4 waves (256 bodies): 32.2 ms at 262144 own bodies
     //                   (one lane per body: 33.6), 16.6 / 8.4 ms at 131072 / 65536 (18.5 / 10.2); from two rounds of rings
     //                   on (131072 own bodies on 256 CUs) in its persistent form (launch_ring_queue)
@@ -419,7 +439,8 @@ void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks,
     // Poll interval of the hand-off wait: s_sleep 8 (512 cycles) where the launch is bound by evaluation - a poll takes
     // issue slots from the waves that evaluate: -0.5 ... -1 % against s_sleep 2 -, s_sleep 2 for the small launches, which
     // are bound by the chain (N = 16384: 0.185 ms; with s_sleep 8: 0.218).
-    if (c->own_upper >= 49152) {
+    if (ring_solo_applies(c, log, nblocks)) launch_ring_solo(c, p, nblocks, log, to, 71);
+    else if (c->own_upper >= 49152) {
         if (!launch_ring_queue<false>(c, p, nblocks, log, to)) launch_ring<4, 32, 8, false, 4>(c, p, nblocks, log, to);
     } else if (c->own_upper >= 24576) launch_ring<8, 32, 8, false, 2>(c, p, nblocks, log, to);
     else launch_ring<8, 32, 2, false, 1>(c, p, nblocks, log, to);
@@ -1442,8 +1463,12 @@ const char* nbody_force_kernel_name(nbody_ctx* c) {
             break;
         case 53: return "forces_ring_f32 (2 rings x 8 waves, 16-position turns)";
         case 54: return "forces_ring_f32 (1 ring x 8 waves per workgroup)";
+        case 70: return "forces_ring_f32 (16 solo waves per workgroup)";
+        case 71: case 72: return "forces_ring_f32 (16 solo waves per workgroup, persistent)";
         default: break;
     }
+    if (ring_solo_applies(c, (c->desc.flags & NBODY_FLAG_RECORD_EVENTS) != 0, c->own_upper / kTile > 0 ? c->own_upper / kTile : 1))
+        return "forces_ring_f32 (16 solo waves per workgroup, persistent)";
     if (c->own_upper >= 49152)
         return ring_queue_slots(c, c->own_upper / kTile) != 0 ? "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)"
                                                               : "forces_ring_f32 (4 rings x 4 waves per workgroup)";
@@ -1755,3 +1780,12 @@ int nbody_tracers_get(nbody_ctx* c, nbody_tracer* out, nbody_field* last, int ca
 }
 
 }  // extern "C"
+
+namespace {
+void launch_ring_solo(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to, int form) {
+    const int tiles = c->n_upper / kTile > 0 ? c->n_upper / kTile : 1;
+    if (form == 70) launch_ring<1, 32, 8, false, 16>(c, p, nblocks, log, to);
+    else if (form == 72) launch_ring<1, 32, 8, false, 16, true>(c, p, nblocks, log, to, 0, 1, 1);
+    else launch_ring<1, 32, 8, false, 16, true>(c, p, nblocks, log, to, 0, tiles / 256 > 0 ? tiles / 256 : 1, tiles - tiles / 8);
+}
+}  // namespace

@@ -759,6 +759,12 @@ __device__ __forceinline__ double dpp_row_shl(double v) {   // K > 1 is fp32 onl
 // then segments of the last round's walks - from a device counter, so that a CU that is ahead takes work over from one that is
 // behind.  A walk that changes slots travels as its two LDS records per lane through global memory.  The turn loop is the
 // one-shot form's; everything else is described where the item loop starts.
+// kW = 1 (16 "rings" per workgroup): the SOLO form, forced variants only.  One wave per 64 bodies takes EVERY turn of its walk:
+// the running sums and `deleted` stay in registers from turn to turn (the rare record stays in LDS), there is no poll, no
+// sequence number, no time-out path in the turn loop; the quarter of the tile a turn's window starts at, a per-wave constant
+// of the other forms, is a scalar that cycles through four values.  What it needs instead of the hand-off is the look that
+// keeps the four waves of a SIMD level (where solo_h is declared).  Its persistent form (kQueue) cuts every walk into a
+// leading item and tail segments and hands them over through the same queue, state and done words.
 // ---------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* LdsPtr;
 typedef int Int4 __attribute__((ext_vector_type(4)));
@@ -819,7 +825,8 @@ struct RingArgs {
     unsigned long long* q_state; // per ring: the two LDS records of its 64 lanes between segments, [ring][4][64] x 8 bytes
     unsigned q_launch;           // number of this force launch on the context, never 0: done words need no clearing
     int q_rings;                 // rings of the launch
-    int q_whole;                 // the first q_whole rings are one item each ...
+    int q_whole;                 // the first q_whole rings are one item each ... (solo form: EVERY walk is one leading item
+                                 // of q_whole TILES, >= 1, and then such segments; the struct stays its size)
     int q_seg_tiles;             // ... the walks of the others are cut into segments of this many tiles
 };
 typedef __attribute__((address_space(1))) unsigned* GlobalU32Ptr;
@@ -850,19 +857,21 @@ void forces_ring_f32(const RingArgs args) {
     typedef Pair<float>::type V2;
     static_assert(kTile % kT == 0 && kT % 8 == 0 && kT <= kWave, "turn length");
     constexpr int kTurnsPerTile = kTile / kT;
-    static_assert(kW % kTurnsPerTile == 0, "a wave's successive turns are whole tiles apart");
+    constexpr bool kSolo = kW == 1;                        // the SOLO form: one wave per 64 bodies takes every turn of its walk
+    static_assert(kSolo || kW % kTurnsPerTile == 0, "a wave's successive turns are whole tiles apart");
     constexpr int kTilesPerRound = kW / kTurnsPerTile;
     constexpr int kWin = kWave + kT;                       // window entries a turn can touch (kWin - 1 used)
-    static_assert(kRings == 1 || kRings == 2 || kRings == 4, "rings (64 bodies each) per workgroup");
-    static_assert(!kQueue || kW == kTurnsPerTile, "persistent form: an item is whole tiles and a wave keeps its part of every tile");
+    static_assert(kSolo ? kRings == 16 && !kProbe : kRings == 1 || kRings == 2 || kRings == 4, "rings (64 bodies each) per workgroup");
+    static_assert(!kQueue || kSolo || kW == kTurnsPerTile, "persistent form: an item is whole tiles and a wave keeps its part of every tile");
     // Per wave, double buffered, COMPONENT-MAJOR: x[kWin] y[kWin] m[kWin] r[kWin].  A lane's walk positions r, r + 1 are
     // then two consecutive words of each component: one ds_read2_b32 fills the register pair a packed fp32 instruction
     // takes, so two walk positions share EVERY instruction of the term (with records in LDS the differences and squares
     // were packed per position: one more instruction per pair, plus moves that paired the mass with its operand).
     __shared__ float win_all[kRings][kW][2][4][kWin];
-    __shared__ Int4 hand_all[kRings][kWave];               // {fx, fy, seq, flags = deleted} per lane
+    __shared__ Int4 hand_all[kSolo ? 1 : kRings][kWave];   // {fx, fy, seq, flags = deleted} per lane (solo form: in registers)
     __shared__ Float4 hand_m_all[kRings][kWave];           // {mnew, rnew, mi, -}: rewritten only when mnew / rnew change
-    __shared__ long long item_all[kQueue ? kRings : 1][2]; // persistent form: {claims of this slot so far << 32 | item}, twice
+    __shared__ int solo_done_all[kSolo ? kRings : 1];      // solo form: turns each wave of the workgroup has taken (see the look)
+    __shared__ long long item_all[kQueue && !kSolo ? kRings : 1][2]; // persistent form: {claims of this slot so far << 32 | item}, twice
     const int N = meta->n, lo = meta->lo, cnt = meta->cnt;
     const bool all_bounded = (meta->summary & kSummaryUnbounded) == 0, any_radius = (meta->summary & kSummaryRadius) != 0;
     // every coordinate of the replica in [2^-16, 2^38), every radius +0, every mass finite: coincident bodies are the only
@@ -876,7 +885,7 @@ void forces_ring_f32(const RingArgs args) {
     const int wg = blockIdx.x;
     const int slot = wg * kRings + ring;                   // ring slot of the launch
     float(&win)[kW][2][4][kWin] = win_all[ring];
-    Int4(&hand)[kWave] = hand_all[ring];
+    Int4(&hand)[kWave] = hand_all[kSolo ? 0 : ring];
     Float4(&hand_m)[kWave] = hand_m_all[ring];
     const int nb = N < kTile ? 1 : N / kTile;              // src/nbody.cu:473
     const bool lit = args.p.literal != 0;
@@ -898,7 +907,18 @@ void forces_ring_f32(const RingArgs args) {
     // priority rule are the ones of the one-shot form.
     int seq_base = 0;                                      // sequence number of the current item's first turn
     int claims = 0;                                        // items this slot has drawn
-    if (kQueue) {
+    Int4 solo_h = Int4{0, 0, 0, 0};                        // solo form: the hand-off record, in registers from turn to turn
+    // SOLO FORM, the look.  The 16 waves of a workgroup are four per SIMD, and the arbiter serves the OLDER wave first at
+    // equal priority (lesson (b) above): left alone the oldest wave of a SIMD runs at full speed, the youngest on what is
+    // left, the walks end far apart and the last ones run alone on their SIMD, where nothing hides a wave's own latencies
+    // (measured without the look: 32.5 ms against the persistent ring's 28.2 at N = 262144; with it 27.7,
+    // profiles/ring_solo.txt).  So every wave posts the turns it has taken, lane l looks at wave l % 16 of the workgroup,
+    // and a wave that is behind any other evaluates at priority 1.  A wave that has left posts 0: nobody is behind it.
+    // The look steers priority only, never a result.
+    typedef volatile __attribute__((address_space(3))) int* LdsIntPtr;
+    int solo_done = 0;
+    if (kSolo) *(LdsIntPtr)&solo_done_all[wv] = 0;
+    if (kQueue && !kSolo) {
         if (w == 0) {
             *(LdsInt4Ptr)&hand[l] = Int4{0, 0, 0, 0};
             if (l < 2) *(LdsI64Ptr)&item_all[ring][l] = 0ll;
@@ -932,15 +952,32 @@ void forces_ring_f32(const RingArgs args) {
                 const long long first = (long long)(lo / kTile + ring_g / 2) * kTile + (ring_g % 2) * kWave;
                 return first >= (long long)lo + cnt ? 1 : 2;
             };
+            // SOLO FORM: every walk is cut the same way - one leading item (segment 0) whose tile count travels in q_whole,
+            // then segments of seg_tiles tiles - and item k is (segment k / rings, ring k % rings): again every ring's
+            // segment s is drawn before anybody's segment s + 1.  A slot is one wave; it draws for itself and shares nothing
+            // with its workgroup.
+            auto decode_solo = [&](int k) -> int {         // (a lambda of its own: decode stays the code it was)
+                const int rings = q_whole + q_cut;                 // (q_rings)
+                const int lead = q_whole < ntiles ? q_whole : ntiles;
+                const int solo_nseg = 1 + (ntiles - lead + seg_tiles - 1) / seg_tiles;
+                if ((long long)k >= (long long)rings * solo_nseg) return 0;
+                seg = k / rings;
+                ring_g = k - seg * rings;
+                tau_lo = seg == 0 ? 0 : (lead + (seg - 1) * seg_tiles) * kTurnsPerTile;
+                tau_hi = seg == 0 ? lead * kTurnsPerTile : tau_lo + seg_tiles * kTurnsPerTile;
+                tau_hi = tau_hi < nturns ? tau_hi : nturns;
+                const long long first = (long long)(lo / kTile + ring_g / 2) * kTile + (ring_g % 2) * kWave;
+                return first >= (long long)lo + cnt ? 1 : 2;
+            };
             int k = 0x7fffffff, what = 0;
             if (w == 0) {
                 do {
                     unsigned drawn = 0;
                     if (l == 0) drawn = __hip_atomic_fetch_add((GlobalU32Ptr)NB_RING_LATE(q_head), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     k = __builtin_amdgcn_readfirstlane((int)(drawn < 0x7fffffffu ? drawn : 0x7fffffffu));
-                    what = decode(k);
+                    what = kSolo ? decode_solo(k) : decode(k);
                 } while (what == 1);
-                if (l == 0) *entry = ((long long)claims << 32) | (long long)k;
+                if (!kSolo && l == 0) *entry = ((long long)claims << 32) | (long long)k;
             } else {
                 for (int spins = 0;;) {
                     const long long e = *entry;
@@ -984,11 +1021,11 @@ void forces_ring_f32(const RingArgs args) {
             asm volatile("" : "+v"(xi), "+v"(yi), "+v"(mi), "+v"(ri));
             if (kQueue) {
                 if (w == 0) {                                  // the chain's state at the item's first turn, sequence number seq_base
-                    Int4 h0 = Int4{0, 0, seq_base, 0};
+                    Int4 h0 = Int4{0, 0, kSolo ? 0 : seq_base, 0};
                     Float4 m0 = Float4{mi, ri, mi, 0.0f};
                     bool late = false;
                     // the records are free: the slot's previous item has been read back (its closing turn, see the epilogue)
-                    for (int spins = 0;;) {
+                    for (int spins = 0; !kSolo;) {
                         const Int4 h = *(LdsInt4Ptr)&hand[l];
                         if (__ballot(h.z < seq_base) == 0ull) break;
                         if (++spins > q_spin_limit) { late = true; break; }
@@ -1010,19 +1047,22 @@ void forces_ring_f32(const RingArgs args) {
                         const unsigned long long s2 = __hip_atomic_load(rs + 2 * kWave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         const unsigned long long s3 = __hip_atomic_load(rs + 3 * kWave, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         h0 = Int4{(int)(unsigned)s0, (int)(unsigned)(s0 >> 32),
-                                  (int)(unsigned)s1 >= kRingDeadSeq ? kRingDeadSeq : seq_base, (int)(unsigned)(s1 >> 32)};
+                                  (int)(unsigned)s1 >= kRingDeadSeq ? kRingDeadSeq : kSolo ? 0 : seq_base, (int)(unsigned)(s1 >> 32)};
                         m0 = Float4{__uint_as_float((unsigned)s2), __uint_as_float((unsigned)(s2 >> 32)), __uint_as_float((unsigned)s3), 0.0f};
                     }
                     if (late) { timeouts += 1; dead = true; }  // reported and poisoned like a hand-off wait that gave up
+                    if (kSolo && __ballot(h0.z >= kRingDeadSeq) != 0ull) dead = true;   // (the ring forms see it in the turn's check)
                     if (dead) {
                         h0 = Int4{(int)0x7fc00000, (int)0x7fc00000, kRingDeadSeq, 0};
                         m0.x = m0.y = __builtin_nanf("");
                     }
                     *(LdsFloat4Ptr)&hand_m[l] = m0;
-                    *(LdsInt4Ptr)&hand[l] = h0;
+                    if (kSolo) solo_h = h0;
+                    else *(LdsInt4Ptr)&hand[l] = h0;
                 }
             } else if (w == 0) {
-                *(LdsInt4Ptr)&hand[l] = Int4{0, 0, 0, 0};
+                if (kSolo) solo_h = Int4{0, 0, 0, 0};
+                else *(LdsInt4Ptr)&hand[l] = Int4{0, 0, 0, 0};
                 *(LdsFloat4Ptr)&hand_m[l] = Float4{mi, ri, mi, 0.0f};            // mnew = mi, rnew = ri (:174-175)
             }
         }
@@ -1033,7 +1073,7 @@ void forces_ring_f32(const RingArgs args) {
         const LdsInt4Ptr hand_l = (LdsInt4Ptr)&hand[l];
         const LdsFloat4Ptr hand_m_l = (LdsFloat4Ptr)&hand_m[l];
         if (!kQueue) {
-            __syncthreads();                                   // the only workgroup barrier: seq = 0 everywhere
+            if (!kSolo) __syncthreads();                       // the only workgroup barrier: seq = 0 everywhere
             if (blk0 + t0 >= (long long)lo + cnt) return;      // a ring without own bodies (after the barrier)
         }
         // Two rings share a CU's SIMDs (two per workgroup here, or two workgroups per CU), and the instruction arbiter
@@ -1052,7 +1092,7 @@ void forces_ring_f32(const RingArgs args) {
         typedef const volatile __attribute__((address_space(3))) int* LdsSeqPtr;
         auto seq_of_ring_of = [&](int lane) -> LdsSeqPtr { return (LdsSeqPtr)&hand_all[lane % kRings][0] + 2; };
         LdsSeqPtr seq_look_kept = seq_of_ring_of(kLog ? 0 : l);
-        if (!kLog && kRings > 1) asm volatile("" : "+v"(seq_look_kept));
+        if (!kLog && !kSolo && kRings > 1) asm volatile("" : "+v"(seq_look_kept));
         auto any_ring_ahead = [&]() -> bool {
             if (kLog) {                                        // as before: one uniform address per ring
                 int ahead = *seq_of_ring_of(ring + 1);
@@ -1087,6 +1127,11 @@ void forces_ring_f32(const RingArgs args) {
         auto round_on = [&](Idx st) -> Idx {
             st += kTilesPerRound * kTile;
             if (lit) while (st >= Nu) st -= Nu;                // a next turn exists only when N > kTilesPerRound tiles: once
+            return st;
+        };
+        auto tile_on = [&](Idx st) -> Idx {                    // solo form: the walk's next tile
+            st += kTile;
+            if (lit) while (st >= Nu) st -= Nu;
             return st;
         };
         auto tile_len = [&](int kk, Idx st) -> int {
@@ -1153,12 +1198,15 @@ void forces_ring_f32(const RingArgs args) {
             load_to_lds_b32(src + 2 * plane, byte_offset, base + 2 * comp_bytes);
             if (any_radius) load_to_lds_b32(src + 3 * plane, byte_offset, base + 3 * comp_bytes);
         };
-        auto issue_window = [&](Idx st, int buf) {
+        // solo form: the wave takes all four quarters of a tile in turn, so the window's first tile entry moves on by kT per
+        // turn: a scalar byte offset added to the kept per-lane constant, wrapped at the tile (2 vector instructions per turn)
+        auto solo_quarter = [&](int tau) -> unsigned { return (unsigned)(tau % kTurnsPerTile) * (kT * (unsigned)sizeof(T)); };
+        auto issue_window = [&](Idx st, int buf, unsigned quarter_bytes) {
             const unsigned base = __builtin_amdgcn_readfirstlane(lds_offset_of(&win[w][buf][0][0]));
             if (kLog) {                                        // as before: entries, not bytes; 64-bit compare
                 int lane = l;
                 asm volatile("" : "+v"(lane));
-                const unsigned e0 = (unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane) & (kTile - 1);
+                const unsigned e0 = (unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane + (kSolo ? quarter_bytes / (unsigned)sizeof(T) : 0u)) & (kTile - 1);
                 const unsigned e1 = e0 ^ kWave;
                 if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= Nu) {
                     const unsigned tile_byte = ((unsigned)st / kTile) * (4u * kTile * (unsigned)sizeof(T));
@@ -1170,7 +1218,7 @@ void forces_ring_f32(const RingArgs args) {
                 }
                 return;
             }
-            const unsigned entry0_bytes = entry0_kept;
+            const unsigned entry0_bytes = kSolo ? (entry0_kept + quarter_bytes) & (kTile * (unsigned)sizeof(T) - 1u) : entry0_kept;
             const unsigned entry1_bytes = entry0_bytes ^ (kWave * (unsigned)sizeof(T));   // the entry 64 further on
             if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= Nu) {
                 // the common case - the window's tile is an aligned tile of Jt -: the tile goes into the scalar base address,
@@ -1289,7 +1337,7 @@ void forces_ring_f32(const RingArgs args) {
         int plain_turns = 0;                                   // turns of this wave that took the common path
         bool first_plain = false;                              // ... the first turn of the walk among them (one pair less)
         int kind = turn_kind(tau0, st);
-        if (kind == 1) issue_window(st, buf);
+        if (kind == 1) issue_window(st, buf, solo_quarter(tau0));
         if (kind == 2) issue_truncated(st, tile_len(tau0 / kTurnsPerTile, st));
         WindowState cur = check_window(kind, tau0 / kTurnsPerTile, buf, st);
         for (int tau = tau0; tau < tau_hi; tau += kW) {
@@ -1299,11 +1347,18 @@ void forces_ring_f32(const RingArgs args) {
             const int off0 = (tau % kTurnsPerTile) * kT;
             const int L = tile_len(kk, st);
             const bool fast = cur.fast;
-            const Idx st_next = round_on(st);
+            const Idx st_next = kSolo ? ((tau + 1) % kTurnsPerTile == 0 ? tile_on(st) : st) : round_on(st);
             const int kind_next = turn_kind(tau + kW, st_next);
-            if (kind_next == 1) issue_window(st_next, buf ^ 1);                  // in flight for the whole turn
+            if (kind_next == 1) issue_window(st_next, buf ^ 1, solo_quarter(tau + kW));   // in flight for the whole turn
             const bool first = lit && tau == 0;                // walk position 0 is the body itself (:200-204)
-            if (kRings > 1) {                                  // behind the furthest ring of the workgroup: evaluate first
+            if (kSolo) {
+                solo_done += 1;
+                *(LdsIntPtr)&solo_done_all[wv] = solo_done;
+                const int theirs = *(LdsIntPtr)&solo_done_all[l % kRings];
+                if (__ballot(solo_done < theirs) != 0ull) __builtin_amdgcn_s_setprio(1);
+                else __builtin_amdgcn_s_setprio(0);
+            }
+            if (!kSolo && kRings > 1) {                        // behind the furthest ring of the workgroup: evaluate first
                 if (any_ring_ahead()) __builtin_amdgcn_s_setprio(1);
                 else __builtin_amdgcn_s_setprio(0);
             }
@@ -1375,9 +1430,10 @@ void forces_ring_f32(const RingArgs args) {
             // within one LDS round trip of the record being written.
             Int4 h = Int4{0, 0, 0, 0};
             bool timed_out = false;
-            __builtin_amdgcn_s_setprio(3);
-            const int sq = tau + dseq;
-            if (kQueue || tau > 0) {
+            if (!kSolo) __builtin_amdgcn_s_setprio(3);
+            const int sq = kSolo ? 0 : tau + dseq;             // (solo form: no sequence numbers, the state is the wave's own)
+            if (kSolo) h = solo_h;
+            if (!kSolo && (kQueue || tau > 0)) {
                 int spins = 0;
                 for (;;) {
                     h = *hand_l;                               // one ds_read_b128
@@ -1393,7 +1449,7 @@ void forces_ring_f32(const RingArgs args) {
             // (x and y chains interleaved: scalar adds need no wait states between dependent instructions, packed ones
             // do), then one LDS write; `flags` passes through untouched.  The last turn publishes too: the epilogue takes the
             // final state from the records.
-            bool plain = fast && flag == 0ull && !dead && !timed_out && __ballot(h.z != sq) == 0ull;
+            bool plain = fast && flag == 0ull && !dead && !timed_out && (kSolo || __ballot(h.z != sq) == 0ull);
             if (__builtin_expect(plain, 1)) {
                 float fx = __int_as_float(h.x), fy = __int_as_float(h.y);
     #pragma unroll
@@ -1407,8 +1463,9 @@ void forces_ring_f32(const RingArgs args) {
                 // flagged in every turn (slow, and right: its collisions still have to be found).
                 if (nan_screen) flag = __builtin_amdgcn_fcmpf(fx, fy, 8 /* llvm::CmpInst::FCMP_UNO */);
                 if (__builtin_expect(flag == 0ull, 1)) {
-                    *hand_l = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), sq + 1, h.w};
-                    __builtin_amdgcn_s_setprio(0);
+                    if (kSolo) solo_h = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), 0, h.w};
+                    else *hand_l = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), sq + 1, h.w};
+                    if (!kSolo) __builtin_amdgcn_s_setprio(0);
                     plain_turns += 1;                          // a scalar: kT pairs per active lane, added up at the end
                     first_plain = first_plain || first;
                 } else {
@@ -1521,9 +1578,10 @@ void forces_ring_f32(const RingArgs args) {
                 // publish: the rare record first, then the one the next wave polls (a wave's LDS operations execute in order)
                 if (__float_as_uint(a.mnew) != m_before || __float_as_uint(a.rnew) != r_before)
                     *hand_m_l = Float4{a.mnew, a.rnew, a.mi, 0.0f};
-                *hand_l = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : sq + 1,
-                               a.deleted & 1};
-                __builtin_amdgcn_s_setprio(0);
+                if (kSolo) solo_h = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : 0, a.deleted & 1};
+                else *hand_l = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : sq + 1,
+                                    a.deleted & 1};
+                if (!kSolo) __builtin_amdgcn_s_setprio(0);
             }
             if (kProbe) pt3 = __builtin_readcyclecounter();
             // the prefetched window of this wave's next turn
@@ -1541,7 +1599,7 @@ void forces_ring_f32(const RingArgs args) {
         // general code's record loads are inline assembly with their own waits): hipcc therefore places no vmcnt wait in
         // the loop, and the only one there is check_window's, for a prefetch issued a whole turn earlier.
         if ((kQueue || mine) && (tau_hi - 1) % kW == w) {      // the wave that took the item's last turn, from the records it has
-            const Int4 hf = *hand_l;                           // just written (a wave's LDS operations execute in order)
+            const Int4 hf = kSolo ? solo_h : *hand_l;          // just written (a wave's LDS operations execute in order)
             const Float4 hm = *hand_m_l;
             if (kQueue && tau_hi < nturns) {
                 // not the walk's last segment: the two records of every lane go to the ring's state, write-through (each store
@@ -1582,7 +1640,7 @@ void forces_ring_f32(const RingArgs args) {
             }
             // the item's CLOSING TURN: one more sequence number, published when the records have been read back - wave 0 of
             // the slot's next item waits for it before it writes that item's starting state over them
-            if (kQueue) *hand_l = Int4{hf.x, hf.y, hf.z >= kRingDeadSeq ? kRingDeadSeq : seq_base + (tau_hi - tau_lo) + 1, hf.w};
+            if (kQueue && !kSolo) *hand_l = Int4{hf.x, hf.y, hf.z >= kRingDeadSeq ? kRingDeadSeq : seq_base + (tau_hi - tau_lo) + 1, hf.w};
         }
         {
             unsigned long long pairs = 0;
@@ -1595,6 +1653,7 @@ void forces_ring_f32(const RingArgs args) {
         seq_base += tau_hi - tau_lo + 1;
     }
     Counters* const ctr = NB_RING_LATE(ctr);
+    if (kSolo) *(LdsIntPtr)&solo_done_all[wv] = 0;
     if (kQueue && w == 0 && l == 0) {                      // the last slot to leave clears the queue for the next launch
         const GlobalU32Ptr head = (GlobalU32Ptr)NB_RING_LATE(q_head);
         if (__hip_atomic_fetch_add(head + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x * kRings - 1u) {
