@@ -447,6 +447,56 @@ int nbody_get_neighbors(nbody_ctx* ctx, const nbody_vec2* points, int m, nbody_n
 int nbody_batch_get_neighbors(struct nbody_batch* b, const nbody_vec2* points, int m, nbody_neighbor* out);
 
 /* ---------------------------------------------------------------------------------------------------
+ * k nearest neighbours (the reference has none): for every row - a current body, or an arbitrary probe
+ * point - the k nearest of the n current bodies and their squared distances, 1 <= k <= NBODY_KNN_MAX: what a local density
+ * from the distance to the k-th neighbour, a kNN graph or an isolation measure is made of.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the
+ * records of nbody_get_neighbors: (X_j, Y_j) of the n current bodies, widened exactly from fp32 or taken as they are from
+ * fp64.  Radii and masses play no part.  For a row at (x, y) and a source j:
+ *     dx = X_j - x;  dy = Y_j - y;  d2_j = (dx*dx) + (dy*dy)               the d2 of nbody_get_neighbors, same bits
+ *   - a source is eligible iff d2_j < +inf: a NaN or +inf d2 is never listed;
+ *   - in the own form the self term is excluded by index: a second body at the same place is eligible at d2 = +0;
+ *   - the row's result is the first k eligible sources under the total order (d2, j) ascending: ties in d2 go to the lower j;
+ *   - entry c of the row is d2[row * k + c], index[row * k + c];
+ *   - with fewer than k eligible sources the remaining entries are {+inf, -1}.
+ * What follows from it:
+ *   - for every k, entry 0 has the bits of nbody_get_neighbors' {d2, index} for that row;
+ *   - the lists of k and k' < k agree on the first k' entries;
+ *   - d2 is non-decreasing along a row; every index of a row is distinct and is not the row's own;
+ *   - the result is a function of the set of sources only, so an implementation may walk j in any order, with any number of
+ *     lanes per row, and keep the list anywhere, as long as it returns exactly this;
+ *   - it is independent of the semantics: a literal context's frozen tail is a source like any other body;
+ *   - a row with no eligible source, or an empty system, is all {+inf, -1}.
+ * nbody_get_knn follows nbody_get_neighbors in every respect not named here.  Explicit points (points != NULL): m probe
+ * points, always nbody_vec2; *n_out = m; m == 0 is legal and launches nothing.  Own positions (points == NULL): the rows are
+ * the current bodies, taken on the device; m is the room in rows, *n_out the current count n; m < n is NBODY_ERR_CAPACITY
+ * with nothing written.  It synchronises, reads the replica only and never changes what later steps compute.  It is NOT
+ * collective: any rank of any world or transport gives the same bits.  The device points, the device entries (12 bytes each)
+ * and their pinned staging are allocated on the first call and grown; a context that never calls it allocates nothing and
+ * launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: NULL ctx, d2, index or n_out; k outside [1, NBODY_KNN_MAX]; m < 0;
+ * m x k x 12 bytes above 2^31 (in the own form too, where m is the room).  NBODY_ERR_STATE: before an upload.
+ * Cost (one MI355X, fp32, stock radii, the N = 262144 state after 3 steps, n = 130965, points == NULL; profiles/knn_probe.txt,
+ * a kernel trace with nbody_get_neighbors' kernel timed in the same run at 9.49 ms): the kernel 6.00 / 5.94 / 6.49 / 8.63 /
+ * 15.76 ms for k = 1 / 4 / 8 / 16 / 32, that is 0.63 / 0.63 / 0.68 / 0.91 / 1.66 times the nearest-neighbour kernel: per pair
+ * it does less (no overlap count, no selects), and pays for an insertion only when some row of a wave lists the source.  The
+ * list has a capacity tier of 4, 8, 16 or 32 entries, the smallest that holds k, so k = 1 costs what k = 4 costs.  Whole
+ * Stepper.knn() calls, with the copy of n x k x 12 bytes and their split into two arrays: 6.1 / 6.6 / 8.2 / 17.0 / 32.4 ms,
+ * next to 9.7 ms for Stepper.neighbors().  65536 explicit points at k = 8 on that state: 5.74 ms of kernel, 6.3 ms the call.  A
+ * batch of 256 x 1024 with points == NULL at k = 8: 0.37 ms of kernel, 3.9 ms for StepperBatch.knn() with its 25 MB of
+ * results.  Not measured: any other precision, state or k; the cost between the tiers' boundaries is the upper tier's.
+ * nbody_batch_get_knn: the same query for every system of a batch in ONE launch, whatever S is, with the one set of points
+ * and the one k for all of them (systems x m x k x 12 bytes at most 2^31).  Explicit points: system s's entries at
+ * [(s * m + p) * k + c].  points == NULL: at [(s * capacity + i) * k + c], one row per current body, the rest of the slice
+ * is left unchanged.  System s gives exactly what an nbody_ctx holding that system's state gives; an empty system gives
+ * {+inf, -1} in every entry of every explicit point and writes nothing in the own form.  A count outside [0, capacity] is
+ * treated as 0 and reported for that system, as by nbody_batch_get_neighbors.
+ * ------------------------------------------------------------------------------------------------- */
+#define NBODY_KNN_MAX 32
+int nbody_get_knn(nbody_ctx* ctx, const nbody_vec2* points, int m, int k, double* d2, int32_t* index, int* n_out);
+int nbody_batch_get_knn(struct nbody_batch* b, const nbody_vec2* points, int m, int k, double* d2, int32_t* index);
+
+/* ---------------------------------------------------------------------------------------------------
  * Group finding (the reference has none): friends-of-friends.  Which of the n current bodies hang together,
  * and how many clumps there are: the connected components of the graph of linked pairs.
  * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the

@@ -25,6 +25,7 @@ FLAG_FORCE_COMM = 4
 FLAG_TRACK_IDS = 8
 TRACER_WALLS = 1
 TRACK_PHI = 1
+KNN_MAX = 32
 COMM_ID_BYTES = 128
 IMAGE_PATH_MAX = 1024
 
@@ -199,6 +200,7 @@ SYMBOLS = {
     "nbody_group_diagnostics": (_i, [_pp, _i, ctypes.POINTER(Diag), _vp]),
     "nbody_get_field": (_i, [_vp, _vp, _i, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
+    "nbody_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp, _ip]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
     "nbody_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_tracers_set": (_i, [_vp, _vp, _i, ctypes.c_uint32]),
@@ -220,6 +222,7 @@ SYMBOLS = {
     "nbody_batch_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_batch_get_field": (_i, [_vp, _vp, _i, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_get_neighbors": (_i, [_vp, _vp, _i, _vp]),
+    "nbody_batch_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "nbody_batch_get_groups": (_i, [_vp, _d, _d, _vp, _vp]),
     "nbody_batch_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_batch_diag_reserve": (_i, [_vp, _i]),
@@ -482,6 +485,11 @@ def _neighbors(call, points, capacity):
     n = ctypes.c_int(0)
     _check(call(None if pts is None else pts.ctypes.data, m, buf.ctypes.data, ctypes.byref(n)))
     return buf[:n.value].copy()
+
+
+def _knn_buffers(shape):
+    """The caller's two arrays of nbody_get_knn, filled with what an empty entry holds."""
+    return np.full(shape, np.inf, dtype=np.float64), np.full(shape, -1, dtype=np.int32)
 
 
 def _groups_dict(label, info):
@@ -756,6 +764,20 @@ class Stepper:
         NEIGHBOR_DTYPE array.  Not collective: any rank of any world may call it on its own."""
         return _neighbors(lambda *a: lib.nbody_get_neighbors(self._ctx, *a), points, self.capacity)
 
+    def knn(self, k, points=None):
+        """nbody_get_knn: for every row - each of `points` (m, 2), or with points=None each current body (self term left
+        out by index) - the k nearest current bodies under (d2, index) ascending, 1 <= k <= KNN_MAX: {"d2": float64
+        (rows, k) squared distances, "index": int32 (rows, k)}, entries past the last eligible source {+inf, -1}.  Entry 0
+        has the bits of neighbors().  Not collective: any rank of any world may call it on its own."""
+        pts = _field_points(points)
+        k = int(k)
+        m = self.capacity if pts is None else len(pts)
+        d2, index = _knn_buffers((max(m, 1), max(k, 1)))
+        n = ctypes.c_int(0)
+        _check(lib.nbody_get_knn(self._ctx, None if pts is None else pts.ctypes.data, m, k, d2.ctypes.data,
+                                 index.ctypes.data, ctypes.byref(n)))
+        return {"d2": d2[:n.value].copy(), "index": index[:n.value].copy()}
+
     def groups(self, link, radius_scale=1.0):
         """nbody_get_groups: friends-of-friends groups of the current bodies, i and j linked where d2 <= s*s with
         s = radius_scale * (r_i + r_j) + link (fp64): {"label": int32 (n,), label[i] the lowest index of body i's group,
@@ -818,6 +840,10 @@ class StepperGroup:
     def neighbors(self, points=None, rank=0):
         """Stepper.neighbors through one rank: every rank's replica holds every body, each gives the same bits."""
         return self.ranks[rank].neighbors(points)
+
+    def knn(self, k, points=None, rank=0):
+        """Stepper.knn through one rank: every rank's replica holds every body, each gives the same bits."""
+        return self.ranks[rank].knn(k, points)
 
     def groups(self, link, radius_scale=1.0, rank=0):
         """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
@@ -991,6 +1017,20 @@ class StepperBatch:
         if pts is None:
             return [buf[s, :int(k)].copy() for s, k in enumerate(self.counts())]
         return np.ascontiguousarray(buf[:, :m])
+
+    def knn(self, k, points=None):
+        """nbody_batch_get_knn: Stepper.knn for every system in one launch, with the one set of points and the one k for all
+        of them, system s having the bits a Stepper holding its state gives.  points=None: a list of S dicts, one row per
+        current body of the system; otherwise one dict of arrays of shape (S, m, k)."""
+        pts = _field_points(points)
+        k = int(k)
+        m = self.capacity if pts is None else len(pts)
+        d2, index = _knn_buffers((self.systems, max(m, 1), max(k, 1)))
+        _check(lib.nbody_batch_get_knn(self._b, None if pts is None else pts.ctypes.data, m, k, d2.ctypes.data,
+                                       index.ctypes.data))
+        if pts is None:
+            return [{"d2": d2[s, :int(c)].copy(), "index": index[s, :int(c)].copy()} for s, c in enumerate(self.counts())]
+        return {"d2": np.ascontiguousarray(d2[:, :m]), "index": np.ascontiguousarray(index[:, :m])}
 
     def groups(self, link, radius_scale=1.0):
         """nbody_batch_get_groups: Stepper.groups for every system, every pair walk one launch for the whole batch: a list

@@ -27,6 +27,7 @@
 #include "nbody_neighbors.hpp"
 #include "nbody_groups.hpp"
 #include "nbody_pairs.hpp"
+#include "nbody_knn.hpp"
 
 using namespace nbk;
 
@@ -85,6 +86,8 @@ struct nbody_batch {
     GroupsState grp;
     // pair-separation counts (nbody_batch_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
     PairsState prs;
+    // k nearest neighbours (nbody_batch_get_knn, nbody_knn.hpp): nothing is allocated before the first call
+    KnnState knn;
     // tracer particles (nbody_batch_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -109,6 +112,7 @@ void free_all(nbody_batch* b) {
     rows_free(b->nbr);
     groups_free(b->grp);
     pairs_free(b->prs);
+    rows_free(b->knn);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
@@ -705,8 +709,8 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_groups, nbody_batch_get_pair_counts;
-// nbody_rows.hpp and the four query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
+// Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_knn, nbody_batch_get_groups,
+// nbody_batch_get_pair_counts; nbody_rows.hpp and the five query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
 // of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -752,6 +756,13 @@ int nbody_batch_get_neighbors(nbody_batch* b, const nbody_vec2* points, int m, n
                                    (b ? (unsigned long long)b->S : 1) * sizeof(nbody_neighbor), " of results");
     if (rc != NBODY_OK) return rc;
     return batch_rows(b, "nbody_batch_get_neighbors", b->nbr, NeighborQuery{}, points, m, out);
+}
+
+int nbody_batch_get_knn(nbody_batch* b, const nbody_vec2* points, int m, int k, double* d2, int32_t* index) {
+    const int rc = knn_check_args("nbody_batch_get_knn", {b, d2, index}, m, k, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK) return rc;
+    KnnResult out{d2, index};
+    return batch_rows(b, "nbody_batch_get_knn", b->knn, KnnQuery{k}, points, m, &out);
 }
 
 int nbody_batch_get_groups(nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info) {

@@ -30,6 +30,7 @@
 #include "nbody_neighbors.hpp"
 #include "nbody_groups.hpp"
 #include "nbody_pairs.hpp"
+#include "nbody_knn.hpp"
 
 using namespace nbk;
 
@@ -191,6 +192,8 @@ struct nbody_ctx {
     GroupsState grp;
     // pair-separation counts (nbody_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
     PairsState prs;
+    // k nearest neighbours (nbody_get_knn, nbody_knn.hpp): nothing is allocated before the first call
+    KnnState knn;
     // tracer particles (nbody_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -621,6 +624,7 @@ void free_all(nbody_ctx* c) {
     rows_free(c->nbr);
     groups_free(c->grp);
     pairs_free(c->prs);
+    rows_free(c->knn);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
@@ -1674,9 +1678,9 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_groups, nbody_get_pair_counts; nbody_rows.hpp and the four
-// query headers).  At the end of the file for the reason the identities are.  They read the replica J only - every rank
-// holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
+// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_groups, nbody_get_pair_counts; nbody_rows.hpp
+// and the five query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
+// every rank holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -1729,6 +1733,13 @@ int nbody_get_neighbors(nbody_ctx* c, const nbody_vec2* points, int m, nbody_nei
     const int rc = rows_check_args("nbody_get_neighbors", {c, out, n_out}, m, sizeof(nbody_neighbor), " of results");
     if (rc != NBODY_OK) return rc;
     return ctx_rows(c, "nbody_get_neighbors", c->nbr, NeighborQuery{}, points, m, out, n_out);
+}
+
+int nbody_get_knn(nbody_ctx* c, const nbody_vec2* points, int m, int k, double* d2, int32_t* index, int* n_out) {
+    const int rc = knn_check_args("nbody_get_knn", {c, d2, index, n_out}, m, k, 1);
+    if (rc != NBODY_OK) return rc;
+    KnnResult out{d2, index};
+    return ctx_rows(c, "nbody_get_knn", c->knn, KnnQuery{k}, points, m, &out, n_out);
 }
 
 int nbody_get_groups(nbody_ctx* c, double link, double radius_scale, int32_t* label, int cap, nbody_groups_info* info) {

@@ -135,9 +135,11 @@ struct FieldQuery {
     void launch(dim3 grid, hipStream_t stream, FieldOut* out, Common... common) const {
         hipLaunchKernelGGL((field_at<T, kOwn, Count>), grid, dim3(kDiagBlock), 0, stream, common..., G, out);
     }
+    size_t width() const { return 1; }
     void empty(int sys) const { coincident[sys] = 0; }
-    void unpack(int sys, const FieldOut* h, size_t cnt, nbody_field* out) const {
+    void unpack(int sys, const FieldOut* h, size_t cnt, nbody_field* out, size_t row0) const {
         long long coin = 0;
+        out += row0;
         for (size_t p = 0; p < cnt; ++p) {
             out[p].ax = h[p].ax; out[p].ay = h[p].ay; out[p].phi = h[p].phi;
             coin += h[p].coincident;

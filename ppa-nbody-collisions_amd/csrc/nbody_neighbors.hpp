@@ -99,8 +99,11 @@ struct NeighborQuery {
     void launch(dim3 grid, hipStream_t stream, NeighborOut* out, Common... common) const {
         hipLaunchKernelGGL((neighbors_at<T, kOwn, Count>), grid, dim3(kDiagBlock), 0, stream, common..., out);
     }
+    size_t width() const { return 1; }
     void empty(int) const {}
-    void unpack(int, const NeighborOut* h, size_t cnt, nbody_neighbor* out) const { memcpy(out, h, cnt * sizeof(NeighborOut)); }
+    void unpack(int, const NeighborOut* h, size_t cnt, nbody_neighbor* out, size_t row0) const {
+        memcpy(out + row0, h, cnt * sizeof(NeighborOut));
+    }
 };
 
 }  // namespace nbk

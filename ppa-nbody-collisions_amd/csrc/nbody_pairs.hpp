@@ -42,13 +42,6 @@ static_assert(sizeof(nbody_pair_info) == 40, "nbody_pair_info layout");
 constexpr int kPairMaxBins = 256;
 constexpr int kPairEdgeSlots = 512;            // the edges in LDS: e2[0 .. B-1], then +inf; a power of two above every probe
 
-// A row query with no per-row result: rows_prologue's write of the empty record is this assignment, which writes nothing.
-struct PairNoOut {
-    PairNoOut() = default;
-    PairNoOut(const PairNoOut&) = default;
-    __host__ __device__ PairNoOut& operator=(const PairNoOut&) { return *this; }
-};
-
 // The number of edges <= d2, for a d2 below the top edge: e[k] is e2[k] for k < B and +inf from there on, `first` is
 // 2^(trips - 1) with trips = ceil(log2(B + 1)), so lo + step - 1 <= 2^trips - 2 < kPairEdgeSlots.
 __device__ __forceinline__ int pair_slot(const double* e, int first, double d2) {
@@ -100,8 +93,8 @@ __global__ __launch_bounds__(kDiagBlock) void pair_counts(const Rec<T>* __restri
                                                           const FieldPoint* __restrict__ points, int m,
                                                           const double* __restrict__ edges2, int bins,
                                                           unsigned long long* __restrict__ hist_all) {
-    RowsLane<T, PairNoOut> L;
-    if (rows_prologue<T, kOwn, Count>(L, J_all, meta_all, ctr_all, stride, n_one, m, (PairNoOut*)nullptr, PairNoOut{})) return;
+    RowsLane<T, RowsNoOut> L;
+    if (rows_prologue<T, kOwn, Count>(L, J_all, meta_all, ctr_all, stride, n_one, m, (RowsNoOut*)nullptr, RowsNoOut{})) return;
     const int sys = Count::kBatch ? (int)blockIdx.y : 0;
     const int tid = threadIdx.x;
     __shared__ double se[kPairEdgeSlots];

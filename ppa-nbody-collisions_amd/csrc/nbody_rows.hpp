@@ -1,8 +1,9 @@
 // csrc/nbody_rows.hpp -- a row per lane over the resident state: what the row queries (field evaluation, nbody_field.hpp;
-// neighbour queries, nbody_neighbors.hpp; group finding, nbody_groups.hpp; pair counts, nbody_pairs.hpp; DESIGN.md 4.8 to
-// 4.11) have in common, on the device and on the host.  Included after nbody_diag.hpp and before the query headers by both
-// translation units: one system (nbody_ctx.hip) and a batch (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride`
-// apart, one set of points for every system) share each query's one kernel.
+// neighbour queries, nbody_neighbors.hpp; group finding, nbody_groups.hpp; pair counts, nbody_pairs.hpp; the k nearest,
+// nbody_knn.hpp) have in common, on the device and on the host.  Included after
+// nbody_diag.hpp and before the query headers by both translation units: one system (nbody_ctx.hip) and a batch
+// (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride` apart, one set of points for every system) share each
+// query's one kernel.
 //
 // A row is a current body (kOwn: read from J on the device, results `stride` apart per system) or an explicit point
 // (results m apart per system).  One lane per row, kDiagBlock lanes per workgroup, grid = (ceil(rows / kDiagBlock),
@@ -17,9 +18,10 @@
 //
 // Adding a row query takes a kernel `<T, kOwn, Count>` that opens with rows_prologue, loads its row with rows_row and hands
 // rows_walk (the tile loop, below) a functor with the query's four pairs of one trip; and a host side built from rows_run
-// (a result record per row: a traits struct such as FieldQuery or NeighborQuery is all it takes) or, for another shape of
-// result, from the pieces of rows_run - RowsSite's grid, count and sync, RowPoints, rows_check_args.  The per-handle
-// preamble and the precision dispatch are in the two .hip files.  field_at walks with diag_walk_sums instead (see rows_walk).
+// (a fixed number of result records per row: a traits struct such as FieldQuery, NeighborQuery or KnnQuery is all it takes)
+// or, for another shape of result, from the pieces of rows_run - RowsSite's grid, count and sync, RowPoints,
+// rows_check_args.  The per-handle preamble and the precision dispatch are in the two .hip files.  field_at walks with
+// diag_walk_sums instead (see rows_walk).
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -54,6 +56,14 @@ struct RowsLane {
     int n, rows, p;             // sources, rows, this lane's row
     int self_tile;              // kOwn: the one j tile that holds this wave's self terms; otherwise -1
     bool valid, wave_works;     // the lane has a row; its wave has one
+};
+
+// For a kernel that writes no record of type Out per row (pair_counts has no per-row result, knn_at writes k entries itself):
+// rows_prologue's write of the empty record is this assignment, which writes nothing.
+struct RowsNoOut {
+    RowsNoOut() = default;
+    RowsNoOut(const RowsNoOut&) = default;
+    __host__ __device__ RowsNoOut& operator=(const RowsNoOut&) { return *this; }
 };
 
 // true: the whole workgroup returns now (it has no row, or the system is empty and its rows have `empty` already).  The
@@ -262,17 +272,19 @@ struct RowsSite {
     int sync(bool launched, ReadMeta read_meta) const { return Count::kBatch || launched ? read_meta() : NBODY_OK; }
 };
 
-// One query with a record per row, from the reservation to the caller's records.
-// Q: the query's traits - Device and Result records, launch<T, kOwn, Count>(grid, stream, out, common kernel arguments...),
-// empty(s) and unpack(s, staged records, how many, the caller's) for system s.
+// One query with q.width() records per row (1: field, neighbours; k: the k nearest), a row's records next to each other on
+// the device, from the reservation to the caller's results.
+// Q: the query's traits - Device records and the caller's Result, launch<T, kOwn, Count>(grid, stream, out, common kernel
+// arguments...), empty(s) and unpack(s, system s's staged records, how many rows, the caller's, system s's first row there).
 template <typename T, typename Count, typename Q, typename ReadMeta>
 int rows_run(const char* who, const RowsSite& s, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points,
              int m, typename Q::Result* out, ReadMeta read_meta) {
     using Device = typename Q::Device;
     const bool own = points == nullptr;
     const int rows = own ? s.n_bound : m;                                  // what the grid covers
-    const size_t per_sys = own ? (size_t)s.stride : (size_t)m;             // results of one system on the device
-    const size_t total = Count::kBatch ? per_sys * (size_t)s.systems : (size_t)rows;
+    const size_t width = q.width();
+    const size_t per_sys = own ? (size_t)s.stride : (size_t)m;             // rows of one system on the device
+    const size_t total = (Count::kBatch ? per_sys * (size_t)s.systems : (size_t)rows) * width;
     for (int sys = 0; sys < s.systems; ++sys) q.empty(sys);
     if (rows > 0) {
         const int rc = rows_reserve(buf, own ? 0 : (size_t)m, total, who);
@@ -293,7 +305,7 @@ int rows_run(const char* who, const RowsSite& s, PointBuffers<typename Q::Device
     if (rc != NBODY_OK || rows == 0) return rc;
     const Device* h = reinterpret_cast<const Device*>(buf.out.h);
     for (int sys = 0; sys < s.systems; ++sys)
-        q.unpack(sys, h + (size_t)sys * per_sys, own ? (size_t)s.count(sys) : (size_t)m, out + (size_t)sys * per_sys);
+        q.unpack(sys, h + (size_t)sys * per_sys * width, own ? (size_t)s.count(sys) : (size_t)m, out, (size_t)sys * per_sys);
     return NBODY_OK;
 }
 
