@@ -609,6 +609,88 @@ int nbody_batch_get_pair_counts(struct nbody_batch* b, const nbody_vec2* points,
                                 uint64_t* counts /* [systems * bins] */, nbody_pair_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Encounter queries (the reference has none): swept contacts within a horizon, by pair.  The stepper finds a
+ * collision only where two bodies overlap at the start of a step (d2 <= (r_i + r_j)^2 on the positions of that instant); a
+ * pair that closes faster than (r_i + r_j) / dt can pass straight through.  This read-out says which pairs touch within the
+ * next h seconds if every body keeps its velocity, when, and which of them a step test at 0 and at h sees at neither end.
+ * PHYSICS: this is the UNIFORM-MOTION estimate, not the stepper's own trajectory.  It leaves out the acceleration within the
+ * horizon and the wall rule; it predicts the stepper exactly only where one step moves a body by fl(x + dt v).
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the
+ * records (X, Y, R) and velocities (VX, VY) of the n current bodies, widened exactly from fp32 or taken as they are from
+ * fp64; masses play no part.  h is the horizon in seconds: h >= 0, +inf allowed.  For an unordered pair i < j
+ *     dx = X_j - X_i;  dy = Y_j - Y_i;  dvx = VX_j - VX_i;  dvy = VY_j - VY_i
+ *     d2 = (dx*dx) + (dy*dy);   s = R_i + R_j;   s2 = s*s;   c = d2 - s2
+ *     b  = (dx*dvx) + (dy*dvy); a = (dvx*dvx) + (dvy*dvy);   disc = (b*b) - (a*c)
+ *     ex = dx + (dvx*h);        ey = dy + (dvy*h);            e2 = (ex*ex) + (ey*ey)
+ *     now = d2 <= s2                                  the overlap predicate of nbody_get_neighbors, same bits
+ *     end = e2 <= s2                                  overlap at time h under uniform motion
+ *     mid = b < 0 && (-b) < (a*h) && disc >= 0        closest approach before h, and close enough
+ *     swept = now || end || mid
+ *     t = now ? +0 : (b < 0 && disc >= 0) ? min(c / (sqrt(disc) - b), h) : h         min(x, h) = x < h ? x : h
+ * A swept pair is reported as {t, i, j, flags} with i < j; flags has NBODY_ENCOUNTER_NOW where now holds and
+ * NBODY_ENCOUNTER_END where end holds (both may be set).  A swept pair with neither bit is MISSED: it touches strictly inside
+ * (0, h) and overlaps at neither end, so with h = dt the stepper's test sees it at neither step.  The list is sorted by
+ * (t, i, j) ascending.  info: n_bodies = n; pairs = the swept pairs; now / end = those with the bit; missed = those with
+ * neither; horizon = h.  What follows from the definition:
+ *   - symmetry: the predicate and t are symmetric bit for bit - the four differences only change sign and every product
+ *     holds two of them - so one orientation suffices;
+ *   - NaN: a NaN coordinate or radius makes d2, e2, b or s2 NaN, every comparison fails and the pair is not swept.  A NaN
+ *     velocity does the same to end and mid; `now` does not read the velocities, so a pair that overlaps is still reported,
+ *     with t = +0;
+ *   - infinite horizon: with h = +inf, end holds only where s2 is +inf, and a*h is +inf or NaN, so for finite radii
+ *     swept = now || (b < 0 && a > 0 && disc >= 0): every pair on a collision course;
+ *   - zero horizon: with h = 0, ex = dx + (dvx*0) squares to what dx squares to wherever the velocities are finite, so end
+ *     equals now, and a*0 is not above -b, so mid never holds: swept = now, and info.now is half the sum of `overlaps` of
+ *     nbody_get_neighbors with points == NULL;
+ *   - it is independent of the semantics, like the other read-outs: a literal context's frozen tail counts with its stored
+ *     velocity;
+ *   - the result is a function of the state and h only: the device appends in any order, the sort fixes the list.
+ * Division of labour: the device decides swept and the flags for all n (n - 1) / 2 pairs, with subtractions, multiplies,
+ * additions and compares only, counts pairs / now / end / missed in 64-bit integers, and appends a raw record per swept pair
+ * - nbody_encounter_raw: i, j, flags, c, b, disc - to a log of cap records per system; records past cap are counted, not
+ * stored.  nbody_encounter_finish, a pure host function in plain C that needs no GPU, computes t from c, b, disc and h with
+ * the C library's sqrt and /, orders (i, j), and sorts `count` records into out; it reads only the NOW and END bits of flags.
+ * A bit-exact contract does not rest on the device's divide and square root (nbody_selftest_rcp_ones_f64 is why).
+ * nbody_get_encounters synchronises, reads only, and never changes what later steps compute: state, pair counter, events,
+ * tracers.  out has room for cap records; info is always filled once the walk has run.  pairs > cap: NBODY_ERR_CAPACITY, out
+ * untouched, info complete - the caller repeats with cap >= info.pairs, so the list is never a nondeterministic subset.  out
+ * may be NULL with cap == 0: the counts only, NBODY_OK whatever pairs is.  An empty or one-body system gives zeros.  The
+ * device log, the counters and their pinned staging are allocated on the first call and grown to the largest cap seen; a
+ * context that never calls it allocates nothing and launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: a NULL handle or info; a NaN or negative horizon; cap < 0; NULL out with
+ * cap > 0; cap x 24 bytes (a batch: systems x cap x 24) above 2^31.  NBODY_ERR_STATE: before an upload; on a context with
+ * world > 1, NBODY_FLAG_GROUP_EXCHANGE or NBODY_FLAG_FORCE_COMM: a rank holds only its own bodies' velocities, and a query
+ * across ranks has not been built (the tracers' restriction).  A device-side failure is reported as by every synchronising
+ * call.
+ * How (csrc/nbody_encounters.hpp): one lane per body over the triangular tile walk of nbody_get_groups (j < i, each pair once
+ * at the higher row) with two more LDS planes for the velocities (10 KiB double-buffered); 5 LDS reads, 27 fp64 arithmetic
+ * instructions and 5 compares per pair against groups_sweep's 3, 10 and 1, so about three times a sweep is what counting gives;
+ * one 64-bit atomic per swept pair for its slot in the log, one per wave for each of the three class counts.  No device-side
+ * waiting, no retry loop.  Every pair evaluates every term: skipping e2 where b >= 0 would be right for exact values only.
+ * Cost (one MI355X, fp32; profiles/encounter_probe.txt): the stock state of N = 262144, n = 130965 bodies after 3 steps
+ * (8.58e9 pairs, max |v| 325), every figure measured in that file.  The kernel 18.69 / 18.91 / 18.97 ms for h = 0 / the time step 0.2 / ten time steps
+ * (5052 / 9201 / 35603 swept pairs, of them 0 / 0 / 433 missed): 2.61 / 2.64 / 2.65 times groups_sweep at (0, 1), which walks the
+ * same triangle (7.17 ms in the same run), and 2.0 times neighbors_at's own-form kernel (9.43 ms); the number of swept pairs
+ * hardly shows.  Whole Stepper.encounters() calls with room for the list: 19.2 / 19.7 / 22.2 ms (the copy, the finish and the
+ * wrapper's repacking of 35603 records are the 3.3 ms); a call that has to be repeated with a larger cap walks twice (38.6
+ * ms).  A batch of 256 x 1024 with h = the time step: 0.333 ms of kernel, 1.02 ms per call.  Not measured: fp64, h = +inf on
+ * that state, any other state.
+ * nbody_batch_get_encounters: the same for every system of a batch in ONE launch, whatever S is, with the one horizon and
+ * the one cap for all of them: system s's list at out + s * cap (pairs records, the rest of the slice is left unchanged), its
+ * record at info[s].  If any system has pairs > cap the call is NBODY_ERR_CAPACITY, out untouched, every info complete.
+ * System s gives exactly what an nbody_ctx holding that system's state gives.  A count outside [0, capacity] is treated as
+ * 0 and reported for that system, as by nbody_batch_get_neighbors.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_encounter { double t; int32_t i, j; uint32_t flags, reserved; } nbody_encounter;   /* 24 bytes */
+typedef struct nbody_encounter_info { int64_t n_bodies, pairs, now, end, missed; double horizon; } nbody_encounter_info;
+typedef struct nbody_encounter_raw { int32_t i, j; uint32_t flags, reserved; double c, b, disc; } nbody_encounter_raw;   /* 40 bytes */
+enum { NBODY_ENCOUNTER_NOW = 1u << 0, NBODY_ENCOUNTER_END = 1u << 1 };
+int nbody_get_encounters(nbody_ctx* ctx, double horizon, nbody_encounter* out, int cap, nbody_encounter_info* info);
+int nbody_batch_get_encounters(struct nbody_batch* b, double horizon, nbody_encounter* out /* [systems * cap] */, int cap,
+                               nbody_encounter_info* info /* [systems] */);
+int nbody_encounter_finish(const nbody_encounter_raw* raw, int count, double horizon, nbody_encounter* out /* [count] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Tracer particles (the reference has none): massless probes advected with every step.
  * A tracer has a position and a velocity {x, y, vx, vy}, always fp64 whatever the context's precision.  It behaves like a
  * body of mass 0 and radius 0 that nothing collides with: it is attracted by the bodies; it attracts nothing and is never a

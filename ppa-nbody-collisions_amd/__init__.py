@@ -132,6 +132,16 @@ GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("
 PAIR_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("rows", np.int64), ("pairs", np.int64), ("below", np.int64),
                             ("rest", np.int64)])
 
+# struct nbody_encounter, nbody_encounter_info, nbody_encounter_raw as numpy records (Stepper.encounters,
+# StepperBatch.encounters, encounter_finish); ENCOUNTER_DTYPE is what they return: the record without its reserved word
+ENCOUNTER_NOW, ENCOUNTER_END = 1, 2
+ENCOUNTER_RECORD_DTYPE = np.dtype([("t", np.float64), ("i", np.int32), ("j", np.int32), ("flags", np.uint32), ("reserved", np.uint32)])
+ENCOUNTER_DTYPE = np.dtype([("t", np.float64), ("i", np.int32), ("j", np.int32), ("flags", np.uint32)])
+ENCOUNTER_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("pairs", np.int64), ("now", np.int64), ("end", np.int64),
+                                 ("missed", np.int64), ("horizon", np.float64)])
+ENCOUNTER_RAW_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("flags", np.uint32), ("reserved", np.uint32),
+                                ("c", np.float64), ("b", np.float64), ("disc", np.float64)])
+
 # struct nbody_tracer / nbody_tracer_info as numpy records (Stepper.set_tracers / tracers, StepperBatch likewise)
 TRACER_DTYPE = np.dtype([("pos", np.float64, (2,)), ("vel", np.float64, (2,))])
 TRACER_INFO_DTYPE = np.dtype([("steps", np.int64), ("coincident", np.int64), ("count", np.int32), ("flags", np.uint32)])
@@ -203,6 +213,9 @@ SYMBOLS = {
     "nbody_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp, _ip]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
     "nbody_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "nbody_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
+    "nbody_batch_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
+    "nbody_encounter_finish": (_i, [_vp, _i, _d, _vp]),
     "nbody_tracers_set": (_i, [_vp, _vp, _i, ctypes.c_uint32]),
     "nbody_tracers_get": (_i, [_vp, _vp, _vp, _i, _vp]),
     "nbody_batch_tracers_set": (_i, [_vp, _vp, _i, ctypes.c_uint32]),
@@ -528,6 +541,62 @@ def _pair_counts(call, systems, edges, points, squared):
     return [_pair_dict(counts[s].copy(), info[s], e2) for s in range(systems)]
 
 
+def _encounter_list(rec):
+    out = np.zeros(len(rec), dtype=ENCOUNTER_DTYPE)
+    for f in ENCOUNTER_DTYPE.names:
+        out[f] = rec[f]
+    return out
+
+
+def _encounter_info(info):
+    d = {k: int(info[k]) for k in ("n_bodies", "pairs", "now", "end", "missed")}
+    d["horizon"] = float(info["horizon"])
+    return d
+
+
+def _encounters(call, systems, horizon, cap):
+    """nbody_get_encounters through `call(horizon, out, cap, info)` -> one (ENCOUNTER_DTYPE array, info dict) per system.  On
+    NBODY_ERR_CAPACITY the call is repeated once with the largest info.pairs."""
+    S = max(systems, 1)
+    info = np.zeros(S, dtype=ENCOUNTER_INFO_DTYPE)
+    cap = max(int(cap), 0)
+    buf = np.zeros((S, max(cap, 1)), dtype=ENCOUNTER_RECORD_DTYPE)
+    status = call(horizon, buf.ctypes.data, cap, info.ctypes.data)
+    if status == -7:                                            # NBODY_ERR_CAPACITY: info is complete
+        cap = int(info["pairs"].max())
+        buf = np.zeros((S, max(cap, 1)), dtype=ENCOUNTER_RECORD_DTYPE)
+        status = call(horizon, buf.ctypes.data, cap, info.ctypes.data)
+    _check(status)
+    return [(_encounter_list(buf[s, :int(info["pairs"][s])]), _encounter_info(info[s])) for s in range(systems)]
+
+
+def encounter_finish(raw, horizon):
+    """nbody_encounter_finish, the host half of encounters(): ENCOUNTER_RAW_DTYPE records {i, j, flags, c, b, disc} of swept
+    pairs -> the ENCOUNTER_DTYPE list {t, i, j, flags} sorted by (t, i, j).  Needs no GPU."""
+    raw = np.ascontiguousarray(raw, dtype=ENCOUNTER_RAW_DTYPE)
+    out = np.zeros(max(len(raw), 1), dtype=ENCOUNTER_RECORD_DTYPE)
+    _check(lib.nbody_encounter_finish(raw.ctypes.data, len(raw), float(horizon), out.ctypes.data))
+    return _encounter_list(out[:len(raw)])
+
+
+def first_contacts(enc, n):
+    """Per body of n, from an encounters() list: {"t": the earliest contact time (+inf: none), "partner": the other body of
+    that encounter (-1; ties in t go to the earlier record of the list), "count": the encounters the body is part of}."""
+    t = np.full(n, np.inf)
+    partner = np.full(n, -1, dtype=np.int32)
+    m = len(enc)
+    body = np.concatenate([enc["i"], enc["j"]]).astype(np.int64)
+    other = np.concatenate([enc["j"], enc["i"]])
+    rec = np.concatenate([np.arange(m), np.arange(m)])
+    order = np.argsort(rec, kind="stable")                      # the list is sorted by t: a body's first record is its earliest
+    body, other, rec = body[order], other[order], rec[order]
+    who, first = np.unique(body, return_index=True)
+    t[who] = enc["t"][rec[first]]
+    partner[who] = other[first]
+    count = np.bincount(body, minlength=n).astype(np.int64)
+    return {"t": t, "partner": partner, "count": count}
+
+
 def _reserve_tracks(call, samples, ids, potential):
     """-> (samples, has_phi): what tracks() needs to size its buffers."""
     k = 0 if ids is None else len(ids)
@@ -795,6 +864,20 @@ class Stepper:
         "pairs": all of them, "n_bodies", "edges2": the squared edges that were sent}.  Not collective."""
         return _pair_counts(lambda *a: lib.nbody_get_pair_counts(self._ctx, *a), 1, edges, points, squared)[0]
 
+    def encounters(self, horizon=None, cap=None):
+        """nbody_get_encounters: the pairs of current bodies that touch within the next `horizon` seconds if every body keeps
+        its velocity (the uniform-motion estimate: no acceleration, no walls) -> (an ENCOUNTER_DTYPE array {"t": time of
+        contact, "i" < "j", "flags": ENCOUNTER_NOW | ENCOUNTER_END} sorted by (t, i, j), {"n_bodies", "pairs", "now", "end",
+        "missed", "horizon"}); a pair with neither flag touches strictly inside the horizon and overlaps at neither end.
+        horizon=None: the context's own time step, widened as the tracers widen it.  cap: the first guess of the room (None:
+        the capacity); a longer list is fetched with a second call.  Single-rank contexts only."""
+        if horizon is None:
+            d, steps = _CtxDesc(), ctypes.c_int64(0)
+            _check(lib.nbody_ctx_info(self._ctx, ctypes.byref(d), ctypes.byref(steps)))
+            horizon = float(np.float32(d.timestep)) if self.precision == F32 else float(d.timestep)
+        cap = max(self.capacity, 64) if cap is None else cap
+        return _encounters(lambda *a: lib.nbody_get_encounters(self._ctx, *a), 1, float(horizon), cap)[0]
+
     def stats(self):
         s = Stats()
         _check(lib.nbody_get_stats(self._ctx, ctypes.byref(s)))
@@ -1045,6 +1128,13 @@ class StepperBatch:
         points for all of them: a list of S dicts in the form (and with the numbers) a Stepper holding the system's state
         gives."""
         return _pair_counts(lambda *a: lib.nbody_batch_get_pair_counts(self._b, *a), self.systems, edges, points, squared)
+
+    def encounters(self, horizon, cap=None):
+        """nbody_batch_get_encounters: Stepper.encounters for every system in one launch: a list of S (array, info) pairs in
+        the form (and with the bits) a Stepper holding the system's state gives.  The kernel takes ONE horizon for the whole
+        batch, so it has to be given: a batch's systems may each have their own time step."""
+        cap = max(self.capacity, 64) if cap is None else cap
+        return _encounters(lambda *a: lib.nbody_batch_get_encounters(self._b, *a), self.systems, float(horizon), cap)
 
     def reserve_diagnostics(self, samples):
         """Room for `samples` recorded samples of every system on the device (0 frees it); empties the series."""

@@ -28,6 +28,7 @@
 #include "nbody_groups.hpp"
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
+#include "nbody_encounters.hpp"
 
 using namespace nbk;
 
@@ -88,6 +89,8 @@ struct nbody_batch {
     PairsState prs;
     // k nearest neighbours (nbody_batch_get_knn, nbody_knn.hpp): nothing is allocated before the first call
     KnnState knn;
+    // encounter queries (nbody_batch_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
+    EncState enc;
     // tracer particles (nbody_batch_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -112,6 +115,7 @@ void free_all(nbody_batch* b) {
     rows_free(b->nbr);
     groups_free(b->grp);
     pairs_free(b->prs);
+    encounters_free(b->enc);
     rows_free(b->knn);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
@@ -710,7 +714,7 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 
 // ---------------------------------------------------------------------------------------------------------
 // Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_knn, nbody_batch_get_groups,
-// nbody_batch_get_pair_counts; nbody_rows.hpp and the five query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
+// nbody_batch_get_pair_counts, nbody_batch_get_encounters; nbody_rows.hpp and the six query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
 // of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -783,6 +787,17 @@ int nbody_batch_get_pair_counts(nbody_batch* b, const nbody_vec2* points, int m,
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
         return pairs_run<decltype(t), RowsBatchCount>(who, site, b->prs, points, m, edges2, bins, counts, info, sync);
+    });
+}
+
+// Encounters (nbody_encounters.hpp): one horizon and one cap for every system, one launch.
+int nbody_batch_get_encounters(nbody_batch* b, double horizon, nbody_encounter* out, int cap, nbody_encounter_info* info) {
+    const char* who = "nbody_batch_get_encounters";
+    RowsSite site;
+    int rc = encounters_check_args(who, b, horizon, out, cap, info, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return encounters_run<decltype(t), RowsBatchCount>(who, site, b->V, b->enc, horizon, out, cap, info, sync);
     });
 }
 

@@ -31,6 +31,7 @@
 #include "nbody_groups.hpp"
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
+#include "nbody_encounters.hpp"
 
 using namespace nbk;
 
@@ -194,6 +195,8 @@ struct nbody_ctx {
     PairsState prs;
     // k nearest neighbours (nbody_get_knn, nbody_knn.hpp): nothing is allocated before the first call
     KnnState knn;
+    // encounter queries (nbody_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
+    EncState enc;
     // tracer particles (nbody_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -624,6 +627,7 @@ void free_all(nbody_ctx* c) {
     rows_free(c->nbr);
     groups_free(c->grp);
     pairs_free(c->prs);
+    encounters_free(c->enc);
     rows_free(c->knn);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
@@ -1678,8 +1682,8 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_groups, nbody_get_pair_counts; nbody_rows.hpp
-// and the five query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
+// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_groups, nbody_get_pair_counts, nbody_get_encounters;
+// nbody_rows.hpp and the six query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
 // every rank holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -1764,6 +1768,23 @@ int nbody_get_pair_counts(nbody_ctx* c, const nbody_vec2* points, int m, const d
     if (rc != NBODY_OK || (rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return pairs_run<decltype(t), RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync);
+    });
+}
+
+// Encounters (nbody_encounters.hpp): the one row query that reads the velocities, which a rank holds for its own range only -
+// with one rank that is everything, Vown indexed like J.  A context of more than one rank is refused, as for the tracers.
+int nbody_get_encounters(nbody_ctx* c, double horizon, nbody_encounter* out, int cap, nbody_encounter_info* info) {
+    const char* who = "nbody_get_encounters";
+    RowsSite site;
+    int rc = encounters_check_args(who, c, horizon, out, cap, info, 1);
+    if (rc != NBODY_OK) return rc;
+    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
+        return nbody_fail(NBODY_ERR_STATE, "%s: encounters need a single-rank context without an exchange (world %d, flags 0x%x): "
+                                           "a rank holds only its own velocities, a query across ranks is not built", who,
+                          c->desc.world, c->desc.flags);
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return encounters_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->enc, horizon, out, cap, info, sync);
     });
 }
 
