@@ -11,6 +11,7 @@ import pytest
 
 import knn_cases as kc
 import neighbor_cases as nc
+import sharded_cases as sc
 from test_gpu_batch import params_of
 from test_gpu_neighbors import dense_bodies, dense_field, small_stepper
 
@@ -227,7 +228,9 @@ def test_not_collective(nb):
     pts = kc.probe_points(nc.widen(b)[0], 300, seed=8, field=dense_field(n))
     grp = nb.StepperGroup(2, cfg=cfg)                             # NBODY_FLAG_GROUP_EXCHANGE, both ranks on the one GPU
     grp.upload(b)
-    grp.step(3)                                                   # past the exchange
+    steps = sc.LAG + 2                                            # past the exchange lag (nbody_ctx::kLag)
+    assert steps > sc.LAG
+    grp.step(steps)
     d = grp.download()
     P, _ = nc.widen(d)
     assert len(P) < n

@@ -2,7 +2,8 @@
 
 The read-outs - nbody_group_diagnostics, nbody_get_field, nbody_get_neighbors, nbody_get_groups, nbody_render_image and the
 state file - were each checked on a StepperGroup two steps after an upload, inside nbody_ctx::kLag = 4: the slots still
-laid out for the uploaded count, every rank with its first range.  Here the runs of sharded_cases.py go 12 steps on 8 and 3
+laid out for the uploaded count, every rank with its first range; nbody_get_knn and nbody_get_pair_counts, which came
+later, each at one state on two or three ranks.  Here the runs of sharded_cases.py go 12 steps on 8 and 3
 ranks (fp32 and fp64) and on the single-rank RCCL context; the count falls below a quarter, ranks - the gathering rank 0
 among them - lose their range, others keep a ragged tail, and the gather areas shrink (tests/test_sharded_cases_cpu.py
 proves all of that on the CPU oracle).
@@ -11,8 +12,8 @@ After EVERY step the state is anchored: the download equals the oracle bit for b
 nbody_partition's, the ranges tile [0, n).  A read-out that then disagrees with its model is wrong itself.  At the
 checkpoints (upload, after steps 4, 5, 8, 12) every read-out is taken through every rank - the ranks that own nothing
 included - and compared with the models (exact_phi / check_totals / check_phi, field_cases, neighbor_cases, group_cases,
-the oracle's renderer) and with a plain Stepper that is stepped alongside and holds the same bits.  Every comparison is
-exact but the two against long-double references, which use the bounds their own test files derive."""
+knn_cases, pair_cases, the oracle's renderer) and with a plain Stepper that is stepped alongside and holds the same bits.
+Every comparison is exact but the two against long-double references, which use the bounds their own test files derive."""
 import ctypes
 import functools
 import os
@@ -23,9 +24,11 @@ import pytest
 
 import field_cases as fc
 import group_cases as gc
+import knn_cases as kc
 import lineage_cases as lc
 import neighbor_cases as nc
 import oracle_lib as ol
+import pair_cases as pc
 import sharded_cases as sc
 import test_gpu_diagnostics as dg
 import test_gpu_field as gf
@@ -90,6 +93,14 @@ def probe_points(run):
     return pts
 
 
+KNN_K = 9                                                       # one past a tier boundary of the k nearest
+
+
+def pair_edges2(run):
+    """The squared edges of the pair counts of a run: 10 geometric bins up to a quarter of the field."""
+    return np.geomspace(1.0, float(lc.FIELD_OF[run[0]]) ** 2 / 16.0, 11)
+
+
 @functools.lru_cache(maxsize=None)
 def references(run, precision, step):
     """What the models say about the oracle's state after `step` steps - the state every context under test has been shown
@@ -107,6 +118,11 @@ def references(run, precision, step):
     ref["touching"] = gc.model_groups(Pw, Rw, 0.0, 1.0)
     ref["centres"] = gc.model_groups(Pw, Rw, sc.CENTRE_LINK[run], 0.0)
     assert 1 < ref["centres"]["n_groups"] < st.n, (run, step, ref["centres"]["n_groups"])
+    ref["knn"] = kc.model_knn(Pw, KNN_K)
+    ref["knn_at_points"] = kc.model_knn(Pw, KNN_K, points=pts)
+    ref["pairs"] = pc.model_pair_counts(Pw, pair_edges2(run))
+    ref["pairs_at_points"] = pc.model_pair_counts(Pw, pair_edges2(run), pts)
+    assert st.n > KNN_K and ref["pairs"]["counts"].sum() > 0 and ref["pairs_at_points"]["counts"].sum() > 0, (run, step)
     if step in sc.EXACT_FIELD_AT:
         ref["field"] = fc.exact_field(P, M, rows=np.arange(st.n))
         ref["field_at_points"] = fc.exact_field(P, M, points=pts)
@@ -159,6 +175,22 @@ def check_readouts(nb, ctx, plain, got, run, precision, step, what):
             grp = r.groups(link, scale)
             gc.assert_same(grp, ref[key], "%s groups %s" % (w, key))
             assert 1 <= grp["sweeps"] <= n + 1, (w, key, grp["sweeps"])
+    # the k nearest and the pair counts: the bit-exact models and the plain context, own rows and explicit points
+    e2 = pair_edges2(run)
+    kc.assert_same(plain.knn(KNN_K), ref["knn"], what + ": knn, plain context")
+    kc.assert_same(plain.knn(KNN_K, pts), ref["knn_at_points"], what + ": knn at points, plain context")
+    pc.assert_same(plain.pair_counts(e2, squared=True), ref["pairs"], what + ": pair counts, plain context")
+    pc.assert_same(plain.pair_counts(e2, points=pts, squared=True), ref["pairs_at_points"], what + ": pair counts at points, plain context")
+    for g, r in enumerate(ranks):
+        w = "%s: rank %d (owns %d)" % (what, g, own[g])
+        kc.assert_same(r.knn(KNN_K), ref["knn"], w + " knn")
+        kc.assert_same(r.knn(KNN_K, pts), ref["knn_at_points"], w + " knn at points")
+        got_pairs = r.pair_counts(e2, squared=True)
+        pc.assert_same(got_pairs, ref["pairs"], w + " pair counts")
+        pc.check_sum(got_pairs, n * (n - 1) // 2, w)
+        got_pairs = r.pair_counts(e2, points=pts, squared=True)
+        pc.assert_same(got_pairs, ref["pairs_at_points"], w + " pair counts at points")
+        pc.check_sum(got_pairs, sc.POINTS * n, w)
     # render: fp32 against the oracle's renderer on the downloaded block, fp64 (the oracle draws fp32 only) against the
     # plain context
     width, height = sc.IMAGE
