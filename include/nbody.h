@@ -691,6 +691,106 @@ int nbody_batch_get_encounters(struct nbody_batch* b, double horizon, nbody_enco
 int nbody_encounter_finish(const nbody_encounter_raw* raw, int count, double horizon, nbody_encounter* out /* [count] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Bound-pair queries (the reference has none): two-body binaries within a separation.  Which pairs of bodies
+ * are gravitationally bound to each other, and on what orbit: the precursor of nearly every merger of this stepper, and the
+ * binary census that goes with the pair counts and the groups.  The one read-out that sets masses and velocities against
+ * positions.  PHYSICS: this is the ISOLATED TWO-BODY estimate on the state of this instant: the energy of the relative orbit
+ * of i and j alone, every other body left out, point masses, no walls.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the
+ * records (X, Y, M, R) and velocities (VX, VY) of the n current bodies, widened exactly from fp32 or taken as they are from
+ * fp64.  G2 = 2.0 * (double)6.67408e-11f, an exact doubling of the library's G.  sep2 is the SQUARED largest separation
+ * looked at: sep2 >= 0, +inf allowed; squared like edges2 of the pair counts.  For an unordered pair i < j
+ *     dx = X_j - X_i;  dy = Y_j - Y_i;  dvx = VX_j - VX_i;  dvy = VY_j - VY_i
+ *     d2 = (dx*dx) + (dy*dy)                          the d2 of nbody_get_neighbors, same bits
+ *     coincident = d2 == 0                            counted, never listed (no orbit)
+ *     near  = 0 < d2 && d2 <= sep2
+ *     v2 = (dvx*dvx) + (dvy*dvy);   mu = G2 * (M_i + M_j)
+ *     w  = (v2*v2) * d2;            k  = mu * mu
+ *     bound = near && 0 < mu && k < +inf && w < k     v2*r < 2G(m_i+m_j), i.e. two-body energy < 0, squared
+ *     hz = (dx*dvy) - (dy*dvx);     b = (dx*dvx) + (dy*dvy);    s = R_i + R_j
+ *     flags: NBODY_BINARY_OVERLAP where d2 <= s*s (the overlap predicate of nbody_get_neighbors, same bits);
+ *            NBODY_BINARY_APPROACHING where b < 0
+ * A bound pair is reported as {a, ecc, period, sep, i, j, flags} with i < j; the list is sorted by (i, j) ascending, a key
+ * that is exact and total whatever the values are (order by `a` in the caller if wanted).  Per bound pair, from its raw
+ * record {d2, v2, mu, hz}, nbody_binary_finish computes with the C library's sqrt and /
+ *     r = sqrt(d2);  gm = 0.5*mu;  eps = (0.5*v2) - (gm/r)
+ *     a      = eps < 0 ? gm / (-(eps+eps)) : +inf                                     semi-major axis
+ *     e2     = 1.0 + (((eps+eps) * (hz*hz)) / (gm*gm));   ecc = e2 > 0 ? sqrt(e2) : +0.0
+ *     period = a < +inf ? 6.283185307179586 * sqrt(((a*a)*a) / gm) : +inf
+ *     sep    = r
+ * The guards eps < 0 and e2 > 0: the device's squared predicate and the host's rounded eps may disagree within a few ulps of
+ * a parabolic orbit, and e2 may round to 0 or below within a few ulps of a circular one; the guards make the outcome defined
+ * (a = period = +inf; ecc = +0), not NaN.
+ * info: n_bodies = n; pairs = the bound pairs, the ones listed; near = all pairs with 0 < d2 <= sep2, bound or not (the
+ * denominator of a binary fraction); coincident = the pairs i < j at d2 == 0, whatever sep2 is; overlapping / approaching =
+ * the listed pairs with that bit; sep2 = the argument.  What follows from the definition:
+ *   - symmetry: the predicate, hz and the flags are symmetric bit for bit - all four differences change sign together and
+ *     every product holds two of them, M_i + M_j and R_i + R_j commute - so one orientation suffices and the result does not
+ *     depend on which;
+ *   - NaN: a NaN coordinate, velocity or mass makes every comparison it reaches fail: the pair is neither bound nor listed.
+ *     A NaN position makes d2 NaN, so the pair does not count in near (or coincident) either; a NaN velocity or mass leaves
+ *     the pair in near;
+ *   - sep2 = +inf: every pair at finite non-zero d2 is near (a pair at d2 = +inf is too, and is never bound: w is +inf or NaN);
+ *   - 2 * coincident == nbody_diag.coincident_pairs on the same state;
+ *   - near + coincident == counts[0] of nbody_get_pair_counts with edges2 = {0, nextafter(sep2, +inf)} on the same state,
+ *     for finite sep2;
+ *   - it is independent of the semantics, like the other read-outs: a literal context's frozen tail counts with its stored
+ *     velocity;
+ *   - the result is a function of the state and sep2 only: the device appends in any order, the sort fixes the list.
+ * Division of labour: the device decides near, bound and the flags for all n (n - 1) / 2 pairs, with subtractions,
+ * multiplies, additions and compares only - boundness needs no divide and no square root - counts pairs / near / coincident
+ * / overlapping / approaching in 64-bit integers, and appends a raw record per bound pair - nbody_binary_raw: i, j, flags,
+ * d2, v2, mu, hz - to a log of cap records per system; records past cap are counted, not stored.  nbody_binary_finish, a
+ * pure host function in plain C that needs no GPU, computes the orbit as above, orders (i, j), and sorts `count` records
+ * into out; it reads only the two flag bits.
+ * nbody_get_binaries synchronises, reads only, and never changes what later steps compute: state, pair counter, events,
+ * tracers.  out has room for cap records; info is always filled once the walk has run.  pairs > cap: NBODY_ERR_CAPACITY, out
+ * untouched, info complete - the caller repeats with cap >= info.pairs, so the list is never a nondeterministic subset.  out
+ * may be NULL with cap == 0: the counts only, NBODY_OK whatever pairs is.  An empty or one-body system gives zeros.  The
+ * device log, the counters and their pinned staging are allocated on the first call and grown to the largest cap seen; a
+ * context or batch that never calls it allocates nothing and launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: a NULL handle or info; a NaN or negative sep2; cap < 0; NULL out with
+ * cap > 0; cap x 48 bytes (a batch: systems x cap x 48) above 2^31; nbody_binary_finish: count < 0, NULL raw or out with
+ * count > 0.  NBODY_ERR_STATE: before an upload; on a context with world > 1, NBODY_FLAG_GROUP_EXCHANGE or
+ * NBODY_FLAG_FORCE_COMM: a rank holds only its own bodies' velocities, and a query across ranks has not been built (the
+ * encounters' restriction).  A device-side failure is reported as by every synchronising call.
+ * How (csrc/nbody_binaries.hpp): one lane per body over the triangular tile walk of nbody_get_encounters (j < i, each pair
+ * once at the higher row) with six LDS planes, x, y, m, r, vx, vy (12 KiB double-buffered).  Per pair the hot loop is that of
+ * nbody_get_pair_counts: 2 LDS reads, 2 subtractions, 3 operations for d2 and one compare, d2 <= sep2, four pairs under one
+ * wave-level branch.  Only a pair that passes reads the four other planes: coincident pairs are set aside, a near pair pays
+ * 10 more fp64 operations and three compares for `bound`, a bound pair 8 more and two compares for hz and the flags, and
+ * one 64-bit atomic for its slot in the log.  near and coincident are counted per lane in 32 bits and added per wave with
+ * one 64-bit atomic each, as are the two flag counts.  A call for the counts only (cap == 0) takes no slot: its lanes count
+ * the bound pairs the same way.  No device-side waiting, no retry loop.
+ * Cost (one MI355X, fp32; profiles/binaries_probe.txt): the stock state of N = 262144, n = 130965 bodies after 3 steps
+ * (8.58e9 pairs, max |v| 325), every figure measured in that file, in one run with nbody_get_pair_counts' kernel at the one
+ * bin [0, sep2) (5.49 ms) and nbody_get_encounters' at h = the time step (18.73 ms).  At sep = 1024 (7.8e-5 of the pairs
+ * near: 666502, of them 652339 bound - the stock bodies start at rest) the kernel takes 5.84 ms for the counts only, 1.07
+ * times the pair counts, and 9.26 ms (1.69 times) with the list: the 652339 slot atomics, all on one address, and their
+ * records are the 3.4 ms.  At sep = 128 (289 near pairs) 5.36 ms, 0.98 times the pair counts: the hot loop is that kernel's.
+ * At sep2 = +inf, the counts only (every pair near, 524411846 bound): 35.2 ms, 1.88 times the encounter kernel - every pair
+ * then takes the branches of the rare path one after the other.  Whole calls: the counts only 5.7 ms at sep = 1024 and 35.4
+ * ms at +inf; Stepper.binaries() with room for the 652339 records 94.6 ms (the 31 MB copy, the finish's sort and the
+ * wrapper's repacking are the 85 ms), 100.4 ms when it has to ask for the counts first.  A batch of 256 x 1024 at sep = 1024
+ * (10247 bound pairs): 0.094 ms of kernel, 1.32 ms per call.  A list at sep2 = +inf on such a cold state pays the slot
+ * atomic 5e8 times (1392 ms measured with slots taken for the counts too, before cap == 0 skipped them) and overflows any cap
+ * the 2^31-byte rule admits: ask for the counts.  Not measured: fp64 contexts, any other state.
+ * nbody_batch_get_binaries: the same for every system of a batch in ONE launch, whatever S is, with the one sep2 and the one
+ * cap for all of them: system s's list at out + s * cap (pairs records, the rest of the slice is left unchanged), its record
+ * at info[s].  If any system has pairs > cap the call is NBODY_ERR_CAPACITY, out untouched, every info complete.  System s
+ * gives exactly what an nbody_ctx holding that system's state gives.  A count outside [0, capacity] is treated as 0 and
+ * reported for that system, as by nbody_batch_get_neighbors.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_binary { double a, ecc, period, sep; int32_t i, j; uint32_t flags, reserved; } nbody_binary;   /* 48 bytes */
+typedef struct nbody_binary_raw { int32_t i, j; uint32_t flags, reserved; double d2, v2, mu, hz; } nbody_binary_raw;   /* 48 bytes */
+typedef struct nbody_binary_info { int64_t n_bodies, pairs, near, coincident, overlapping, approaching; double sep2; } nbody_binary_info;   /* 56 bytes */
+enum { NBODY_BINARY_OVERLAP = 1u << 0, NBODY_BINARY_APPROACHING = 1u << 1 };
+int nbody_get_binaries(nbody_ctx* ctx, double sep2, nbody_binary* out, int cap, nbody_binary_info* info);
+int nbody_batch_get_binaries(struct nbody_batch* b, double sep2, nbody_binary* out /* [systems * cap] */, int cap,
+                             nbody_binary_info* info /* [systems] */);
+int nbody_binary_finish(const nbody_binary_raw* raw, int count, nbody_binary* out /* [count] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Tracer particles (the reference has none): massless probes advected with every step.
  * A tracer has a position and a velocity {x, y, vx, vy}, always fp64 whatever the context's precision.  It behaves like a
  * body of mass 0 and radius 0 that nothing collides with: it is attracted by the bodies; it attracts nothing and is never a

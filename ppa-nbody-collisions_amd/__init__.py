@@ -142,6 +142,18 @@ ENCOUNTER_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("pairs", np.int64), ("
 ENCOUNTER_RAW_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("flags", np.uint32), ("reserved", np.uint32),
                                 ("c", np.float64), ("b", np.float64), ("disc", np.float64)])
 
+# struct nbody_binary, nbody_binary_raw, nbody_binary_info as numpy records (Stepper.binaries, StepperBatch.binaries,
+# binary_finish); BINARY_DTYPE is what they return: the record without its reserved word
+BINARY_OVERLAP, BINARY_APPROACHING = 1, 2
+BINARY_RECORD_DTYPE = np.dtype([("a", np.float64), ("ecc", np.float64), ("period", np.float64), ("sep", np.float64),
+                                ("i", np.int32), ("j", np.int32), ("flags", np.uint32), ("reserved", np.uint32)])
+BINARY_DTYPE = np.dtype([("a", np.float64), ("ecc", np.float64), ("period", np.float64), ("sep", np.float64),
+                         ("i", np.int32), ("j", np.int32), ("flags", np.uint32)])
+BINARY_RAW_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("flags", np.uint32), ("reserved", np.uint32),
+                             ("d2", np.float64), ("v2", np.float64), ("mu", np.float64), ("hz", np.float64)])
+BINARY_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("pairs", np.int64), ("near", np.int64), ("coincident", np.int64),
+                              ("overlapping", np.int64), ("approaching", np.int64), ("sep2", np.float64)])
+
 # struct nbody_tracer / nbody_tracer_info as numpy records (Stepper.set_tracers / tracers, StepperBatch likewise)
 TRACER_DTYPE = np.dtype([("pos", np.float64, (2,)), ("vel", np.float64, (2,))])
 TRACER_INFO_DTYPE = np.dtype([("steps", np.int64), ("coincident", np.int64), ("count", np.int32), ("flags", np.uint32)])
@@ -216,6 +228,9 @@ SYMBOLS = {
     "nbody_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
     "nbody_batch_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
     "nbody_encounter_finish": (_i, [_vp, _i, _d, _vp]),
+    "nbody_get_binaries": (_i, [_vp, _d, _vp, _i, _vp]),
+    "nbody_batch_get_binaries": (_i, [_vp, _d, _vp, _i, _vp]),
+    "nbody_binary_finish": (_i, [_vp, _i, _vp]),
     "nbody_tracers_set": (_i, [_vp, _vp, _i, ctypes.c_uint32]),
     "nbody_tracers_get": (_i, [_vp, _vp, _vp, _i, _vp]),
     "nbody_batch_tracers_set": (_i, [_vp, _vp, _i, ctypes.c_uint32]),
@@ -597,6 +612,47 @@ def first_contacts(enc, n):
     return {"t": t, "partner": partner, "count": count}
 
 
+def _binary_list(rec):
+    out = np.zeros(len(rec), dtype=BINARY_DTYPE)
+    for f in BINARY_DTYPE.names:
+        out[f] = rec[f]
+    return out
+
+
+def _binary_info(info):
+    d = {k: int(info[k]) for k in ("n_bodies", "pairs", "near", "coincident", "overlapping", "approaching")}
+    d["sep2"] = float(info["sep2"])
+    return d
+
+
+def _binaries(call, systems, max_sep, squared, cap):
+    """nbody_get_binaries through `call(sep2, out, cap, info)` -> one (BINARY_DTYPE array, info dict) per system.  max_sep is
+    squared with one float64 multiply unless `squared`.  On NBODY_ERR_CAPACITY the call is repeated once with the largest
+    info.pairs."""
+    sep = float(max_sep)
+    sep2 = sep if squared else sep * sep
+    S = max(systems, 1)
+    info = np.zeros(S, dtype=BINARY_INFO_DTYPE)
+    cap = max(int(cap), 0)
+    buf = np.zeros((S, max(cap, 1)), dtype=BINARY_RECORD_DTYPE)
+    status = call(sep2, buf.ctypes.data, cap, info.ctypes.data)
+    if status == -7:                                            # NBODY_ERR_CAPACITY: info is complete
+        cap = int(info["pairs"].max())
+        buf = np.zeros((S, max(cap, 1)), dtype=BINARY_RECORD_DTYPE)
+        status = call(sep2, buf.ctypes.data, cap, info.ctypes.data)
+    _check(status)
+    return [(_binary_list(buf[s, :int(info["pairs"][s])]), _binary_info(info[s])) for s in range(systems)]
+
+
+def binary_finish(raw):
+    """nbody_binary_finish, the host half of binaries(): BINARY_RAW_DTYPE records {i, j, flags, d2, v2, mu, hz} of bound pairs
+    -> the BINARY_DTYPE list {a, ecc, period, sep, i, j, flags} sorted by (i, j).  Needs no GPU."""
+    raw = np.ascontiguousarray(raw, dtype=BINARY_RAW_DTYPE)
+    out = np.zeros(max(len(raw), 1), dtype=BINARY_RECORD_DTYPE)
+    _check(lib.nbody_binary_finish(raw.ctypes.data, len(raw), out.ctypes.data))
+    return _binary_list(out[:len(raw)])
+
+
 def _reserve_tracks(call, samples, ids, potential):
     """-> (samples, has_phi): what tracks() needs to size its buffers."""
     k = 0 if ids is None else len(ids)
@@ -878,6 +934,16 @@ class Stepper:
         cap = max(self.capacity, 64) if cap is None else cap
         return _encounters(lambda *a: lib.nbody_get_encounters(self._ctx, *a), 1, float(horizon), cap)[0]
 
+    def binaries(self, max_sep, squared=False, cap=None):
+        """nbody_get_binaries: the pairs of current bodies no further apart than `max_sep` (a length; a squared length with
+        squared=True; inf allowed) that are gravitationally bound as an isolated two-body system -> (a BINARY_DTYPE array
+        {"a": semi-major axis, "ecc", "period", "sep": the separation now, "i" < "j", "flags": BINARY_OVERLAP |
+        BINARY_APPROACHING} sorted by (i, j), {"n_bodies", "pairs", "near": all pairs within max_sep, "coincident",
+        "overlapping", "approaching", "sep2"}).  cap: the first guess of the room (None: the capacity); a longer list is
+        fetched with a second call.  Single-rank contexts only."""
+        cap = max(self.capacity, 64) if cap is None else cap
+        return _binaries(lambda *a: lib.nbody_get_binaries(self._ctx, *a), 1, max_sep, squared, cap)[0]
+
     def stats(self):
         s = Stats()
         _check(lib.nbody_get_stats(self._ctx, ctypes.byref(s)))
@@ -1135,6 +1201,12 @@ class StepperBatch:
         batch, so it has to be given: a batch's systems may each have their own time step."""
         cap = max(self.capacity, 64) if cap is None else cap
         return _encounters(lambda *a: lib.nbody_batch_get_encounters(self._b, *a), self.systems, float(horizon), cap)
+
+    def binaries(self, max_sep, squared=False, cap=None):
+        """nbody_batch_get_binaries: Stepper.binaries for every system in one launch, with the one separation for all of
+        them: a list of S (array, info) pairs in the form (and with the bits) a Stepper holding the system's state gives."""
+        cap = max(self.capacity, 64) if cap is None else cap
+        return _binaries(lambda *a: lib.nbody_batch_get_binaries(self._b, *a), self.systems, max_sep, squared, cap)
 
     def reserve_diagnostics(self, samples):
         """Room for `samples` recorded samples of every system on the device (0 frees it); empties the series."""

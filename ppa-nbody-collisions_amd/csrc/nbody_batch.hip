@@ -29,6 +29,7 @@
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
 #include "nbody_encounters.hpp"
+#include "nbody_binaries.hpp"
 
 using namespace nbk;
 
@@ -91,6 +92,8 @@ struct nbody_batch {
     KnnState knn;
     // encounter queries (nbody_batch_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
+    // bound-pair queries (nbody_batch_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
+    BinState bin;
     // tracer particles (nbody_batch_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -116,6 +119,7 @@ void free_all(nbody_batch* b) {
     groups_free(b->grp);
     pairs_free(b->prs);
     encounters_free(b->enc);
+    binaries_free(b->bin);
     rows_free(b->knn);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
@@ -714,7 +718,7 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 
 // ---------------------------------------------------------------------------------------------------------
 // Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_knn, nbody_batch_get_groups,
-// nbody_batch_get_pair_counts, nbody_batch_get_encounters; nbody_rows.hpp and the six query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
+// nbody_batch_get_pair_counts, nbody_batch_get_encounters, nbody_batch_get_binaries; nbody_rows.hpp and the seven query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
 // of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -798,6 +802,17 @@ int nbody_batch_get_encounters(nbody_batch* b, double horizon, nbody_encounter* 
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
         return encounters_run<decltype(t), RowsBatchCount>(who, site, b->V, b->enc, horizon, out, cap, info, sync);
+    });
+}
+
+// Bound pairs (nbody_binaries.hpp): one sep2 and one cap for every system, one launch.
+int nbody_batch_get_binaries(nbody_batch* b, double sep2, nbody_binary* out, int cap, nbody_binary_info* info) {
+    const char* who = "nbody_batch_get_binaries";
+    RowsSite site;
+    int rc = binaries_check_args(who, b, sep2, out, cap, info, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return binaries_run<decltype(t), RowsBatchCount>(who, site, b->V, b->bin, sep2, out, cap, info, sync);
     });
 }
 

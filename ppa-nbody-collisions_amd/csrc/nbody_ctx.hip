@@ -32,6 +32,7 @@
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
 #include "nbody_encounters.hpp"
+#include "nbody_binaries.hpp"
 
 using namespace nbk;
 
@@ -197,6 +198,8 @@ struct nbody_ctx {
     KnnState knn;
     // encounter queries (nbody_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
+    // bound-pair queries (nbody_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
+    BinState bin;
     // tracer particles (nbody_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -628,6 +631,7 @@ void free_all(nbody_ctx* c) {
     groups_free(c->grp);
     pairs_free(c->prs);
     encounters_free(c->enc);
+    binaries_free(c->bin);
     rows_free(c->knn);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
@@ -1682,8 +1686,8 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_groups, nbody_get_pair_counts, nbody_get_encounters;
-// nbody_rows.hpp and the six query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
+// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_groups, nbody_get_pair_counts, nbody_get_encounters,
+// nbody_get_binaries; nbody_rows.hpp and the seven query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
 // every rank holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -1785,6 +1789,22 @@ int nbody_get_encounters(nbody_ctx* c, double horizon, nbody_encounter* out, int
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return encounters_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->enc, horizon, out, cap, info, sync);
+    });
+}
+
+// Bound pairs (nbody_binaries.hpp): reads the velocities too, so the encounters' restriction holds.
+int nbody_get_binaries(nbody_ctx* c, double sep2, nbody_binary* out, int cap, nbody_binary_info* info) {
+    const char* who = "nbody_get_binaries";
+    RowsSite site;
+    int rc = binaries_check_args(who, c, sep2, out, cap, info, 1);
+    if (rc != NBODY_OK) return rc;
+    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
+        return nbody_fail(NBODY_ERR_STATE, "%s: binaries need a single-rank context without an exchange (world %d, flags 0x%x): "
+                                           "a rank holds only its own velocities, a query across ranks is not built", who,
+                          c->desc.world, c->desc.flags);
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return binaries_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->bin, sep2, out, cap, info, sync);
     });
 }
 

@@ -1,6 +1,6 @@
 // csrc/nbody_rows.hpp -- a row per lane over the resident state: what the row queries (field evaluation, nbody_field.hpp;
 // neighbour queries, nbody_neighbors.hpp; group finding, nbody_groups.hpp; pair counts, nbody_pairs.hpp; the k nearest,
-// nbody_knn.hpp; encounters, nbody_encounters.hpp) have in common, on the device and
+// nbody_knn.hpp; encounters, nbody_encounters.hpp; bound pairs, nbody_binaries.hpp) have in common, on the device and
 // on the host.  Included after nbody_diag.hpp and before the query headers by both translation units: one system
 // (nbody_ctx.hip) and a batch (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride` apart, one set of points for
 // every system) share each query's one kernel.
@@ -21,8 +21,8 @@
 // (a fixed number of result records per row: a traits struct such as FieldQuery, NeighborQuery or KnnQuery is all it takes)
 // or, for another shape of result, from the pieces of rows_run - RowsSite's grid, count and sync, RowPoints,
 // rows_check_args.  The per-handle preamble and the precision dispatch are in the two .hip files.  field_at walks with
-// diag_walk_sums instead (see rows_walk); encounters_walk, which needs the velocities in two more planes, has its own copy of
-// the triangular walk.
+// diag_walk_sums instead (see rows_walk); encounters_walk and binaries_walk, which need the velocities (and masses) in more planes,
+// each have their own copy of the triangular walk.
 #pragma once
 #include <stddef.h>
 #include <string.h>
