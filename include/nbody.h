@@ -552,6 +552,62 @@ int nbody_get_groups(nbody_ctx* ctx, double link, double radius_scale, int32_t* 
 int nbody_batch_get_groups(struct nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Group energies (the reference has none): is a group held together by its own gravity?  The O(N^2) part on
+ * the device, the O(N) catalogue in plain C on the host.
+ * nbody_get_group_potential: with label[] the labels of nbody_get_groups for the same (link, radius_scale), for every
+ * current body i
+ *     phi_in[i] = -G * sum_{ j != i, label[j] == label[i], r_ij > 0 }  m_j / r_ij
+ * ONE running sum over j = 0 .. n-1 ascending, in fp64 on exactly widened records, a term being that of
+ * nbody_get_diagnostics (d2 = fma(dx, dx, dy*dy), the refined reciprocal square root, s = fma(m_j, y, s)).
+ * The contract in bits, the sub-state rule: let a group's members be i_0 < i_1 < ... < i_k; phi_in[i_a] has the bits that
+ * nbody_get_diagnostics puts in phi[a] for a context holding exactly those k + 1 bodies in that order.  A body that is no
+ * member is left out: its pair never reaches the sum, not even as a NaN.  Members at distance exactly 0 are left out and
+ * counted, as by the diagnostics; a row whose fast sum is not finite is redone with IEEE sqrt and divide over its members.
+ * label: bit for bit what nbody_get_groups returns for the same arguments; info: its four counts with the same values, and
+ * coincident = the ordered pairs (i, j) of one group at distance 0.  Arguments, errors and the cap rule (room in label AND in
+ * phi_in) are those of nbody_get_groups, with phi_in one more pointer that must not be NULL.  The call synchronises and reads
+ * positions, masses and radii of the replica only; it never changes what later steps compute and it is NOT collective.  No
+ * bodies: a zero record.  One body: phi_in[0] = -0.0 (-G * +0, as the diagnostics).
+ * nbody_batch_get_group_potential: the same for every system of a batch, every sweep and the potential ONE launch each
+ * whatever S is; system s's labels and potentials go to label + s * capacity and phi_in + s * capacity, the rest of each
+ * slice is left unchanged; info: one record per system (an empty system: {0, 0, 0, sweeps, 0}, as nbody_batch_get_groups).
+ * How (csrc/nbody_group_energy.hpp): the group finding as it is, then one lane per body over a full tile walk with the
+ * labels staged next to {x, y, m}; per four sources four integer compares, and a wave none of whose rows has a member among
+ * them skips the fp64 chain - exact, because a non-member is left out of the sum anyway.
+ *
+ * nbody_group_catalog (csrc/nbody_group_energy.c, no device): one record per group from the bodies, the labels and phi_in,
+ * sorted by label ascending.  Every sum is a plain s = s + term over the group's members in ascending index, every
+ * operation rounded on its own, no fma:
+ *     pass 1:  mass, sum m x, sum m y, sum m vx, sum m vy;   cx = (sum m x) / mass and likewise cy, vx, vy (mass == 0: NaN)
+ *     pass 2:  dvx = vx_i - vx;  dvy = vy_i - vy;  w = (dvx*dvx) + (dvy*dvy);  K2 += m_i * w;  P += m_i * phi_in_i;
+ *              bound member  <=>  ((0.5*w) + phi_in_i) < 0
+ *     kinetic = 0.5*K2;  potential = 0.5*P;  energy = kinetic + potential;  flags bit 0: energy < 0
+ * Groups past cap are counted in *n_groups and not stored; out == NULL with cap == 0 returns the count.  O(n) in time and
+ * memory.  NBODY_ERR_INVALID: n < 0; cap < 0; NULL n_groups; NULL out with cap > 0; with n > 0 a NULL array; a label outside
+ * [0, n) or one that is not the lowest index of its class (label[label[i]] != label[i], or label[i] > i) - found before
+ * anything is indexed by it.  NBODY_ERR_NOMEM: the one work array (n slots).
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_group_energy_info {
+    int32_t n_bodies, n_groups, largest, sweeps;   /* nbody_groups_info's, same values */
+    int64_t coincident;                            /* ordered pairs (i, j) of one group at distance 0, left out */
+} nbody_group_energy_info;                         /* 24 bytes */
+int nbody_get_group_potential(nbody_ctx* ctx, double link, double radius_scale, int32_t* label, double* phi_in, int cap,
+                              nbody_group_energy_info* info);
+int nbody_batch_get_group_potential(struct nbody_batch* b, double link, double radius_scale, int32_t* label /* [systems * capacity] */,
+                                    double* phi_in /* [systems * capacity] */, nbody_group_energy_info* info /* [systems] */);
+
+#define NBODY_GROUP_BOUND 1u                       /* nbody_group_record.flags bit 0: energy < 0 */
+typedef struct nbody_group_record {
+    double mass, cx, cy, vx, vy;     /* total mass, centre of mass, its velocity            */
+    double kinetic, potential;       /* T in the centre-of-mass frame; W = 0.5 sum m_i phi_in */
+    double energy;                   /* T + W                                               */
+    int32_t label, count;            /* lowest member index; members                        */
+    int32_t bound_members, flags;    /* members with 0.5|v_i - V|^2 + phi_in_i < 0; bit 0: energy < 0 */
+} nbody_group_record;                /* 80 bytes */
+int nbody_group_catalog(int n, const double* x, const double* y, const double* vx, const double* vy, const double* m,
+                        const int32_t* label, const double* phi_in, nbody_group_record* out, int cap, int32_t* n_groups);
+
+/* ---------------------------------------------------------------------------------------------------
  * Pair-separation counts (the reference has none): how many pairs lie in each bin of separation - the DD
  * (bodies with bodies) and DR (probe points with bodies) counts from which a two-point correlation function, a radial
  * distribution function g(r) or a Landy-Szalay estimate is made.  The one read-out that says how the bodies lie relative to

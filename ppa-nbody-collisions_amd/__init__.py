@@ -127,6 +127,13 @@ NEIGHBOR_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("overlaps",
 
 # struct nbody_groups_info as a numpy record (Stepper.groups, StepperBatch.groups)
 GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
+# nbody_group_energy_info (24 bytes) and nbody_group_record (80 bytes), include/nbody.h
+GROUP_ENERGY_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32),
+                                    ("coincident", np.int64)])
+GROUP_RECORD_DTYPE = np.dtype([("mass", np.float64), ("cx", np.float64), ("cy", np.float64), ("vx", np.float64),
+                               ("vy", np.float64), ("kinetic", np.float64), ("potential", np.float64), ("energy", np.float64),
+                               ("label", np.int32), ("count", np.int32), ("bound_members", np.int32), ("flags", np.int32)])
+GROUP_BOUND = 1                                                 # nbody_group_record.flags bit 0: energy < 0
 
 # struct nbody_pair_info as a numpy record (Stepper.pair_counts, StepperBatch.pair_counts)
 PAIR_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("rows", np.int64), ("pairs", np.int64), ("below", np.int64),
@@ -224,6 +231,9 @@ SYMBOLS = {
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
     "nbody_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp, _ip]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
+    "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
+    "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
+    "nbody_group_catalog": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
     "nbody_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
     "nbody_batch_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
@@ -522,6 +532,40 @@ def _knn_buffers(shape):
 
 def _groups_dict(label, info):
     return {"label": label, "n_groups": int(info["n_groups"]), "largest": int(info["largest"]), "sweeps": int(info["sweeps"])}
+
+
+def _group_potential_dict(label, phi, info):
+    d = _groups_dict(label, info)
+    d["phi"] = phi
+    d["coincident"] = int(info["coincident"])
+    return d
+
+
+def group_catalog(pos, vel, mass, label, phi):
+    """nbody_group_catalog, the host half of group_energies(): positions and velocities (n, 2), masses, the labels and the
+    in-group potential of group_potential() -> a GROUP_RECORD_DTYPE array, one record per group sorted by label: {mass,
+    cx, cy, vx, vy: the centre of mass and its velocity, kinetic: in that frame, potential: 0.5 sum m phi, energy, label,
+    count, bound_members: members with 0.5 |v - V|^2 + phi < 0, flags: GROUP_BOUND where energy < 0}.  Every sum is a plain
+    fp64 running sum over the group's members in ascending index.  Needs no GPU."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
+    vel = np.asarray(vel, dtype=np.float64).reshape(-1, 2)
+    n = len(pos)
+    cols = [np.ascontiguousarray(a, dtype=np.float64) for a in (pos[:, 0], pos[:, 1], vel[:, 0], vel[:, 1], mass, phi)]
+    label = np.ascontiguousarray(label, dtype=np.int32)
+    if len(vel) != n or label.shape != (n,) or any(c.shape != (n,) for c in cols):
+        raise ValueError("group_catalog: pos and vel (n, 2), mass, label and phi (n,) for the same n")
+    x, y, vx, vy, m, ph = cols
+    count = ctypes.c_int(0)
+    _check(lib.nbody_group_catalog(n, x.ctypes.data, y.ctypes.data, vx.ctypes.data, vy.ctypes.data, m.ctypes.data,
+                                   label.ctypes.data, ph.ctypes.data, None, 0, ctypes.byref(count)))
+    out = np.zeros(max(count.value, 1), dtype=GROUP_RECORD_DTYPE)
+    _check(lib.nbody_group_catalog(n, x.ctypes.data, y.ctypes.data, vx.ctypes.data, vy.ctypes.data, m.ctypes.data,
+                                   label.ctypes.data, ph.ctypes.data, out.ctypes.data, count.value, ctypes.byref(count)))
+    return out[:count.value]
+
+
+def _group_energies(bodies, g):
+    return group_catalog(bodies.Positions, bodies.Velocities, bodies.Masses, g["label"], g["phi"])
 
 
 def pair_edges2(edges, squared=False):
@@ -913,6 +957,28 @@ class Stepper:
         _check(lib.nbody_get_groups(self._ctx, link, radius_scale, label.ctypes.data, self.capacity, info.ctypes.data))
         return _groups_dict(label[:int(info["n_bodies"][0])].copy(), info[0])
 
+    def group_potential(self, link, radius_scale=1.0):
+        """nbody_get_group_potential: groups() and, for every current body, "phi": the potential (fp64) due to the other
+        members of its own group only, with the bits diagnostics(potential=True) gives for a context that holds exactly the
+        group's members in ascending order -> {"label", "phi", "n_groups", "largest", "sweeps", "coincident": ordered
+        pairs of one group at distance 0, left out}.  Not collective."""
+        label = np.zeros(max(self.capacity, 1), dtype=np.int32)
+        phi = np.zeros(max(self.capacity, 1), dtype=np.float64)
+        info = np.zeros(1, dtype=GROUP_ENERGY_INFO_DTYPE)
+        _check(lib.nbody_get_group_potential(self._ctx, link, radius_scale, label.ctypes.data, phi.ctypes.data, self.capacity,
+                                             info.ctypes.data))
+        n = int(info["n_bodies"][0])
+        return _group_potential_dict(label[:n].copy(), phi[:n].copy(), info[0])
+
+    def group_energies(self, link, radius_scale=1.0):
+        """group_potential(), a download and group_catalog(): one GROUP_RECORD_DTYPE record per group, sorted by label - is
+        the group held together by its own gravity?  Single-rank contexts only: a rank holds only its own velocities."""
+        if self.world > 1:
+            raise NbodyError(-9, "group_energies: a single-rank context is needed (world %d): a rank holds only its own "
+                                 "velocities, a catalogue across ranks is not built" % self.world)
+        g = self.group_potential(link, radius_scale)
+        return _group_energies(self.download(), g)
+
     def pair_counts(self, edges, points=None, squared=False):
         """nbody_get_pair_counts: the number of pairs in each bin of separation between the B + 1 `edges` (lengths; squared
         lengths with squared=True) - the unordered pairs of current bodies, or with `points` (m, 2) every (point, body)
@@ -997,6 +1063,10 @@ class StepperGroup:
     def groups(self, link, radius_scale=1.0, rank=0):
         """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
         return self.ranks[rank].groups(link, radius_scale)
+
+    def group_potential(self, link, radius_scale=1.0, rank=0):
+        """Stepper.group_potential through one rank: every rank's replica holds every position and mass."""
+        return self.ranks[rank].group_potential(link, radius_scale)
 
     def pair_counts(self, edges, points=None, squared=False, rank=0):
         """Stepper.pair_counts through one rank: every rank's replica holds every body, each gives the same numbers."""
@@ -1188,6 +1258,22 @@ class StepperBatch:
         info = np.zeros(max(self.systems, 1), dtype=GROUPS_INFO_DTYPE)
         _check(lib.nbody_batch_get_groups(self._b, link, radius_scale, label.ctypes.data, info.ctypes.data))
         return [_groups_dict(label[s, :int(info["n_bodies"][s])].copy(), info[s]) for s in range(self.systems)]
+
+    def group_potential(self, link, radius_scale=1.0):
+        """nbody_batch_get_group_potential: Stepper.group_potential for every system, every pair walk and the potential one
+        launch each for the whole batch: a list of S dicts in the form (and with the bits) a Stepper holding the system's
+        state gives."""
+        label = np.zeros((self.systems, max(self.capacity, 1)), dtype=np.int32)
+        phi = np.zeros((self.systems, max(self.capacity, 1)), dtype=np.float64)
+        info = np.zeros(max(self.systems, 1), dtype=GROUP_ENERGY_INFO_DTYPE)
+        _check(lib.nbody_batch_get_group_potential(self._b, link, radius_scale, label.ctypes.data, phi.ctypes.data,
+                                                   info.ctypes.data))
+        return [_group_potential_dict(label[s, :int(info["n_bodies"][s])].copy(), phi[s, :int(info["n_bodies"][s])].copy(),
+                                      info[s]) for s in range(self.systems)]
+
+    def group_energies(self, link, radius_scale=1.0):
+        """Stepper.group_energies for every system: a list of S GROUP_RECORD_DTYPE arrays."""
+        return [_group_energies(self.download(s), g) for s, g in enumerate(self.group_potential(link, radius_scale))]
 
     def pair_counts(self, edges, points=None, squared=False):
         """nbody_batch_get_pair_counts: Stepper.pair_counts for every system in one launch, with the one set of edges and

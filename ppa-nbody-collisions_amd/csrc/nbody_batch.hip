@@ -26,6 +26,7 @@
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
 #include "nbody_groups.hpp"
+#include "nbody_group_energy.hpp"
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
 #include "nbody_encounters.hpp"
@@ -86,6 +87,8 @@ struct nbody_batch {
     NeighborState nbr;
     // group finding (nbody_batch_get_groups, nbody_groups.hpp): nothing is allocated before the first call
     GroupsState grp;
+    // group energies (nbody_batch_get_group_potential, nbody_group_energy.hpp): nothing is allocated before the first call
+    GroupEnergyState gen;
     // pair-separation counts (nbody_batch_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
     PairsState prs;
     // k nearest neighbours (nbody_batch_get_knn, nbody_knn.hpp): nothing is allocated before the first call
@@ -117,6 +120,7 @@ void free_all(nbody_batch* b) {
     rows_free(b->fld);
     rows_free(b->nbr);
     groups_free(b->grp);
+    rows_free(b->gen);
     pairs_free(b->prs);
     encounters_free(b->enc);
     binaries_free(b->bin);
@@ -829,6 +833,19 @@ int nbody_batch_tracers_get(nbody_batch* b, nbody_tracer* out, nbody_field* last
     if (!b || !info) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_tracers_get: NULL argument");
     HIP_TRY(hipSetDevice(b->desc.device));
     return tracers_get(b->trc, b->stream, b->S, out, last, out ? b->trc.m : 0, info, [b] { return read_meta(b); });
+}
+
+// Group energies (nbody_group_energy.hpp): every sweep and the potential ONE launch each for the whole batch.
+int nbody_batch_get_group_potential(nbody_batch* b, double link, double radius_scale, int32_t* label, double* phi_in,
+                                    nbody_group_energy_info* info) {
+    const char* who = "nbody_batch_get_group_potential";
+    RowsSite site;
+    int rc = groups_check_args(who, link, radius_scale, {b, label, phi_in, info});
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return group_energy_run<decltype(t), RowsBatchCount>(who, site, b->grp, b->gen, (double)kG, link, radius_scale, label, phi_in,
+                                                             info, sync);
+    });
 }
 
 }  // extern "C"

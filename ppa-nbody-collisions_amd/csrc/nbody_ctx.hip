@@ -29,6 +29,7 @@
 #include "nbody_tracks.hpp"
 #include "nbody_neighbors.hpp"
 #include "nbody_groups.hpp"
+#include "nbody_group_energy.hpp"
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
 #include "nbody_encounters.hpp"
@@ -192,6 +193,8 @@ struct nbody_ctx {
     NeighborState nbr;
     // group finding (nbody_get_groups, nbody_groups.hpp): nothing is allocated before the first call
     GroupsState grp;
+    // group energies (nbody_get_group_potential, nbody_group_energy.hpp): nothing is allocated before the first call
+    GroupEnergyState gen;
     // pair-separation counts (nbody_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
     PairsState prs;
     // k nearest neighbours (nbody_get_knn, nbody_knn.hpp): nothing is allocated before the first call
@@ -629,6 +632,7 @@ void free_all(nbody_ctx* c) {
     rows_free(c->fld);
     rows_free(c->nbr);
     groups_free(c->grp);
+    rows_free(c->gen);
     pairs_free(c->prs);
     encounters_free(c->enc);
     binaries_free(c->bin);
@@ -1841,3 +1845,25 @@ void launch_ring_solo(nbody_ctx* c, const StepParams<float>& p, int nblocks, boo
     else launch_ring<1, 32, 8, false, 16, true>(c, p, nblocks, log, to, 0, tiles / 256 > 0 ? tiles / 256 : 1, tiles - tiles / 8);
 }
 }  // namespace
+
+// Group energies (nbody_group_energy.hpp): nbody_get_groups' arguments and errors, and the replica only - any rank may call
+// it.  Last in the file, so that the kernels before it are emitted as they were.
+extern "C" {
+
+int nbody_get_group_potential(nbody_ctx* c, double link, double radius_scale, int32_t* label, double* phi_in, int cap,
+                              nbody_group_energy_info* info) {
+    const char* who = "nbody_get_group_potential";
+    RowsSite site;
+    int rc = groups_check_args(who, link, radius_scale, {c, label, phi_in, info});
+    if (rc != NBODY_OK) return rc;
+    if (cap < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: cap = %d", who, cap);
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if (cap < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d rows, the context holds %d bodies", who, cap, site.n_bound);
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return group_energy_run<decltype(t), RowsOneCount>(who, site, c->grp, c->gen, (double)kG, link, radius_scale, label, phi_in,
+                                                           info, sync);
+    });
+}
+
+}  // extern "C"
