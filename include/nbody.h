@@ -395,6 +395,57 @@ struct nbody_batch;   /* the batched stepper, below */
 int nbody_batch_get_field(struct nbody_batch* b, const nbody_vec2* points, int m, nbody_field* out, int64_t* coincident);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Tidal tensor and jerk (the reference has none): how the field of nbody_get_field changes in space and, along
+ * the motion, in time.  The conventions are nbody_get_field's: over the n current bodies, IEEE fp64 (fp32 states widened
+ * exactly), G = (double)6.67408e-11f, independent of the semantics.  With d = x_j - x, r = |d| > 0 and dv = v_j - v:
+ *     T_ab(x)     = da_a/dx_b = G sum_j m_j (3 d_a d_b / r^5 - delta_ab / r^3)             -> tide[p].txx, txy, tyy
+ *     adot_a(x,v) = da_a/dt   = G sum_j m_j (dv_a / r^3 - 3 (d . dv) d_a / r^5)            -> jerk[p].X, Y
+ * (the tensor is the gradient of the Newtonian acceleration, the tidal approximation of e.g. Binney & Tremaine, Galactic
+ * Dynamics, 2nd ed., ch. 8; the jerk is the Hermite scheme's, Makino & Aarseth 1992, PASJ 44, 141, eq. 2, and feeds the step
+ * check eta sqrt(|a| / |adot|)).  A source at distance exactly 0 is left out of every sum and counted in *coincident.  The
+ * force law is the 3-D one in a plane: txx + tyy = G sum_j m_j / r_j^3 > 0, the tensor is not traceless and the missing tzz is
+ * the negative of that sum.  With every source at rest adot = T v.  A body's tidal (Hill) radius is (G m / lambda_max)^(1/3),
+ * lambda_max the larger eigenvalue of T.
+ * Rows.  points != NULL: m probe points, *n_out = m, m == 0 is legal and launches nothing; v is point_vel[p], or 0 with
+ * point_vel == NULL (a point at rest).  points == NULL: the current bodies' own positions and velocities; body i's self term
+ * is excluded by index and not counted, so *coincident equals nbody_get_field's; m is the room in tide (and jerk), *n_out the
+ * current count n; m < n is NBODY_ERR_CAPACITY with nothing written.
+ * jerk == NULL: the tensor alone, read from the replica only.  This form is NOT collective: any context may call it on its own -
+ * world > 1, a rank of a NBODY_FLAG_GROUP_EXCHANGE group, a NBODY_FLAG_FORCE_COMM context - and gets the bits of a plain context.
+ * jerk != NULL: the velocities are read, which a rank holds for its own range only: NBODY_ERR_STATE on a context with
+ * world > 1, NBODY_FLAG_GROUP_EXCHANGE or NBODY_FLAG_FORCE_COMM (the rule of nbody_get_encounters and the tracers).
+ * Order contract.  Every reported number is built from running sums over j = 0 .. n-1 ascending (sum m/r^3, the three sums
+ * 3 m u_a u_b / r^3 with u = d / r, and the two jerk sums): the bits depend on the state, the point and its velocity only, not on
+ * rank, world, transport, force kernel, m, the point's place in points, or whether the call also asks for the jerk - tide[] of a
+ * call with jerk has the bits of a call without.  A sum whose fast chain is not finite is redone by general code (IEEE sqrt and
+ * divide, hypot outside the normal range, distance-0 sources skipped and counted) in which a term overflows only where
+ * m_j / r_j^3 itself does; a finite sum is never replaced.  Error bounds, u = 2^-53 (derived in DESIGN.md 4.17):
+ *     |error of T_ab|  <= (n + 26) u G sum_j m_j (3 |d_a d_b| / r^2 + delta_ab) / r^3
+ *     |error of adot_a| <= (2 n + 28) u G sum_j m_j (|dv_a| + 3 (|dx dvx| + |dy dvy|) |d_a| / r^2) / r^3
+ * Non-finite inputs may give non-finite outputs.
+ * Both calls synchronise and read only: stepping after any number of calls is bit-identical to stepping without them.  The
+ * device points, point velocities, results and their pinned staging are allocated on the first call and grown to the largest m
+ * seen; a context that never calls allocates nothing and launches nothing more.
+ * NBODY_ERR_INVALID, found before any device call: a NULL handle, tide, n_out or coincident; m < 0; point_vel without points;
+ * point_vel with jerk == NULL; m x 24 bytes (a batch: systems x m x 24) above 2^31.  NBODY_ERR_STATE: before an upload.  A
+ * device-side failure is reported as by every synchronising call.
+ * Cost (one MI355X, fp32; profiles/tides_probe.txt): a whole call at N = 262144 with points == NULL 53.7 ms for the tensor (the
+ * kernel 51.4 ms: 1.28 times the time per pair of nbody_get_field's kernel, 1.34 expected from the 21 + 1 against 15 + 1 fp64
+ * instructions per pair) and 74.0 ms with the jerk (the kernel 71.1 ms: 1.76 times, 1.83 expected from 30 + 1), against 41.9 ms
+ * for nbody_get_field and 28.1 ms for a step; 65536 explicit points on that state 16.2 ms and, moving, with the jerk 21.1 ms
+ * (1.25 and 1.62 times nbody_get_field's kernel at the same points); a batch of 256 x 1024 with points == NULL 1.82 and 2.34 ms
+ * per call, 0.22 and 0.29 ms of it the kernel.
+ * nbody_batch_get_tides: the same for every system of a batch in ONE launch, with the one set of points and point velocities
+ * for all of them.  The layout of tide and jerk, the per-system coincident, the treatment of an empty system and of a count
+ * outside [0, capacity] are nbody_batch_get_field's.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_tide { double txx, txy, tyy; } nbody_tide;   /* 24 bytes */
+int nbody_get_tides(nbody_ctx* ctx, const nbody_vec2* points, const nbody_vec2* point_vel, int m, nbody_tide* tide,
+                    nbody_vec2* jerk /* may be NULL */, int* n_out, int64_t* coincident);
+int nbody_batch_get_tides(struct nbody_batch* b, const nbody_vec2* points, const nbody_vec2* point_vel, int m, nbody_tide* tide,
+                          nbody_vec2* jerk /* may be NULL */, int64_t* coincident /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Neighbour queries (the reference has none): for every row - a current body, or an arbitrary probe point -
  * the nearest of the n current bodies, its squared distance, and how many of them satisfy the reference's collision
  * predicate d^2 <= (r_i + r_j)^2 (src/nbody.cu:126-134) with the row right now.

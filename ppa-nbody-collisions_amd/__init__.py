@@ -102,6 +102,11 @@ class Field(ctypes.Structure):
     _fields_ = [("ax", ctypes.c_double), ("ay", ctypes.c_double), ("phi", ctypes.c_double)]
 
 
+class Tide(ctypes.Structure):
+    """struct nbody_tide (include/nbody.h): the tidal tensor da/dx at one point, fp64."""
+    _fields_ = [("txx", ctypes.c_double), ("txy", ctypes.c_double), ("tyy", ctypes.c_double)]
+
+
 class Neighbor(ctypes.Structure):
     """struct nbody_neighbor (include/nbody.h): the nearest source of one row and the row's overlap count."""
     _fields_ = [("d2", ctypes.c_double), ("index", ctypes.c_int32), ("overlaps", ctypes.c_int32)]
@@ -121,6 +126,9 @@ DIAG_DTYPE = np.dtype([("step", np.int64), ("n_bodies", np.int64), ("coincident_
 
 # struct nbody_field as a numpy record (Stepper.field, StepperBatch.field)
 FIELD_DTYPE = np.dtype([("acc", np.float64, (2,)), ("phi", np.float64)])
+
+# struct nbody_tide as a numpy record; Stepper.tides and StepperBatch.tides return it as (..., 3) float64: txx, txy, tyy
+TIDE_DTYPE = np.dtype([("txx", np.float64), ("txy", np.float64), ("tyy", np.float64)])
 
 # struct nbody_neighbor as a numpy record (Stepper.neighbors, StepperBatch.neighbors)
 NEIGHBOR_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("overlaps", np.int32)])
@@ -228,6 +236,7 @@ SYMBOLS = {
     "nbody_get_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_group_diagnostics": (_i, [_pp, _i, ctypes.POINTER(Diag), _vp]),
     "nbody_get_field": (_i, [_vp, _vp, _i, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
+    "nbody_get_tides": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
     "nbody_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp, _ip]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
@@ -259,6 +268,7 @@ SYMBOLS = {
     "nbody_batch_kernel_name": (ctypes.c_char_p, [_vp]),
     "nbody_batch_diagnostics": (_i, [_vp, ctypes.POINTER(Diag), _vp]),
     "nbody_batch_get_field": (_i, [_vp, _vp, _i, _vp, ctypes.POINTER(ctypes.c_int64)]),
+    "nbody_batch_get_tides": (_i, [_vp, _vp, _vp, _i, _vp, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_get_neighbors": (_i, [_vp, _vp, _i, _vp]),
     "nbody_batch_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "nbody_batch_get_groups": (_i, [_vp, _d, _d, _vp, _vp]),
@@ -484,6 +494,57 @@ def _field(call, points, capacity):
     _check(call(None if pts is None else pts.ctypes.data, m, buf.ctypes.data, ctypes.byref(n), ctypes.byref(coin)))
     return {"acc": np.ascontiguousarray(buf["acc"][:n.value]), "phi": np.ascontiguousarray(buf["phi"][:n.value]),
             "coincident": coin.value}
+
+
+def _tide_points(points, point_vel, jerk):
+    """The rows of tides(): _field_points' points, and their velocities - None (at rest), or shape (m, 2) like the points;
+    they need points and jerk=True.  Checked here, before the library is called."""
+    pts = _field_points(points)
+    if point_vel is None:
+        return pts, None
+    if pts is None:
+        raise ValueError("point_vel needs points: the bodies' own rows have their own velocities")
+    if not jerk:
+        raise ValueError("point_vel needs jerk=True: the tensor does not depend on a velocity")
+    vel = np.ascontiguousarray(np.asarray(point_vel, dtype=np.float64))
+    if vel.shape != pts.shape:
+        raise ValueError("point_vel must have the points' shape %r, got %r" % (pts.shape, vel.shape))
+    return pts, vel
+
+
+def _tides(call, points, point_vel, jerk, capacity):
+    """nbody_get_tides through `call(points, point_vel, m, tide, jerk, n_out, coincident)` -> {"tide", ["jerk",]
+    "coincident"}."""
+    pts, vel = _tide_points(points, point_vel, jerk)
+    m = capacity if pts is None else len(pts)
+    tide = np.zeros(max(m, 1), dtype=TIDE_DTYPE)
+    jk = np.zeros((max(m, 1), 2), dtype=np.float64) if jerk else None
+    n, coin = ctypes.c_int(0), ctypes.c_int64(0)
+    _check(call(None if pts is None else pts.ctypes.data, None if vel is None else vel.ctypes.data, m, tide.ctypes.data,
+                jk.ctypes.data if jerk else None, ctypes.byref(n), ctypes.byref(coin)))
+    out = {"tide": tide[:n.value].view(np.float64).reshape(-1, 3).copy(), "coincident": coin.value}
+    if jerk:
+        out["jerk"] = np.ascontiguousarray(jk[:n.value])
+    return out
+
+
+def tide_eigen(tide):
+    """The eigenvalues of the symmetric 2 x 2 tensors `tide` (..., 3: txx, txy, tyy) -> (lam_max, lam_min), each (...).
+    lam = mean +- hypot(half the difference, txy).  Needs no GPU."""
+    t = np.asarray(tide, dtype=np.float64)
+    if t.shape[-1:] != (3,):
+        raise ValueError("tide must have shape (..., 3): txx, txy, tyy, got %r" % (t.shape,))
+    mean, half = 0.5 * (t[..., 0] + t[..., 2]), np.hypot(0.5 * (t[..., 0] - t[..., 2]), t[..., 1])
+    return mean + half, mean - half
+
+
+def tidal_radius(tide, mass, G):
+    """The tidal (Hill) radius (G m / lam_max)^(1/3) of bodies of mass `mass` in the tides `tide` (..., 3), lam_max the
+    larger eigenvalue of tide_eigen; inf where lam_max <= 0 (the tide compresses along every axis).  Needs no GPU."""
+    lam = tide_eigen(tide)[0]
+    gm = G * np.asarray(mass, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(lam > 0, np.cbrt(gm / np.where(lam > 0, lam, 1.0)), np.inf)
 
 
 def _tracer_records(pos, vel, systems=None):
@@ -904,6 +965,14 @@ class Stepper:
         diagnostics(potential=True)["phi"].  Not collective: any rank of any world may call it on its own."""
         return _field(lambda *a: lib.nbody_get_field(self._ctx, *a), points, self.capacity)
 
+    def tides(self, points=None, point_vel=None, jerk=False):
+        """nbody_get_tides: the tidal tensor da/dx (fp64) of the current bodies at `points` (m, 2), or with points=None at
+        the bodies' own positions (self term left out): {"tide": (m, 3) txx, txy, tyy, "coincident": sources at distance 0,
+        left out and counted}; with jerk=True also "jerk": (m, 2), da/dt along the motion - of the bodies with their own
+        velocities, of points with `point_vel` (m, 2; None: at rest).  The tensor alone is not collective: any rank of any
+        world may call it on its own; jerk=True needs a single-rank context.  "tide" has the same bits either way."""
+        return _tides(lambda *a: lib.nbody_get_tides(self._ctx, *a), points, point_vel, jerk, self.capacity)
+
     def set_tracers(self, pos, vel=None, walls=False):
         """nbody_tracers_set: m massless tracers at `pos` (m, 2) with velocities `vel` (m, 2; None: zeros), fp64 whatever
         the precision, advanced inside every later step from the field of the state the step starts from.  walls=True:
@@ -1051,6 +1120,11 @@ class StepperGroup:
     def field(self, points=None, rank=0):
         """Stepper.field through one rank: every rank's replica holds every position and mass, each gives the same bits."""
         return self.ranks[rank].field(points)
+
+    def tides(self, points=None, rank=0):
+        """Stepper.tides (the tensor only: a rank holds only its own velocities) through one rank: each gives the same
+        bits."""
+        return self.ranks[rank].tides(points)
 
     def neighbors(self, points=None, rank=0):
         """Stepper.neighbors through one rank: every rank's replica holds every body, each gives the same bits."""
@@ -1202,6 +1276,24 @@ class StepperBatch:
                                          coin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return {"acc": np.ascontiguousarray(buf["acc"][:, :m]), "phi": np.ascontiguousarray(buf["phi"][:, :m]),
                 "coincident": coin}
+
+    def tides(self, points=None, point_vel=None, jerk=False):
+        """nbody_batch_get_tides: Stepper.tides for every system in one launch, with the one set of points and point
+        velocities for all of them: {"tide": (S, m, 3), ["jerk": (S, m, 2),] "coincident": (S,) int64}, system s having the
+        bits a Stepper holding its state gives.  points=None: m is `capacity`, and the entries past a system's count are
+        zero."""
+        pts, vel = _tide_points(points, point_vel, jerk)
+        m = self.capacity if pts is None else len(pts)
+        tide = np.zeros((self.systems, max(m, 1)), dtype=TIDE_DTYPE)
+        jk = np.zeros((self.systems, max(m, 1), 2), dtype=np.float64) if jerk else None
+        coin = np.zeros(self.systems, dtype=np.int64)
+        _check(lib.nbody_batch_get_tides(self._b, None if pts is None else pts.ctypes.data,
+                                         None if vel is None else vel.ctypes.data, m, tide.ctypes.data,
+                                         jk.ctypes.data if jerk else None, coin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        out = {"tide": tide.view(np.float64).reshape(self.systems, -1, 3)[:, :m].copy(), "coincident": coin}
+        if jerk:
+            out["jerk"] = np.ascontiguousarray(jk[:, :m])
+        return out
 
     def set_tracers(self, pos, vel=None, walls=False):
         """nbody_batch_tracers_set: Stepper.set_tracers for every system, the same m each: pos and vel of shape (S, m, 2);

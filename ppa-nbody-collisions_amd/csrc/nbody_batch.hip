@@ -31,6 +31,7 @@
 #include "nbody_knn.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
+#include "nbody_tides.hpp"
 
 using namespace nbk;
 
@@ -97,6 +98,8 @@ struct nbody_batch {
     EncState enc;
     // bound-pair queries (nbody_batch_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
     BinState bin;
+    // tidal tensor and jerk (nbody_batch_get_tides, nbody_tides.hpp): nothing is allocated before the first call
+    TidesState tid;
     // tracer particles (nbody_batch_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -124,6 +127,7 @@ void free_all(nbody_batch* b) {
     pairs_free(b->prs);
     encounters_free(b->enc);
     binaries_free(b->bin);
+    tides_free(b->tid);
     rows_free(b->knn);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
@@ -722,7 +726,7 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 
 // ---------------------------------------------------------------------------------------------------------
 // Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_knn, nbody_batch_get_groups,
-// nbody_batch_get_pair_counts, nbody_batch_get_encounters, nbody_batch_get_binaries; nbody_rows.hpp and the seven query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
+// nbody_batch_get_pair_counts, nbody_batch_get_encounters, nbody_batch_get_binaries, nbody_batch_get_tides; nbody_rows.hpp and the eight query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
 // of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -817,6 +821,19 @@ int nbody_batch_get_binaries(nbody_batch* b, double sep2, nbody_binary* out, int
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
         return binaries_run<decltype(t), RowsBatchCount>(who, site, b->V, b->bin, sep2, out, cap, info, sync);
+    });
+}
+
+// Tidal tensor and jerk (nbody_tides.hpp): one set of points and point velocities for every system, one launch.
+int nbody_batch_get_tides(nbody_batch* b, const nbody_vec2* points, const nbody_vec2* point_vel, int m, nbody_tide* tide,
+                          nbody_vec2* jerk, int64_t* coincident) {
+    const char* who = "nbody_batch_get_tides";
+    RowsSite site;
+    int rc = tides_check_args(who, {b, tide, coincident}, points, point_vel, jerk, m, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return tides_run<decltype(t), RowsBatchCount>(who, site, b->tid, (double)kG, b->V, points, point_vel, m, tide, jerk,
+                                                      coincident, sync);
     });
 }
 

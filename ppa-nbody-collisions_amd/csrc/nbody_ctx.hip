@@ -34,6 +34,7 @@
 #include "nbody_knn.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
+#include "nbody_tides.hpp"
 
 using namespace nbk;
 
@@ -203,6 +204,8 @@ struct nbody_ctx {
     EncState enc;
     // bound-pair queries (nbody_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
     BinState bin;
+    // tidal tensor and jerk (nbody_get_tides, nbody_tides.hpp): nothing is allocated before the first call
+    TidesState tid;
     // tracer particles (nbody_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
     TracerState trc;
 };
@@ -636,6 +639,7 @@ void free_all(nbody_ctx* c) {
     pairs_free(c->prs);
     encounters_free(c->enc);
     binaries_free(c->bin);
+    tides_free(c->tid);
     rows_free(c->knn);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
@@ -1691,7 +1695,7 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 
 // ---------------------------------------------------------------------------------------------------------
 // Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_groups, nbody_get_pair_counts, nbody_get_encounters,
-// nbody_get_binaries; nbody_rows.hpp and the seven query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
+// nbody_get_binaries, nbody_get_tides; nbody_rows.hpp and the eight query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
 // every rank holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -1809,6 +1813,28 @@ int nbody_get_binaries(nbody_ctx* c, double sep2, nbody_binary* out, int cap, nb
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return binaries_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->bin, sep2, out, cap, info, sync);
+    });
+}
+
+// Tidal tensor and jerk (nbody_tides.hpp).  The tensor alone reads J only and is any context's to call; the jerk reads the
+// velocities, so the encounters' restriction holds for it.
+int nbody_get_tides(nbody_ctx* c, const nbody_vec2* points, const nbody_vec2* point_vel, int m, nbody_tide* tide, nbody_vec2* jerk,
+                    int* n_out, int64_t* coincident) {
+    const char* who = "nbody_get_tides";
+    RowsSite site;
+    int rc = tides_check_args(who, {c, tide, n_out, coincident}, points, point_vel, jerk, m, 1);
+    if (rc != NBODY_OK) return rc;
+    if (jerk && (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM))))
+        return nbody_fail(NBODY_ERR_STATE, "%s: the jerk needs a single-rank context without an exchange (world %d, flags 0x%x): "
+                                           "a rank holds only its own velocities, a query across ranks is not built", who,
+                          c->desc.world, c->desc.flags);
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if (!points && m < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, site.n_bound);
+    *n_out = points ? m : site.n_bound;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return tides_run<decltype(t), RowsOneCount>(who, site, c->tid, (double)kG, c->Vown, points, point_vel, m, tide, jerk,
+                                                    coincident, sync);
     });
 }
 

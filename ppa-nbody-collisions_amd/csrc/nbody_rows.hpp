@@ -22,7 +22,8 @@
 // or, for another shape of result, from the pieces of rows_run - RowsSite's grid, count and sync, RowPoints,
 // rows_check_args.  The per-handle preamble and the precision dispatch are in the two .hip files.  field_at walks with
 // diag_walk_sums instead (see rows_walk); encounters_walk and binaries_walk, which need the velocities (and masses) in more planes,
-// each have their own copy of the triangular walk.
+// each have their own copy of the triangular walk.  tides_at (nbody_tides.hpp) walks with diag_walk_sums as
+// field_at does, and for the jerk, which needs the velocities in two more planes, with its own copy of that ascending walk.
 #pragma once
 #include <stddef.h>
 #include <string.h>
