@@ -858,6 +858,9 @@ void forces_ring_f32(const RingArgs args) {
     static_assert(kTile % kT == 0 && kT % 8 == 0 && kT <= kWave, "turn length");
     constexpr int kTurnsPerTile = kTile / kT;
     constexpr bool kSolo = kW == 1;                        // the SOLO form: one wave per 64 bodies takes every turn of its walk
+    // the solo builds without the event log carry a trimmed turn (profiles/ring_solo_trim.txt); the event-logging solo
+    // builds, like every other event-logging build, keep the code they had
+    constexpr bool kTrim = kSolo && !kLog;
     static_assert(kSolo || kW % kTurnsPerTile == 0, "a wave's successive turns are whole tiles apart");
     constexpr int kTilesPerRound = kW / kTurnsPerTile;
     constexpr int kWin = kWave + kT;                       // window entries a turn can touch (kWin - 1 used)
@@ -908,6 +911,11 @@ void forces_ring_f32(const RingArgs args) {
     int seq_base = 0;                                      // sequence number of the current item's first turn
     int claims = 0;                                        // items this slot has drawn
     Int4 solo_h = Int4{0, 0, 0, 0};                        // solo form: the hand-off record, in registers from turn to turn
+    // trimmed solo form: the record's words one by one - the two sums and `deleted`; the dead mark is `dead` itself (the
+    // record's third word is kRingDeadSeq exactly when the wave is dead) - so that a plain turn writes the sums and nothing else
+    float solo_fx = 0.0f, solo_fy = 0.0f;
+    int solo_del = 0;
+    unsigned long long pairs_slot = 0;                     // trimmed solo form: pairs of all the slot's items, flushed when it leaves
     // SOLO FORM, the look.  The 16 waves of a workgroup are four per SIMD, and the arbiter serves the OLDER wave first at
     // equal priority (lesson (b) above): left alone the oldest wave of a SIMD runs at full speed, the youngest on what is
     // left, the walks end far apart and the last ones run alone on their SIMD, where nothing hides a wave's own latencies
@@ -1057,11 +1065,13 @@ void forces_ring_f32(const RingArgs args) {
                         m0.x = m0.y = __builtin_nanf("");
                     }
                     *(LdsFloat4Ptr)&hand_m[l] = m0;
-                    if (kSolo) solo_h = h0;
+                    if (kTrim) { solo_fx = __int_as_float(h0.x); solo_fy = __int_as_float(h0.y); solo_del = h0.w; }
+                    else if (kSolo) solo_h = h0;
                     else *(LdsInt4Ptr)&hand[l] = h0;
                 }
             } else if (w == 0) {
-                if (kSolo) solo_h = Int4{0, 0, 0, 0};
+                if (kTrim) { solo_fx = solo_fy = 0.0f; solo_del = 0; }
+                else if (kSolo) solo_h = Int4{0, 0, 0, 0};
                 else *(LdsInt4Ptr)&hand[l] = Int4{0, 0, 0, 0};
                 *(LdsFloat4Ptr)&hand_m[l] = Float4{mi, ri, mi, 0.0f};            // mnew = mi, rnew = ri (:174-175)
             }
@@ -1163,8 +1173,17 @@ void forces_ring_f32(const RingArgs args) {
         auto entry_bytes_of = [&](int lane) -> unsigned {
             return ((unsigned)(wbase0 + (w % kTurnsPerTile) * kT + lane) & (kTile - 1)) * (unsigned)sizeof(T);
         };
-        unsigned entry0_kept = kLog ? 0u : entry_bytes_of(l);
-        if (!kLog) asm volatile("" : "+v"(entry0_kept));
+        unsigned entry0_kept = kLog || kTrim ? 0u : entry_bytes_of(l);
+        if (!kLog && !kTrim) asm volatile("" : "+v"(entry0_kept));
+        // Trimmed solo form.  The wave takes the four quarters of a tile in turn, so the lane's first entry is
+        // (4 l + 128 h) mod 512 bytes with h = quarter + 2 * (second half of the block) mod 4, a SCALAR, and the entry 64
+        // further on is the same with h + 2.  4 l is below 256: for h = 0, 1, 2 nothing wraps and 128 h goes into the scalar
+        // base address of the loads; only h = 3 wraps, for the upper half of the lanes, and that offset is the second
+        // kept register.  A window's two entry offsets therefore cost no vector instruction (they were three per turn).
+        static_assert(!kTrim || (kT == 32 && kWave == 64 && kTile == 128), "the quarter is 128 bytes, the lanes' offsets 256");
+        unsigned entry_lane_kept = kTrim ? (unsigned)l * (unsigned)sizeof(T) : 0u;
+        unsigned entry_wrap_kept = kTrim ? ((unsigned)l * (unsigned)sizeof(T) + 384u) & 511u : 0u;
+        if (kTrim) asm volatile("" : "+v"(entry_lane_kept), "+v"(entry_wrap_kept));
         auto window_offset = [&](Idx st, unsigned e) -> unsigned {   // byte offset of the body's x in the tiled copy Jt
             const unsigned src = (unsigned)st + e;
             const unsigned wrapped = src - (unsigned)N;                // huge when src < N
@@ -1218,6 +1237,25 @@ void forces_ring_f32(const RingArgs args) {
                 }
                 return;
             }
+            if (kTrim) {
+                const unsigned h0 = ((quarter_bytes >> 7) + ((unsigned)wbase0 >> 5)) & 3u, h1 = h0 ^ 2u;
+                if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= Nu) {
+                    const unsigned tile_byte = ((unsigned)st / kTile) * (4u * kTile * (unsigned)sizeof(T));
+                    if (l < nwin) {
+                        if (h0 == 3u) issue_entries(tile_byte, entry_wrap_kept, base, kWin * (unsigned)sizeof(T));
+                        else issue_entries(tile_byte + (h0 << 7), entry_lane_kept, base, kWin * (unsigned)sizeof(T));
+                    }
+                    if (l + kWave < nwin) {
+                        if (h1 == 3u) issue_entries(tile_byte, entry_wrap_kept, base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+                        else issue_entries(tile_byte + (h1 << 7), entry_lane_kept, base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+                    }
+                } else {                                       // a window that wraps or starts inside a tile: entries, per lane
+                    const unsigned e0 = ((entry_lane_kept + (h0 << 7)) & 511u) / (unsigned)sizeof(T), e1 = e0 ^ kWave;
+                    if (l < nwin) issue_entries(0u, window_offset(st, e0), base, kWin * (unsigned)sizeof(T));
+                    if (l + kWave < nwin) issue_entries(0u, window_offset(st, e1), base + kWave * (unsigned)sizeof(T), kWin * (unsigned)sizeof(T));
+                }
+                return;
+            }
             const unsigned entry0_bytes = kSolo ? (entry0_kept + quarter_bytes) & (kTile * (unsigned)sizeof(T) - 1u) : entry0_kept;
             const unsigned entry1_bytes = entry0_bytes ^ (kWave * (unsigned)sizeof(T));   // the entry 64 further on
             if (((unsigned)st & (kTile - 1)) == 0u && st + kTile <= Nu) {
@@ -1261,13 +1299,19 @@ void forces_ring_f32(const RingArgs args) {
             const float rab = ra > rb ? ra : rb;
             return rab > rw ? rab : rw;
         };
+        // trimmed solo form: the bound is the same in every lane and travels from turn to turn as a scalar - with every
+        // radius +0 the next window's bound then costs no vector instruction (it was a v_mov 0 per turn)
+        auto window_rmax_scalar = [&](Idx st) -> float {
+            if (!any_radius) return 0.0f;                      // (a constant HERE: behind the readfirstlane it is a v_mov and the read)
+            return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(window_rmax(st))));
+        };
         struct WindowState { bool fast; float rmax; };
         auto check_window = [&](int kind, int kk, int buf, Idx st_w) -> WindowState {
             if (kind != 1) return WindowState{false, 0.0f};    // (a truncated tile is waited for where it is read)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // issued a whole turn ago
             __builtin_amdgcn_wave_barrier();
             // the whole replica is bounded (Meta::summary): no scan of the window; all its radii are +0 or not, globally
-            if (all_bounded) return WindowState{wave_ok && fast_tile(kk), window_rmax(st_w)};
+            if (all_bounded) return WindowState{wave_ok && fast_tile(kk), kTrim ? window_rmax_scalar(st_w) : window_rmax(st_w)};
             Rec<T> r0{0, 0, 0, 0}, r1{0, 0, 0, 0};
             if (l < nwin) r0 = window_record(&win[w][buf][0][0], kWin, l);
             if (l + kWave < nwin) r1 = window_record(&win[w][buf][0][0], kWin, l + kWave);
@@ -1275,7 +1319,7 @@ void forces_ring_f32(const RingArgs args) {
             const bool bad1 = !((abs_(r1.x) < kCoordBound) && (abs_(r1.y) < kCoordBound));
             WindowState ws;
             ws.fast = __ballot(bad0 || bad1) == 0ull && wave_ok && fast_tile(kk);
-            ws.rmax = window_rmax(st_w);
+            ws.rmax = kTrim ? window_rmax_scalar(st_w) : window_rmax(st_w);
             return ws;
         };
         // the general code on this turn's walk positions, records from the window (kind 1) / the whole tile (kind 2)
@@ -1351,7 +1395,9 @@ void forces_ring_f32(const RingArgs args) {
             const int kind_next = turn_kind(tau + kW, st_next);
             if (kind_next == 1) issue_window(st_next, buf ^ 1, solo_quarter(tau + kW));   // in flight for the whole turn
             const bool first = lit && tau == 0;                // walk position 0 is the body itself (:200-204)
-            if (kSolo) {
+            // trimmed solo form: the look is taken at a tile's first turn only (solo_done counts tiles) and the priority it
+            // sets holds for the tile's turns; an item starts at a tile, so every item's first turn looks
+            if (kSolo && (!kTrim || tau % kTurnsPerTile == 0)) {
                 solo_done += 1;
                 *(LdsIntPtr)&solo_done_all[wv] = solo_done;
                 const int theirs = *(LdsIntPtr)&solo_done_all[l % kRings];
@@ -1432,7 +1478,8 @@ void forces_ring_f32(const RingArgs args) {
             bool timed_out = false;
             if (!kSolo) __builtin_amdgcn_s_setprio(3);
             const int sq = kSolo ? 0 : tau + dseq;             // (solo form: no sequence numbers, the state is the wave's own)
-            if (kSolo) h = solo_h;
+            if (kTrim) h = Int4{(int)__float_as_uint(solo_fx), (int)__float_as_uint(solo_fy), dead ? kRingDeadSeq : 0, solo_del};
+            else if (kSolo) h = solo_h;
             if (!kSolo && (kQueue || tau > 0)) {
                 int spins = 0;
                 for (;;) {
@@ -1457,13 +1504,15 @@ void forces_ring_f32(const RingArgs args) {
                     fx = fx + term_x(r);
                     asm("" : "+v"(fx));                        // keeps hipcc from pairing the two adds into one v_pk_add_f32
                     fy = fy + term_y(r);
+                    if (kTrim) asm("" : "+v"(fy));             // (the sums are two variables there: hipcc packs fy's adds with dead halves)
                 }
                 // nan_screen: a coincident pair (d2 = 0: a collision, :215-226) made its term NaN, and a NaN among the kT terms
                 // is a NaN sum.  ONE comparison per turn instead of a v_min3 per two pairs; a lane whose sum was NaN already is
                 // flagged in every turn (slow, and right: its collisions still have to be found).
                 if (nan_screen) flag = __builtin_amdgcn_fcmpf(fx, fy, 8 /* llvm::CmpInst::FCMP_UNO */);
                 if (__builtin_expect(flag == 0ull, 1)) {
-                    if (kSolo) solo_h = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), 0, h.w};
+                    if (kTrim) { solo_fx = fx; solo_fy = fy; }
+                    else if (kSolo) solo_h = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), 0, h.w};
                     else *hand_l = Int4{(int)__float_as_uint(fx), (int)__float_as_uint(fy), sq + 1, h.w};
                     if (!kSolo) __builtin_amdgcn_s_setprio(0);
                     plain_turns += 1;                          // a scalar: kT pairs per active lane, added up at the end
@@ -1578,7 +1627,8 @@ void forces_ring_f32(const RingArgs args) {
                 // publish: the rare record first, then the one the next wave polls (a wave's LDS operations execute in order)
                 if (__float_as_uint(a.mnew) != m_before || __float_as_uint(a.rnew) != r_before)
                     *hand_m_l = Float4{a.mnew, a.rnew, a.mi, 0.0f};
-                if (kSolo) solo_h = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : 0, a.deleted & 1};
+                if (kTrim) { solo_fx = a.fx; solo_fy = a.fy; solo_del = a.deleted & 1; }
+                else if (kSolo) solo_h = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : 0, a.deleted & 1};
                 else *hand_l = Int4{(int)__float_as_uint(a.fx), (int)__float_as_uint(a.fy), dead ? kRingDeadSeq : sq + 1,
                                     a.deleted & 1};
                 if (!kSolo) __builtin_amdgcn_s_setprio(0);
@@ -1599,7 +1649,8 @@ void forces_ring_f32(const RingArgs args) {
         // general code's record loads are inline assembly with their own waits): hipcc therefore places no vmcnt wait in
         // the loop, and the only one there is check_window's, for a prefetch issued a whole turn earlier.
         if ((kQueue || mine) && (tau_hi - 1) % kW == w) {      // the wave that took the item's last turn, from the records it has
-            const Int4 hf = kSolo ? solo_h : *hand_l;          // just written (a wave's LDS operations execute in order)
+            const Int4 hf = kTrim ? Int4{(int)__float_as_uint(solo_fx), (int)__float_as_uint(solo_fy), dead ? kRingDeadSeq : 0, solo_del}
+                          : kSolo ? solo_h : *hand_l;          // just written (a wave's LDS operations execute in order)
             const Float4 hm = *hand_m_l;
             if (kQueue && tau_hi < nturns) {
                 // not the walk's last segment: the two records of every lane go to the ring's state, write-through (each store
@@ -1642,7 +1693,18 @@ void forces_ring_f32(const RingArgs args) {
             // the slot's next item waits for it before it writes that item's starting state over them
             if (kQueue && !kSolo) *hand_l = Int4{hf.x, hf.y, hf.z >= kRingDeadSeq ? kRingDeadSeq : seq_base + (tau_hi - tau_lo) + 1, hf.w};
         }
-        {
+        if (kTrim) {
+            // every active lane took the same plain turns: their pairs are scalar arithmetic; only an item with turns off the
+            // common path adds its lanes' counts up across the wave
+            const long long lanes = (long long)__builtin_popcountll(__ballot(active));
+            pairs_slot += (unsigned long long)(lanes * ((long long)plain_turns * kT - (first_plain ? 1 : 0)));
+            if (__ballot(pairs_rare != 0) != 0ull) {       // (pairs_rare only ever counts for an active lane)
+                unsigned long long pairs = (unsigned long long)(long long)pairs_rare;
+                for (int sh = kWave / 2; sh > 0; sh >>= 1) pairs += __shfl_down(pairs, sh, kWave);
+                pairs_slot += ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(pairs >> 32)) << 32) |
+                              (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)pairs);
+            }
+        } else {
             unsigned long long pairs = 0;
             if (active) pairs = (unsigned long long)((long long)plain_turns * kT - (first_plain ? 1 : 0) + pairs_rare);
             for (int sh = kWave / 2; sh > 0; sh >>= 1) pairs += __shfl_down(pairs, sh, kWave);
@@ -1653,6 +1715,7 @@ void forces_ring_f32(const RingArgs args) {
         seq_base += tau_hi - tau_lo + 1;
     }
     Counters* const ctr = NB_RING_LATE(ctr);
+    if (kTrim && l == 0 && pairs_slot) atomicAdd(&ctr->pairs, pairs_slot);   // once per slot, for all its items
     if (kSolo) *(LdsIntPtr)&solo_done_all[wv] = 0;
     if (kQueue && w == 0 && l == 0) {                      // the last slot to leave clears the queue for the next launch
         const GlobalU32Ptr head = (GlobalU32Ptr)NB_RING_LATE(q_head);
