@@ -548,6 +548,73 @@ int nbody_get_knn(nbody_ctx* ctx, const nbody_vec2* points, int m, int k, double
 int nbody_batch_get_knn(struct nbody_batch* b, const nbody_vec2* points, int m, int k, double* d2, int32_t* index);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Shell sums (the reference has none): for every row - a current body, or an arbitrary probe point - the
+ * mass and the number of the current bodies in each shell of distance around it, 1 <= bins <= NBODY_SHELLS_MAX: what a
+ * local surface density, the enclosed mass M(<r), a half-mass radius or the density profile of a clump is made of; the
+ * per-row, mass-weighted counterpart of nbody_get_pair_counts.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma.  The
+ * records are (X_j, Y_j, M_j) of the n current bodies, widened exactly from fp32 or taken as they are from fp64.  Radii and
+ * velocities play no part.  For a row at (x, y) and a source j:
+ *     dx = X_j - x;  dy = Y_j - y;  d2_j = (dx*dx) + (dy*dy)               the d2 of nbody_get_neighbors, same bits
+ *     in(k, j)  <=>  edges2[k] <= d2_j && d2_j < edges2[k+1]                k = 0 .. bins-1, the rule of nbody_get_pair_counts
+ *     count[row*bins + k] = the number of sources j with in(k, j)
+ *     mass [row*bins + k] = acc after:  acc = +0.0;  for j = 0 .. n-1 ascending:  if in(k, j)  acc = acc + M_j
+ * The order of the mass sum is part of the contract, as it is for the field and the diagnostics: the masses span thirteen
+ * decades.  edges2 follows the rules of nbody_get_pair_counts: bins + 1 squared edges, strictly increasing, no NaN,
+ * edges2[0] >= 0, the last edge may be +inf; the one difference is 1 <= bins <= NBODY_SHELLS_MAX.
+ * What is left out: a source below the first edge, a source at or above the last edge and a NaN d2 are not counted anywhere;
+ * a +inf d2 is not counted even under a +inf top edge.  There is no `below` and no `rest`: a caller who wants everything
+ * sends edges2[0] = 0.
+ * Own form (points == NULL): the rows are the current bodies, taken on the device; the self term is excluded by index, so a
+ * second body at the same place is a source at d2 = +0 and lands in bin 0 where edges2[0] == 0; m is the room in rows,
+ * *n_out the current count n; m < n is NBODY_ERR_CAPACITY with nothing written.  Points form: m probe points, always
+ * nbody_vec2, no self exclusion; *n_out = m; m == 0 is legal and launches nothing.
+ * What follows from the definition:
+ *   - count is exact whatever order the device counts in;
+ *   - mass is a function of the state, the row and the edges only: it does not depend on rank, world, transport, force
+ *     kernel, m, the row's place in `points`, or the capacity tier the kernel runs at;
+ *   - the mass of bin k under edges [.., a, b, ..] equals the mass of the one bin of a call with edges [a, b]: bins are
+ *     independent of each other;
+ *   - it is independent of the semantics: a literal context's frozen tail is a source like any other body;
+ *   - a body of mass 0 counts and adds +0; a NaN mass makes its bin's mass NaN and still counts;
+ *   - summed over the own rows, count[:, k] is exactly twice nbody_get_pair_counts' counts[k] for the same edges; summed
+ *     over explicit points it is exactly its DR counts[k];
+ *   - where every mass is 1.0, mass == count exactly.
+ * nbody_get_shells follows nbody_get_knn in every respect not named here.  It synchronises, reads the replica only and never
+ * changes what later steps compute: stepping after any number of calls is bit-identical to stepping without them.  It is NOT
+ * collective: any rank of any world, a rank of a NBODY_FLAG_GROUP_EXCHANGE group and a NBODY_FLAG_FORCE_COMM context each
+ * give the same bits.  The device points, the device entries (12 bytes each) and their pinned staging are allocated on the
+ * first call and grown; the edges travel as a kernel argument.  A context that never calls it allocates nothing, launches
+ * nothing more, and the kernels it runs keep their code.
+ * NBODY_ERR_INVALID, found before any device call: NULL ctx, edges2, mass, count or n_out; bins outside
+ * [1, NBODY_SHELLS_MAX]; a bad edge (as nbody_get_pair_counts reports it); m < 0; m x bins x 12 bytes above 2^31 (in the own
+ * form too, where m is the room).  NBODY_ERR_STATE: before an upload.
+ * Cost (one MI355X, fp32, the N = 262144 state after 3 steps, n = 130965; profiles/shells_probe.txt, a kernel trace with
+ * nbody_get_pair_counts' kernel timed in the same run, medians of 3 rounds, spreads <= 0.1 ms).  The accumulators have a
+ * capacity tier of 4, 8, 16 or 32 bins, the smallest that holds `bins`.  Per pair the kernel does what the points form of
+ * nbody_get_pair_counts does, and pays for its sums only where some row of a wave has a source below the top edge.  On 65536
+ * explicit points and the same 32 edges: 5.200 ms against 5.203 ms for nbody_get_pair_counts where 6.8e-6 of the pairs are in
+ * range (top edge 381.8 as a length), 5.767 against 5.363 ms (1.075) where 4.9e-5 are (824.8).  points == NULL: 5.76 / 5.90 ms
+ * for 8 / 32 bins under the first top edge, 6.27 / 6.94 ms under the second - every ordered pair is walked, yet that is 1.11 to
+ * 1.25 times the triangular nbody_get_pair_counts call (5.20 / 5.54 ms), not twice: the full walk is even over the workgroups.
+ * One bin [0, +inf), every pair added: 26.45 ms.  Whole Stepper.shells() calls add the copy of rows x bins x 12 bytes and its
+ * split into two arrays: 7.2 ms at 8 bins, 17.0 / 17.4 ms at 32 bins (50 MB).  A batch of 256 x 1024 with points == NULL and 8
+ * bins: 0.133 ms of kernel, 3.1 ms for StepperBatch.shells() with its 25 MB of results.  Not measured: fp64 records, other
+ * states, bins between the tiers (the cost is the upper tier's by construction).
+ * nbody_batch_get_shells: the same query for every system of a batch in ONE launch, whatever S is, with the one set of
+ * points and edges for all of them (systems x m x bins x 12 bytes at most 2^31).  Explicit points: system s's entries at
+ * [(s * m + p) * bins + k].  points == NULL: at [(s * capacity + i) * bins + k], one row per current body, the rest of the
+ * slice is left unchanged.  System s gives exactly the bits an nbody_ctx holding that system's state gives; an empty system
+ * gives {+0.0, 0} in every bin of every explicit point and writes nothing in the own form.  A count outside [0, capacity] is
+ * treated as 0 and reported for that system, as by nbody_batch_get_knn.
+ * ------------------------------------------------------------------------------------------------- */
+#define NBODY_SHELLS_MAX 32
+int nbody_get_shells(nbody_ctx* ctx, const nbody_vec2* points, int m, const double* edges2, int bins,
+                     double* mass /* [rows * bins] */, int32_t* count /* [rows * bins] */, int* n_out);
+int nbody_batch_get_shells(struct nbody_batch* b, const nbody_vec2* points, int m, const double* edges2, int bins,
+                           double* mass, int32_t* count);
+
+/* ---------------------------------------------------------------------------------------------------
  * Group finding (the reference has none): friends-of-friends.  Which of the n current bodies hang together,
  * and how many clumps there are: the connected components of the graph of linked pairs.
  * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the

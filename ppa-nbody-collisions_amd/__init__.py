@@ -26,6 +26,7 @@ FLAG_TRACK_IDS = 8
 TRACER_WALLS = 1
 TRACK_PHI = 1
 KNN_MAX = 32
+SHELLS_MAX = 32
 COMM_ID_BYTES = 128
 IMAGE_PATH_MAX = 1024
 
@@ -239,6 +240,7 @@ SYMBOLS = {
     "nbody_get_tides": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _ip, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
     "nbody_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp, _ip]),
+    "nbody_get_shells": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _ip]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
     "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
     "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
@@ -271,6 +273,7 @@ SYMBOLS = {
     "nbody_batch_get_tides": (_i, [_vp, _vp, _vp, _i, _vp, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "nbody_batch_get_neighbors": (_i, [_vp, _vp, _i, _vp]),
     "nbody_batch_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "nbody_batch_get_shells": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_batch_get_groups": (_i, [_vp, _d, _d, _vp, _vp]),
     "nbody_batch_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_batch_diag_reserve": (_i, [_vp, _i]),
@@ -661,6 +664,35 @@ def _pair_counts(call, systems, edges, points, squared):
     return [_pair_dict(counts[s].copy(), info[s], e2) for s in range(systems)]
 
 
+def _shell_buffers(shape):
+    """The caller's two arrays of nbody_get_shells, filled with what an empty bin holds."""
+    return np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.int32)
+
+
+def shell_profile(shells):
+    """What the radial read-outs are made of, from one result of shells() ({"mass": (rows, B), "count": (rows, B), "edges2":
+    (B + 1,)}): {"area": pi * (e2[k+1] - e2[k]) per bin - squared edges give the area of an annulus directly,
+    "surface_density": mass / area, "number_density": count / area, "enclosed_mass" and "enclosed_count": cumulative over the
+    bins, so they count only what lies at or above the first edge, "half_mass_radius2": per row the squared edge at which
+    the enclosed mass first reaches half of the last bin's enclosed mass, NaN for a row without mass}.  Plain numpy in float64
+    on the host; needs no GPU and no library call."""
+    mass = np.asarray(shells["mass"], dtype=np.float64)
+    count = np.asarray(shells["count"])
+    e2 = np.asarray(shells["edges2"], dtype=np.float64)
+    if mass.ndim != 2 or count.shape != mass.shape or e2.shape != (mass.shape[1] + 1,):
+        raise ValueError("shell_profile: mass and count (rows, B) and edges2 (B + 1,) of one shells() result")
+    area = np.pi * (e2[1:] - e2[:-1])
+    enclosed_mass = np.cumsum(mass, axis=1)
+    enclosed_count = np.cumsum(count.astype(np.int64), axis=1)
+    total = enclosed_mass[:, -1]
+    with np.errstate(invalid="ignore"):
+        reached = enclosed_mass >= 0.5 * total[:, None]
+    first = np.argmax(reached, axis=1)                          # the first bin that reaches half: its upper edge
+    half = np.where(reached.any(axis=1) & (enclosed_count[:, -1] > 0), e2[1:][first], np.nan)
+    return {"area": area, "surface_density": mass / area, "number_density": count / area, "enclosed_mass": enclosed_mass,
+            "enclosed_count": enclosed_count, "half_mass_radius2": half}
+
+
 def _encounter_list(rec):
     out = np.zeros(len(rec), dtype=ENCOUNTER_DTYPE)
     for f in ENCOUNTER_DTYPE.names:
@@ -1016,6 +1048,23 @@ class Stepper:
                                  index.ctypes.data, ctypes.byref(n)))
         return {"d2": d2[:n.value].copy(), "index": index[:n.value].copy()}
 
+    def shells(self, edges, points=None, squared=False):
+        """nbody_get_shells: for every row - each of `points` (m, 2), or with points=None each current body (self term left
+        out by index) - the mass and the number of the current bodies in each bin of distance between the B + 1 `edges`
+        (lengths; squared lengths with squared=True), 1 <= B <= SHELLS_MAX: {"mass": float64 (rows, B), summed in ascending
+        index, "count": int32 (rows, B), "edges2": the squared edges that were sent}.  A source counts in bin k where
+        edges2[k] <= d2 < edges2[k+1], and nowhere otherwise.  shell_profile() turns it into densities and enclosed masses.
+        Not collective: any rank of any world may call it on its own."""
+        e2 = pair_edges2(edges, squared)
+        pts = _field_points(points)
+        bins = len(e2) - 1
+        m = self.capacity if pts is None else len(pts)
+        mass, count = _shell_buffers((max(m, 1), bins))
+        n = ctypes.c_int(0)
+        _check(lib.nbody_get_shells(self._ctx, None if pts is None else pts.ctypes.data, m, e2.ctypes.data, bins,
+                                    mass.ctypes.data, count.ctypes.data, ctypes.byref(n)))
+        return {"mass": mass[:n.value].copy(), "count": count[:n.value].copy(), "edges2": e2}
+
     def groups(self, link, radius_scale=1.0):
         """nbody_get_groups: friends-of-friends groups of the current bodies, i and j linked where d2 <= s*s with
         s = radius_scale * (r_i + r_j) + link (fp64): {"label": int32 (n,), label[i] the lowest index of body i's group,
@@ -1133,6 +1182,10 @@ class StepperGroup:
     def knn(self, k, points=None, rank=0):
         """Stepper.knn through one rank: every rank's replica holds every body, each gives the same bits."""
         return self.ranks[rank].knn(k, points)
+
+    def shells(self, edges, points=None, squared=False, rank=0):
+        """Stepper.shells through one rank: every rank's replica holds every body, each gives the same bits."""
+        return self.ranks[rank].shells(edges, points, squared)
 
     def groups(self, link, radius_scale=1.0, rank=0):
         """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
@@ -1342,6 +1395,22 @@ class StepperBatch:
         if pts is None:
             return [{"d2": d2[s, :int(c)].copy(), "index": index[s, :int(c)].copy()} for s, c in enumerate(self.counts())]
         return {"d2": np.ascontiguousarray(d2[:, :m]), "index": np.ascontiguousarray(index[:, :m])}
+
+    def shells(self, edges, points=None, squared=False):
+        """nbody_batch_get_shells: Stepper.shells for every system in one launch, with the one set of edges and points for
+        all of them, system s having the bits a Stepper holding its state gives.  points=None: a list of S dicts, one row
+        per current body of the system; otherwise one dict of arrays of shape (S, m, B)."""
+        e2 = pair_edges2(edges, squared)
+        pts = _field_points(points)
+        bins = len(e2) - 1
+        m = self.capacity if pts is None else len(pts)
+        mass, count = _shell_buffers((self.systems, max(m, 1), bins))
+        _check(lib.nbody_batch_get_shells(self._b, None if pts is None else pts.ctypes.data, m, e2.ctypes.data, bins,
+                                          mass.ctypes.data, count.ctypes.data))
+        if pts is None:
+            return [{"mass": mass[s, :int(c)].copy(), "count": count[s, :int(c)].copy(), "edges2": e2}
+                    for s, c in enumerate(self.counts())]
+        return {"mass": np.ascontiguousarray(mass[:, :m]), "count": np.ascontiguousarray(count[:, :m]), "edges2": e2}
 
     def groups(self, link, radius_scale=1.0):
         """nbody_batch_get_groups: Stepper.groups for every system, every pair walk one launch for the whole batch: a list

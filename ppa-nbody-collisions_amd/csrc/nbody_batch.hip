@@ -29,6 +29,7 @@
 #include "nbody_group_energy.hpp"
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
+#include "nbody_shells.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -94,6 +95,8 @@ struct nbody_batch {
     PairsState prs;
     // k nearest neighbours (nbody_batch_get_knn, nbody_knn.hpp): nothing is allocated before the first call
     KnnState knn;
+    // shell sums (nbody_batch_get_shells, nbody_shells.hpp): nothing is allocated before the first call
+    ShellState shl;
     // encounter queries (nbody_batch_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_batch_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -129,6 +132,7 @@ void free_all(nbody_batch* b) {
     binaries_free(b->bin);
     tides_free(b->tid);
     rows_free(b->knn);
+    rows_free(b->shl);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
@@ -725,8 +729,8 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_knn, nbody_batch_get_groups,
-// nbody_batch_get_pair_counts, nbody_batch_get_encounters, nbody_batch_get_binaries, nbody_batch_get_tides; nbody_rows.hpp and the eight query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
+// Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_knn, nbody_batch_get_shells, nbody_batch_get_groups,
+// nbody_batch_get_pair_counts, nbody_batch_get_encounters, nbody_batch_get_binaries, nbody_batch_get_tides; nbody_rows.hpp and the nine query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
 // of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -779,6 +783,15 @@ int nbody_batch_get_knn(nbody_batch* b, const nbody_vec2* points, int m, int k, 
     if (rc != NBODY_OK) return rc;
     KnnResult out{d2, index};
     return batch_rows(b, "nbody_batch_get_knn", b->knn, KnnQuery{k}, points, m, &out);
+}
+
+int nbody_batch_get_shells(nbody_batch* b, const nbody_vec2* points, int m, const double* edges2, int bins, double* mass,
+                           int32_t* count) {
+    const int rc = shells_check_args("nbody_batch_get_shells", {b, edges2, mass, count}, m, edges2, bins,
+                                     b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK) return rc;
+    ShellResult out{mass, count};
+    return batch_rows(b, "nbody_batch_get_shells", b->shl, ShellQuery{edges2, bins}, points, m, &out);
 }
 
 int nbody_batch_get_groups(nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info) {

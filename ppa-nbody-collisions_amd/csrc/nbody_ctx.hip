@@ -32,6 +32,7 @@
 #include "nbody_group_energy.hpp"
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
+#include "nbody_shells.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -200,6 +201,8 @@ struct nbody_ctx {
     PairsState prs;
     // k nearest neighbours (nbody_get_knn, nbody_knn.hpp): nothing is allocated before the first call
     KnnState knn;
+    // shell sums (nbody_get_shells, nbody_shells.hpp): nothing is allocated before the first call
+    ShellState shl;
     // encounter queries (nbody_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -641,6 +644,7 @@ void free_all(nbody_ctx* c) {
     binaries_free(c->bin);
     tides_free(c->tid);
     rows_free(c->knn);
+    rows_free(c->shl);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
@@ -1694,8 +1698,8 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
-// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_groups, nbody_get_pair_counts, nbody_get_encounters,
-// nbody_get_binaries, nbody_get_tides; nbody_rows.hpp and the eight query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
+// Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_shells, nbody_get_groups, nbody_get_pair_counts, nbody_get_encounters,
+// nbody_get_binaries, nbody_get_tides; nbody_rows.hpp and the nine query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
 // every rank holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -1756,6 +1760,14 @@ int nbody_get_knn(nbody_ctx* c, const nbody_vec2* points, int m, int k, double* 
     if (rc != NBODY_OK) return rc;
     KnnResult out{d2, index};
     return ctx_rows(c, "nbody_get_knn", c->knn, KnnQuery{k}, points, m, &out, n_out);
+}
+
+int nbody_get_shells(nbody_ctx* c, const nbody_vec2* points, int m, const double* edges2, int bins, double* mass, int32_t* count,
+                     int* n_out) {
+    const int rc = shells_check_args("nbody_get_shells", {c, edges2, mass, count, n_out}, m, edges2, bins, 1);
+    if (rc != NBODY_OK) return rc;
+    ShellResult out{mass, count};
+    return ctx_rows(c, "nbody_get_shells", c->shl, ShellQuery{edges2, bins}, points, m, &out, n_out);
 }
 
 int nbody_get_groups(nbody_ctx* c, double link, double radius_scale, int32_t* label, int cap, nbody_groups_info* info) {
