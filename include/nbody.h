@@ -615,6 +615,82 @@ int nbody_batch_get_shells(struct nbody_batch* b, const nbody_vec2* points, int 
                            double* mass, int32_t* count);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Shell moments (the reference has none): nbody_get_shells with the velocities.  For every row - a current
+ * body with its own velocity, or a probe point with a velocity of its own - and every bin of squared distance, nine fp64
+ * running sums and a count over the sources in the bin, 1 <= bins <= NBODY_SHELL_MOMENTS_MAX: what a velocity dispersion
+ * profile, the mean radial and tangential motion of a clump (is it contracting? rotating?), the angular momentum around an
+ * accreting body or an anisotropy is made of.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, no divide,
+ * no square root.  The records are (X_j, Y_j, VX_j, VY_j, M_j) of the n current bodies, widened exactly from fp32 or taken
+ * as they are from fp64.  Radii play no part.  For a row at (x, y) with velocity (vx, vy) and a source j:
+ *     dx = X_j - x;  dy = Y_j - y;  d2 = (dx*dx) + (dy*dy)               the d2 of nbody_get_shells, same bits
+ *     in(k, j)  <=>  edges2[k] <= d2 && d2 < edges2[k+1]                  the rule of nbody_get_shells
+ *     ux = VX_j - vx;  uy = VY_j - vy
+ *     w2 = (ux*ux) + (uy*uy)
+ *     s  = (dx*ux) + (dy*uy)                                              d . u  = r v_r
+ *     c  = (dx*uy) - (dy*ux)                                              d x u  = r v_t
+ * and per (row, k) each sum is  acc = +0.0;  for j = 0 .. n-1 ascending:  if in(k, j)  acc = acc + term  with the terms
+ *     mass  M_j            the bits of nbody_get_shells
+ *     px    M_j*ux         momentum relative to the row
+ *     py    M_j*uy
+ *     ke    M_j*w2         twice the kinetic energy relative to the row
+ *     mr2   M_j*d2         moment of inertia about the row
+ *     rad   M_j*s          half of d(mr2)/dt: its sign tells infall from outflow
+ *     ang   M_j*c          angular momentum about the row
+ *     rad2  M_j*(s*s)      r^2-weighted radial second moment
+ *     ang2  M_j*(c*c)      r^2-weighted tangential second moment
+ * count is the number of sources with in(k, j); pad is 0.  The result is [rows * bins] records of 80 bytes, a row's bins next
+ * to each other: out[row*bins + k].  The order of every sum is part of the contract.
+ * Bins: 1 <= bins <= NBODY_SHELL_MOMENTS_MAX = 8.  The accumulators are registers, nine doubles per bin, and a tier of 16
+ * bins would not fit without scratch memory; a caller with more bins makes several calls over adjoining edges, which give the
+ * same bits bin for bin (below).  edges2 follows the rules of nbody_get_shells: bins + 1 squared edges, strictly increasing,
+ * no NaN, edges2[0] >= 0, the last edge may be +inf.
+ * What is left out: a source below the first edge, a source at or above the last edge and a NaN or +inf d2 are counted
+ * nowhere, as in nbody_get_shells.
+ * Own form (points == NULL): the rows are the current bodies with their own velocities, taken on the device; the self term is
+ * excluded by index; m is the room in rows, *n_out the current count n; m < n is NBODY_ERR_CAPACITY with nothing written.
+ * Points form: m probe points with the velocities point_vel[p], or at rest with point_vel == NULL - V - (+0.0) is V bit for
+ * bit, so a point at rest and a point_vel of zeros give the same bits; no self exclusion; *n_out = m; m == 0 is legal and
+ * launches nothing.  point_vel without points is NBODY_ERR_INVALID.
+ * What follows from the definition:
+ *   - mass and count have the bits of nbody_get_shells for the same edges and rows;
+ *   - every sum is a function of the state, the row, its velocity and the two edges of its bin only: bins are independent of
+ *     each other, of the capacity tier the kernel runs at (4 or 8), of m and of the row's place in `points`;
+ *   - with every source at rest and the row at rest every velocity sum (px, py, ke, rad, ang, rad2, ang2) is +0.0;
+ *   - where every mass is 1.0, mass == count exactly;
+ *   - a NaN velocity of source j makes the velocity sums of its bin NaN and it still counts; mass and mr2 stay as they were.
+ *     A NaN is a NaN: IEEE 754 leaves the sign and the payload of a NaN result open, and they are no part of the contract
+ *     (the device subtracts by adding the negated operand, which flips the sign of a NaN operand);
+ *   - it is independent of the semantics: a literal context's frozen tail is a source like any other body.
+ * It synchronises and never changes what later steps compute.  The velocities of other ranks' bodies are not on a rank, so
+ * the query needs a single-rank context: NBODY_ERR_STATE on a context with world > 1, NBODY_FLAG_GROUP_EXCHANGE or
+ * NBODY_FLAG_FORCE_COMM, as for nbody_get_encounters and the jerk of nbody_get_tides.  The device points, their velocities,
+ * the device records and their pinned staging are allocated on the first call and grown; the edges travel as a kernel
+ * argument.  A context that never calls it allocates nothing and the kernels it runs keep their code.
+ * NBODY_ERR_INVALID, found before any device call, the values before the handle: bins outside [1, NBODY_SHELL_MOMENTS_MAX];
+ * point_vel without points; NULL edges2; m < 0; m x bins x 80 bytes above 2^31 (in the own form too, where m is the room); a
+ * bad edge (as nbody_get_pair_counts reports it); NULL ctx, out or n_out.  NBODY_ERR_STATE: before an upload; more than one
+ * rank.
+ * Cost: DESIGN.md 4.19 has the counts and what was measured.  Per pair the kernel does what nbody_get_shells does and pays
+ * for its sums only where some row of a wave has a source below the top edge.
+ * nbody_batch_get_shell_moments: the same query for every system of a batch in ONE launch, with the one set of points, point
+ * velocities and edges for all of them (systems x m x bins x 80 bytes at most 2^31), in nbody_batch_get_shells' layouts.
+ * Explicit points: system s's records at [(s * m + p) * bins + k].  points == NULL: at [(s * capacity + i) * bins + k], one
+ * row per current body, the rest of the slice is left unchanged.  System s gives exactly the bits an nbody_ctx holding that
+ * system's state gives; an empty system gives zeroed records for every explicit point and writes nothing in the own form.
+ * ------------------------------------------------------------------------------------------------- */
+#define NBODY_SHELL_MOMENTS_MAX 8
+typedef struct nbody_shell_moment {
+    double mass, px, py, ke, mr2, rad, ang, rad2, ang2;
+    int32_t count;
+    int32_t pad;                     /* 0 */
+} nbody_shell_moment;                /* 80 bytes */
+int nbody_get_shell_moments(nbody_ctx* ctx, const nbody_vec2* points, const nbody_vec2* point_vel, int m, const double* edges2,
+                            int bins, nbody_shell_moment* out /* [rows * bins] */, int* n_out);
+int nbody_batch_get_shell_moments(struct nbody_batch* b, const nbody_vec2* points, const nbody_vec2* point_vel, int m,
+                                  const double* edges2, int bins, nbody_shell_moment* out);
+
+/* ---------------------------------------------------------------------------------------------------
  * Group finding (the reference has none): friends-of-friends.  Which of the n current bodies hang together,
  * and how many clumps there are: the connected components of the graph of linked pairs.
  * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma, on the

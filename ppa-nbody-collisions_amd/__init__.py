@@ -27,6 +27,8 @@ TRACER_WALLS = 1
 TRACK_PHI = 1
 KNN_MAX = 32
 SHELLS_MAX = 32
+SHELL_MOMENTS_MAX = 8                                           # NBODY_SHELL_MOMENTS_MAX: bins of one library call
+SHELL_MOMENTS_WRAPPER_MAX = 32                                  # bins of one shell_moments(): split into calls of <= 8
 COMM_ID_BYTES = 128
 IMAGE_PATH_MAX = 1024
 
@@ -133,6 +135,10 @@ TIDE_DTYPE = np.dtype([("txx", np.float64), ("txy", np.float64), ("tyy", np.floa
 
 # struct nbody_neighbor as a numpy record (Stepper.neighbors, StepperBatch.neighbors)
 NEIGHBOR_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("overlaps", np.int32)])
+
+# struct nbody_shell_moment (80 bytes) as a numpy record (Stepper.shell_moments, StepperBatch.shell_moments)
+SHELL_MOMENT_FIELDS = ("mass", "px", "py", "ke", "mr2", "rad", "ang", "rad2", "ang2")
+SHELL_MOMENT_DTYPE = np.dtype([(f, np.float64) for f in SHELL_MOMENT_FIELDS] + [("count", np.int32), ("pad", np.int32)])
 
 # struct nbody_groups_info as a numpy record (Stepper.groups, StepperBatch.groups)
 GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
@@ -241,6 +247,8 @@ SYMBOLS = {
     "nbody_get_neighbors": (_i, [_vp, _vp, _i, _vp, _ip]),
     "nbody_get_knn": (_i, [_vp, _vp, _i, _i, _vp, _vp, _ip]),
     "nbody_get_shells": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _ip]),
+    "nbody_get_shell_moments": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _ip]),
+    "nbody_batch_get_shell_moments": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
     "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
     "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
@@ -693,6 +701,74 @@ def shell_profile(shells):
             "enclosed_count": enclosed_count, "half_mass_radius2": half}
 
 
+def _shell_moment_rows(points, point_vel):
+    """The rows of shell_moments(): _field_points' points, and their velocities - None (at rest), or shape (m, 2) like the
+    points; they need points.  Checked here, before the library is called."""
+    pts = _field_points(points)
+    if point_vel is None:
+        return pts, None
+    if pts is None:
+        raise ValueError("point_vel needs points: the bodies' own rows have their own velocities")
+    vel = np.ascontiguousarray(np.asarray(point_vel, dtype=np.float64))
+    if vel.shape != pts.shape:
+        raise ValueError("point_vel must have the points' shape %r, got %r" % (pts.shape, vel.shape))
+    return pts, vel
+
+
+def _shell_moments(call, shape, e2):
+    """nbody_get_shell_moments through `call(edges2, bins, out)` for up to SHELL_MOMENTS_WRAPPER_MAX bins: one library call
+    per SHELL_MOMENTS_MAX adjoining bins, each into a buffer of `shape` + (bins of the call,), put side by side.  The bits
+    are the same bin for bin: a bin's sums depend on its own two edges only."""
+    bins = len(e2) - 1
+    if bins > SHELL_MOMENTS_WRAPPER_MAX:
+        raise ValueError("shell_moments takes at most %d bins, got %d" % (SHELL_MOMENTS_WRAPPER_MAX, bins))
+    out = np.zeros(shape + (bins,), dtype=SHELL_MOMENT_DTYPE)
+    for k0 in range(0, bins, SHELL_MOMENTS_MAX):
+        k1 = min(k0 + SHELL_MOMENTS_MAX, bins)
+        part = np.zeros(shape + (k1 - k0,), dtype=SHELL_MOMENT_DTYPE)
+        edges = np.ascontiguousarray(e2[k0:k1 + 1])
+        _check(call(edges.ctypes.data, k1 - k0, part.ctypes.data))
+        out[..., k0:k1] = part
+    return out
+
+
+def shell_kinematics(result):
+    """What the kinematic read-outs are made of, from one result of shell_moments() ({"moments": (..., B) of
+    SHELL_MOMENT_DTYPE, ...}) or from such an array itself.  Per (row, bin), float64, with u the sources' velocity relative to
+    the row and d their offset from it:
+      "mean_velocity" (..., B, 2): (px, py) / mass, the mass-weighted mean of u;
+      "sigma2": ke / mass - |mean_velocity|^2, the velocity dispersion about that mean (both components together);
+      "mean_r2": mr2 / mass, the mass-weighted mean squared distance;
+      "expansion_rate": rad / mr2 and "rotation_rate": ang / mr2 - H and Omega of the mass-weighted least-squares fit of
+        u = H d + Omega z x d to the bin (the normal equations are sum m d.u = H sum m d2 and sum m d x u = Omega sum m d2);
+      "vr2": rad2 / mr2 and "vt2": ang2 / mr2, the r^2-weighted mean squares of the radial and the tangential velocity;
+      "anisotropy": 1 - (vt2 - rotation_rate^2 mean_r2) / (vr2 - expansion_rate^2 mean_r2): the fitted flow's share H^2 r^2 or
+        Omega^2 r^2 is taken off each mean square with r^2 = mean_r2, which is exact for a thin bin and an estimate for a
+        wide one (the r^2-weighted mean of r^2 is sum m d2^2 / sum m d2, which the sums do not hold).  0 for isotropic
+        residuals, towards 1 for radial ones, negative for tangential ones.  Where the residual radial motion is nothing
+        but rounding - a pure rotation, a pure expansion, a bin at rest - the denominator is noise or 0 and the value is
+        meaningless or NaN.
+    Every entry of an empty bin (count == 0) is NaN.  Plain numpy on the host; needs no GPU and no library call."""
+    mom = result["moments"] if isinstance(result, dict) else result
+    mom = np.asarray(mom)
+    if mom.dtype != SHELL_MOMENT_DTYPE:
+        raise ValueError("shell_kinematics: the \"moments\" of one shell_moments() result, got dtype %r" % (mom.dtype,))
+    empty = mom["count"] == 0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        mass, mr2 = mom["mass"], mom["mr2"]
+        mean = np.stack([mom["px"] / mass, mom["py"] / mass], axis=-1)
+        sigma2 = mom["ke"] / mass - ((mean[..., 0] * mean[..., 0]) + (mean[..., 1] * mean[..., 1]))
+        mean_r2 = mr2 / mass
+        H, W = mom["rad"] / mr2, mom["ang"] / mr2
+        vr2, vt2 = mom["rad2"] / mr2, mom["ang2"] / mr2
+        beta = 1.0 - (vt2 - (W * W) * mean_r2) / (vr2 - (H * H) * mean_r2)
+    out = {"mean_velocity": mean, "sigma2": sigma2, "mean_r2": mean_r2, "expansion_rate": H, "rotation_rate": W, "vr2": vr2,
+           "vt2": vt2, "anisotropy": beta}
+    for name, a in out.items():
+        a[empty] = np.nan
+    return out
+
+
 def _encounter_list(rec):
     out = np.zeros(len(rec), dtype=ENCOUNTER_DTYPE)
     for f in ENCOUNTER_DTYPE.names:
@@ -1065,6 +1141,23 @@ class Stepper:
                                     mass.ctypes.data, count.ctypes.data, ctypes.byref(n)))
         return {"mass": mass[:n.value].copy(), "count": count[:n.value].copy(), "edges2": e2}
 
+    def shell_moments(self, edges, points=None, point_vel=None, squared=False):
+        """nbody_get_shell_moments: shells() with the velocities.  For every row - each of `points` (m, 2) moving with
+        `point_vel` (m, 2; None: at rest), or with points=None each current body with its own velocity (self term left out
+        by index) - and each bin between the B + 1 `edges` (lengths; squared lengths with squared=True), nine fp64 sums
+        over the bin's sources in ascending index and their number: {"moments": SHELL_MOMENT_DTYPE (rows, B) - mass, px, py,
+        ke, mr2, rad, ang, rad2, ang2, count - "edges2": the squared edges that were sent}.  1 <= B <= 32: the library takes
+        SHELL_MOMENTS_MAX bins a call, more are split into calls over adjoining edges, which gives the same bits bin for
+        bin.  shell_kinematics() turns the sums into mean velocities, dispersions and rates.  Needs a single-rank context."""
+        e2 = pair_edges2(edges, squared)
+        pts, vel = _shell_moment_rows(points, point_vel)
+        m = self.capacity if pts is None else len(pts)
+        n = ctypes.c_int(0)
+        mom = _shell_moments(lambda edges2, bins, out: lib.nbody_get_shell_moments(
+            self._ctx, None if pts is None else pts.ctypes.data, None if vel is None else vel.ctypes.data, m, edges2, bins, out,
+            ctypes.byref(n)), (max(m, 1),), e2)
+        return {"moments": mom[:n.value].copy(), "edges2": e2}
+
     def groups(self, link, radius_scale=1.0):
         """nbody_get_groups: friends-of-friends groups of the current bodies, i and j linked where d2 <= s*s with
         s = radius_scale * (r_i + r_j) + link (fp64): {"label": int32 (n,), label[i] the lowest index of body i's group,
@@ -1411,6 +1504,21 @@ class StepperBatch:
             return [{"mass": mass[s, :int(c)].copy(), "count": count[s, :int(c)].copy(), "edges2": e2}
                     for s, c in enumerate(self.counts())]
         return {"mass": np.ascontiguousarray(mass[:, :m]), "count": np.ascontiguousarray(count[:, :m]), "edges2": e2}
+
+    def shell_moments(self, edges, points=None, point_vel=None, squared=False):
+        """nbody_batch_get_shell_moments: Stepper.shell_moments for every system in one launch (per 8 bins), with the one set
+        of edges, points and point velocities for all of them, system s having the bits a Stepper holding its state gives.
+        points=None: a list of S dicts, one row per current body of the system; otherwise one dict with "moments" of shape
+        (S, m, B)."""
+        e2 = pair_edges2(edges, squared)
+        pts, vel = _shell_moment_rows(points, point_vel)
+        m = self.capacity if pts is None else len(pts)
+        mom = _shell_moments(lambda edges2, bins, out: lib.nbody_batch_get_shell_moments(
+            self._b, None if pts is None else pts.ctypes.data, None if vel is None else vel.ctypes.data, m, edges2, bins, out),
+            (self.systems, max(m, 1)), e2)
+        if pts is None:
+            return [{"moments": mom[s, :int(c)].copy(), "edges2": e2} for s, c in enumerate(self.counts())]
+        return {"moments": np.ascontiguousarray(mom[:, :m]), "edges2": e2}
 
     def groups(self, link, radius_scale=1.0):
         """nbody_batch_get_groups: Stepper.groups for every system, every pair walk one launch for the whole batch: a list

@@ -30,6 +30,7 @@
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
 #include "nbody_shells.hpp"
+#include "nbody_shell_moments.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -97,6 +98,8 @@ struct nbody_batch {
     KnnState knn;
     // shell sums (nbody_batch_get_shells, nbody_shells.hpp): nothing is allocated before the first call
     ShellState shl;
+    // shell moments (nbody_batch_get_shell_moments, nbody_shell_moments.hpp): nothing is allocated before the first call
+    ShellMomentState shm;
     // encounter queries (nbody_batch_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_batch_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -133,6 +136,7 @@ void free_all(nbody_batch* b) {
     tides_free(b->tid);
     rows_free(b->knn);
     rows_free(b->shl);
+    shell_moments_free(b->shm);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
@@ -730,7 +734,7 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 
 // ---------------------------------------------------------------------------------------------------------
 // Row queries (nbody_batch_get_field, nbody_batch_get_neighbors, nbody_batch_get_knn, nbody_batch_get_shells, nbody_batch_get_groups,
-// nbody_batch_get_pair_counts, nbody_batch_get_encounters, nbody_batch_get_binaries, nbody_batch_get_tides; nbody_rows.hpp and the nine query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
+// nbody_batch_get_pair_counts, nbody_batch_get_encounters, nbody_batch_get_binaries, nbody_batch_get_tides, nbody_batch_get_shell_moments; nbody_rows.hpp and the ten query headers): one launch (groups: per sweep) for every system, system = blockIdx.y, one set
 // of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -792,6 +796,19 @@ int nbody_batch_get_shells(nbody_batch* b, const nbody_vec2* points, int m, cons
     if (rc != NBODY_OK) return rc;
     ShellResult out{mass, count};
     return batch_rows(b, "nbody_batch_get_shells", b->shl, ShellQuery{edges2, bins}, points, m, &out);
+}
+
+// Shell moments (nbody_shell_moments.hpp): one set of points, point velocities and edges for every system, one launch.
+int nbody_batch_get_shell_moments(nbody_batch* b, const nbody_vec2* points, const nbody_vec2* point_vel, int m,
+                                  const double* edges2, int bins, nbody_shell_moment* out) {
+    const char* who = "nbody_batch_get_shell_moments";
+    RowsSite site;
+    int rc = shell_moments_check_args(who, {b, out}, points, point_vel, m, edges2, bins, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return shell_moments_run<decltype(t), RowsBatchCount>(who, site, b->shm, b->V, points, point_vel, m, edges2, bins, out,
+                                                              sync);
+    });
 }
 
 int nbody_batch_get_groups(nbody_batch* b, double link, double radius_scale, int32_t* label, nbody_groups_info* info) {

@@ -33,6 +33,7 @@
 #include "nbody_pairs.hpp"
 #include "nbody_knn.hpp"
 #include "nbody_shells.hpp"
+#include "nbody_shell_moments.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -203,6 +204,8 @@ struct nbody_ctx {
     KnnState knn;
     // shell sums (nbody_get_shells, nbody_shells.hpp): nothing is allocated before the first call
     ShellState shl;
+    // shell moments (nbody_get_shell_moments, nbody_shell_moments.hpp): nothing is allocated before the first call
+    ShellMomentState shm;
     // encounter queries (nbody_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -645,6 +648,7 @@ void free_all(nbody_ctx* c) {
     tides_free(c->tid);
     rows_free(c->knn);
     rows_free(c->shl);
+    shell_moments_free(c->shm);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
@@ -1699,7 +1703,7 @@ int nbody_track_read(nbody_ctx* c, nbody_track_row* rows, void* rec, int32_t* in
 
 // ---------------------------------------------------------------------------------------------------------
 // Row queries (nbody_get_field, nbody_get_neighbors, nbody_get_knn, nbody_get_shells, nbody_get_groups, nbody_get_pair_counts, nbody_get_encounters,
-// nbody_get_binaries, nbody_get_tides; nbody_rows.hpp and the nine query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
+// nbody_get_binaries, nbody_get_tides, nbody_get_shell_moments; nbody_rows.hpp and the ten query headers).  At the end of the file for the reason the identities are.  They read the replica J only -
 // every rank holds every {x, y, m, r} - so any context may call them on its own, whatever its world or transport.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -1768,6 +1772,27 @@ int nbody_get_shells(nbody_ctx* c, const nbody_vec2* points, int m, const double
     if (rc != NBODY_OK) return rc;
     ShellResult out{mass, count};
     return ctx_rows(c, "nbody_get_shells", c->shl, ShellQuery{edges2, bins}, points, m, &out, n_out);
+}
+
+// Shell moments (nbody_shell_moments.hpp): the shell sums with the velocities, so the encounters' restriction holds.
+int nbody_get_shell_moments(nbody_ctx* c, const nbody_vec2* points, const nbody_vec2* point_vel, int m, const double* edges2,
+                            int bins, nbody_shell_moment* out, int* n_out) {
+    const char* who = "nbody_get_shell_moments";
+    RowsSite site;
+    int rc = shell_moments_check_args(who, {c, out, n_out}, points, point_vel, m, edges2, bins, 1);
+    if (rc != NBODY_OK) return rc;
+    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
+        return nbody_fail(NBODY_ERR_STATE, "%s: shell moments need a single-rank context without an exchange (world %d, flags 0x%x): "
+                                           "a rank holds only its own velocities, a query across ranks is not built", who,
+                          c->desc.world, c->desc.flags);
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if (!points && m < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, site.n_bound);
+    *n_out = points ? m : site.n_bound;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return shell_moments_run<decltype(t), RowsOneCount>(who, site, c->shm, c->Vown, points, point_vel, m, edges2, bins, out,
+                                                            sync);
+    });
 }
 
 int nbody_get_groups(nbody_ctx* c, double link, double radius_scale, int32_t* label, int cap, nbody_groups_info* info) {
