@@ -131,8 +131,8 @@ void free_all(nbody_batch* b) {
     groups_free(b->grp);
     rows_free(b->gen);
     pairs_free(b->prs);
-    encounters_free(b->enc);
-    binaries_free(b->bin);
+    pair_log_free(b->enc);
+    pair_log_free(b->bin);
     tides_free(b->tid);
     rows_free(b->knn);
     rows_free(b->shl);
@@ -836,10 +836,10 @@ int nbody_batch_get_pair_counts(nbody_batch* b, const nbody_vec2* points, int m,
 int nbody_batch_get_encounters(nbody_batch* b, double horizon, nbody_encounter* out, int cap, nbody_encounter_info* info) {
     const char* who = "nbody_batch_get_encounters";
     RowsSite site;
-    int rc = encounters_check_args(who, b, horizon, out, cap, info, b ? (unsigned long long)b->S : 1);
+    int rc = pair_log_check_args(who, b, EncQuery{horizon}, out, cap, info, b ? (unsigned long long)b->S : 1);
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return encounters_run<decltype(t), RowsBatchCount>(who, site, b->V, b->enc, horizon, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsBatchCount>(who, site, b->V, b->enc, EncQuery{horizon}, out, cap, info, sync);
     });
 }
 
@@ -847,10 +847,10 @@ int nbody_batch_get_encounters(nbody_batch* b, double horizon, nbody_encounter* 
 int nbody_batch_get_binaries(nbody_batch* b, double sep2, nbody_binary* out, int cap, nbody_binary_info* info) {
     const char* who = "nbody_batch_get_binaries";
     RowsSite site;
-    int rc = binaries_check_args(who, b, sep2, out, cap, info, b ? (unsigned long long)b->S : 1);
+    int rc = pair_log_check_args(who, b, BinQuery{sep2}, out, cap, info, b ? (unsigned long long)b->S : 1);
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return binaries_run<decltype(t), RowsBatchCount>(who, site, b->V, b->bin, sep2, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsBatchCount>(who, site, b->V, b->bin, BinQuery{sep2}, out, cap, info, sync);
     });
 }
 

@@ -643,8 +643,8 @@ void free_all(nbody_ctx* c) {
     groups_free(c->grp);
     rows_free(c->gen);
     pairs_free(c->prs);
-    encounters_free(c->enc);
-    binaries_free(c->bin);
+    pair_log_free(c->enc);
+    pair_log_free(c->bin);
     tides_free(c->tid);
     rows_free(c->knn);
     rows_free(c->shl);
@@ -1825,7 +1825,7 @@ int nbody_get_pair_counts(nbody_ctx* c, const nbody_vec2* points, int m, const d
 int nbody_get_encounters(nbody_ctx* c, double horizon, nbody_encounter* out, int cap, nbody_encounter_info* info) {
     const char* who = "nbody_get_encounters";
     RowsSite site;
-    int rc = encounters_check_args(who, c, horizon, out, cap, info, 1);
+    int rc = pair_log_check_args(who, c, EncQuery{horizon}, out, cap, info, 1);
     if (rc != NBODY_OK) return rc;
     if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
         return nbody_fail(NBODY_ERR_STATE, "%s: encounters need a single-rank context without an exchange (world %d, flags 0x%x): "
@@ -1833,7 +1833,7 @@ int nbody_get_encounters(nbody_ctx* c, double horizon, nbody_encounter* out, int
                           c->desc.world, c->desc.flags);
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return encounters_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->enc, horizon, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->enc, EncQuery{horizon}, out, cap, info, sync);
     });
 }
 
@@ -1841,7 +1841,7 @@ int nbody_get_encounters(nbody_ctx* c, double horizon, nbody_encounter* out, int
 int nbody_get_binaries(nbody_ctx* c, double sep2, nbody_binary* out, int cap, nbody_binary_info* info) {
     const char* who = "nbody_get_binaries";
     RowsSite site;
-    int rc = binaries_check_args(who, c, sep2, out, cap, info, 1);
+    int rc = pair_log_check_args(who, c, BinQuery{sep2}, out, cap, info, 1);
     if (rc != NBODY_OK) return rc;
     if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
         return nbody_fail(NBODY_ERR_STATE, "%s: binaries need a single-rank context without an exchange (world %d, flags 0x%x): "
@@ -1849,7 +1849,7 @@ int nbody_get_binaries(nbody_ctx* c, double sep2, nbody_binary* out, int cap, nb
                           c->desc.world, c->desc.flags);
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return binaries_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->bin, sep2, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->bin, BinQuery{sep2}, out, cap, info, sync);
     });
 }
 

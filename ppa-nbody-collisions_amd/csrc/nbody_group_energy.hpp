@@ -3,9 +3,9 @@
 // members of its own friends-of-friends group,
 //     phi_in[i] = -G sum_{ j != i, label[j] == label[i], r_ij > 0 } m_j / r_ij,
 // label[] being the labels of nbody_get_groups for the same (link, radius_scale).  Included after nbody_groups.hpp by both
-// translation units.  The launch geometry, the count and the early exits are those of every row query (nbody_rows.hpp); this
-// file has the masked pair, its own copy of the full tile walk (a fourth LDS plane for the labels, which neither rows_walk
-// nor diag_walk_sums has), the general row and the host driver.  The O(N) catalogue is plain C on the host
+// translation units.  The launch geometry, the count, the early exits and the tile loop (rows_walk, full shape) are those of
+// every row query (nbody_rows.hpp); this file has the masked pair, the stage of its {x, y, m} and label
+// planes, the general row and the host driver.  The O(N) catalogue is plain C on the host
 // (nbody_group_energy.c).
 //
 // The sub-state rule, which is the contract in bits.  Let a group's members be i_0 < i_1 < ... < i_k.  phi_in[i_a] has the
@@ -71,7 +71,7 @@ __device__ __forceinline__ DiagRow group_row_general(const Rec<T>* __restrict__ 
     return DiagRow{s, c};
 }
 
-// The four pairs of one trip of group_walk: four integer compares, and the fp64 chain behind one branch.
+// The four pairs of one trip of rows_walk: four integer compares, and the fp64 chain behind one branch.
 struct GroupFour {
     const DiagPlanes *sx, *sy, *sm;
     const GroupLabels* sl;
@@ -100,44 +100,9 @@ struct GroupFour {
     }
 };
 
-// The full tile walk, j = 0 .. n-1 ascending: all kDiagBlock lanes call it after rows_prologue.  rows_walk's shape (kOwn,
-// not triangular) with the {x, y, m} planes of diag_walk_sums and the label plane; the padding and the lanes without a row
-// as the head of the file says.
-template <typename T>
-__device__ __forceinline__ void group_walk(const RowsLane<T, GroupPhiOut>& L, const int32_t* __restrict__ label, DiagPlanes& sx,
-                                           DiagPlanes& sy, DiagPlanes& sm, GroupLabels& sl, GroupFour& carried) {
-    GroupFour f = carried;                                       // as rows_walk: a local of the function that has the loops
-    const Rec<T>* __restrict__ J = L.J;
-    const int n = L.n, tid = threadIdx.x;
-    const int jtiles = (n + kTile - 1) / kTile;                  // workgroup-uniform
-    for (int t = 0; t < jtiles; ++t) {
-        const int b = t & 1;
-        const int j0 = t * kTile;
-        const int jn = n - j0 < kTile ? n - j0 : kTile;
-        if (tid < kTile) {
-            double x = 0.0, y = 0.0, m = 0.0;
-            int32_t l = -1;                                      // padding: no row's label
-            if (tid < jn) {
-                const Rec<T> s = J[j0 + tid];
-                x = (double)s.x; y = (double)s.y; m = (double)s.m;
-                l = label[j0 + tid];
-            }
-            sx[b][tid] = x; sy[b][tid] = y; sm[b][tid] = m; sl[b][tid] = l;
-        }
-        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
-        __syncthreads();
-        if (!L.wave_works) continue;
-        const int jn4 = (jn + 3) & ~3;                           // <= kTile: the padding is there
-        if (t != L.self_tile) {
-            for (int q = 0; q < jn4; q += 4) f.template four<false>(b, q, j0 + q);
-        } else {
-            for (int q = 0; q < jn4; q += 4) f.template four<true>(b, q, j0 + q);
-        }
-    }
-    carried = f;
-}
-
-// grid and early exits: rows_prologue (nbody_rows.hpp).  label_all: the labels groups_flatten left, `stride` apart per system.
+// grid and early exits: rows_prologue; the full walk, j = 0 .. n-1 ascending along a lane: rows_walk (nbody_rows.hpp) over the
+// {x, y, m} planes of diag_walk_sums and a label plane; the padding and the lanes without a row as the head of the file says.
+// label_all: the labels groups_flatten left, `stride` apart per system.
 template <typename T, typename Count>
 __global__ __launch_bounds__(kDiagBlock) void group_potential(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
                                                               Counters* __restrict__ ctr_all, int stride, int n_one,
@@ -157,7 +122,17 @@ __global__ __launch_bounds__(kDiagBlock) void group_potential(const Rec<T>* __re
     __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
     __shared__ int32_t sl[2][kTile];
     GroupFour f{&sx, &sy, &sm, &sl, L.p, li, xi, yi, DiagPhiSum{}};
-    group_walk<T>(L, label, sx, sy, sm, sl, f);
+    const Rec<T>* __restrict__ J = L.J;
+    rows_walk<true, false>(L, [J, label](int b, int e, bool live, int j) {
+        double x = 0.0, y = 0.0, m = 0.0;
+        int32_t l = -1;                                          // padding: no row's label
+        if (live) {
+            const Rec<T> s = J[j];
+            x = (double)s.x; y = (double)s.y; m = (double)s.m;
+            l = label[j];
+        }
+        sx[b][e] = x; sy[b][e] = y; sm[b][e] = m; sl[b][e] = l;
+    }, f);
     if (!L.valid) return;
     double acc = f.a.s;
     long long coin = 0;

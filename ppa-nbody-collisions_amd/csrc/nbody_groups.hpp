@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kDiagBlock) void groups_sweep(const Rec<T>* __restr
     if (prev[sys] == 0) return;                                  // converged in an earlier sweep: the whole workgroup
     __shared__ double sx[2][kTile], sy[2][kTile], sr[2][kTile];
     GroupsFour f{&sx, &sy, &sr, L.p, rows_row<T, true>(L, nullptr), link, scale, L.out, cur + sys};
-    rows_walk<true, true, true>(L, sx, sy, &sr, f);
+    rows_walk<true, true>(L, RowsStage<true, T>{L.J, &sx, &sy, &sr}, f);
 }
 
 // label[i] = find(i), after the sweep that changed nothing: the lowest index of i's component.

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kDiagBlock) void knn_at(const Rec<T>* __restrict__ 
     KnnFour<K> f{&sx, &sy, L.p, rows_row<T, kOwn>(L, points), {}};
 #pragma unroll
     for (int c = 0; c < K; ++c) { f.a.d2[c] = __builtin_inf(); f.a.index[c] = -1; }
-    rows_walk<kOwn, false, false>(L, sx, sy, nullptr, f);
+    rows_walk<kOwn, false>(L, RowsStage<false, T>{L.J, &sx, &sy, nullptr}, f);
     if (L.valid) {
 #pragma unroll
         for (int c = 0; c < K; ++c)

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(kDiagBlock) void neighbors_at(const Rec<T>* __restr
         return;
     __shared__ double sx[2][kTile], sy[2][kTile], sr[2][kTile];
     NeighborFour<kOwn> f{&sx, &sy, &sr, L.p, rows_row<T, kOwn>(L, points), NeighborBest{}};
-    rows_walk<kOwn, false, true>(L, sx, sy, &sr, f);
+    rows_walk<kOwn, false>(L, RowsStage<true, T>{L.J, &sx, &sy, &sr}, f);
     if (L.valid) L.out[L.p] = NeighborOut{f.a.best, f.a.index, f.a.overlaps};
 }
 

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kDiagBlock) void pair_counts(const Rec<T>* __restri
     int first = 1;
     while (2 * first <= bins) first *= 2;                        // 2^(ceil(log2(bins + 1)) - 1): workgroup-uniform
     PairFour f{&sx, &sy, L.p, rows_row<T, kOwn>(L, points), edges2[bins], se, first, hist};
-    rows_walk<kOwn, kOwn, false>(L, sx, sy, nullptr, f);
+    rows_walk<kOwn, kOwn>(L, RowsStage<false, T>{L.J, &sx, &sy, nullptr}, f);
     __syncthreads();                                             // every LDS count of the workgroup is in
     unsigned long long* __restrict__ g = hist_all + (size_t)sys * (size_t)(bins + 1);
     for (int k = tid; k <= bins; k += kDiagBlock) {

@@ -1,7 +1,8 @@
 // csrc/nbody_rows.hpp -- a row per lane over the resident state: what the row queries (field evaluation, nbody_field.hpp;
 // neighbour queries, nbody_neighbors.hpp; group finding, nbody_groups.hpp; pair counts, nbody_pairs.hpp; the k nearest,
-// nbody_knn.hpp; encounters, nbody_encounters.hpp; bound pairs, nbody_binaries.hpp) have in common, on the device and
-// on the host.  Included after nbody_diag.hpp and before the query headers by both translation units: one system
+// nbody_knn.hpp; encounters, nbody_encounters.hpp; bound pairs, nbody_binaries.hpp; group energies, nbody_group_energy.hpp;
+// shell sums and moments, nbody_shells.hpp and nbody_shell_moments.hpp)
+// have in common, on the device and on the host.  Included after nbody_diag.hpp and before the query headers by both translation units: one system
 // (nbody_ctx.hip) and a batch (nbody_batch.hip: system = blockIdx.y, per-body arrays `stride` apart, one set of points for
 // every system) share each query's one kernel.
 //
@@ -17,13 +18,16 @@
 //     128-body tile: wave-uniform), so only that tile runs a checked loop.  Points have no checked loop at all.
 //
 // Adding a row query takes a kernel `<T, kOwn, Count>` that opens with rows_prologue, loads its row with rows_row and hands
-// rows_walk (the tile loop, below) a functor with the query's four pairs of one trip; and a host side built from rows_run
-// (a fixed number of result records per row: a traits struct such as FieldQuery, NeighborQuery or KnnQuery is all it takes)
-// or, for another shape of result, from the pieces of rows_run - RowsSite's grid, count and sync, RowPoints,
-// rows_check_args.  The per-handle preamble and the precision dispatch are in the two .hip files.  field_at walks with
-// diag_walk_sums instead (see rows_walk); encounters_walk and binaries_walk, which need the velocities (and masses) in more planes,
-// each have their own copy of the triangular walk.  tides_at (nbody_tides.hpp) walks with diag_walk_sums as
-// field_at does, and for the jerk, which needs the velocities in two more planes, with its own copy of that ascending walk.
+// rows_walk (the one tile loop, below) a stage and a functor with the query's four pairs of one trip.  The
+// stage says which LDS planes a tile's entry goes into and what a padding entry holds: RowsStage for {x, y[, r]}, a lambda
+// in the kernel for a query that needs more (velocities, masses, labels).  A kernel whose lanes count ends with rows_wave_add.
+// The host side is built from rows_run (a fixed number of result records per row: a traits struct such as FieldQuery,
+// NeighborQuery or KnnQuery is all it takes), from the pair-log driver at the end of this file (a capped list of found
+// pairs per system and counters: a traits struct such as EncQuery or BinQuery) or, for another shape of result, from the
+// pieces of rows_run - RowsSite's grid, count and sync, RowPoints, rows_check_args.  The per-handle preamble and the
+// precision dispatch are in the two .hip files.  Only the ordered family stays out of rows_walk (see there): field_at and
+// tides_at (nbody_tides.hpp) walk with diag_walk_sums, and the jerk, which needs the velocities in two more
+// planes, with its own copy of that ascending walk.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -114,15 +118,17 @@ __device__ __forceinline__ RowsRow rows_row(const RowsLane<T, Out>& L, const Fie
     return w;
 }
 
-// The tile walk of a row query whose pairs need no order: all kDiagBlock lanes call it after rows_prologue.  A tile's
-// {x, y[, r]} are widened to fp64 ONCE into the caller's double-buffered LDS planes (one barrier per tile; sr is staged only
-// for kRadius and may be NULL otherwise) and read back by the functor as wave-uniform broadcasts.  The ragged tile is padded
-// with x = NaN (y = r = +0): a padding entry has d2 = NaN and passes no comparison, so the pair loop carries no bound test
-// and no remainder loop - it runs in fours up to the tile's count rounded up to 4 (not to kTile: a 64-body system of a batch
-// would pay 128 pairs per row).  The functor is called as f.template four<kChecked>(b, q, j): the sources j .. j + 3 are
-// entries q .. q + 3 of buffer b; kChecked: the tile holds the wave's own rows, the functor applies its index test.  It is
-// walked in a copy and handed back at the end: what it carries from pair to pair (NeighborFour's best), carried through the
-// reference, is promoted from memory twice and every pair pays two more selects.
+// The tile walk of every row query whose pairs need no order - the only tile loop of the NaN-padded family: all kDiagBlock
+// lanes call it after rows_prologue.  A tile's entries are widened to fp64 ONCE into the query's own double-buffered LDS
+// planes (one barrier per tile) and read back by the functor as wave-uniform broadcasts.  Which planes, the walk does not
+// know: lane e < kTile calls stage(b, e, live, j), which fills entry e of buffer b from source j where `live` and with the
+// query's padding otherwise.  The padding of the ragged tile passes no comparison of the query (RowsStage: x = NaN, so
+// d2 = NaN), so the pair loop carries no bound test and no remainder loop - it runs in fours up to the tile's count rounded
+// up to 4 (not to kTile: a 64-body system of a batch would pay 128 pairs per row).  The functor is called as
+// f.template four<kChecked>(b, q, j): the sources j .. j + 3 are entries q .. q + 3 of buffer b; kChecked: the tile holds
+// the wave's own rows, the functor applies its index test.  It is walked in a copy and handed back at the end: what it
+// carries from pair to pair (NeighborFour's best), carried through the reference, is promoted from memory twice and every
+// pair pays two more selects.
 //   * kTri = false, the full walk: every tile; kOwn runs the whole self tile checked, points have no checked loop.
 //   * kTri = true (kOwn only), the triangular walk for symmetric pairs, each counted at the higher row: only the tiles up
 //     to the one that holds the workgroup's last row are staged (a workgroup-uniform bound: the barriers need it); a wave
@@ -130,11 +136,10 @@ __device__ __forceinline__ RowsRow rows_row(const RowsLane<T, Out>& L, const Fie
 // Not one walk with diag_walk_sums (nbody_diag.hpp), which field_at calls: that one sums in ascending order under an order
 // contract with fma-contracted arithmetic, so it cannot pad with NaN, keeps a remainder loop, votes per tile for gathered
 // rows, and its comment records that a function boundary inside it changes the code of every potential kernel.
-template <bool kOwn, bool kTri, bool kRadius, typename T, typename Out, typename Four>
-__device__ __forceinline__ void rows_walk(const RowsLane<T, Out>& L, DiagPlanes& sx, DiagPlanes& sy, DiagPlanes* sr, Four& carried) {
+template <bool kOwn, bool kTri, typename T, typename Out, typename Stage, typename Four>
+__device__ __forceinline__ void rows_walk(const RowsLane<T, Out>& L, const Stage stage, Four& carried) {
     static_assert(kOwn || !kTri, "the triangular walk is over own rows");
     Four f = carried;                                            // see above: a local of the function that has the loops
-    const Rec<T>* __restrict__ J = L.J;
     const int n = L.n, tid = threadIdx.x;
     const int row0 = blockIdx.x * kDiagBlock;
     const int last = (row0 + kDiagBlock < n ? row0 + kDiagBlock : n) - 1;   // kTri: the workgroup's last row
@@ -144,15 +149,7 @@ __device__ __forceinline__ void rows_walk(const RowsLane<T, Out>& L, DiagPlanes&
         const int b = t & 1;
         const int j0 = t * kTile;
         const int jn = n - j0 < kTile ? n - j0 : kTile;
-        if (tid < kTile) {
-            double x = __builtin_nan(""), y = 0.0, r = 0.0;      // padding: d2 = NaN
-            if (tid < jn) {
-                const Rec<T> s = J[j0 + tid];
-                x = (double)s.x; y = (double)s.y; r = (double)s.r;
-            }
-            sx[b][tid] = x; sy[b][tid] = y;
-            if constexpr (kRadius) (*sr)[b][tid] = r;
-        }
+        if (tid < kTile) stage(b, tid, tid < jn, j0 + tid);
         // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
         __syncthreads();
         if (!L.wave_works || (kTri && t > L.self_tile)) continue;
@@ -166,6 +163,42 @@ __device__ __forceinline__ void rows_walk(const RowsLane<T, Out>& L, DiagPlanes&
         }
     }
     carried = f;
+}
+
+// The stage of the queries that need positions only: {x, y[, r]} of the system's records J, the padding x = NaN (y = r = +0).
+// sr is staged only for kRadius and may be NULL otherwise.
+template <bool kRadius, typename T>
+struct RowsStage {
+    const Rec<T>* __restrict__ J;
+    DiagPlanes *sx, *sy, *sr;
+    __device__ __forceinline__ void operator()(int b, int e, bool live, int j) const {
+        double x = __builtin_nan(""), y = 0.0, r = 0.0;          // padding: d2 = NaN
+        if (live) {
+            const Rec<T> s = J[j];
+            x = (double)s.x; y = (double)s.y; r = (double)s.r;
+        }
+        (*sx)[b][e] = x; (*sy)[b][e] = y;
+        if constexpr (kRadius) (*sr)[b][e] = r;
+    }
+};
+
+// The tail of a kernel whose lanes count: each of the N lane counts is summed over the wave and added to its 64-bit counter
+// with one atomic from the wave's first lane; a sum of zero adds nothing.  Every lane of the wave calls it.  The N sums go
+// through the shuffles together, ahead of the one branch to the first lane.
+template <int N>
+__device__ __forceinline__ void rows_wave_add(unsigned long long* const (&counter)[N], const unsigned (&lane_count)[N]) {
+    unsigned long long c[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) c[k] = lane_count[k];
+    for (int sh = kWave / 2; sh > 0; sh >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) c[k] += __shfl_down(c[k], sh, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if (c[k]) atomicAdd(counter[k], c[k]);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -308,6 +341,109 @@ int rows_run(const char* who, const RowsSite& s, PointBuffers<typename Q::Device
     const Device* h = reinterpret_cast<const Device*>(buf.out.h);
     for (int sys = 0; sys < s.systems; ++sys)
         q.unpack(sys, h + (size_t)sys * per_sys * width, own ? (size_t)s.count(sys) : (size_t)m, out, (size_t)sys * per_sys);
+    return NBODY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The pair-log driver: the host side of a query whose kernel appends one raw record per found pair to a capped log per
+// system and counts into one Counts per system (encounters, nbody_encounters.hpp; bound pairs, nbody_binaries.hpp).
+// Q: the query's traits, an object that holds the call's value (the horizon, sep2) -
+//     Raw, Counts (first member `pairs`), Info (a member `pairs`) and Record, the caller's;  kNoun, for the messages;
+//     check_value(who);  launch<T, Count>(grid, stream, J, V, meta, counters, stride, n_one, log, cap, cnt);
+//     info(n, counts) -> Info;  finish(raw, pairs, out): the host's O(pairs) part for one system.
+// The buffers of one context or batch: the counters on the first call, the log (cap records per system) and its pinned
+// staging grown to the largest cap seen.
+// ---------------------------------------------------------------------------------------------------------
+template <typename Q>
+struct PairLogState {
+    typename Q::Counts* cnt = nullptr;      // [systems]
+    typename Q::Counts* h_cnt = nullptr;    // pinned [systems]
+    RowsArray<typename Q::Raw> log;         // [systems * cap]: device and pinned
+};
+
+template <typename Q>
+inline void pair_log_free(PairLogState<Q>& g) {
+    (void)hipFree(g.cnt);
+    if (g.h_cnt) (void)hipHostFree(g.h_cnt);
+    rows_free(g.log);
+    g = PairLogState<Q>{};
+}
+
+template <typename Q>
+inline int pair_log_reserve(PairLogState<Q>& g, size_t systems, size_t cap, const char* who) {
+    using Counts = typename Q::Counts;
+    hipError_t e = hipSuccess;
+    if (!g.h_cnt) {
+        e = hipMalloc((void**)&g.cnt, systems * sizeof(Counts));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&g.h_cnt, systems * sizeof(Counts), hipHostMallocDefault);
+        if (e != hipSuccess) g.h_cnt = nullptr;
+    }
+    if (e == hipSuccess) e = rows_reserve(g.log, systems * (cap > 0 ? cap : 1));     // never a NULL log
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        pair_log_free(g);
+        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, counters and log: %s", who,
+                          hipGetErrorString(e));
+    }
+    return NBODY_OK;
+}
+
+// The argument checks an entry point makes before any device call; the value's own check is the query's.
+template <typename Q>
+inline int pair_log_check_args(const char* who, const void* handle, const Q& q, const typename Q::Record* out, int cap,
+                               const typename Q::Info* info, unsigned long long systems) {
+    if (!handle || !info) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL argument", who);
+    const int rc = q.check_value(who);
+    if (rc != NBODY_OK) return rc;
+    if (cap < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: cap = %d", who, cap);
+    if (!out && cap > 0) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL out with cap = %d", who, cap);
+    if (systems * (unsigned long long)cap * sizeof(typename Q::Record) > kFieldMaxBytes)
+        return nbody_fail(NBODY_ERR_INVALID, "%s: %d %s in each of %llu system(s) are more than 2^31 bytes", who, cap, Q::kNoun, systems);
+    return NBODY_OK;
+}
+
+// One call, from the reservation to the caller's list; the site, Count and read_meta as for rows_run.  V: the velocities,
+// indexed like the site's J.  Two waits: the counters first - they say whether the log is complete and how much of it to
+// read - then the records.  On NBODY_ERR_CAPACITY info is complete and out untouched.
+template <typename T, typename Count, typename Q, typename ReadMeta>
+int pair_log_run(const char* who, const RowsSite& s, const void* V, PairLogState<Q>& g, const Q& q, typename Q::Record* out, int cap,
+                 typename Q::Info* info, ReadMeta read_meta) {
+    using Raw = typename Q::Raw;
+    using Counts = typename Q::Counts;
+    const size_t S = (size_t)s.systems;
+    const bool launched = s.n_bound > 0;
+    if (launched) {
+        const int rc = pair_log_reserve(g, S, (size_t)cap, who);
+        if (rc != NBODY_OK) return rc;
+        NBK_ROWS_TRY(hipMemsetAsync(g.cnt, 0, S * sizeof(Counts), s.stream));
+        q.template launch<T, Count>(s.grid(s.n_bound), s.stream, (const Rec<T>*)s.J, (const Vec2<T>*)V, s.meta, s.counters, s.stride,
+                                    s.n_one<Count>(), g.log.d, cap, g.cnt);
+        NBK_ROWS_TRY(hipGetLastError());
+        NBK_ROWS_TRY(hipMemcpyAsync(g.h_cnt, g.cnt, S * sizeof(Counts), hipMemcpyDeviceToHost, s.stream));
+    }
+    const int rc = s.sync<Count>(launched, read_meta);
+    if (rc != NBODY_OK) return rc;
+    int over = -1;
+    size_t used = 0;                                             // records of the log up to the last one written
+    for (int sys = 0; sys < s.systems; ++sys) {
+        const int64_t n = s.count(sys);
+        const Counts c = launched && n > 0 ? g.h_cnt[sys] : Counts{};
+        info[sys] = q.info(n, c);
+        if (c.pairs > (unsigned long long)cap && over < 0) over = sys;
+        if (c.pairs) used = (size_t)sys * (size_t)cap + (size_t)c.pairs;
+    }
+    if (!out) return NBODY_OK;                                   // cap == 0: the counts only
+    if (over >= 0)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d %s, system %d has %lld: call again with that cap", who, cap, Q::kNoun,
+                          over, (long long)info[over].pairs);
+    if (used == 0) return NBODY_OK;
+    NBK_ROWS_TRY(hipMemcpyAsync(g.log.h, g.log.d, used * sizeof(Raw), hipMemcpyDeviceToHost, s.stream));
+    NBK_ROWS_TRY(hipStreamSynchronize(s.stream));
+    const Raw* raw = reinterpret_cast<const Raw*>(g.log.h);
+    for (int sys = 0; sys < s.systems; ++sys) {
+        const int fin = q.finish(raw + (size_t)sys * (size_t)cap, (int)info[sys].pairs, out + (size_t)sys * (size_t)cap);
+        if (fin != NBODY_OK) return fin;
+    }
     return NBODY_OK;
 }
 

@@ -2,8 +2,9 @@
 // include/nbody.h): for every row - a current body with its own velocity, or a probe point with a velocity of
 // its own - nine fp64 running sums and a count over the sources in each bin of squared distance, 1 <= bins <=
 // NBODY_SHELL_MOMENTS_MAX.  It is nbody_get_shells (nbody_shells.hpp) with the velocity terms: the launch geometry, the count
-// and the early exits are those of every row query (nbody_rows.hpp), the pair, the edges and the hot path are the shell sums'.
-// This file has the terms, the accumulators, the rare path, the kernel and the host side.
+// and the early exits are those of every row query (nbody_rows.hpp), the pair, the edges and the four-pair functor (ShellFour,
+// hot path and all) are the shell sums'.  This file has the terms, the accumulator with its rare path, the kernel and the
+// host side.
 //
 // The definition (include/nbody.h has it in full).  IEEE fp64, every operation rounded on its own, no fma, no divide, no
 // square root.  A row at (x, y) with velocity (vx, vy) and a source j with (X_j, Y_j, VX_j, VY_j, M_j) widened exactly:
@@ -16,7 +17,7 @@
 // every accumulator starting at +0.0.  Own form: j != i by index.  The order of every sum is part of the contract.
 //
 // shell_moments_at<T, kOwn, Count, B>: shells_at's shape - one lane per row, rows_walk's full walk over {x, y} planes, 4 KiB of
-// LDS - with ShellMomentSums<B> for ShellSums<B>: nine doubles and a count per bin in registers, 18 VGPRs per bin for the
+// LDS - with ShellMomentSums<T, B> for ShellSums<B> as ShellFour's accumulator: nine doubles and a count per bin in registers, 18 VGPRs per bin for the
 // doubles, so the tiers are B = 4 and 8 and there is none of 16 (288 VGPRs of accumulators would not fit without scratch).
 //   * Hot path, per pair: shells_at's, through the same pair_d2 - 2 subtractions, 2 multiplies, 1 add and ONE compare,
 //     d2 < e2[bins]; four pairs share one wave-level branch around the rare path.  No velocity is read here: the LDS planes
@@ -24,7 +25,7 @@
 //   * Rare path (some lane's pair is below the top edge): the four sources in ascending j; a source that no lane of the wave
 //     has hit is skipped; for the others M_j and V_j are read from the system's arrays (J, V) at the wave-uniform index
 //     clamped to n - 1 - and only here - dx and dy are formed again from the LDS entry (the same operands, the same bits as
-//     inside pair_d2), the nine terms are built ONCE per source, and shell_moments_add runs the fully unrolled select-add
+//     inside pair_d2), the nine terms are built ONCE per source, and ShellMomentSums::hit runs the fully unrolled select-add
 //     over the B bins: per edge one compare, per bin in = ge[k] && !ge[k+1] and  acc[k] = acc[k] + (in ? term : +0.0)  for each
 //     of the nine sums, count[k] += in.
 //     The select-add is exact although seven of the terms are signed: an accumulator that started at +0.0 is never -0.0 -
@@ -56,13 +57,6 @@ namespace nbk {
 
 static_assert(sizeof(nbody_shell_moment) == 80 && offsetof(nbody_shell_moment, count) == 72, "nbody_shell_moment layout");
 
-// What a row carries along the j stream.
-template <int B>
-struct ShellMomentSums {
-    double mass[B], px[B], py[B], ke[B], mr2[B], rad[B], ang[B], rad2[B], ang2[B];
-    int count[B];
-};
-
 // The nine terms of one source, built once (the head of the file has the chain).
 struct ShellMomentTerms { double mass, px, py, ke, mr2, rad, ang, rad2, ang2; };
 
@@ -73,64 +67,37 @@ __device__ __forceinline__ ShellMomentTerms shell_moment_terms(double mj, double
     return ShellMomentTerms{mj, mj * ux, mj * uy, mj * w2, mj * d2, mj * s, mj * c, mj * (s * s), mj * (c * c)};
 }
 
-// Source with the terms t at squared distance d2 below the top edge (hence no NaN): the one bin that holds d2 takes them and
-// one count, every other bin adds +0.0 and 0 (exact: see the head of the file).
-template <int B>
-__device__ __forceinline__ void shell_moments_add(ShellMomentSums<B>& a, const ShellEdges<B>& e, double d2, const ShellMomentTerms& t) {
-    bool ge = e.e[0] <= d2;                                      // of edge k
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-        const bool next = e.e[k + 1] <= d2;                      // of edge k + 1
-        const bool in = ge && !next;
-        a.mass[k] = a.mass[k] + (in ? t.mass : 0.0);
-        a.px[k] = a.px[k] + (in ? t.px : 0.0);
-        a.py[k] = a.py[k] + (in ? t.py : 0.0);
-        a.ke[k] = a.ke[k] + (in ? t.ke : 0.0);
-        a.mr2[k] = a.mr2[k] + (in ? t.mr2 : 0.0);
-        a.rad[k] = a.rad[k] + (in ? t.rad : 0.0);
-        a.ang[k] = a.ang[k] + (in ? t.ang : 0.0);
-        a.rad2[k] = a.rad2[k] + (in ? t.rad2 : 0.0);
-        a.ang2[k] = a.ang2[k] + (in ? t.ang2 : 0.0);
-        a.count[k] += in ? 1 : 0;
-        ge = next;
-    }
-}
-
-// The four pairs of one trip of rows_walk: sources j .. j + 3 at entries q .. q + 3 of buffer b.  kChecked: the tile holds
-// the wave's own rows, the self term j == i is no source.  The hot part is ShellFour's (nbody_shells.hpp), line for line.
+// What a row carries along the j stream, and ShellFour's accumulator (nbody_shells.hpp): the sums, and what the rare path
+// needs beyond the positions - the system's velocities V, indexed like J, and the row's own velocity.
 template <typename T, int B>
-struct ShellMomentFour {
-    const DiagPlanes *sx, *sy;
-    int i; RowsRow w;               // the row
-    double vx, vy;                  // its velocity
-    const Rec<T>* J; const Vec2<T>* V; int last;   // the system's sources and n - 1: where the rare path reads M_j and V_j
-    double top;                     // e2[bins]
-    ShellEdges<B> e;
-    ShellMomentSums<B> a;
-    template <bool kChecked>
-    __device__ __forceinline__ void four(int b, int q, int j) {
-        bool hit[4];
-        double d2[4];
-        int any = 0;
+struct ShellMomentSums {
+    const Vec2<T>* V;
+    double vx, vy;
+    double mass[B], px[B], py[B], ke[B], mr2[B], rad[B], ang[B], rad2[B], ang2[B];
+    int count[B];
+    // Source ju at squared distance d2 below the top edge (hence no NaN), dx and dy the differences d2 was made of: M_j and
+    // V_j are read here and only here, the terms are built once, and the one bin that holds d2 takes them and one count; every
+    // other bin adds +0.0 and 0 (exact: see the head of the file).
+    __device__ __forceinline__ void hit(const ShellEdges<B>& e, double d2, const Rec<T>* __restrict__ J, int ju, double dx, double dy) {
+        const Rec<T> r = J[ju];
+        const Vec2<T> v = V[ju];
+        const ShellMomentTerms t = shell_moment_terms((double)r.m, dx, dy, d2, (double)v.x - vx, (double)v.y - vy);
+        bool ge = e.e[0] <= d2;                                  // of edge k
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            d2[u] = pair_d2((*sx)[b][q + u], (*sy)[b][q + u], w.x, w.y);
-            hit[u] = (!kChecked || j + u != i) && d2[u] < top;
-            any += hit[u] ? 1 : 0;
-            asm("" : "+v"(any));                                 // as neighbor_pair: one add-with-carry per compare mask
-        }
-        if (any) {                                               // rare where the top edge is small against the system
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {                        // in j order
-                const int ju = j + u < last ? j + u : last;      // a padding entry: no lane has hit it
-                if (hit[u]) {                                    // skipped where no lane of the wave has hit source u
-                    const Rec<T> r = J[ju];
-                    const Vec2<T> v = V[ju];
-                    const double dx = (*sx)[b][q + u] - w.x, dy = (*sy)[b][q + u] - w.y;   // pair_d2's, same bits
-                    shell_moments_add(a, e, d2[u],
-                                      shell_moment_terms((double)r.m, dx, dy, d2[u], (double)v.x - vx, (double)v.y - vy));
-                }
-            }
+        for (int k = 0; k < B; ++k) {
+            const bool next = e.e[k + 1] <= d2;                  // of edge k + 1
+            const bool in = ge && !next;
+            mass[k] = mass[k] + (in ? t.mass : 0.0);
+            px[k] = px[k] + (in ? t.px : 0.0);
+            py[k] = py[k] + (in ? t.py : 0.0);
+            ke[k] = ke[k] + (in ? t.ke : 0.0);
+            mr2[k] = mr2[k] + (in ? t.mr2 : 0.0);
+            rad[k] = rad[k] + (in ? t.rad : 0.0);
+            ang[k] = ang[k] + (in ? t.ang : 0.0);
+            rad2[k] = rad2[k] + (in ? t.rad2 : 0.0);
+            ang2[k] = ang2[k] + (in ? t.ang2 : 0.0);
+            count[k] += in ? 1 : 0;
+            ge = next;
         }
     }
 };
@@ -167,13 +134,13 @@ __global__ __launch_bounds__(kDiagBlock) void shell_moments_at(const Rec<T>* __r
         }
     }
     __shared__ double sx[2][kTile], sy[2][kTile];
-    ShellMomentFour<T, B> f{&sx, &sy, L.p, rows_row<T, kOwn>(L, points), vx, vy, L.J, V, L.n - 1, top, edges, {}};
+    ShellFour<T, B, ShellMomentSums<T, B>> f{&sx, &sy, L.p, rows_row<T, kOwn>(L, points), L.J, L.n - 1, top, edges, {V, vx, vy}};
 #pragma unroll
     for (int k = 0; k < B; ++k) {
         f.a.mass[k] = 0.0; f.a.px[k] = 0.0; f.a.py[k] = 0.0; f.a.ke[k] = 0.0; f.a.mr2[k] = 0.0;
         f.a.rad[k] = 0.0; f.a.ang[k] = 0.0; f.a.rad2[k] = 0.0; f.a.ang2[k] = 0.0; f.a.count[k] = 0;
     }
-    rows_walk<kOwn, false, false>(L, sx, sy, nullptr, f);
+    rows_walk<kOwn, false>(L, RowsStage<false, T>{L.J, &sx, &sy, nullptr}, f);
     if (L.valid) {
 #pragma unroll
         for (int k = 0; k < B; ++k)
@@ -204,10 +171,8 @@ struct ShellMomentQuery {
     const FieldPoint* point_vel;    // device, [m], or NULL
     template <int B, typename T, bool kOwn, typename Count, typename... Common>
     void tier(dim3 grid, hipStream_t stream, nbody_shell_moment* out, Common... common) const {
-        ShellEdges<B> e;
-        for (int k = 0; k <= B; ++k) e.e[k] = k <= bins ? edges2[k] : __builtin_inf();
         hipLaunchKernelGGL((shell_moments_at<T, kOwn, Count, B>), grid, dim3(kDiagBlock), 0, stream, common..., (const Vec2<T>*)V,
-                           point_vel, bins, edges2[bins], e, out);
+                           point_vel, bins, edges2[bins], shell_edges<B>(edges2, bins), out);
     }
     template <typename T, bool kOwn, typename Count, typename... Common>
     void launch(dim3 grid, hipStream_t stream, nbody_shell_moment* out, Common... common) const {

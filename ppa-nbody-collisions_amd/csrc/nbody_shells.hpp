@@ -24,7 +24,7 @@
 //     NaN passes no compare; so does d2 = +inf under a +inf top edge.  kOwn: only the wave's self tile applies j != i.
 //   * Rare path (some lane's pair is below the top edge): the four sources in ascending j; per source M_j is read from the
 //     replica (the index is wave-uniform and clamped to n - 1, so a padding entry reads a body, which no lane adds), then
-//     for the lanes that hit it - a source that no lane of the wave has hit is skipped - shells_add, fully unrolled: per edge
+//     for the lanes that hit it - a source that no lane of the wave has hit is skipped - ShellSums::hit, fully unrolled: per edge
 //     one compare ge[k] = e2[k] <= d2, per bin in = ge[k] && !ge[k+1] (for a d2 that is no NaN - it is below the top edge -
 //     !(e <= d2) is d2 < e) and one select-add,  mass[k] += in ? M_j : +0.0;  count[k] += in.
 //     The select-add is exact: an accumulator that started at +0.0 is never -0.0 (a sum is -0.0 only where both terms are),
@@ -79,38 +79,48 @@ static_assert(sizeof(ShellEntry) == 12, "an entry is the caller's 8 + 4 bytes");
 template <int B>
 struct ShellEdges { double e[B + 1]; };
 
-// What a row carries along the j stream.
+// The squared edges of a tier as the host fills them: the caller's bins + 1, +inf from there on.
+template <int B>
+inline ShellEdges<B> shell_edges(const double* edges2, int bins) {
+    ShellEdges<B> e;
+    for (int k = 0; k <= B; ++k) e.e[k] = k <= bins ? edges2[k] : __builtin_inf();
+    return e;
+}
+
+// What a row carries along the j stream, and ShellFour's accumulator: hit() is the rare path's one source.
 template <int B>
 struct ShellSums {
     double mass[B];
     int count[B];
+    // Source ju at squared distance d2 below the top edge (hence no NaN): the one bin that holds d2 takes M_j and one count,
+    // every other bin adds +0.0 and 0.
+    template <typename T>
+    __device__ __forceinline__ void hit(const ShellEdges<B>& e, double d2, const Rec<T>* __restrict__ J, int ju, double, double) {
+        const double mj = (double)J[ju].m;
+        bool ge = e.e[0] <= d2;                                  // of edge k
+#pragma unroll
+        for (int k = 0; k < B; ++k) {
+            const bool next = e.e[k + 1] <= d2;                  // of edge k + 1
+            const bool in = ge && !next;
+            mass[k] = mass[k] + (in ? mj : 0.0);
+            count[k] += in ? 1 : 0;
+            ge = next;
+        }
+    }
 };
 
-// Source of mass mj at squared distance d2 below the top edge (hence no NaN): the one bin that holds d2 takes mj and one
-// count, every other bin adds +0.0 and 0.
-template <int B>
-__device__ __forceinline__ void shells_add(ShellSums<B>& a, const ShellEdges<B>& e, double d2, double mj) {
-    bool ge = e.e[0] <= d2;                                      // of edge k
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-        const bool next = e.e[k + 1] <= d2;                      // of edge k + 1
-        const bool in = ge && !next;
-        a.mass[k] = a.mass[k] + (in ? mj : 0.0);
-        a.count[k] += in ? 1 : 0;
-        ge = next;
-    }
-}
-
-// The four pairs of one trip of rows_walk: sources j .. j + 3 at entries q .. q + 3 of buffer b.  kChecked: the tile holds
-// the wave's own rows, the self term j == i is no source.
-template <typename T, int B>
+// The four pairs of one trip of rows_walk, for shells_at and shell_moments_at (nbody_shell_moments.hpp): sources j .. j + 3 at
+// entries q .. q + 3 of buffer b.  kChecked: the tile holds the wave's own rows, the self term j == i is no source.  Acc: the
+// sums of the query, called as a.hit(e, d2, J, ju, dx, dy) for a source that the lane has hit - dx and dy from the LDS
+// operands d2 was made of, the same bits as inside pair_d2; an accumulator that does not use them costs nothing.
+template <typename T, int B, typename Acc>
 struct ShellFour {
     const DiagPlanes *sx, *sy;
     int i; RowsRow w;               // the row
-    const Rec<T>* J; int last;      // the system's sources and n - 1: where the rare path reads M_j
+    const Rec<T>* J; int last;      // the system's sources and n - 1: where the rare path reads source j
     double top;                     // e2[bins]
     ShellEdges<B> e;
-    ShellSums<B> a;
+    Acc a;
     template <bool kChecked>
     __device__ __forceinline__ void four(int b, int q, int j) {
         bool hit[4];
@@ -127,7 +137,8 @@ struct ShellFour {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {                        // in j order
                 const int ju = j + u < last ? j + u : last;      // a padding entry: no lane has hit it
-                if (hit[u]) shells_add(a, e, d2[u], (double)J[ju].m);   // skipped where no lane of the wave has hit source u
+                if (hit[u])                                      // skipped where no lane of the wave has hit source u
+                    a.hit(e, d2[u], J, ju, (*sx)[b][q + u] - w.x, (*sy)[b][q + u] - w.y);
             }
         }
     }
@@ -151,10 +162,10 @@ __global__ __launch_bounds__(kDiagBlock) void shells_at(const Rec<T>* __restrict
         return;
     }
     __shared__ double sx[2][kTile], sy[2][kTile];
-    ShellFour<T, B> f{&sx, &sy, L.p, rows_row<T, kOwn>(L, points), L.J, L.n - 1, top, edges, {}};
+    ShellFour<T, B, ShellSums<B>> f{&sx, &sy, L.p, rows_row<T, kOwn>(L, points), L.J, L.n - 1, top, edges, {}};
 #pragma unroll
     for (int k = 0; k < B; ++k) { f.a.mass[k] = 0.0; f.a.count[k] = 0; }
-    rows_walk<kOwn, false, false>(L, sx, sy, nullptr, f);
+    rows_walk<kOwn, false>(L, RowsStage<false, T>{L.J, &sx, &sy, nullptr}, f);
     if (L.valid) {
 #pragma unroll
         for (int k = 0; k < B; ++k)
@@ -174,9 +185,8 @@ struct ShellQuery {
     int bins;
     template <int B, typename T, bool kOwn, typename Count, typename... Common>
     void tier(dim3 grid, hipStream_t stream, ShellEntry* out, Common... common) const {
-        ShellEdges<B> e;
-        for (int k = 0; k <= B; ++k) e.e[k] = k <= bins ? edges2[k] : __builtin_inf();
-        hipLaunchKernelGGL((shells_at<T, kOwn, Count, B>), grid, dim3(kDiagBlock), 0, stream, common..., bins, edges2[bins], e, out);
+        hipLaunchKernelGGL((shells_at<T, kOwn, Count, B>), grid, dim3(kDiagBlock), 0, stream, common..., bins, edges2[bins],
+                           shell_edges<B>(edges2, bins), out);
     }
     template <typename T, bool kOwn, typename Count, typename... Common>
     void launch(dim3 grid, hipStream_t stream, ShellEntry* out, Common... common) const {

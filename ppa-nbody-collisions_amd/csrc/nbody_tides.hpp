@@ -41,7 +41,7 @@
 // self tile comes with it, and the potential's fma into `s`, which nothing reads, is dead code.  kJerk = true needs {vx, vy}
 // of the j tile in LDS - five double-buffered planes, 10 KiB - and has its own ascending full walk, tides_walk_jerk: the shape
 // of diag_walk_sums for contiguous rows (ordered: no NaN padding, a remainder loop, a checked self tile) with the two planes
-// more.  diag_walk_sums and rows_walk are left as they are, so no existing kernel is compiled differently.  Both walks add
+// more.  diag_walk_sums is left as it is (its comment says why), and rows_walk is the NaN-padded family's.  Both walks add
 // the pairs through the one TideSums::more, in the same order: the tensor of a kJerk = true launch has the bits of a
 // kJerk = false launch.  Plain C++ loads and stores only, no device-side waiting.
 #pragma once

@@ -2,7 +2,8 @@
 """This library against the parent commit's, on the work of the kernels that share a rule with another kernel: the
 compaction's offsets (compact_count / compact_scatter, batch_count / batch_commit, ids_scatter), the potential's walk
 (diag_potential, batch_diag_potential, track_potential), the finish of the diagnostics (batch_diag_reduce) and the row
-queries' prologue, tile walk and host driver (field_at, neighbors_at, groups_sweep, pair_counts; nbody_rows.hpp).
+queries' prologue, tile walk and host drivers (field_at, neighbors_at, groups_sweep, pair_counts, encounters_walk,
+binaries_walk, group_potential, shells_at, shell_moments_at; nbody_rows.hpp).
 
     python3 csrc/tune/ab_parent.py --baseline-root DIR [--lines a,b256,...] [--rounds 3] [--out FILE]
     python3 csrc/tune/ab_parent.py --trace [--root DIR]     (every line once, target of rocprofv3 --kernel-trace --stats)
@@ -30,6 +31,13 @@ Lines (fp32, literal, stock configuration with stock radii):
     grp, prs  the shapes of groups_probe.py and pairs_probe.py: Stepper N = 262144 after 3      ms per call
               steps, groups(0, 1) / pair_counts() over the 32 "sparse" bins; prspts: the same
               bins from 65536 explicit points; ...256: StepperBatch 256 x 1024 after 3 steps
+    enc, bin  the shapes of encounter_probe.py and binary_probe.py on the grp state: encounters(h  ms per call
+              = the time step) and binaries(128), binaries(1024) for the batch (the probe's sep
+              / 8 and sep), each with room for its list: one walk per call
+    gpe       group_energy_probe.py's overlap case, group_potential(0, 1), on the grp state     ms per call
+    shl, shm  the shapes of shells_probe.py and shell_moments_probe.py on the grp state: shells() ms per call
+              / shell_moments() over 8 bins below the prs top edge; shlpts: 32 bins from 65536
+              explicit points; shmpts: 8 bins from 65536 moving points; ...256 as above
 A line passes when the candidate's median is not above the parent's median by more than max(the parent's round spread
 (max - min), |control median - parent median|).  Exit status 1 if a line does not pass.
 """
@@ -47,11 +55,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.abspath(os.path.join(HERE, "..", "..", ".."))
 REPLY_TIMEOUT_S = 240           # a side that does not answer within this is killed and the probe fails
 LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024", "d256x1024", "d64x4096",
-         "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256")
+         "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256",
+         "enc", "enc256", "bin", "bin256", "gpe", "gpe256", "shl", "shlpts", "shl256", "shm", "shmpts", "shm256")
 BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
 STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
 ROWS = {"": 3, "pts": 8, "256": 100}    # the row queries' shapes (field_probe.py, neighbor_probe.py): calls per window
-SCANS = {"grp": 8, "grp256": 100, "prs": 20, "prspts": 30, "prs256": 200}    # groups and pair counts: calls per window
+SCANS = {"grp": 8, "grp256": 100, "prs": 20, "prspts": 30, "prs256": 200,     # the queries on the state after 3 steps:
+         "enc": 6, "enc256": 100, "bin": 20, "bin256": 80, "gpe": 6, "gpe256": 80,    # calls per window
+         "shl": 20, "shlpts": 20, "shl256": 60, "shm": 20, "shmpts": 20, "shm256": 40}
+ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm")
 N_BIG = 262144
 M_POINTS = 65536
 
@@ -81,6 +93,15 @@ def diag_parts(d):
     return out
 
 
+def result_parts(r):
+    """What a query returned - an array, a dict, or a list or tuple of those - as the parts of a digest."""
+    if isinstance(r, dict):
+        return diag_parts(r)
+    if isinstance(r, (list, tuple)):
+        return [p for e in r for p in result_parts(e)]
+    return [r.tobytes()]
+
+
 class Line:
     """One line of the table: setup() builds the state, window() times the work once and digests what it gave."""
 
@@ -96,7 +117,7 @@ class Line:
             if name == "c":
                 self.st.step(8)
                 self.sel = [int(x) for x in np.unique(np.linspace(0, N_BIG - 1, 64).astype(np.int32))]
-        elif name[:3] in ("fld", "nbr", "grp", "prs"):
+        elif name[:3] in ROW_LINES:
             self.unit, self.reps = "ms per call", SCANS[name] if name in SCANS else ROWS[name[3:]]
             self.pts = None
             if name.endswith("256"):
@@ -114,11 +135,30 @@ class Line:
                     self.pts = np.random.default_rng(2).uniform(0, 1, size=(M_POINTS, 2)) * [cfg.fieldWidth, cfg.fieldHeight]
             if name.startswith("grp"):
                 self.call = lambda pts: self.st.groups(0.0, 1.0)
-            elif name.startswith("prs"):                                    # pairs_probe.py's (a): 1.5 others within the top edge
-                P = np.asarray((self.st.download(0) if self.batch else self.st.download()).Positions, dtype=np.float64)
+            elif name.startswith("gpe"):
+                self.call = lambda pts: self.st.group_potential(0.0, 1.0)
+            elif name[:3] in ("enc", "bin"):
+                if name.startswith("enc"):
+                    query = lambda cap: self.st.encounters(float(np.float32(cfg.timestep)), cap=cap)
+                else:
+                    query = lambda cap: self.st.binaries(1024.0 if self.batch else 128.0, cap=cap)
+                found = query(None)
+                cap = max([g[1]["pairs"] for g in (found if self.batch else [found])] + [1])    # room for the list: one walk
+                self.call = lambda pts: query(cap)
+            elif name[:3] in ("prs", "shl", "shm"):                         # pairs_probe.py's (a): 1.5 others within the top edge
+                down = self.st.download(0) if self.batch else self.st.download()
+                P = np.asarray(down.Positions, dtype=np.float64)
                 top = float(np.sqrt(1.5 * np.prod(P.max(axis=0) - P.min(axis=0)) / (np.pi * len(P))))
-                e2 = np.geomspace(top / 1000.0, top, 33) ** 2
-                self.call = lambda pts: self.st.pair_counts(e2, points=pts, squared=True)
+                e2 = np.geomspace(top / 1000.0, top, 9 if name in ("shl", "shl256") or name.startswith("shm") else 33) ** 2
+                if name.startswith("prs"):
+                    self.call = lambda pts: self.st.pair_counts(e2, points=pts, squared=True)
+                elif name.startswith("shl"):
+                    self.call = lambda pts: self.st.shells(e2, pts, squared=True)
+                else:
+                    vel = None
+                    if self.pts is not None:
+                        vel = np.random.default_rng(3).uniform(-1, 1, size=(M_POINTS, 2)) * np.abs(np.asarray(down.Velocities)).max()
+                    self.call = lambda pts: self.st.shell_moments(e2, pts, vel, squared=True)
             else:
                 self.call = self.st.field if name.startswith("fld") else self.st.neighbors
         elif name in STEPS:
@@ -160,16 +200,12 @@ class Line:
                 o, ids = (st.download(s), st.ids(s)) if self.batch else (st.download(), st.ids())
                 parts += [b"%d:" % o.numBodies, o.block.tobytes(), ids.tobytes()]
             return seconds, digest_of(parts)
-        if name[:3] in ("fld", "nbr", "grp", "prs"):
+        if name[:3] in ROW_LINES:
             t0 = time.perf_counter()
             for _ in range(self.reps):                                      # each call ends in a copy back and a synchronise
                 r = self.call(self.pts)
             seconds = time.perf_counter() - t0
-            if isinstance(r, dict):
-                return seconds, digest_of(diag_parts(r))
-            if isinstance(r, list) and r and isinstance(r[0], dict):
-                return seconds, digest_of([p for e in r for p in diag_parts(e)])
-            return seconds, digest_of([a.tobytes() for a in (r if isinstance(r, list) else [r])])
+            return seconds, digest_of(result_parts(r))
         if name == "c":
             st.reserve_tracks(self.reps, ids=self.sel, potential=True)      # empties the log; synchronises
             t0 = time.perf_counter()

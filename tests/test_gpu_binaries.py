@@ -352,19 +352,20 @@ def test_batch_equals_stepper_and_model(nb, semantics):
 
 
 def test_batch_of_many_small_systems(nb):
-    S, k = 1024, 64
-    cfg = nb.stock_config(particleCount=k, fieldWidth=600, fieldHeight=600)
-    states = [bc.standard_state(k, np.float32, seed=5000 + s) for s in range(S)]
-    with nb.StepperBatch(S, k, cfg=cfg) as batch:
-        batch.upload([bodies_of(nb, *state, 0) for state in states])
-        got = batch.binaries(bc.SEP)
-        total = dict.fromkeys(bc.COUNTS[1:], 0)
-        for s in range(S):
-            bc.assert_same(got[s], bc.model_binaries(*states[s], SEP2), "system %d" % s)
-            for f in total:
-                total[f] += got[s][1][f]
-        print("1024 x 64: %s" % (total,))
-        again = batch.binaries(bc.SEP, cap=0)                       # the counts first (no slot is taken), then the lists
-        for s in range(0, S, 37):
-            bc.assert_same(again[s], got[s], "system %d, cap 0" % s)
-        assert total["pairs"] > 16 * S and total["near"] - total["pairs"] > 16 * S and total["overlapping"] > S and total["approaching"] > 4 * S
+    # 1024 systems of one wave's rows; then 64 systems on both sides of a wave (63, 65) and of a tile (127, 129) in one batch
+    for S, sizes in ((1024, [64]), (64, [63, 65, 127, 129])):
+        cfg = nb.stock_config(particleCount=max(sizes), fieldWidth=600, fieldHeight=600)
+        states = [bc.standard_state(sizes[s % len(sizes)], np.float32, seed=5000 + s) for s in range(S)]
+        with nb.StepperBatch(S, max(sizes), cfg=cfg) as batch:
+            batch.upload([bodies_of(nb, *state, 0) for state in states])
+            got = batch.binaries(bc.SEP)
+            total = dict.fromkeys(bc.COUNTS[1:], 0)
+            for s in range(S):
+                bc.assert_same(got[s], bc.model_binaries(*states[s], SEP2), "system %d of %d" % (s, S))
+                for f in total:
+                    total[f] += got[s][1][f]
+            print("%d x %s: %s" % (S, sizes, total))
+            again = batch.binaries(bc.SEP, cap=0)                   # the counts first (no slot is taken), then the lists
+            for s in range(0, S, 37):
+                bc.assert_same(again[s], got[s], "system %d of %d, cap 0" % (s, S))
+            assert total["pairs"] > 16 * S and total["near"] - total["pairs"] > 16 * S and total["overlapping"] > S and total["approaching"] > 4 * S

@@ -333,15 +333,16 @@ def test_batch_equals_stepper_and_model(nb, semantics):
 
 
 def test_batch_of_many_small_systems(nb):
-    S, k = 1024, 64
-    cfg = nb.stock_config(particleCount=k, fieldWidth=600, fieldHeight=600)
-    bodies = [bodies_of(nb, *ec.standard_state(k, np.float32, seed=5000 + s), 0) for s in range(S)]
-    with nb.StepperBatch(S, k, cfg=cfg) as batch:
-        batch.upload(bodies)
-        got = batch.encounters(ec.H)
-        total = [0, 0, 0]
-        for s in range(S):
-            ec.assert_same(got[s], ec.model_encounters(*ec.widen(bodies[s]), ec.H), "system %d" % s)
-            total = [a + b for a, b in zip(total, ec.classes(got[s][0]))]
-        print("1024 x 64: now %d, end only %d, missed %d" % tuple(total))
-        assert min(total) > S
+    # 1024 systems of one wave's rows; then 64 systems on both sides of a wave (63, 65) and of a tile (127, 129) in one batch
+    for S, sizes in ((1024, [64]), (64, [63, 65, 127, 129])):
+        cfg = nb.stock_config(particleCount=max(sizes), fieldWidth=600, fieldHeight=600)
+        bodies = [bodies_of(nb, *ec.standard_state(sizes[s % len(sizes)], np.float32, seed=5000 + s), 0) for s in range(S)]
+        with nb.StepperBatch(S, max(sizes), cfg=cfg) as batch:
+            batch.upload(bodies)
+            got = batch.encounters(ec.H)
+            total = [0, 0, 0]
+            for s in range(S):
+                ec.assert_same(got[s], ec.model_encounters(*ec.widen(bodies[s]), ec.H), "system %d of %d" % (s, S))
+                total = [a + b for a, b in zip(total, ec.classes(got[s][0]))]
+            print("%d x %s: now %d, end only %d, missed %d" % (S, sizes, *total))
+            assert min(total) > S
