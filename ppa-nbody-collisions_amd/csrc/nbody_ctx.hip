@@ -1728,16 +1728,30 @@ int ctx_rows_run(nbody_ctx* c, Run run) {
     return c->desc.precision == NBODY_F64 ? run(double(), sync) : run(float(), sync);
 }
 
-// A query with a record per row (rows_run): own rows need room for every body.
+// Own rows need room for every body; *n_out: the rows the call will fill.
+int ctx_rows_room(const char* who, const RowsSite& site, const nbody_vec2* points, int m, int* n_out) {
+    if (!points && m < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, site.n_bound);
+    *n_out = points ? m : site.n_bound;
+    return NBODY_OK;
+}
+
+// The refusal of what reads the velocities or advances against the replica: `needs` ("encounters need") and the reason.
+const char kOwnVelocities[] = "a rank holds only its own velocities, a query across ranks is not built";
+int ctx_single_rank(const nbody_ctx* c, const char* who, const char* needs, const char* why) {
+    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
+        return nbody_fail(NBODY_ERR_STATE, "%s: %s a single-rank context without an exchange (world %d, flags 0x%x): %s", who, needs,
+                          c->desc.world, c->desc.flags, why);
+    return NBODY_OK;
+}
+
+// A query with a record per row (rows_run).
 template <typename Q>
 int ctx_rows(nbody_ctx* c, const char* who, PointBuffers<typename Q::Device>& buf, const Q& q, const nbody_vec2* points, int m,
              typename Q::Result* out, int* n_out) {
     RowsSite site;
-    const int rc = ctx_rows_site(c, who, site);
-    if (rc != NBODY_OK) return rc;
-    if (!points && m < site.n_bound)
-        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, site.n_bound);
-    *n_out = points ? m : site.n_bound;
+    int rc = ctx_rows_site(c, who, site);
+    if (rc != NBODY_OK || (rc = ctx_rows_room(who, site, points, m, n_out)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return rows_run<decltype(t), RowsOneCount>(who, site, buf, q, points, m, out, sync);
     });
@@ -1780,15 +1794,8 @@ int nbody_get_shell_moments(nbody_ctx* c, const nbody_vec2* points, const nbody_
     const char* who = "nbody_get_shell_moments";
     RowsSite site;
     int rc = shell_moments_check_args(who, {c, out, n_out}, points, point_vel, m, edges2, bins, 1);
-    if (rc != NBODY_OK) return rc;
-    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
-        return nbody_fail(NBODY_ERR_STATE, "%s: shell moments need a single-rank context without an exchange (world %d, flags 0x%x): "
-                                           "a rank holds only its own velocities, a query across ranks is not built", who,
-                          c->desc.world, c->desc.flags);
-    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
-    if (!points && m < site.n_bound)
-        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, site.n_bound);
-    *n_out = points ? m : site.n_bound;
+    if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "shell moments need", kOwnVelocities)) != NBODY_OK) return rc;
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK || (rc = ctx_rows_room(who, site, points, m, n_out)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return shell_moments_run<decltype(t), RowsOneCount>(who, site, c->shm, c->Vown, points, point_vel, m, edges2, bins, out,
                                                             sync);
@@ -1826,11 +1833,7 @@ int nbody_get_encounters(nbody_ctx* c, double horizon, nbody_encounter* out, int
     const char* who = "nbody_get_encounters";
     RowsSite site;
     int rc = pair_log_check_args(who, c, EncQuery{horizon}, out, cap, info, 1);
-    if (rc != NBODY_OK) return rc;
-    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
-        return nbody_fail(NBODY_ERR_STATE, "%s: encounters need a single-rank context without an exchange (world %d, flags 0x%x): "
-                                           "a rank holds only its own velocities, a query across ranks is not built", who,
-                          c->desc.world, c->desc.flags);
+    if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "encounters need", kOwnVelocities)) != NBODY_OK) return rc;
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->enc, EncQuery{horizon}, out, cap, info, sync);
@@ -1842,11 +1845,7 @@ int nbody_get_binaries(nbody_ctx* c, double sep2, nbody_binary* out, int cap, nb
     const char* who = "nbody_get_binaries";
     RowsSite site;
     int rc = pair_log_check_args(who, c, BinQuery{sep2}, out, cap, info, 1);
-    if (rc != NBODY_OK) return rc;
-    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
-        return nbody_fail(NBODY_ERR_STATE, "%s: binaries need a single-rank context without an exchange (world %d, flags 0x%x): "
-                                           "a rank holds only its own velocities, a query across ranks is not built", who,
-                          c->desc.world, c->desc.flags);
+    if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "binaries need", kOwnVelocities)) != NBODY_OK) return rc;
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->bin, BinQuery{sep2}, out, cap, info, sync);
@@ -1860,15 +1859,8 @@ int nbody_get_tides(nbody_ctx* c, const nbody_vec2* points, const nbody_vec2* po
     const char* who = "nbody_get_tides";
     RowsSite site;
     int rc = tides_check_args(who, {c, tide, n_out, coincident}, points, point_vel, jerk, m, 1);
-    if (rc != NBODY_OK) return rc;
-    if (jerk && (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM))))
-        return nbody_fail(NBODY_ERR_STATE, "%s: the jerk needs a single-rank context without an exchange (world %d, flags 0x%x): "
-                                           "a rank holds only its own velocities, a query across ranks is not built", who,
-                          c->desc.world, c->desc.flags);
-    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
-    if (!points && m < site.n_bound)
-        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d results, the context holds %d bodies", who, m, site.n_bound);
-    *n_out = points ? m : site.n_bound;
+    if (rc != NBODY_OK || (jerk && (rc = ctx_single_rank(c, who, "the jerk needs", kOwnVelocities)) != NBODY_OK)) return rc;
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK || (rc = ctx_rows_room(who, site, points, m, n_out)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return tides_run<decltype(t), RowsOneCount>(who, site, c->tid, (double)kG, c->Vown, points, point_vel, m, tide, jerk,
                                                     coincident, sync);
@@ -1879,12 +1871,9 @@ int nbody_get_tides(nbody_ctx* c, const nbody_vec2* points, const nbody_vec2* po
 // behind for the other ranks' bodies until the exchange.
 int nbody_tracers_set(nbody_ctx* c, const nbody_tracer* t, int m, uint32_t flags) {
     const char* who = "nbody_tracers_set";
-    const int rc = tracers_check_set(who, c, t, m, flags, 1);
+    int rc = tracers_check_set(who, c, t, m, flags, 1);
+    if (rc == NBODY_OK) rc = ctx_single_rank(c, who, "tracers need", "an advance against a rank's lagging replica is not built");
     if (rc != NBODY_OK) return rc;
-    if (c->desc.world > 1 || (c->desc.flags & (NBODY_FLAG_GROUP_EXCHANGE | NBODY_FLAG_FORCE_COMM)))
-        return nbody_fail(NBODY_ERR_STATE, "%s: tracers need a single-rank context without an exchange (world %d, flags 0x%x): "
-                                           "an advance against a rank's lagging replica is not built", who, c->desc.world,
-                          c->desc.flags);
     HIP_TRY(hipSetDevice(c->desc.device));
     return tracers_set(who, c->trc, c->stream, 1, t, m, flags);
 }

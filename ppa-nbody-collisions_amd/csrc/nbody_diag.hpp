@@ -1,9 +1,12 @@
 // csrc/nbody_diag.hpp -- physical diagnostics of the resident state (nbody_get_diagnostics, include/nbody.h): the
 // per-body potential phi_i = -G sum_{j != i, r_ij > 0} m_j / r_ij and the O(N) moments, all in fp64 (fp32 inputs are
-// widened exactly).  Included after nbody_kernels.hpp.  What every potential kernel and every finish of the totals must
-// agree on bit for bit lives here once: diag_walk (the sum over j; also batch_diag_potential's, track_potential's and, as
-// diag_walk_sums, field_at's),
-// diag_row_general, and diag_add / diag_finish (host and device: diag_collect in nbody_ctx.hip, batch_diag_reduce).
+// widened exactly).  Included after nbody_kernels.hpp.  What every kernel that sums over j in ascending order and every
+// finish of the totals must agree on bit for bit lives here once:
+//   * diag_walk_sums, the ordered walk: the one ascending tile loop of diag_potential, batch_diag_potential, track_potential
+//     (through diag_walk), field_at, tracers_advance and tides_at, the jerk's two more planes included;
+//   * diag_general_walk, the exact walk of a flagged row: the one loop under diag_row_general, field_acc_general,
+//     tides_general and group_row_general;
+//   * diag_add / diag_finish (host and device: diag_collect in nbody_ctx.hip, batch_diag_reduce).
 //
 // Order contract.  phi_i is ONE running sum over j = 0, 1, ..., n-1 in ascending order, whatever the
 // launch: it depends on (i, n) only, never on the rank, the world, the own count or the CU count.  The totals are
@@ -103,9 +106,9 @@ __device__ __forceinline__ double diag_rinv(double d2) {
 }
 
 // What a row carries along the j stream: the potential's running sum `s`, and for kMore whatever else is summed over
-// the same pairs (FieldSums, nbody_field.hpp: the two acceleration components).  The per-pair expressions - dx, dy, d2,
-// diag_rinv and the fma into s - are written here and in diag_walk_sums' checked loop, nowhere else: every kernel that
-// sums over j calls the one walk.
+// the same pairs (FieldSums, nbody_field.hpp: the two acceleration components; TideSums, nbody_tides.hpp: the tensor's and
+// the jerk's).  The per-pair expressions - dx, dy, d2, diag_rinv and the fma into s - are written here and in
+// diag_walk_sums' checked loop, nowhere else: every kernel that sums over j calls the one walk.
 struct DiagPhiSum {
     static constexpr bool kMore = false;
     double s = 0.0;
@@ -122,26 +125,42 @@ __device__ __forceinline__ void diag_pair(Sums& a, const double& xj, const doubl
     if constexpr (Sums::kMore) a.more(mj, dx, dy, diag_rinv(d2));   // the same d2, mj and diag_rinv: evaluated once
 }
 
-// The general code of a flagged row: exact on the whole range, coincident pairs counted and skipped.
-struct DiagRow { double s; long long coincident; };
-template <typename T>
-__device__ __forceinline__ DiagRow diag_row_general(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi) {
-    double s = 0.0;
+// The exact walk of a flagged row, the only one: j = 0 .. n-1 ascending, the self term j == i left out (i < 0: a point
+// that is no body), then every j that keep(j) refuses (a membership test; DiagKeepAll: none), then every source at distance
+// exactly 0, which is counted.  What remains goes to f(j, mj, dx, dy, d) with d = |(dx, dy)| by IEEE sqrt, by hypot where
+// d2 leaves the normal range.  -> the count.  Every general code below and in the query headers is a functor on top of
+// this: the same pairs skipped, the same d.
+struct DiagKeepAll { __device__ __forceinline__ bool operator()(int) const { return true; } };
+template <typename T, typename Keep, typename F>
+__device__ __forceinline__ long long diag_general_walk(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi,
+                                                       const Keep keep, F f) {
     long long c = 0;
     for (int j = 0; j < n; ++j) {
-        if (j == i) continue;
+        if (j == i || !keep(j)) continue;
         const Rec<T> r = J[j];
         const double dx = (double)r.x - xi, dy = (double)r.y - yi;
         if (dx == 0.0 && dy == 0.0) { ++c; continue; }
         const double d2 = __builtin_fma(dx, dx, dy * dy);
         const double d = (d2 >= DBL_MIN && d2 <= DBL_MAX) ? __builtin_sqrt(d2) : hypot(dx, dy);
-        s = s + (double)r.m / d;
+        f(j, (double)r.m, dx, dy, d);
     }
+    return c;
+}
+
+// The general code of a flagged row's potential: s = s + mj / d over the kept pairs (group_potential keeps the members of
+// the row's group, nbody_group_energy.hpp), and the count.
+struct DiagRow { double s; long long coincident; };
+template <typename T, typename Keep = DiagKeepAll>
+__device__ __forceinline__ DiagRow diag_row_general(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi,
+                                                    const Keep keep = Keep{}) {
+    double s = 0.0;
+    const long long c = diag_general_walk<T>(J, n, i, xi, yi, keep, [&s](int, double mj, double, double, double d) { s = s + mj / d; });
     return DiagRow{s, c};
 }
 
-// The sum over j of row i at (xi, yi), j = 0 .. n-1 ascending: every potential kernel's inner walk, and field_at's.  Called
-// by all kDiagBlock lanes of the workgroup (it owns the tile buffers and the barriers), lanes without a row included.
+// The ordered walk, the only ascending tile loop: the sum over j of row i at (xi, yi), j = 0 .. n-1 - every potential
+// kernel's inner walk, field_at's, tracers_advance's and tides_at's.  Called by all kDiagBlock lanes of the workgroup (it has
+// the barriers), lanes without a row included.
 // self_tile: the j tile that holds the lane's self term j == i.
 // kGatheredRows = false: the rows of a wave are contiguous and within one tile; self_tile is that tile, wave-uniform
 //                        (lanes past the last row carry it too: they compute and are not stored).
@@ -149,11 +168,20 @@ __device__ __forceinline__ DiagRow diag_row_general(const Rec<T>* __restrict__ J
 // kSelfTerms = false   : no row is a body (probe points): there is no checked loop at all.
 // wave_works (wave-uniform): a wave without any row only loads tiles.
 // sx, sy, sm: the caller's LDS planes - diag_walk's for the potential kernels, so that their LDS layout stays what it was.
+// planes: what a caller stages besides {x, y, m} and looks at before each pair.  planes.stage(b, e, j): lane e fills entry e
+//         of buffer b of its own planes from source j; planes.look(a, b, q): just before the pair of entry q goes into a
+//         (TideVel, nbody_tides.hpp: the jerk's {vx, vy} planes, and dvx, dvy set in the sums).  DiagNoPlanes: nothing, and
+//         no code.
 typedef double DiagPlanes[2][kTile];          // one component of the double-buffered j tile, in LDS
-template <bool kGatheredRows, bool kSelfTerms, typename T, typename Sums>
+struct DiagNoPlanes {
+    __device__ __forceinline__ void stage(int, int, int) const {}
+    template <typename Sums>
+    __device__ __forceinline__ void look(Sums&, int, int) const {}
+};
+template <bool kGatheredRows, bool kSelfTerms, typename T, typename Sums, typename Planes = DiagNoPlanes>
 __device__ __forceinline__ void diag_walk_sums(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi,
                                                int self_tile, bool wave_works, Sums& a, DiagPlanes& sx, DiagPlanes& sy,
-                                               DiagPlanes& sm) {
+                                               DiagPlanes& sm, const Planes planes = Planes{}) {
     const int tid = threadIdx.x;
     const int jtiles = (n + kTile - 1) / kTile;
     for (int t = 0; t < jtiles; ++t) {
@@ -163,6 +191,7 @@ __device__ __forceinline__ void diag_walk_sums(const Rec<T>* __restrict__ J, int
         if (tid < jn) {
             const Rec<T> r = J[j0 + tid];
             sx[b][tid] = (double)r.x; sy[b][tid] = (double)r.y; sm[b][tid] = (double)r.m;
+            planes.stage(b, tid, j0 + tid);
         }
         // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
         __syncthreads();
@@ -171,9 +200,15 @@ __device__ __forceinline__ void diag_walk_sums(const Rec<T>* __restrict__ J, int
             int q = 0;
             for (; q + 4 <= jn; q += 4) {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) diag_pair(a, sx[b][q + u], sy[b][q + u], sm[b][q + u], xi, yi);
+                for (int u = 0; u < 4; ++u) {
+                    planes.look(a, b, q + u);
+                    diag_pair(a, sx[b][q + u], sy[b][q + u], sm[b][q + u], xi, yi);
+                }
             }
-            for (; q < jn; ++q) diag_pair(a, sx[b][q], sy[b][q], sm[b][q], xi, yi);
+            for (; q < jn; ++q) {
+                planes.look(a, b, q);
+                diag_pair(a, sx[b][q], sy[b][q], sm[b][q], xi, yi);
+            }
         } else {
             // diag_pair with the self term masked (m = 0 at d2 = 1: an exact +0).  Written out: a function boundary around
             // the conditional LDS read changes the code of every kernel that has this loop.
@@ -181,6 +216,7 @@ __device__ __forceinline__ void diag_walk_sums(const Rec<T>* __restrict__ J, int
                 const bool self = j0 + q == i;
                 const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
                 const double d2 = self ? 1.0 : __builtin_fma(dx, dx, dy * dy);
+                planes.look(a, b, q);
                 a.s = __builtin_fma(self ? 0.0 : sm[b][q], diag_rinv(d2), a.s);
                 if constexpr (Sums::kMore) a.more(self ? 0.0 : sm[b][q], dx, dy, diag_rinv(d2));
             }

@@ -12,8 +12,9 @@
 //     y2 = y*y;  w = mj * (y2*y);  ax = fma(w, dx, ax);  ay = fma(w, dy, ay)          (5)          dx = xj - x
 // so the sums are those of +m_j (x_j - x) / r_j^3 and the results are G * ax, G * ay and -G * s.
 // A sum whose chain accumulator is not finite (a source at distance 0, d2 outside the chain's range, y^3 or a product out of
-// range, a non-finite input) is redone by the general code, again ascending walks over j: diag_row_general for the potential
-// and the count, field_acc_general over the same pairs with
+// range, a non-finite input) is redone by the general code, again ascending walks over j, both of them the one exact walk
+// (diag_general_walk, nbody_diag.hpp: the pairs it skips and its d are not restated here): diag_row_general for the
+// potential and the count, field_acc_general with
 //     q = (mj / d) / d;  ax = fma(q, dx / d, ax)
 // (IEEE sqrt and divide, hypot outside the normal range of d2): q is m_j / r_j^2 itself, |dx / d| <= 1, so a term overflows
 // only where m_j / r_j^2 does.  Each of the three sums is replaced on its own and only when it is not finite: a finite chain
@@ -23,7 +24,8 @@
 // moderate size - every pair of an fp32 state, whose d2 lies within [2^-298, 2^257].  Above that range a term's weight
 // underflows gradually instead of being flagged (below it, it overflows and the sum is redone).
 //
-// field_at: kOwn leaves the self term out by index through diag_walk's checked self tile.  The result record carries the
+// field_at: kOwn leaves the self term out by index through diag_walk_sums' checked self tile.  Its row is loaded here, not
+// by rows_row, whose x = NaN for a lane without a row compiles to other code than this +0.  The result record carries the
 // point's coincident count; the host adds them up.  What follows the walk is field_finish, which the tracers' advance
 // (tracers_advance, nbody_tracers.hpp) calls after the same walk: a tracer's field has the bits of a probe point's.
 #pragma once
@@ -56,24 +58,18 @@ struct FieldSums {
     }
 };
 
-// The general code of a flagged point's acceleration: diag_row_general's walk (the same pairs skipped, the same d), with
+// The general code of a flagged point's acceleration: the exact walk (diag_general_walk, nbody_diag.hpp) with
 //     q = (mj / d) / d;  ax = fma(q, dx / d, ax).
 // i < 0: a point that is no body, nothing is left out by index.
 struct FieldAcc { double ax, ay; };
 template <typename T>
 __device__ __forceinline__ FieldAcc field_acc_general(const Rec<T>* __restrict__ J, int n, int i, double xi, double yi) {
     double ax = 0.0, ay = 0.0;
-    for (int j = 0; j < n; ++j) {
-        if (j == i) continue;
-        const Rec<T> r = J[j];
-        const double dx = (double)r.x - xi, dy = (double)r.y - yi;
-        if (dx == 0.0 && dy == 0.0) continue;
-        const double d2 = __builtin_fma(dx, dx, dy * dy);
-        const double d = (d2 >= DBL_MIN && d2 <= DBL_MAX) ? __builtin_sqrt(d2) : hypot(dx, dy);
-        const double q = ((double)r.m / d) / d;
+    diag_general_walk<T>(J, n, i, xi, yi, DiagKeepAll{}, [&](int, double mj, double dx, double dy, double d) {
+        const double q = (mj / d) / d;
         ax = __builtin_fma(q, dx / d, ax);
         ay = __builtin_fma(q, dy / d, ay);
-    }
+    });
     return FieldAcc{ax, ay};
 }
 
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(kDiagBlock) void field_at(const Rec<T>* __restrict_
     if (rows_prologue<T, kOwn, Count>(L, J_all, meta_all, ctr_all, stride, n_one, m, out_all, FieldOut{0.0, 0.0, 0.0, 0})) return;
     const Rec<T>* __restrict__ J = L.J;
     const int n = L.n, p = L.p;
-    double xi = 0.0, yi = 0.0;
+    double xi = 0.0, yi = 0.0;                                   // not rows_row: see the head of the file
     if (L.valid) {
         if (kOwn) {
             const Rec<T> r = J[p];

@@ -24,8 +24,8 @@
 // in [0, n), so neither ever matches and the loop runs in fours without a bound test.  Labels are only compared, never used
 // as an index.
 // A row whose accumulator is not finite after the walk (a member at distance 0, a member's d2 outside the chain's range,
-// non-finite input) is redone by group_row_general: diag_row_general with the label test, members at distance exactly 0 left
-// out and counted.  The walk is full, not triangular: a row needs its members on both sides in order, and there are no float
+// non-finite input) is redone by group_row_general: diag_row_general itself (nbody_diag.hpp), handed the label test as the
+// exact walk's membership test - members at distance exactly 0 left out and counted.  The walk is full, not triangular: a row needs its members on both sides in order, and there are no float
 // atomics.  Every row writes its own record: plain loads and stores only.
 #pragma once
 #include <float.h>
@@ -53,22 +53,11 @@ static_assert(sizeof(GroupPhiOut) == 16, "GroupPhiOut layout");
 
 typedef int32_t GroupLabels[2][kTile];        // the labels of the double-buffered j tile, in LDS
 
-// The general code of a flagged row: diag_row_general (nbody_diag.hpp) over the members of the row's group only.
+// The general code of a flagged row: diag_row_general (nbody_diag.hpp) keeping the members of the row's group only.
 template <typename T>
 __device__ __forceinline__ DiagRow group_row_general(const Rec<T>* __restrict__ J, const int32_t* __restrict__ label, int n, int i,
                                                      int32_t li, double xi, double yi) {
-    double s = 0.0;
-    long long c = 0;
-    for (int j = 0; j < n; ++j) {
-        if (j == i || label[j] != li) continue;
-        const Rec<T> r = J[j];
-        const double dx = (double)r.x - xi, dy = (double)r.y - yi;
-        if (dx == 0.0 && dy == 0.0) { ++c; continue; }
-        const double d2 = __builtin_fma(dx, dx, dy * dy);
-        const double d = (d2 >= DBL_MIN && d2 <= DBL_MAX) ? __builtin_sqrt(d2) : hypot(dx, dy);
-        s = s + (double)r.m / d;
-    }
-    return DiagRow{s, c};
+    return diag_row_general<T>(J, n, i, xi, yi, [label, li](int j) { return label[j] == li; });
 }
 
 // The four pairs of one trip of rows_walk: four integer compares, and the fp64 chain behind one branch.

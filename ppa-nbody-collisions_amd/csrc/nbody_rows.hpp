@@ -26,8 +26,8 @@
 // pairs per system and counters: a traits struct such as EncQuery or BinQuery) or, for another shape of result, from the
 // pieces of rows_run - RowsSite's grid, count and sync, RowPoints, rows_check_args.  The per-handle preamble and the
 // precision dispatch are in the two .hip files.  Only the ordered family stays out of rows_walk (see there): field_at and
-// tides_at (nbody_tides.hpp) walk with diag_walk_sums, and the jerk, which needs the velocities in two more
-// planes, with its own copy of that ascending walk.
+// tides_at (nbody_tides.hpp) walk with diag_walk_sums (nbody_diag.hpp), the ascending
+// family's one tile loop; the jerk hands it the velocities' two planes.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -133,9 +133,10 @@ __device__ __forceinline__ RowsRow rows_row(const RowsLane<T, Out>& L, const Fie
 //   * kTri = true (kOwn only), the triangular walk for symmetric pairs, each counted at the higher row: only the tiles up
 //     to the one that holds the workgroup's last row are staged (a workgroup-uniform bound: the barriers need it); a wave
 //     computes on the tiles below its own rows unchecked, on its own tile checked and only up to its last row, on none above.
-// Not one walk with diag_walk_sums (nbody_diag.hpp), which field_at calls: that one sums in ascending order under an order
-// contract with fma-contracted arithmetic, so it cannot pad with NaN, keeps a remainder loop, votes per tile for gathered
-// rows, and its comment records that a function boundary inside it changes the code of every potential kernel.
+// Two tile loops, not one: diag_walk_sums (nbody_diag.hpp), which the potential kernels, field_at, tracers_advance and tides_at
+// call, is the ordered family's.  It sums in ascending order under the order contract: a padding entry would
+// have to add an exact +0 to every sum instead of failing a comparison, so it keeps a remainder loop; it votes per tile for
+// gathered rows; and its self term is masked inside the pair, not tested by the functor.
 template <bool kOwn, bool kTri, typename T, typename Out, typename Stage, typename Four>
 __device__ __forceinline__ void rows_walk(const RowsLane<T, Out>& L, const Stage stage, Four& carried) {
     static_assert(kOwn || !kTri, "the triangular walk is over own rows");
@@ -245,6 +246,23 @@ inline hipError_t rows_reserve(RowsArray<E>& f, size_t n) {
 inline hipError_t rows_upload(RowPoints& f, const nbody_vec2* points, int m, hipStream_t stream) {
     memcpy(f.h, points, (size_t)m * sizeof(FieldPoint));
     return hipMemcpyAsync(f.d, f.h, (size_t)m * sizeof(FieldPoint), hipMemcpyHostToDevice, stream);
+}
+
+// The explicit points' velocities of a query that takes them (tides, shell moments), reserved and uploaded like the points.
+// *pv: the device array, or NULL for points at rest.
+inline int rows_point_vel(const char* who, RowPoints& vel, const nbody_vec2* point_vel, int m, hipStream_t stream,
+                          const FieldPoint** pv) {
+    *pv = nullptr;
+    if (!point_vel || m <= 0) return NBODY_OK;
+    const hipError_t e = rows_reserve(vel, (size_t)m);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point velocities: %s", who,
+                          hipGetErrorString(e));
+    }
+    NBK_ROWS_TRY(rows_upload(vel, point_vel, m, stream));
+    *pv = vel.d;
+    return NBODY_OK;
 }
 
 // The buffers of one query with a record per row: the points and the results.

@@ -207,17 +207,9 @@ template <typename T, typename Count, typename ReadMeta>
 int shell_moments_run(const char* who, const RowsSite& s, ShellMomentState& st, const void* V, const nbody_vec2* points,
                       const nbody_vec2* point_vel, int m, const double* edges2, int bins, nbody_shell_moment* out,
                       ReadMeta read_meta) {
-    const FieldPoint* pv = nullptr;
-    if (point_vel && m > 0) {
-        const hipError_t e = rows_reserve(st.vel, (size_t)m);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point velocities: %s", who,
-                              hipGetErrorString(e));
-        }
-        NBK_ROWS_TRY(rows_upload(st.vel, point_vel, m, s.stream));
-        pv = st.vel.d;
-    }
+    const FieldPoint* pv;
+    const int rc = rows_point_vel(who, st.vel, point_vel, m, s.stream, &pv);
+    if (rc != NBODY_OK) return rc;
     return rows_run<T, Count>(who, s, st.buf, ShellMomentQuery{edges2, bins, V, pv}, points, m, out, read_meta);
 }
 

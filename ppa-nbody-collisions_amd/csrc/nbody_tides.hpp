@@ -6,7 +6,7 @@
 //     adot_a(x,v) = G sum_j m_j (dv_a / r^3 - 3 (d . dv) d_a / r^5)                   -> jx, jy
 // a source at distance exactly 0 left out of every sum and counted.  The force law is the 3-D one in a plane: txx + tyy =
 // G sum m_j / r_j^3, not 0.  The launch geometry, the count and the early exits are those of every row query (nbody_rows.hpp:
-// rows_prologue, rows_row); this file has the pair, the jerk's own tile walk, the general code and the host side.
+// rows_prologue, rows_row); this file has the pair, the jerk's planes for the ordered walk, the general code and the host side.
 //
 // Order contract.  Six running sums per row, each over j = 0, 1, ..., n-1 in ascending order:
 //     sw = sum w          sxx, sxy, syy = sum 3 w u_a u_b          jx, jy = sum (w dv_a - 3 w (u . dv) u_a)
@@ -30,20 +30,20 @@
 //
 // Flagged sums (the policy of nbody_field.hpp).  A sum whose chain accumulator is not finite - a source at distance 0, d2
 // outside the range, an overflowing product, a non-finite input - is redone by the general code, tides_general: one more
-// ascending walk over j with IEEE sqrt and divide, hypot outside the normal range of d2, and
+// ascending walk over j, the exact walk of every flagged row (diag_general_walk, nbody_diag.hpp: IEEE sqrt and divide, hypot
+// outside the normal range of d2), with
 //     q = ((mj / d) / d) / d;  q3 = 3*q;  ux = dx / d;  uy = dy / d
 // in place of w, w3 and u in the very same sums: q is m_j / r_j^3 itself and |u| <= 1, so a term overflows only where
 // m_j / r_j^3 does.  Each of the six sums is replaced on its own and only when it is not finite; a finite chain sum is never
 // replaced.  The count of coincident sources comes from diag_row_general, which every point with one takes (d2 = 0 makes
 // every chain NaN).
 //
-// Walks.  kJerk = false rides diag_walk_sums with TideSums as the kMore object, as field_at does with FieldSums: the checked
-// self tile comes with it, and the potential's fma into `s`, which nothing reads, is dead code.  kJerk = true needs {vx, vy}
-// of the j tile in LDS - five double-buffered planes, 10 KiB - and has its own ascending full walk, tides_walk_jerk: the shape
-// of diag_walk_sums for contiguous rows (ordered: no NaN padding, a remainder loop, a checked self tile) with the two planes
-// more.  diag_walk_sums is left as it is (its comment says why), and rows_walk is the NaN-padded family's.  Both walks add
-// the pairs through the one TideSums::more, in the same order: the tensor of a kJerk = true launch has the bits of a
-// kJerk = false launch.  Plain C++ loads and stores only, no device-side waiting.
+// The walk.  Both launches ride diag_walk_sums (nbody_diag.hpp) with TideSums as the kMore object, as field_at
+// does with FieldSums: the checked self tile comes with it, and the potential's fma into `s`, which nothing reads, is dead
+// code.  kJerk = true needs {vx, vy} of the j tile in LDS - five double-buffered planes, 10 KiB: it hands the walk TideVel, which
+// stages the two planes more and sets dv in the sums before each pair.  One loop adds the pairs through the one
+// TideSums::more, in one order: the tensor of a kJerk = true launch has the bits of a kJerk = false launch.  rows_walk is the
+// NaN-padded family's.  Plain C++ loads and stores only, no device-side waiting.
 #pragma once
 #include <float.h>
 #include <stddef.h>
@@ -63,7 +63,7 @@ static_assert(sizeof(nbody_tide) == 24 && offsetof(nbody_tide, txx) == 0 && offs
               offsetof(nbody_tide, tyy) == 16, "nbody_tide layout");
 
 // The running sums of one row and the pair's chain (the head of the file has it).  `s` is what diag_pair adds the
-// potential's term to: never read here.  dvx, dvy (kJerk): v_j - v of the pair about to be added, set by the walk.
+// potential's term to: never read here.  dvx, dvy (kJerk): v_j - v of the pair about to be added, set by TideVel::look.
 template <bool kJerk>
 struct TideSums {
     static constexpr bool kMore = true;
@@ -99,77 +99,35 @@ struct TideSums {
     }
 };
 
-// The jerk's walk: the sum over j of row i at (xi, yi) with velocity (vxi, vyi), j = 0 .. n-1 ascending.  Called by all
-// kDiagBlock lanes of the workgroup (it has the barriers), lanes without a row included.  self_tile: the one j tile that
-// holds the wave's self terms (kOwn; wave-uniform: 64 contiguous rows inside one tile).  A self term is masked as
-// diag_walk_sums masks it - m = 0 at d2 = 1: every sum gets an exact +0 - so which loop a wave took does not show in the bits.
-// The sums are walked in a copy and handed back, as rows_walk does it.
-template <bool kOwn, typename T>
-__device__ __forceinline__ void tides_walk_jerk(const Rec<T>* __restrict__ J, const Vec2<T>* __restrict__ V, int n, int i, double xi,
-                                                double yi, double vxi, double vyi, int self_tile, bool wave_works,
-                                                TideSums<true>& carried, DiagPlanes& sx, DiagPlanes& sy, DiagPlanes& sm,
-                                                DiagPlanes& svx, DiagPlanes& svy) {
-    TideSums<true> a = carried;
-    const int tid = threadIdx.x;
-    const int jtiles = (n + kTile - 1) / kTile;
-    for (int t = 0; t < jtiles; ++t) {
-        const int b = t & 1;
-        const int j0 = t * kTile;
-        const int jn = n - j0 < kTile ? n - j0 : kTile;
-        if (tid < jn) {
-            const Rec<T> r = J[j0 + tid];
-            const Vec2<T> v = V[j0 + tid];
-            sx[b][tid] = (double)r.x; sy[b][tid] = (double)r.y; sm[b][tid] = (double)r.m;
-            svx[b][tid] = (double)v.x; svy[b][tid] = (double)v.y;
-        }
-        // buffer b was last read in tile t-2: every lane has passed tile t-1's barrier since
-        __syncthreads();
-        if (!wave_works) continue;
-        if (!kOwn || t != self_tile) {
-            int q = 0;
-            for (; q + 4 <= jn; q += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    a.dvx = svx[b][q + u] - vxi; a.dvy = svy[b][q + u] - vyi;
-                    diag_pair(a, sx[b][q + u], sy[b][q + u], sm[b][q + u], xi, yi);
-                }
-            }
-            for (; q < jn; ++q) {
-                a.dvx = svx[b][q] - vxi; a.dvy = svy[b][q] - vyi;
-                diag_pair(a, sx[b][q], sy[b][q], sm[b][q], xi, yi);
-            }
-        } else {
-            for (int q = 0; q < jn; ++q) {
-                const bool self = j0 + q == i;
-                const double dx = sx[b][q] - xi, dy = sy[b][q] - yi;
-                const double d2 = self ? 1.0 : __builtin_fma(dx, dx, dy * dy);
-                a.dvx = svx[b][q] - vxi; a.dvy = svy[b][q] - vyi;
-                a.more(self ? 0.0 : sm[b][q], dx, dy, diag_rinv(d2));
-            }
-        }
+// What the jerk adds to the ordered walk (diag_walk_sums' `planes`): {vx, vy} of the j tile in two more LDS planes, and
+// dv = v_j - v of the row's velocity (vxi, vyi) put into the sums before each pair.  V: the velocities, indexed like J.
+template <typename T>
+struct TideVel {
+    const Vec2<T>* __restrict__ V;
+    double vxi, vyi;
+    DiagPlanes *svx, *svy;
+    __device__ __forceinline__ void stage(int b, int e, int j) const {
+        const Vec2<T> v = V[j];
+        (*svx)[b][e] = (double)v.x; (*svy)[b][e] = (double)v.y;
     }
-    carried = a;
-}
+    __device__ __forceinline__ void look(TideSums<true>& a, int b, int q) const {
+        a.dvx = (*svx)[b][q] - vxi; a.dvy = (*svy)[b][q] - vyi;
+    }
+};
 
-// The general code of a flagged row: diag_row_general's walk (the same pairs skipped, the same d) into the same sums.
+// The general code of a flagged row: the exact walk (diag_general_walk, nbody_diag.hpp) into the same sums.
 // i < 0: a point that is no body, nothing is left out by index.  V is read only for kJerk.
 template <typename T, bool kJerk>
 __device__ __forceinline__ TideSums<kJerk> tides_general(const Rec<T>* __restrict__ J, const Vec2<T>* __restrict__ V, int n, int i,
                                                         double xi, double yi, double vxi, double vyi) {
     TideSums<kJerk> g;
-    for (int j = 0; j < n; ++j) {
-        if (j == i) continue;
-        const Rec<T> r = J[j];
-        const double dx = (double)r.x - xi, dy = (double)r.y - yi;
-        if (dx == 0.0 && dy == 0.0) continue;
-        const double d2 = __builtin_fma(dx, dx, dy * dy);
-        const double d = (d2 >= DBL_MIN && d2 <= DBL_MAX) ? __builtin_sqrt(d2) : hypot(dx, dy);
+    diag_general_walk<T>(J, n, i, xi, yi, DiagKeepAll{}, [&](int j,double mj, double dx, double dy, double d) {
         if constexpr (kJerk) {
             const Vec2<T> v = V[j];
             g.dvx = (double)v.x - vxi; g.dvy = (double)v.y - vyi;
         }
-        g.add((((double)r.m / d) / d) / d, dx / d, dy / d);
-    }
+        g.add(((mj / d) / d) / d, dx / d, dy / d);
+    });
     return g;
 }
 
@@ -201,7 +159,7 @@ __global__ __launch_bounds__(kDiagBlock) void tides_at(const Rec<T>* __restrict_
             }
         }
         __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile], svx[2][kTile], svy[2][kTile];
-        tides_walk_jerk<kOwn, T>(J, V, n, i, w.x, w.y, vxi, vyi, L.self_tile, L.wave_works, a, sx, sy, sm, svx, svy);
+        diag_walk_sums<false, kOwn, T>(J, n, i, w.x, w.y, L.self_tile, L.wave_works, a, sx, sy, sm, TideVel<T>{V, vxi, vyi, &svx, &svy});
     } else {
         __shared__ double sx[2][kTile], sy[2][kTile], sm[2][kTile];
         diag_walk_sums<false, kOwn, T>(J, n, i, w.x, w.y, L.self_tile, L.wave_works, a, sx, sy, sm);
@@ -289,17 +247,9 @@ inline int tides_check_args(const char* who, std::initializer_list<const void*> 
 template <typename T, typename Count, typename ReadMeta>
 int tides_run(const char* who, const RowsSite& s, TidesState& st, double G, const void* V, const nbody_vec2* points,
               const nbody_vec2* point_vel, int m, nbody_tide* tide, nbody_vec2* jerk, int64_t* coincident, ReadMeta read_meta) {
-    const FieldPoint* pv = nullptr;
-    if (point_vel && m > 0) {
-        const hipError_t e = rows_reserve(st.vel, (size_t)m);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point velocities: %s", who,
-                              hipGetErrorString(e));
-        }
-        NBK_ROWS_TRY(rows_upload(st.vel, point_vel, m, s.stream));
-        pv = st.vel.d;
-    }
+    const FieldPoint* pv;
+    const int rc = rows_point_vel(who, st.vel, point_vel, m, s.stream, &pv);
+    if (rc != NBODY_OK) return rc;
     TideResult out{tide, jerk};
     return rows_run<T, Count>(who, s, st.buf, TidesQuery{G, V, pv, jerk != nullptr, coincident}, points, m, &out, read_meta);
 }

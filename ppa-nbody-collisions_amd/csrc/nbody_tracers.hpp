@@ -5,8 +5,9 @@
 // = blockIdx.y, the same m per system) share the one kernel.
 //
 // The advance of one tracer (the whole contract is in include/nbody.h):
-//     (ax, ay, phi, coincident) = the field at (x, y) over the n bodies of J_t: diag_walk_sums with FieldSums and
-//                                 field_finish (nbody_field.hpp), called, not restated - the bits of nbody_get_field
+//     (ax, ay, phi, coincident) = the field at (x, y) over the n bodies of J_t: the ordered walk (diag_walk_sums,
+//                                 nbody_diag.hpp) with FieldSums, then field_finish (nbody_field.hpp) with the exact walk
+//                                 for a flagged tracer - called, not restated: the bits of nbody_get_field
 //     dvx = dt * ax;  [walls: tx = x + (ax * dt); if (tx > hi_x || tx < lo_x) vx = vx * -1.0]
 //     vx = vx + dvx;  x = x + (dt * vx)                              (y likewise; finish_body's rule with r = 0)
 // every operation IEEE fp64 and rounded on its own.  The launch sits between the step's compute and its commit: J still

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """This library against the parent commit's, on the work of the kernels that share a rule with another kernel: the
 compaction's offsets (compact_count / compact_scatter, batch_count / batch_commit, ids_scatter), the potential's walk
-(diag_potential, batch_diag_potential, track_potential), the finish of the diagnostics (batch_diag_reduce) and the row
-queries' prologue, tile walk and host drivers (field_at, neighbors_at, groups_sweep, pair_counts, encounters_walk,
-binaries_walk, group_potential, shells_at, shell_moments_at; nbody_rows.hpp).
+(diag_potential, batch_diag_potential, track_potential, and with it field_at, tides_at and tracers_advance: the ordered
+walk and the exact walk of nbody_diag.hpp), the finish of the diagnostics (batch_diag_reduce) and the row queries'
+prologue, tile walk and host drivers (field_at, neighbors_at, groups_sweep, pair_counts, encounters_walk, binaries_walk,
+group_potential, shells_at, shell_moments_at; nbody_rows.hpp).
 
     python3 csrc/tune/ab_parent.py --baseline-root DIR [--lines a,b256,...] [--rounds 3] [--out FILE]
     python3 csrc/tune/ab_parent.py --trace [--root DIR]     (every line once, target of rocprofv3 --kernel-trace --stats)
@@ -38,6 +39,12 @@ Lines (fp32, literal, stock configuration with stock radii):
     shl, shm  the shapes of shells_probe.py and shell_moments_probe.py on the grp state: shells() ms per call
               / shell_moments() over 8 bins below the prs top edge; shlpts: 32 bins from 65536
               explicit points; shmpts: 8 bins from 65536 moving points; ...256 as above
+    tid, tidj the shapes of tides_probe.py: Stepper N = 262144, tides() / tides(jerk=True); tidpts,   ms per call
+              tidjpts: the same state with 65536 explicit points, tidjpts' moving; tid256,
+              tidj256: StepperBatch 256 x 1024 after 3 steps, points=None
+    trc       stepping with 65536 tracers set, from a fresh upload and a fresh set: trc Stepper  ms | us per step
+              N = 262144 (8 steps), trc256 StepperBatch 256 x 1024 with 256 tracers in each
+              system (500 steps)
 A line passes when the candidate's median is not above the parent's median by more than max(the parent's round spread
 (max - min), |control median - parent median|).  Exit status 1 if a line does not pass.
 """
@@ -56,14 +63,17 @@ ROOT = os.path.abspath(os.path.join(HERE, "..", "..", ".."))
 REPLY_TIMEOUT_S = 240           # a side that does not answer within this is killed and the probe fails
 LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024", "d256x1024", "d64x4096",
          "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256",
-         "enc", "enc256", "bin", "bin256", "gpe", "gpe256", "shl", "shlpts", "shl256", "shm", "shmpts", "shm256")
+         "enc", "enc256", "bin", "bin256", "gpe", "gpe256", "shl", "shlpts", "shl256", "shm", "shmpts", "shm256",
+         "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "trc", "trc256")
 BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
 STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
-ROWS = {"": 3, "pts": 8, "256": 100}    # the row queries' shapes (field_probe.py, neighbor_probe.py): calls per window
+TRACERS = {"trc": 8, "trc256": 500}     # steps per window with M_POINTS tracers set
+ROWS = {"": 3, "pts": 8, "256": 100}    # the row queries' shapes (field_probe.py, neighbor_probe.py): calls per window;
+                                        # the tides' too: 51 to 71 ms a call on own rows, 16 to 21 on the points
 SCANS = {"grp": 8, "grp256": 100, "prs": 20, "prspts": 30, "prs256": 200,     # the queries on the state after 3 steps:
          "enc": 6, "enc256": 100, "bin": 20, "bin256": 80, "gpe": 6, "gpe256": 80,    # calls per window
          "shl": 20, "shlpts": 20, "shl256": 60, "shm": 20, "shmpts": 20, "shm256": 40}
-ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm")
+ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm", "tid")
 N_BIG = 262144
 M_POINTS = 65536
 
@@ -118,7 +128,7 @@ class Line:
                 self.st.step(8)
                 self.sel = [int(x) for x in np.unique(np.linspace(0, N_BIG - 1, 64).astype(np.int32))]
         elif name[:3] in ROW_LINES:
-            self.unit, self.reps = "ms per call", SCANS[name] if name in SCANS else ROWS[name[3:]]
+            self.unit, self.reps = "ms per call", SCANS[name] if name in SCANS else ROWS[name[3:].lstrip("j")]
             self.pts = None
             if name.endswith("256"):
                 cfg = nb.stock_config(particleCount=1024)
@@ -159,8 +169,27 @@ class Line:
                     if self.pts is not None:
                         vel = np.random.default_rng(3).uniform(-1, 1, size=(M_POINTS, 2)) * np.abs(np.asarray(down.Velocities)).max()
                     self.call = lambda pts: self.st.shell_moments(e2, pts, vel, squared=True)
+            elif name.startswith("tid"):
+                jerk, vel = name[3:4] == "j", None
+                if jerk and self.pts is not None:
+                    vel = np.random.default_rng(3).uniform(-1, 1, size=(M_POINTS, 2)) * np.abs(np.asarray(self.st.download().Velocities)).max()
+                self.call = lambda pts: self.st.tides(pts, vel, jerk=jerk)
             else:
                 self.call = self.st.field if name.startswith("fld") else self.st.neighbors
+        elif name in TRACERS:
+            self.steps = min(200, TRACERS[name]) if short else TRACERS[name]
+            if name.endswith("256"):
+                cfg = nb.stock_config(particleCount=1024)
+                self.bodies = [nb.init_bodies(cfg, seed=100 + s) for s in range(256)]
+                self.st = self.batch = nb.StepperBatch(256, 1024, cfg=cfg)
+                self.unit, m = "us per step", M_POINTS // 256           # the one set for every system
+            else:
+                cfg = nb.stock_config(particleCount=N_BIG)
+                self.bodies = nb.init_bodies(cfg, seed=1)
+                self.st = nb.Stepper(cfg)
+                self.unit, m = "ms per step", M_POINTS
+            self.reps = self.steps
+            self.pts = np.random.default_rng(2).uniform(0, 1, size=(m, 2)) * [cfg.fieldWidth, cfg.fieldHeight]
         elif name in STEPS:
             shape = name[1:]
             self.steps = 200 if short else STEPS[name]
@@ -200,6 +229,15 @@ class Line:
                 o, ids = (st.download(s), st.ids(s)) if self.batch else (st.download(), st.ids())
                 parts += [b"%d:" % o.numBodies, o.block.tobytes(), ids.tobytes()]
             return seconds, digest_of(parts)
+        if name in TRACERS:
+            st.upload(self.bodies)
+            st.set_tracers(self.pts)                                        # zeroes their counters; synchronises
+            st.sync()
+            t0 = time.perf_counter()
+            st.step(self.steps)
+            st.sync()
+            seconds = time.perf_counter() - t0
+            return seconds, digest_of(result_parts(st.tracers()))
         if name[:3] in ROW_LINES:
             t0 = time.perf_counter()
             for _ in range(self.reps):                                      # each call ends in a copy back and a synchronise
