@@ -1102,6 +1102,75 @@ int nbody_batch_tracers_get(struct nbody_batch* b, nbody_tracer* out /* [systems
                             nbody_tracer_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Cell sums (the reference has none): for every cell of a caller-given uniform grid the number, the mass, the
+ * momentum and twice the kinetic energy of the current bodies in it - what a surface density map, a mean velocity or a
+ * dispersion map and a counts-in-cells statistic are made of - and on request the cell of every body and the cell list in
+ * CSR form: cell offsets plus the bodies in cell order.  The one query about a place rather than a body or a point, the one
+ * query whose cost is O(n), and the project's only spatial index.
+ * The grid: nx x ny cells from (x0, y0), sx and sy cells per unit length.  The caller computes sx and sy once (Python's
+ * make_grid: sx = nx / (x1 - x0) in fp64) and the definition uses those doubles as they are.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma.  Body j
+ * with the record (X, Y, M) and the velocity (VX, VY), widened exactly from fp32 or taken as they are from fp64:
+ *     tx = (X - x0) * sx;   ty = (Y - y0) * sy
+ *     inside(j)  <=>  0 <= tx && tx < nx && 0 <= ty && ty < ny      decided on the doubles; a NaN is outside
+ *     cell(j) = (int)ty * nx + (int)tx   if inside(j), else -1      converted only after the compares
+ * so a coordinate of 1e30 never reaches a float-to-int conversion, a body on a cell boundary belongs to the cell above and
+ * to the right, a body at the grid's upper bound is outside and -0.0 at x0 = 0 is in column 0.  Per cell c, with its members
+ * - the bodies with cell(j) == c - taken in ASCENDING j and every accumulator starting at +0.0:
+ *     count = the number of members;   first = the lowest member index, -1 for an empty cell
+ *     mass = mass + M
+ *     px = px + (M*VX);   py = py + (M*VY);   k2 = k2 + (M*((VX*VX) + (VY*VY)))
+ * The order of the sums is part of the contract, as for every fp64 sum of this library: the masses span thirteen decades.
+ * Without NBODY_CELLS_MOMENTS the velocities are not read and px, py and k2 are +0.0; mass, count and first are the same
+ * bits either way.  Radii play no part.  The optional lists, each NULL or given:
+ *     cell_of[j] = cell(j)                                           j = 0 .. n-1
+ *     start[c]   = the exclusive prefix sum of the counts            c = 0 .. nx*ny;  start[nx*ny] = inside
+ *     order[start[c] .. start[c+1])  = the members of c in ascending index;  `inside` entries in all
+ * order needs start; cap is the room of cell_of and of order in entries and is looked at only where one of them is given:
+ * cap < n is NBODY_ERR_CAPACITY with nothing written, as for nbody_get_groups.  info: n, the bodies inside and outside
+ * (inside + outside == n), the occupied cells, the largest count and the lowest cell that has it (0 and cell 0 where no body
+ * is inside).
+ * What follows from the definition: the result is a function of the state and the grid only - not of rank, world,
+ * transport, force kernel, the flags (for mass, count, first and the lists) or the order the device's waves ran in; a 1 x 1
+ * grid that holds every body has in `mass` the bits of nbody_get_shells' one bin [0, +inf) at a far probe point; it is
+ * independent of the semantics: a literal context's frozen tail is binned like any other body; a NaN mass makes its cell's
+ * mass NaN and still counts.
+ * nbody_get_cells synchronises, reads the replica (and with NBODY_CELLS_MOMENTS the velocities) and never changes what later
+ * steps compute.  Without NBODY_CELLS_MOMENTS it is NOT collective: any rank of any world may call it on its own and each
+ * gives the same bits.  With it the velocities are read, which a rank holds for its own range only: NBODY_ERR_STATE on a
+ * context with world > 1, NBODY_FLAG_GROUP_EXCHANGE or NBODY_FLAG_FORCE_COMM, as for nbody_get_shell_moments.  The device
+ * scratch and the pinned staging are allocated on the first call and grown with the grid; a context that never calls it
+ * allocates nothing, launches nothing more, and the kernels it runs keep their code.  An empty system: every cell
+ * {+0.0, +0.0, +0.0, +0.0, 0, -1}, start all 0.
+ * NBODY_ERR_INVALID, found before any device call, the values before the handle: a NULL grid; nx or ny below 1 or nx * ny
+ * above NBODY_CELLS_MAX; x0 or y0 not finite; sx or sy not finite or not above 0; unknown flag bits; order without start;
+ * cap < 0 with a list; a NULL handle, cells or info.  NBODY_ERR_CAPACITY, found there too: a batch with systems * nx * ny
+ * above 1 << 22.  NBODY_ERR_STATE: before an upload; moments on more than one rank.
+ * How (csrc/nbody_cells.hpp): five kernels on the handle's stream and one wait - the cell of every body and the counts by
+ * integer atomics (their sum does not depend on arrival), a prefix sum, the scatter through per-cell cursors, a counting
+ * sort inside every cell that makes the list independent of the order of arrival, and the four ordered chains per cell over
+ * the sorted list, a whole wave to a cell of 64 members or more.  No float atomic takes part.  Cost: DESIGN.md 4.20 has the
+ * counts and what was measured (profiles/cells_probe.txt).
+ * nbody_batch_get_cells: the same query for every system of a batch, each stage ONE launch whatever S is, with the one grid
+ * for all of them.  System s's cells at [s * nx*ny + c], its start at [s * (nx*ny + 1) + c], its cell_of and order at
+ * [s * capacity + .], n and `inside` entries of them, the rest of the slice left unchanged; info[s].  The lists' room is the
+ * batch's capacity.  System s gives exactly the bits an nbody_ctx holding that system's state gives.  A count outside
+ * [0, capacity] is treated as 0 and reported for that system, as by nbody_batch_get_knn.
+ * ------------------------------------------------------------------------------------------------- */
+#define NBODY_CELLS_MAX (1 << 20)            /* nx * ny of one call */
+#define NBODY_CELLS_MOMENTS 1u               /* read the velocities: px, py, k2 */
+typedef struct nbody_grid { double x0, y0, sx, sy; int32_t nx, ny; } nbody_grid;            /* 40 bytes */
+typedef struct nbody_cell { double mass, px, py, k2; int32_t count, first; } nbody_cell;    /* 40 bytes */
+typedef struct nbody_cells_info { int32_t n, inside, outside, occupied, largest, largest_cell; } nbody_cells_info;
+int nbody_get_cells(nbody_ctx* ctx, const nbody_grid* grid, uint32_t flags, nbody_cell* cells /* [nx*ny] */,
+                    int32_t* cell_of /* [cap] or NULL */, int32_t* start /* [nx*ny+1] or NULL */,
+                    int32_t* order /* [cap] or NULL */, int cap, nbody_cells_info* info);
+int nbody_batch_get_cells(struct nbody_batch* b, const nbody_grid* grid, uint32_t flags,
+                          nbody_cell* cells /* [systems*nx*ny] */, int32_t* cell_of /* [systems*capacity] or NULL */,
+                          int32_t* start /* [systems*(nx*ny+1)] or NULL */, int32_t* order /* [systems*capacity] or NULL */,
+                          nbody_cells_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

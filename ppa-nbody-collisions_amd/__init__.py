@@ -29,6 +29,8 @@ KNN_MAX = 32
 SHELLS_MAX = 32
 SHELL_MOMENTS_MAX = 8                                           # NBODY_SHELL_MOMENTS_MAX: bins of one library call
 SHELL_MOMENTS_WRAPPER_MAX = 32                                  # bins of one shell_moments(): split into calls of <= 8
+CELLS_MAX = 1 << 20                                             # NBODY_CELLS_MAX: nx * ny of one call
+CELLS_MOMENTS = 1                                               # NBODY_CELLS_MOMENTS
 COMM_ID_BYTES = 128
 IMAGE_PATH_MAX = 1024
 
@@ -141,6 +143,13 @@ SHELL_MOMENT_FIELDS = ("mass", "px", "py", "ke", "mr2", "rad", "ang", "rad2", "a
 SHELL_MOMENT_DTYPE = np.dtype([(f, np.float64) for f in SHELL_MOMENT_FIELDS] + [("count", np.int32), ("pad", np.int32)])
 
 # struct nbody_groups_info as a numpy record (Stepper.groups, StepperBatch.groups)
+# nbody_grid, nbody_cell and nbody_cells_info (include/nbody.h): the grid, one cell's sums and the summary of cells()
+GRID_DTYPE = np.dtype([("x0", np.float64), ("y0", np.float64), ("sx", np.float64), ("sy", np.float64), ("nx", np.int32),
+                       ("ny", np.int32)])
+CELL_DTYPE = np.dtype([("mass", np.float64), ("px", np.float64), ("py", np.float64), ("k2", np.float64), ("count", np.int32),
+                       ("first", np.int32)])
+CELLS_INFO_DTYPE = np.dtype([("n", np.int32), ("inside", np.int32), ("outside", np.int32), ("occupied", np.int32),
+                             ("largest", np.int32), ("largest_cell", np.int32)])
 GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
 # nbody_group_energy_info (24 bytes) and nbody_group_record (80 bytes), include/nbody.h
 GROUP_ENERGY_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32),
@@ -250,6 +259,8 @@ SYMBOLS = {
     "nbody_get_shell_moments": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _ip]),
     "nbody_batch_get_shell_moments": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
+    "nbody_get_cells": (_i, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i, _vp]),
+    "nbody_batch_get_cells": (_i, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
     "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
     "nbody_group_catalog": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
@@ -769,6 +780,90 @@ def shell_kinematics(result):
     return out
 
 
+def make_grid(nx, ny=None, bounds=None):
+    """The nbody_grid of cells(): nx x ny cells (ny=None: nx) over bounds = (x0, x1, y0, y1), the half-open rectangle
+    [x0, x1) x [y0, y1) -> a GRID_DTYPE record with sx = nx / (x1 - x0) and sy = ny / (y1 - y0), computed once in fp64: the
+    definition of the cell sums uses those doubles as they are.  A GRID_DTYPE record passes through unchanged."""
+    if isinstance(nx, np.ndarray) or isinstance(nx, np.void):
+        g = np.zeros(1, dtype=GRID_DTYPE)
+        g[0] = np.asarray(nx, dtype=GRID_DTYPE).reshape(-1)[0]
+        return g
+    if bounds is None:
+        raise ValueError("make_grid needs bounds = (x0, x1, y0, y1)")
+    x0, x1, y0, y1 = (np.float64(v) for v in bounds)
+    nx = int(nx)
+    ny = nx if ny is None else int(ny)
+    g = np.zeros(1, dtype=GRID_DTYPE)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g[0] = (x0, y0, np.float64(nx) / (x1 - x0), np.float64(ny) / (y1 - y0), nx, ny)
+    return g
+
+
+def _field_bounds(field):
+    """The default bounds of cells(): the field, where nbody_init_bodies places bodies."""
+    if field is None:
+        raise ValueError("cells() needs bounds: this handle was created without field sizes")
+    w, h = field
+    return (-float(w), float(w), -float(h), float(h))
+
+
+def _cells_grid(grid_or_nx, ny, bounds, field):
+    if isinstance(grid_or_nx, (np.ndarray, np.void)):
+        return make_grid(grid_or_nx)
+    return make_grid(grid_or_nx, ny, _field_bounds(field) if bounds is None else bounds)
+
+
+def _cells(call, systems, capacity, grid, moments, lists):
+    """nbody_get_cells through `call(grid, flags, cells, cell_of, start, order, info)` for `systems` systems (None: a
+    context) -> the raw arrays (cells (S, ny, nx), cell_of (S, capacity), start (S, cells + 1), order (S, capacity), info (S,));
+    the lists None without `lists`."""
+    S = 1 if systems is None else systems
+    nx, ny = int(grid["nx"][0]), int(grid["ny"][0])
+    room = max(nx, 0) * max(ny, 0) if 0 < nx * ny <= CELLS_MAX else 1
+    cells = np.zeros((max(S, 1), room), dtype=CELL_DTYPE)
+    info = np.zeros(max(S, 1), dtype=CELLS_INFO_DTYPE)
+    cell_of = start = order = None
+    if lists:
+        cell_of = np.full((max(S, 1), max(capacity, 1)), -1, dtype=np.int32)
+        order = np.full((max(S, 1), max(capacity, 1)), -1, dtype=np.int32)
+        start = np.zeros((max(S, 1), room + 1), dtype=np.int32)
+    _check(call(grid.ctypes.data, CELLS_MOMENTS if moments else 0, cells.ctypes.data,
+                cell_of.ctypes.data if lists else None, start.ctypes.data if lists else None,
+                order.ctypes.data if lists else None, info.ctypes.data))
+    return cells.reshape(max(S, 1), ny, nx), cell_of, start, order, info
+
+
+def _cells_dict(cells, cell_of, start, order, info, grid):
+    out = {"cells": cells, "grid": grid[0].copy(), "info": {k: int(info[k]) for k in CELLS_INFO_DTYPE.names}}
+    if cell_of is not None:
+        out["cell_of"] = cell_of[:out["info"]["n"]].copy()
+        out["start"] = start.copy()
+        out["order"] = order[:out["info"]["inside"]].copy()
+    return out
+
+
+def cell_maps(result):
+    """What the sums of cells() are for, on the host in numpy, from its result (a dict with "cells" and "grid", one system):
+    {"area": of one cell, "surface_density": mass / area, "mean_velocity": (ny, nx, 2) p / mass, "dispersion": the velocity
+    dispersion k2 / mass - |p|^2 / mass^2 (both NaN where a cell is empty; they need moments=True), "cic_mean", "cic_variance",
+    "cic_ratio": the mean, the population variance and variance / mean of the counts over the cells - 1 for a Poisson
+    process, above for a clustered one."""
+    cells, g = np.asarray(result["cells"]), result["grid"]
+    if cells.dtype != CELL_DTYPE or cells.ndim != 2:
+        raise ValueError("cell_maps takes the result of one system: a CELL_DTYPE array (ny, nx)")
+    area = (1.0 / float(g["sx"])) * (1.0 / float(g["sy"]))
+    mass, count = cells["mass"], cells["count"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vel = np.stack([cells["px"] / mass, cells["py"] / mass], axis=-1)
+        disp = cells["k2"] / mass - (cells["px"] * cells["px"] + cells["py"] * cells["py"]) / (mass * mass)
+    vel[count == 0] = np.nan
+    disp = np.where(count == 0, np.nan, disp)
+    mean = float(count.mean())
+    var = float(count.astype(np.float64).var())
+    return {"area": area, "surface_density": mass / area, "mean_velocity": vel, "dispersion": disp, "cic_mean": mean,
+            "cic_variance": var, "cic_ratio": var / mean if mean > 0 else float("nan")}
+
+
 def _encounter_list(rec):
     out = np.zeros(len(rec), dtype=ENCOUNTER_DTYPE)
     for f in ENCOUNTER_DTYPE.names:
@@ -922,6 +1017,7 @@ class Stepper:
         self.precision = precision
         self.capacity = d.capacity
         self.world, self.rank = world, rank
+        self._field = (d.fieldWidth, d.fieldHeight) if d.fieldWidth > 0 and d.fieldHeight > 0 else None
         self._tracks = (0, False)                               # (samples, potential) of the track log's reservation
         self._tracks_all = False                                # reserved with ids=None: tracks() trims to the uploaded count
         self._uploaded = 0
@@ -1158,6 +1254,21 @@ class Stepper:
             ctypes.byref(n)), (max(m, 1),), e2)
         return {"moments": mom[:n.value].copy(), "edges2": e2}
 
+    def cells(self, grid_or_nx, ny=None, bounds=None, moments=True, lists=False):
+        """nbody_get_cells: for every cell of a uniform grid - make_grid(nx, ny, bounds), or a grid made by it; bounds=None:
+        the field, [-fieldWidth, fieldWidth) x [-fieldHeight, fieldHeight) - the number, the mass and (moments=True) the
+        momentum and twice the kinetic energy of the current bodies in it, summed in ascending index: {"cells": CELL_DTYPE
+        (ny, nx) - mass, px, py, k2, count, first - "grid", "info": n, inside, outside, occupied, largest, largest_cell}; with
+        lists=True also "cell_of": int32 (n,), the cell of every body (-1: outside), "start": int32 (nx*ny + 1,) and "order":
+        int32 (inside,), the bodies in cell order, ascending inside a cell.  cell_maps() turns the sums into maps.
+        moments=False is not collective: any rank of any world may call it; moments=True needs a single-rank context."""
+        grid = _cells_grid(grid_or_nx, ny, bounds, self._field)
+        cells, cell_of, start, order, info = _cells(
+            lambda g, flags, c, co, st, od, inf: lib.nbody_get_cells(self._ctx, g, flags, c, co, st, od, self.capacity, inf),
+            None, self.capacity, grid, moments, lists)
+        return _cells_dict(cells[0], None if cell_of is None else cell_of[0], None if start is None else start[0],
+                           None if order is None else order[0], info[0], grid)
+
     def groups(self, link, radius_scale=1.0):
         """nbody_get_groups: friends-of-friends groups of the current bodies, i and j linked where d2 <= s*s with
         s = radius_scale * (r_i + r_j) + link (fp64): {"label": int32 (n,), label[i] the lowest index of body i's group,
@@ -1280,6 +1391,11 @@ class StepperGroup:
         """Stepper.shells through one rank: every rank's replica holds every body, each gives the same bits."""
         return self.ranks[rank].shells(edges, points, squared)
 
+    def cells(self, grid_or_nx, ny=None, bounds=None, moments=False, lists=False, rank=0):
+        """Stepper.cells through one rank, moments=False only (a rank holds only its own velocities): every rank's replica
+        holds every position and mass, each gives the same bits."""
+        return self.ranks[rank].cells(grid_or_nx, ny, bounds, moments, lists)
+
     def groups(self, link, radius_scale=1.0, rank=0):
         """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
         return self.ranks[rank].groups(link, radius_scale)
@@ -1326,6 +1442,7 @@ class StepperBatch:
                 if not isinstance(p, (tuple, list)):
                     p = (p.timestep, p.growthRate, p.fieldWidth, p.fieldHeight)
                 arr[s].timestep, arr[s].growthRate, arr[s].fieldWidth, arr[s].fieldHeight = p
+        self._field = (arr[0].fieldWidth, arr[0].fieldHeight) if arr is not None and len(params) > 0 else None
         d = _BatchDesc()
         d.precision, d.semantics, d.systems, d.capacity, d.device = precision, semantics, systems, capacity, device
         d.flags = (FLAG_RECORD_EVENTS if record_events else 0) | (FLAG_TRACK_IDS if track_ids else 0)
@@ -1519,6 +1636,21 @@ class StepperBatch:
         if pts is None:
             return [{"moments": mom[s, :int(c)].copy(), "edges2": e2} for s, c in enumerate(self.counts())]
         return {"moments": np.ascontiguousarray(mom[:, :m]), "edges2": e2}
+
+    def cells(self, grid_or_nx, ny=None, bounds=None, moments=True, lists=False):
+        """nbody_batch_get_cells: Stepper.cells for every system, each stage one launch for the whole batch, with the one
+        grid for all of them (bounds=None: the field of system 0), system s having the bits a Stepper holding its state
+        gives: {"cells": CELL_DTYPE (S, ny, nx), "grid", "info": a CELLS_INFO_DTYPE array (S,)}; with lists=True also
+        "cell_of": int32 (S, capacity), -1 past a system's count, "start": int32 (S, nx*ny + 1) and "order": int32 (S, capacity),
+        -1 past a system's `inside`."""
+        grid = _cells_grid(grid_or_nx, ny, bounds, self._field)
+        cells, cell_of, start, order, info = _cells(
+            lambda g, flags, c, co, st, od, inf: lib.nbody_batch_get_cells(self._b, g, flags, c, co, st, od, inf),
+            self.systems, self.capacity, grid, moments, lists)
+        out = {"cells": cells[:self.systems], "grid": grid[0].copy(), "info": info[:self.systems]}
+        if lists:
+            out.update(cell_of=cell_of[:self.systems], start=start[:self.systems], order=order[:self.systems])
+        return out
 
     def groups(self, link, radius_scale=1.0):
         """nbody_batch_get_groups: Stepper.groups for every system, every pair walk one launch for the whole batch: a list

@@ -31,6 +31,7 @@
 #include "nbody_knn.hpp"
 #include "nbody_shells.hpp"
 #include "nbody_shell_moments.hpp"
+#include "nbody_cells.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -100,6 +101,8 @@ struct nbody_batch {
     ShellState shl;
     // shell moments (nbody_batch_get_shell_moments, nbody_shell_moments.hpp): nothing is allocated before the first call
     ShellMomentState shm;
+    // cell sums (nbody_batch_get_cells, nbody_cells.hpp): nothing is allocated before the first call
+    CellState cel;
     // encounter queries (nbody_batch_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_batch_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -137,6 +140,7 @@ void free_all(nbody_batch* b) {
     rows_free(b->knn);
     rows_free(b->shl);
     shell_moments_free(b->shm);
+    cells_free(b->cel);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
@@ -892,6 +896,23 @@ int nbody_batch_get_group_potential(nbody_batch* b, double link, double radius_s
     return batch_rows_run(b, [&](auto t, auto sync) {
         return group_energy_run<decltype(t), RowsBatchCount>(who, site, b->grp, b->gen, (double)kG, link, radius_scale, label, phi_in,
                                                              info, sync);
+    });
+}
+
+}  // extern "C"
+
+// Cell sums (nbody_cells.hpp): one grid for every system, each stage ONE launch for the whole batch.  After everything else,
+// for the group energies' reason.
+extern "C" {
+
+int nbody_batch_get_cells(nbody_batch* b, const nbody_grid* grid, uint32_t flags, nbody_cell* cells, int32_t* cell_of,
+                          int32_t* start, int32_t* order, nbody_cells_info* info) {
+    const char* who = "nbody_batch_get_cells";
+    RowsSite site;
+    int rc = cells_check_args(who, {b, cells, info}, grid, flags, cell_of, start, order, 0, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return cells_run<decltype(t), RowsBatchCount>(who, site, b->cel, b->V, *grid, flags, cells, cell_of, start, order, info, sync);
     });
 }
 

@@ -34,6 +34,7 @@
 #include "nbody_knn.hpp"
 #include "nbody_shells.hpp"
 #include "nbody_shell_moments.hpp"
+#include "nbody_cells.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -206,6 +207,8 @@ struct nbody_ctx {
     ShellState shl;
     // shell moments (nbody_get_shell_moments, nbody_shell_moments.hpp): nothing is allocated before the first call
     ShellMomentState shm;
+    // cell sums (nbody_get_cells, nbody_cells.hpp): nothing is allocated before the first call
+    CellState cel;
     // encounter queries (nbody_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -649,6 +652,7 @@ void free_all(nbody_ctx* c) {
     rows_free(c->knn);
     rows_free(c->shl);
     shell_moments_free(c->shm);
+    cells_free(c->cel);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
@@ -1915,6 +1919,28 @@ int nbody_get_group_potential(nbody_ctx* c, double link, double radius_scale, in
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return group_energy_run<decltype(t), RowsOneCount>(who, site, c->grp, c->gen, (double)kG, link, radius_scale, label, phi_in,
                                                            info, sync);
+    });
+}
+
+}  // extern "C"
+
+// Cell sums (nbody_cells.hpp).  The sums without moments read the replica only and are any context's to call; the moments
+// read the velocities, so the encounters' restriction holds for them.  After everything else, for the group energies' reason.
+extern "C" {
+
+int nbody_get_cells(nbody_ctx* c, const nbody_grid* grid, uint32_t flags, nbody_cell* cells, int32_t* cell_of, int32_t* start,
+                    int32_t* order, int cap, nbody_cells_info* info) {
+    const char* who = "nbody_get_cells";
+    RowsSite site;
+    int rc = cells_check_args(who, {c, cells, info}, grid, flags, cell_of, start, order, cap, 1);
+    if (rc != NBODY_OK) return rc;
+    if ((flags & NBODY_CELLS_MOMENTS) && (rc = ctx_single_rank(c, who, "the moments need", kOwnVelocities)) != NBODY_OK) return rc;
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if ((cell_of || order) && cap < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d list entries, the context holds %d bodies", who, cap, site.n_bound);
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return cells_run<decltype(t), RowsOneCount>(who, site, c->cel, c->Vown, *grid, flags, cells, cell_of, start, order, info,
+                                                    sync);
     });
 }
 
