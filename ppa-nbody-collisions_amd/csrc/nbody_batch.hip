@@ -416,22 +416,14 @@ int nbody_batch_upload(nbody_batch* b, const void* const* blocks, const int* cou
     int n_upper = 0;
     for (int s = 0; s < b->S; ++s) {
         const int n = counts[s];
-        const float* P = (const float*)blocks[s];
-        const float* V = P + 2 * (size_t)n;
-        const float* M = V + 2 * (size_t)n;
-        const float* R = M + (size_t)n;
         Rec<float>* r = st + (size_t)s * b->cap;
         Vec2<float>* v = sv + (size_t)s * b->cap;
-        for (int i = 0; i < n; ++i) {
-            r[i] = Rec<float>{P[2 * i], P[2 * i + 1], M[i], R[i]};
-            v[i] = Vec2<float>{V[2 * i], V[2 * i + 1]};
-        }
+        nbody_block_pack(blocks[s], n, NBODY_F32, r, v, nullptr, 0);   // no batch kernel looks at a summary: it stays 0
         if (n < b->cap) {                                  // never read; defined all the same
             memset(r + n, 0, (size_t)(b->cap - n) * sizeof(Rec<float>));
             memset(v + n, 0, (size_t)(b->cap - n) * sizeof(Vec2<float>));
         }
-        Meta& m = b->h_meta[s];
-        m.n = n; m.lo = 0; m.cnt = n; m.step = 0; m.n_prev = n; m.summary = 0; m.pad[0] = m.pad[1] = 0;
+        b->h_meta[s] = meta_at_upload(n, 0, n, 0);
         if (n > n_upper) n_upper = n;
     }
     HIP_TRY(hipMemcpyAsync(b->J, st, bodies * sizeof(Rec<float>), hipMemcpyHostToDevice, b->stream));
@@ -498,16 +490,7 @@ int nbody_batch_download(nbody_batch* b, int system, void* block, int* n_out) {
         HIP_TRY(hipMemcpyAsync(sv, b->V + base, (size_t)n * sizeof(Vec2<float>), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
     }
-    float* P = (float*)block;                              // the survivors' re-carved block, src/nbody.cu:496-510
-    float* V = P + 2 * (size_t)n;
-    float* M = V + 2 * (size_t)n;
-    float* R = M + (size_t)n;
-    for (int i = 0; i < n; ++i) {
-        P[2 * i] = st[i].x; P[2 * i + 1] = st[i].y;
-        V[2 * i] = sv[i].x; V[2 * i + 1] = sv[i].y;
-        M[i] = st[i].m;
-        R[i] = st[i].r;
-    }
+    nbody_block_unpack(block, n, NBODY_F32, st, sv);       // the survivors' re-carved block, src/nbody.cu:496-510
     *n_out = n;
     return NBODY_OK;
 }

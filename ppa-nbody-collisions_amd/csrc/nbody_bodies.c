@@ -7,7 +7,7 @@
  */
 #include "nbody.h"
 #include "nbody_error.h"
-#include "nbody_partition.h"
+#include "nbody_screen.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -90,6 +90,54 @@ int nbody_block_compact(void* block, int n, int precision) {
         free(keep);
         return newN;
     }
+}
+
+/* ------------------------------------------------------------------------------------------------------
+ * A block [P|V|M|R] to and from what a context keeps: {x,y,m,r} records and velocities (nbody_screen.h declares
+ * these; internal to the library).  The ONLY place besides the carving above that knows where a block keeps what.
+ * ---------------------------------------------------------------------------------------------------- */
+void* nbody_block_velocity(const void* block, int n, int precision, int i) {
+    const size_t real = precision == NBODY_F64 ? 8 : 4;
+    return (unsigned char*)block + 2 * real * ((size_t)n + (size_t)i);
+}
+
+#define NBODY_DEFINE_PACK(T, SUFFIX, SCREEN_BITS)                                                                  \
+    static int pack_##SUFFIX(const T* P, int n, T* rec, T* vel, uint32_t* tile_bits) {                             \
+        const T *V = P + 2 * (size_t)n, *M = V + 2 * (size_t)n, *R = M + (size_t)n;                                \
+        int summary = 0;                                                                                           \
+        for (int i = 0; i < n; ++i) {                                                                              \
+            const T x = P[2 * i], y = P[2 * i + 1], m = M[i], r = R[i];                                            \
+            rec[4 * (size_t)i] = x; rec[4 * (size_t)i + 1] = y; rec[4 * (size_t)i + 2] = m; rec[4 * (size_t)i + 3] = r; \
+            summary |= SCREEN_BITS;                                                                                \
+            if (tile_bits) {                                                                                       \
+                const uint32_t b = nbody_radius_bits_##SUFFIX(r);                                                  \
+                if (b > tile_bits[i / NBODY_BLOCK]) tile_bits[i / NBODY_BLOCK] = b;                                \
+            }                                                                                                      \
+        }                                                                                                          \
+        if (vel && n > 0) memcpy(vel, V, 2 * sizeof(T) * (size_t)n);                                               \
+        return summary;                                                                                            \
+    }                                                                                                              \
+    static void unpack_##SUFFIX(T* P, int n, const T* rec, const T* vel) {                                         \
+        T *V = P + 2 * (size_t)n, *M = V + 2 * (size_t)n, *R = M + (size_t)n;                                      \
+        for (int i = 0; i < n; ++i) {                                                                              \
+            P[2 * i] = rec[4 * (size_t)i]; P[2 * i + 1] = rec[4 * (size_t)i + 1];                                  \
+            M[i] = rec[4 * (size_t)i + 2]; R[i] = rec[4 * (size_t)i + 3];                                          \
+        }                                                                                                          \
+        if (vel && n > 0) memcpy(V, vel, 2 * sizeof(T) * (size_t)n);                                               \
+    }
+NBODY_DEFINE_PACK(float, f32, nbody_screen_bits_f32(x, y, m, r))
+NBODY_DEFINE_PACK(double, f64, nbody_screen_bits_f64(x, y, r))
+#undef NBODY_DEFINE_PACK
+
+int nbody_block_pack(const void* block, int n, int precision, void* rec, void* vel, uint32_t* tile_bits, int n_tiles) {
+    if (tile_bits) memset(tile_bits, 0, sizeof(uint32_t) * (size_t)n_tiles);
+    return precision == NBODY_F64 ? pack_f64((const double*)block, n, (double*)rec, (double*)vel, tile_bits)
+                                  : pack_f32((const float*)block, n, (float*)rec, (float*)vel, tile_bits);
+}
+
+void nbody_block_unpack(void* block, int n, int precision, const void* rec, const void* vel) {
+    if (precision == NBODY_F64) unpack_f64((double*)block, n, (const double*)rec, (const double*)vel);
+    else unpack_f32((float*)block, n, (const float*)rec, (const float*)vel);
 }
 
 /* ------------------------------------------------------------------------------------------------------

@@ -229,9 +229,6 @@ int ring_spin_limit() {                                    // read when a contex
     return v > 0 && v < (1l << 30) ? (int)v : (1 << 24);
 }
 
-inline bool not_plus_zero_host(float x) { uint32_t u; memcpy(&u, &x, 4); return u != 0; }
-inline bool not_plus_zero_host(double x) { uint64_t u; memcpy(&u, &x, 8); return u != 0; }
-
 template <typename T>
 StepParams<T> make_params(const nbody_ctx_desc& d, int spin_limit = 1 << 24) {
     return nbk::make_params<T>(d.timestep, d.growthRate, d.fieldWidth, d.fieldHeight, d.semantics, spin_limit);
@@ -311,6 +308,14 @@ int read_meta(nbody_ctx* c) {
 //                 31,32 v3 K = 1 with 256-thread workgroups, registers sized for 4 / 2 waves per SIMD |
 //                 50,52,54 ring of waves with 2x8, 4x4, 1x8 (rings x waves) per workgroup; 53,55,56,58,59 its tuning forms |
 //                 60-63 the persistent 4x4 form | 70 solo waves, one-shot; 71 persistent; 72 with one-tile items
+// A FORM is one of these numbers other than 0: what resolve_form (below) makes of a context's kernel_variant, every
+// fall-through taken.  launch_forces and nbody_force_kernel_name both go by the form, never by kernel_variant.
+//
+// Workgroups of a force launch cover every reference block of the own range, which starts on a block boundary
+// (nbody_own_range_of).  The body count only shrinks between syncs, so the host-side upper bound is safe; the kernel takes
+// the exact range from the device-side Meta and workgroups past it exit at once.
+int force_blocks(const nbody_ctx* c) { return c->own_upper / kTile > 0 ? c->own_upper / kTile : 1; }
+
 // Where a force launch goes: the context's own stream and velocities, or - the reference-shaped launch through the
 // workspace context - the caller's stream and the velocities where they lie in the caller's block.
 struct LaunchTarget {
@@ -318,6 +323,8 @@ struct LaunchTarget {
     const void* vown;
 };
 LaunchTarget own_target(const nbody_ctx* c) { return LaunchTarget{c->stream, c->Vown}; }
+
+int resolve_form(const nbody_ctx* c, bool log, int nblocks);   // below, with what it decides by
 
 template <typename T>
 void launch_forces(nbody_ctx* c, const StepParams<T>& p, int nblocks, bool log, LaunchTarget to);
@@ -328,7 +335,7 @@ void launch_forces(nbody_ctx* c, const StepParams<T>& p, int nblocks, bool log, 
 
 template <>
 void launch_forces<double>(nbody_ctx* c, const StepParams<double>& p, int nblocks, bool log, LaunchTarget to) {
-    if (c->desc.kernel_variant == 1) {                     // general kernel: compiler IEEE sqrt / divide per pair
+    if (resolve_form(c, log, nblocks) == 1) {              // general kernel: compiler IEEE sqrt / divide per pair
         if (log) hipLaunchKernelGGL((forces_v1<double, true>), dim3(nblocks), dim3(kTile), 0, to.stream, NB_FORCES_ARGS(double));
         else hipLaunchKernelGGL((forces_v1<double, false>), dim3(nblocks), dim3(kTile), 0, to.stream, NB_FORCES_ARGS(double));
         return;
@@ -392,8 +399,8 @@ void launch_ring(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log
 // there are ring slots - cut into 32 segments, because only near the end does a CU that is ahead find work to take over
 // (measured on MI355X at N = 262144, profiles/ring_queue_probe.txt: the last 1024 rings in 12 / 24 / 32 / 48 / 96 segments
 // -0.09 / -0.2 / -0.25 / -0.23 / -0.15 ms of 29.2; the last 1536 in 32: -0.20; the last 512 in 24: +0.14; every walk in 16:
-// -0.03).  Returns false where that does not apply - fewer than two rounds of rings, so that a segment would be a large
-// part of the launch -: the caller launches the one-shot form.
+// -0.03).  It does not apply with fewer than two rounds of rings - a segment would be a large part of the launch -:
+// ring_queue_slots is 0 there, and resolve_form never hands such a launch to this form.
 constexpr int kQueueSegments = 32;
 int ring_queue_slots(const nbody_ctx* c, int nblocks) {    // ring slots of the persistent launch, 0 where it does not apply
     const int rings = nblocks * 2;
@@ -401,12 +408,10 @@ int ring_queue_slots(const nbody_ctx* c, int nblocks) {    // ring slots of the 
     return rings < 2 * slots || rings > c->q_rings_cap ? 0 : slots;
 }
 template <bool kProbe>
-bool launch_ring_queue(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to) {
-    const int slots = ring_queue_slots(c, nblocks);
-    if (slots == 0) return false;
+void launch_ring_queue(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to) {
     const int tiles = c->n_upper / kTile > 0 ? c->n_upper / kTile : 1;
-    launch_ring<4, 32, 8, kProbe, 4, true>(c, p, nblocks, log, to, slots, (tiles + kQueueSegments - 1) / kQueueSegments);
-    return true;
+    launch_ring<4, 32, 8, kProbe, 4, true>(c, p, nblocks, log, to, ring_queue_slots(c, nblocks),
+                                           (tiles + kQueueSegments - 1) / kQueueSegments);
 }
 // The SOLO form: one wave per 64 bodies takes every turn of its walk - no hand-off, no poll -, 16 such waves per workgroup.
 // Its persistent form cuts EVERY walk - all walks start together and last the whole launch -: the last eighth of the tiles
@@ -422,9 +427,56 @@ bool ring_solo_applies(const nbody_ctx* c, bool log, int nblocks) {
 // The solo launches are DEFINED at the end of this file: their kernels are then instantiated last and the code object keeps
 // every other kernel where it was (form 70 one-shot, 71 persistent with the cut above, 72 persistent with one-tile items).
 void launch_ring_solo(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to, int form);
+
+// From (context, event log on / off, block count) to the form that runs: every fall-through is taken HERE, and
+// launch_forces and nbody_force_kernel_name both go by the answer.
+// The automatic choice is by how many bodies this rank owns, i.e. how many ordered chains there are to fill the chip with
+// (measured on MI355X with csrc/tune/ring_probe.py, profiles/r02_ring_*):
+//   one wave per wave slot, exactly, and no event log: the solo form (ring_solo_applies)
+//   >= 48k bodies : ring kernel, workgroups of 4 rings x 4 waves (256 bodies): 32.2 ms at 262144 own bodies
+//                   (one lane per body: 33.6), 16.6 / 8.4 ms at 131072 / 65536 (18.5 / 10.2); from two rounds of rings
+//                   on (131072 own bodies on 256 CUs) in its persistent form (launch_ring_queue)
+//   >= 24k bodies : ring kernel, workgroups of 2 rings x 8 waves (128 bodies): fills the chip with half the bodies
+//                   (4.35 ms at 32768 own bodies of 262144; 4 x 4: 5.4)
+//   below         : ring kernel, one ring of 8 waves per workgroup: twice the workgroups to spread over the CUs
+//                   (0.21 ms at N = 16384; 2 x 8: 0.29; the producer/consumer kernel of round 1: 0.31)
+// Poll interval of the hand-off wait: s_sleep 8 (512 cycles) where the launch is bound by evaluation - a poll takes
+// issue slots from the waves that evaluate: -0.5 ... -1 % against s_sleep 2 -, s_sleep 2 for the small launches, which
+// are bound by the chain (N = 16384: 0.185 ms; with s_sleep 8: 0.218).
+int resolve_form(const nbody_ctx* c, bool log, int nblocks) {
+    const int v = c->desc.kernel_variant;
+    if (c->desc.precision == NBODY_F64) return v == 1 ? 1 : 31;            // the general kernel, or v3 (forces_v3w_f64)
+    switch (v) {
+        case 60: case 63: if (ring_queue_slots(c, nblocks) == 0) break;    // where the persistent form does not apply: automatic
+            [[fallthrough]];
+        case 1: case 11: case 12: case 14: case 18: case 31: case 32: case 50: case 52: case 53: case 54: case 55: case 56:
+        case 58: case 59: case 61: case 62: case 70: case 71: case 72: return v;
+        default: break;
+    }
+    if (ring_solo_applies(c, log, nblocks)) return 71;
+    if (c->own_upper >= 49152) return ring_queue_slots(c, nblocks) != 0 ? 60 : 52;
+    if (c->own_upper >= 24576) return 50;
+    return 54;
+}
+const char* form_name(int form) {                          // fp32; bench.py prints it as the kernel it measured
+    switch (form) {
+        case 1: return "forces_v1<float>";
+        case 11: case 12: case 14: case 18: return "forces_v3_f32";
+        case 31: case 32: return "forces_v3w_f32";
+        case 50: case 55: case 56: case 58: return "forces_ring_f32 (2 rings x 8 waves per workgroup)";
+        case 52: case 59: return "forces_ring_f32 (4 rings x 4 waves per workgroup)";
+        case 60: case 61: case 62: case 63: return "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)";
+        case 53: return "forces_ring_f32 (2 rings x 8 waves, 16-position turns)";
+        case 54: return "forces_ring_f32 (1 ring x 8 waves per workgroup)";
+        case 70: return "forces_ring_f32 (16 solo waves per workgroup)";
+        default: return "forces_ring_f32 (16 solo waves per workgroup, persistent)";   // 71, 72
+    }
+}
+
 template <>
 void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks, bool log, LaunchTarget to) {
-    switch (c->desc.kernel_variant) {
+    const int form = resolve_form(c, log, nblocks);
+    switch (form) {                                         // (the order in which the kernels are first named is the code object's)
         case 1:
             if (log) hipLaunchKernelGGL((forces_v1<float, true>), dim3(nblocks), dim3(kTile), 0, to.stream, NB_FORCES_ARGS(float));
             else hipLaunchKernelGGL((forces_v1<float, false>), dim3(nblocks), dim3(kTile), 0, to.stream, NB_FORCES_ARGS(float));
@@ -443,31 +495,12 @@ void launch_forces<float>(nbody_ctx* c, const StepParams<float>& p, int nblocks,
         case 56: launch_ring<8, 32, 4, false, 2>(c, p, nblocks, log, to); return;   // tuning: 2 x 8 with a 256-cycle poll interval
         case 58: launch_ring<8, 32, 8, true, 2>(c, p, nblocks, log, to); return;    // tuning: in-kernel phase stamps
         case 59: launch_ring<4, 32, 8, true, 4>(c, p, nblocks, log, to); return;    // tuning: the same stamps at 4 x 4
-        case 60: if (launch_ring_queue<false>(c, p, nblocks, log, to)) return; break;  // 4 x 4 persistent where it applies
+        case 60: launch_ring_queue<false>(c, p, nblocks, log, to); return;          // 4 x 4 persistent
         case 61: launch_ring<4, 32, 8, false, 4, true>(c, p, nblocks, log, to, nblocks * 2, 1); return;   // ... every walk in segments of 1 tile
         case 62: launch_ring<4, 32, 8, false, 4, true>(c, p, nblocks, log, to, nblocks * 2, 3); return;   // ... of 3 tiles
-        case 63: if (launch_ring_queue<true>(c, p, nblocks, log, to)) return; break;   // tuning: stamps of the persistent form
-        case 70: case 71: case 72: launch_ring_solo(c, p, nblocks, log, to, c->desc.kernel_variant); return;   // the solo form
-        default: break;
+        case 63: launch_ring_queue<true>(c, p, nblocks, log, to); return;           // tuning: stamps of the persistent form
+        default: launch_ring_solo(c, p, nblocks, log, to, form); return;            // 70, 71, 72: the solo form
     }
-    // default: chosen by how many bodies this rank owns, i.e. how many ordered chains there are to fill the chip with
-    // (measured on MI355X with csrc/tune/ring_probe.py, profiles/r02_ring_*):
-    //   one wave per wave slot, exactly, and no event log: the solo form (ring_solo_applies)
-    //   >= 48k bodies : ring kernel, workgroups of 4 rings x 4 waves (256 bodies): 32.2 ms at 262144 own bodies
-    //                   (one lane per body: 33.6), 16.6 / 8.4 ms at 131072 / 65536 (18.5 / 10.2); from two rounds of rings
-    //                   on (131072 own bodies on 256 CUs) in its persistent form (launch_ring_queue)
-    //   >= 24k bodies : ring kernel, workgroups of 2 rings x 8 waves (128 bodies): fills the chip with half the bodies
-    //                   (4.35 ms at 32768 own bodies of 262144; 4 x 4: 5.4)
-    //   below         : ring kernel, one ring of 8 waves per workgroup: twice the workgroups to spread over the CUs
-    //                   (0.21 ms at N = 16384; 2 x 8: 0.29; the producer/consumer kernel of round 1: 0.31)
-    // Poll interval of the hand-off wait: s_sleep 8 (512 cycles) where the launch is bound by evaluation - a poll takes
-    // issue slots from the waves that evaluate: -0.5 ... -1 % against s_sleep 2 -, s_sleep 2 for the small launches, which
-    // are bound by the chain (N = 16384: 0.185 ms; with s_sleep 8: 0.218).
-    if (ring_solo_applies(c, log, nblocks)) launch_ring_solo(c, p, nblocks, log, to, 71);
-    else if (c->own_upper >= 49152) {
-        if (!launch_ring_queue<false>(c, p, nblocks, log, to)) launch_ring<4, 32, 8, false, 4>(c, p, nblocks, log, to);
-    } else if (c->own_upper >= 24576) launch_ring<8, 32, 8, false, 2>(c, p, nblocks, log, to);
-    else launch_ring<8, 32, 2, false, 1>(c, p, nblocks, log, to);
 }
 
 template <typename T>
@@ -511,11 +544,7 @@ int launch_compute(nbody_ctx* c) {
         int rc = refresh_bound(c);
         if (rc != NBODY_OK) return rc;
     }
-    // Workgroups cover every reference block of the own range, which starts on a block boundary (nbody_own_range_of).  The
-    // body count only shrinks between syncs, so the host-side upper bound is safe; the kernel takes the exact range
-    // from the device-side Meta and workgroups past it exit at once.
-    const int nblocks = c->own_upper / kTile > 0 ? c->own_upper / kTile : 1;
-    int rc = launch_force_kernel<T>(c, p, nblocks);
+    int rc = launch_force_kernel<T>(c, p, force_blocks(c));
     if (rc != NBODY_OK) return rc;
     const int nblk = (c->own_upper + kCompactBlock - 1) / kCompactBlock > 0
                          ? (c->own_upper + kCompactBlock - 1) / kCompactBlock : 1;
@@ -917,53 +946,20 @@ int nbody_upload(nbody_ctx* c, const void* block, int n) {
     int lo = 0, cnt = 0;
     nbody_own_range_of(n, c->desc.rank, c->desc.world, &lo, &cnt);
     if (cnt > c->cap_own) return nbody_fail(NBODY_ERR_CAPACITY, "own range %d > own capacity %d", cnt, c->cap_own);
-    // pack [P|V|M|R] (src/nbody.cu:66-77) into {x,y,m,r} records; Meta::summary as unpack_slots computes it per step
-    int summary = 0;
-    if (c->desc.precision == NBODY_F64) {
-        const double* P = (const double*)block;
-        const double* V = P + 2 * (size_t)n;
-        const double* M = V + 2 * (size_t)n;
-        const double* R = M + (size_t)n;
-        Rec<double>* st = (Rec<double>*)c->h_stage;
-        for (int i = 0; i < n; ++i) {
-            st[i] = Rec<double>{P[2 * i], P[2 * i + 1], M[i], R[i]};
-            const bool bounded = fabs(st[i].x) < FastDomain<double>::coord && fabs(st[i].y) < FastDomain<double>::coord;
-            summary |= (bounded ? 0 : kSummaryUnbounded) | (not_plus_zero_host(R[i]) ? kSummaryRadius : 0);
-        }
-        HIP_TRY(hipMemcpyAsync(c->J, st, (size_t)n * sizeof(Rec<double>), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->Vown, V + 2 * (size_t)lo, (size_t)cnt * 16, hipMemcpyHostToDevice, c->stream));
-    } else {
-        const float* P = (const float*)block;
-        const float* V = P + 2 * (size_t)n;
-        const float* M = V + 2 * (size_t)n;
-        const float* R = M + (size_t)n;
-        Rec<float>* st = (Rec<float>*)c->h_stage;
-        for (int i = 0; i < n; ++i) {
-            st[i] = Rec<float>{P[2 * i], P[2 * i + 1], M[i], R[i]};
-            const bool bounded = fabsf(st[i].x) < FastDomain<float>::coord && fabsf(st[i].y) < FastDomain<float>::coord;
-            const bool small = !(fabsf(st[i].x) >= kCoordFloor && fabsf(st[i].y) >= kCoordFloor);
-            summary |= (bounded ? 0 : kSummaryUnbounded) | (not_plus_zero_host(R[i]) ? kSummaryRadius : 0) |
-                       (small ? kSummarySmall : 0) | (fabsf(st[i].m) < kMassBound ? 0 : kSummaryMass);
-        }
-        HIP_TRY(hipMemcpyAsync(c->J, st, (size_t)n * sizeof(Rec<float>), hipMemcpyHostToDevice, c->stream));
-        if (n > 0) hipLaunchKernelGGL(records_to_tiles_f32, dim3((n + 255) / 256), dim3(256), 0, c->stream,
-                                      (const Rec<float>*)c->J, n, c->Jt);
-        HIP_TRY(hipMemcpyAsync(c->Vown, V + 2 * (size_t)lo, (size_t)cnt * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    {   // per-tile radius bounds, as unpack_slots maintains them from then on
-        std::vector<unsigned> tr((size_t)c->n_tiles, 0u);
-        for (int i = 0; i < n; ++i) {
-            const float ar = c->desc.precision == NBODY_F64 ? (float)fabs(((const double*)block)[5 * (size_t)n + i])
-                                                            : fabsf(((const float*)block)[5 * (size_t)n + i]);
-            unsigned bits;
-            memcpy(&bits, &ar, 4);
-            if (ar == ar && bits > tr[i / kTile]) tr[i / kTile] = bits;
-        }
-        HIP_TRY(hipMemcpyAsync(c->tile_rmax, tr.data(), sizeof(unsigned) * tr.size(), hipMemcpyHostToDevice, c->stream));
+    // [P|V|M|R] (src/nbody.cu:66-77) into {x,y,m,r} records, with Meta::summary and the per-tile radius bounds that
+    // unpack_slots maintains from then on: one pass, one rule (nbody_block_pack, csrc/nbody_screen.h)
+    {
+        std::vector<uint32_t> tr((size_t)c->n_tiles);
+        const int summary = nbody_block_pack(block, n, c->desc.precision, c->h_stage, nullptr, tr.data(), c->n_tiles);
+        *c->h_meta = meta_at_upload(n, lo, cnt, summary);
+        HIP_TRY(hipMemcpyAsync(c->J, c->h_stage, (size_t)n * c->rec_bytes, hipMemcpyHostToDevice, c->stream));
+        if (c->Jt != nullptr && n > 0)                     // fp32 contexts
+            hipLaunchKernelGGL(records_to_tiles_f32, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const Rec<float>*)c->J, n, c->Jt);
+        HIP_TRY(hipMemcpyAsync(c->Vown, nbody_block_velocity(block, n, c->desc.precision, lo), (size_t)cnt * 2 * c->real_bytes,
+                               hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->tile_rmax, tr.data(), sizeof(uint32_t) * tr.size(), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));   // tr goes out of scope
     }
-    c->h_meta->n = n; c->h_meta->lo = lo; c->h_meta->cnt = cnt; c->h_meta->step = 0; c->h_meta->n_prev = n;
-    c->h_meta->summary = summary; c->h_meta->pad[0] = c->h_meta->pad[1] = 0;
     *c->h_meta_async = *c->h_meta;
     HIP_TRY(hipMemcpyAsync(c->meta, c->h_meta, sizeof(Meta), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(Counters), c->stream));
@@ -1215,19 +1211,11 @@ int nbody_download(nbody_ctx* c, void* block, int* n_out) {
     const size_t rb = c->real_bytes;
     HIP_TRY(hipMemcpyAsync(c->h_stage, c->J, (size_t)n * c->rec_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    unsigned char* P = (unsigned char*)block;
-    unsigned char* V = P + 2 * rb * (size_t)n;
-    unsigned char* M = V + 2 * rb * (size_t)n;
-    unsigned char* R = M + rb * (size_t)n;
-    const unsigned char* st = (const unsigned char*)c->h_stage;
-    for (int i = 0; i < n; ++i) {
-        memcpy(P + 2 * rb * i, st + c->rec_bytes * i, 2 * rb);
-        memcpy(M + rb * i, st + c->rec_bytes * i + 2 * rb, rb);
-        memcpy(R + rb * i, st + c->rec_bytes * i + 3 * rb, rb);
-    }
+    nbody_block_unpack(block, n, c->desc.precision, c->h_stage, nullptr);
+    auto vel_of = [&](int i) { return (unsigned char*)nbody_block_velocity(block, n, c->desc.precision, i); };
     // velocities: own range from this rank; other ranks' through the same all-gather interface as the step's exchange
     if (c->desc.world == 1 && !c->comm) {
-        HIP_TRY(hipMemcpyAsync(V, c->Vown, (size_t)cnt * 2 * rb, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(vel_of(0), c->Vown, (size_t)cnt * 2 * rb, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     } else if (c->comm || c->peers) {
         // padded all-gather of the own velocities into the slot receive area: own_upper_of(n) vec2 entries per rank (n is
@@ -1250,13 +1238,13 @@ int nbody_download(nbody_ctx* c, void* block, int* n_out) {
                 (long long)h_all[g].lo + h_all[g].cnt > n)
                 return nbody_fail(NBODY_ERR_STATE, "rank %d reports range [%d, +%d) of %d bodies, this rank has %d bodies",
                                   g, h_all[g].lo, h_all[g].cnt, h_all[g].n, n);
-            HIP_TRY(hipMemcpy(V + 2 * rb * (size_t)h_all[g].lo, c->gather + (size_t)g * vbytes,
+            HIP_TRY(hipMemcpy(vel_of(h_all[g].lo), c->gather + (size_t)g * vbytes,
                               (size_t)h_all[g].cnt * 2 * rb, hipMemcpyDeviceToHost));
         }
     } else {
         // a group context on its own: only the own range lives here; nbody_group_download assembles the whole state
-        memset(V, 0, 2 * rb * (size_t)n);
-        HIP_TRY(hipMemcpyAsync(V + 2 * rb * (size_t)lo, c->Vown, (size_t)cnt * 2 * rb, hipMemcpyDeviceToHost,
+        memset(vel_of(0), 0, 2 * rb * (size_t)n);
+        HIP_TRY(hipMemcpyAsync(vel_of(lo), c->Vown, (size_t)cnt * 2 * rb, hipMemcpyDeviceToHost,
                                c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
@@ -1448,8 +1436,8 @@ int nbody_launch_compute_forces_f32(void* d_bodyData, float* d_updM, float* d_up
         c->own_upper = c->n_upper = numBodies;             // (kernel choice by size, as in a context of this many bodies)
         StepParams<float> pr = p;
         pr.spin_limit = c->spin_limit;
-        launch_forces<float>(c, pr, numBodies / kTile > 0 ? numBodies / kTile : 1, false,
-                             LaunchTarget{s, (const float*)d_bodyData + 2 * (size_t)numBodies});
+        launch_forces<float>(c, pr, force_blocks(c), false,
+                             LaunchTarget{s, nbody_block_velocity(d_bodyData, numBodies, NBODY_F32, 0)});
         const int n_active = numBodies < kTile ? numBodies : (numBodies / kTile) * kTile;
         hipLaunchKernelGGL(ref_layout_finish_f32, dim3((n_active + 255) / 256), dim3(256), 0, s, d_bodyData, d_updM, d_updR,
                            numBodies, n_active, (const Rec<float>*)c->S_J, (const Vec2<float>*)c->S_V);
@@ -1480,39 +1468,16 @@ int nbody_launch_move_bodies_f32(void* d_bodyData, const float* d_updM, const fl
 
 const char* nbody_force_kernel_name(nbody_ctx* c) {
     if (!c) return "";
-    if (c->desc.precision == NBODY_F64)
-        return c->desc.kernel_variant == 1 ? "forces_v1<double>" : "forces_v3w_f64";
-    switch (c->desc.kernel_variant) {
-        case 1: return "forces_v1<float>";
-        case 11: case 12: case 14: case 18: return "forces_v3_f32";
-        case 31: case 32: return "forces_v3w_f32";
-        case 50: case 55: case 56: case 58: return "forces_ring_f32 (2 rings x 8 waves per workgroup)";
-        case 52: case 59: return "forces_ring_f32 (4 rings x 4 waves per workgroup)";
-        case 61: case 62: return "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)";
-        case 60: case 63:
-            if (ring_queue_slots(c, c->own_upper / kTile > 0 ? c->own_upper / kTile : 1) != 0)
-                return "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)";
-            break;
-        case 53: return "forces_ring_f32 (2 rings x 8 waves, 16-position turns)";
-        case 54: return "forces_ring_f32 (1 ring x 8 waves per workgroup)";
-        case 70: return "forces_ring_f32 (16 solo waves per workgroup)";
-        case 71: case 72: return "forces_ring_f32 (16 solo waves per workgroup, persistent)";
-        default: break;
-    }
-    if (ring_solo_applies(c, (c->desc.flags & NBODY_FLAG_RECORD_EVENTS) != 0, c->own_upper / kTile > 0 ? c->own_upper / kTile : 1))
-        return "forces_ring_f32 (16 solo waves per workgroup, persistent)";
-    if (c->own_upper >= 49152)
-        return ring_queue_slots(c, c->own_upper / kTile) != 0 ? "forces_ring_f32 (4 rings x 4 waves per workgroup, persistent)"
-                                                              : "forces_ring_f32 (4 rings x 4 waves per workgroup)";
-    if (c->own_upper >= 24576) return "forces_ring_f32 (2 rings x 8 waves per workgroup)";
-    return "forces_ring_f32 (1 ring x 8 waves per workgroup)";
+    const int form = resolve_form(c, (c->desc.flags & NBODY_FLAG_RECORD_EVENTS) != 0, force_blocks(c));
+    if (c->desc.precision == NBODY_F64) return form == 1 ? "forces_v1<double>" : "forces_v3w_f64";
+    return form_name(form);
 }
 
 int nbody_debug_force_only(nbody_ctx* c, int reps) {
     if (!c || reps < 0) return nbody_fail(NBODY_ERR_INVALID, "nbody_debug_force_only: bad argument");
     if (!c->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_debug_force_only before nbody_upload");
     HIP_TRY(hipSetDevice(c->desc.device));
-    const int nblocks = c->own_upper / kTile > 0 ? c->own_upper / kTile : 1;
+    const int nblocks = force_blocks(c);
     for (int r = 0; r < reps; ++r) {
         int rc = c->desc.precision == NBODY_F64
                      ? launch_force_kernel<double>(c, make_params<double>(c->desc, c->spin_limit), nblocks)

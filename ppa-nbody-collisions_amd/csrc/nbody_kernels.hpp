@@ -22,6 +22,7 @@
 
 #include "nbody.h"
 #include "nbody_partition.h"
+#include "nbody_screen.h"
 
 #pragma clang fp contract(off)
 
@@ -53,13 +54,14 @@ struct Meta {
     int cnt;      // number of bodies owned by this rank
     int step;     // step counter since upload
     int n_prev;   // body count before the last step's compaction (the reference renders with its block count)
-    int summary;  // of the replica: bit 0 some coordinate is not below kCoordBound in magnitude (or NaN), bit 1 some
-                  // radius is not +0, bit 2 some coordinate is below kCoordFloor in magnitude (zero included), bit 3 some
-                  // mass is not below kMassBound in magnitude (or NaN).  OR-ed together by unpack_slots (cleared by
+    int summary;  // of the replica: the bits of csrc/nbody_screen.h.  OR-ed together by unpack_slots (cleared by
                   // compact_count), set by nbody_upload.
     int pad[2];
 };
-constexpr int kSummaryUnbounded = 1, kSummaryRadius = 2, kSummarySmall = 4, kSummaryMass = 8;
+constexpr int kSummaryUnbounded = NBODY_SUMMARY_UNBOUNDED, kSummaryRadius = NBODY_SUMMARY_RADIUS,
+              kSummarySmall = NBODY_SUMMARY_SMALL, kSummaryMass = NBODY_SUMMARY_MASS;
+// Meta of a state that was just uploaded (host side: nbody_upload, nbody_batch_upload)
+inline Meta meta_at_upload(int n, int lo, int cnt, int summary) { return Meta{n, lo, cnt, 0, n, summary, {0, 0}}; }
 
 struct Event { int32_t step, i, j, kind; };
 
@@ -324,22 +326,27 @@ __global__ __launch_bounds__(kTile) void forces_v1(const Rec<T>* __restrict__ J,
 // ---------------------------------------------------------------------------------------------------------
 constexpr float kFastLo = 0x1p-80f;        // lower edge of the proved domain (and the flag margin)
 constexpr float kFastHi = 0x1p80f;         // upper edge of the proved domain
-constexpr float kCoordBound = 0x1p38f;     // |x|,|y| < 2^38 for both bodies  =>  d2 <= 2^79 < kFastHi
+constexpr float kCoordBound = NBODY_COORD_BOUND_F32;     // |x|,|y| < 2^38 for both bodies  =>  d2 <= 2^79 < kFastHi
 // |x|,|y| >= 2^-16 for both bodies  =>  a coordinate difference is 0 or at least 2^-39 (the spacing of fp32 at 2^-16), so
 // d2 is exactly 0 or at least 2^-78: with all radii +0 the only pairs outside the fast chain's domain - and the only
 // collisions - are COINCIDENT bodies, and those turn their term into NaN (v_rsq_f32(0) = inf, 0 * inf = NaN): the ring
 // kernel then needs no screen per pair at all, it looks at the sum after the turn's adds (see its turn loop).
-constexpr float kCoordFloor = 0x1p-16f;
+constexpr float kCoordFloor = NBODY_COORD_FLOOR_F32;
 // That look at the sum also fires for a sum that is NaN for any other reason, and a lane whose sum is NaN takes the exact
 // path in every turn from then on: right, but slow.  A NaN or infinite mass would do that to every body at once, so the
 // NaN-sum screen is only used while every mass of the replica is finite and below 2^90 (a term then only overflows for
 // bodies closer than the coordinates' spacing allows at ordinary magnitudes).
-constexpr float kMassBound = 0x1p90f;
-__device__ __forceinline__ int coord_summary(float x, float y, float m) {
-    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
-    return ((ax < kCoordBound && ay < kCoordBound) ? 0 : kSummaryUnbounded) |
-           ((ax >= kCoordFloor && ay >= kCoordFloor) ? 0 : kSummarySmall) |
-           (__builtin_fabsf(m) < kMassBound ? 0 : kSummaryMass);
+constexpr float kMassBound = NBODY_MASS_BOUND_F32;
+// The per-body rule itself is csrc/nbody_screen.h's, one function per kind of context; and what a wave publishes of it.
+__device__ __forceinline__ int screen_bits(const Rec<float>& r) { return nbody_screen_bits_f32(r.x, r.y, r.m, r.r); }
+__device__ __forceinline__ int screen_bits(const Rec<double>& r) { return nbody_screen_bits_f64(r.x, r.y, r.r); }
+__device__ __forceinline__ unsigned radius_bits(float r) { return nbody_radius_bits_f32(r); }
+__device__ __forceinline__ unsigned radius_bits(double r) { return nbody_radius_bits_f64(r); }
+__device__ __forceinline__ int wave_summary(int bits) {    // OR over the wave, one ballot per bit
+    return (__ballot(bits & kSummaryUnbounded) != 0ull ? kSummaryUnbounded : 0) |
+           (__ballot(bits & kSummaryRadius) != 0ull ? kSummaryRadius : 0) |
+           (__ballot(bits & kSummarySmall) != 0ull ? kSummarySmall : 0) |
+           (__ballot(bits & kSummaryMass) != 0ull ? kSummaryMass : 0);
 }
 
 struct FastChain { float d, inv; };
@@ -479,7 +486,7 @@ template <typename T> struct FastDomain;
 // the format there, so d2 is exactly 0 or above `lo` (fp32: 2^-39 squared = 2^-78; fp64: 2^-242 squared = 2^-484): with
 // all radii +0 the only pairs outside the fast domain are coincident bodies (see kCoordFloor)
 template <> struct FastDomain<float> { static constexpr float lo = kFastLo, coord = kCoordBound, floor = kCoordFloor; };
-template <> struct FastDomain<double> { static constexpr double lo = 0x1p-500, coord = 0x1p249, floor = 0x1p-190; };
+template <> struct FastDomain<double> { static constexpr double lo = 0x1p-500, coord = NBODY_COORD_BOUND_F64, floor = 0x1p-190; };
 
 __device__ __forceinline__ float abs_(float x) { return __builtin_fabsf(x); }
 __device__ __forceinline__ double abs_(double x) { return __builtin_fabs(x); }
@@ -1905,11 +1912,8 @@ __global__ __launch_bounds__(256) void unpack_slots(const unsigned char* __restr
         J[i] = r;
         if (Jt != nullptr) store_tiled(Jt, i, r);          // fp32 contexts
         if (i >= lo && i < lo + cnt) Vown[i - lo] = vels[q];
-        const bool bounded = abs_(r.x) < FastDomain<T>::coord && abs_(r.y) < FastDomain<T>::coord;
-        bits = (bounded ? 0 : kSummaryUnbounded) | (not_plus_zero(r.r) ? kSummaryRadius : 0);
-        if (Jt != nullptr) bits |= coord_summary((float)r.x, (float)r.y, (float)r.m) & (kSummarySmall | kSummaryMass);   // fp32 contexts (ring kernel)
-        const float ar = (float)abs_(r.r);
-        rbits = (ar == ar) ? __float_as_uint(ar) : 0u;      // a NaN radius never collides (the predicate is false): skipped
+        bits = screen_bits(r);
+        rbits = radius_bits(r.r);
     }
     // Largest |radius| per aligned 128-body tile of the new replica, for the ring kernel's collision screen.  The 64
     // lanes of a wave hold consecutive bodies, i.e. at most two tiles: one wave reduction per tile, two atomics per wave.
@@ -1928,10 +1932,7 @@ __global__ __launch_bounds__(256) void unpack_slots(const unsigned char* __restr
             if (m1 != 0u) atomicMax(&tile_rmax[t0 + 1], m1);
         }
     }
-    const int wave_bits = (__ballot(bits & kSummaryUnbounded) != 0ull ? kSummaryUnbounded : 0) |
-                          (__ballot(bits & kSummaryRadius) != 0ull ? kSummaryRadius : 0) |
-                          (__ballot(bits & kSummarySmall) != 0ull ? kSummarySmall : 0) |
-                          (__ballot(bits & kSummaryMass) != 0ull ? kSummaryMass : 0);
+    const int wave_bits = wave_summary(bits);
     if (wave_bits != 0 && (threadIdx.x & (kWave - 1)) == 0) atomicOr(&meta->summary, wave_bits);
     if (g == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
         // every block has read meta-independent data only, so the in-place update is race-free
@@ -2007,7 +2008,7 @@ __global__ __launch_bounds__(kTile) void ref_layout_forces_f32(void* bodyData, f
 
 // The reference-shaped launch through the ring kernel (nbody_launch_compute_forces_f32 with the reference's own block
 // count): the device block [P|V|M|R] is packed into the {x,y,m,r} replica of a process-wide workspace - with Meta and
-// the per-tile radius bounds exactly as nbody_upload / unpack_slots produce them -, the ring kernel reads the
+// the per-tile radius bounds by the rule of nbody_upload and unpack_slots (csrc/nbody_screen.h) -, the ring kernel reads the
 // velocities where they lie in the block, and its staged output is written back in the reference's form:
 // velocities in place, updatedMasses / updatedRadii (src/nbody.cu:245-246,264).  meta and tile_rmax are zeroed before.
 __global__ __launch_bounds__(256) void ref_layout_pack_f32(const void* bodyData, int N, Rec<float>* __restrict__ J,
@@ -2024,18 +2025,14 @@ __global__ __launch_bounds__(256) void ref_layout_pack_f32(const void* bodyData,
         const Rec<float> r{pi.x, pi.y, M[i], R[i]};
         J[i] = r;
         store_tiled(Jt, i, r);
-        bits = coord_summary(r.x, r.y, r.m) | (not_plus_zero(r.r) ? kSummaryRadius : 0);
-        const float ar = abs_(r.r);
-        rbits = (ar == ar) ? __float_as_uint(ar) : 0u;
+        bits = screen_bits(r);
+        rbits = radius_bits(r.r);
     }
     for (int sh = kWave / 2; sh > 0; sh >>= 1) {           // a wave's 64 bodies lie in one aligned 128-body tile
         const unsigned o = __shfl_xor(rbits, sh, kWave);
         rbits = o > rbits ? o : rbits;
     }
-    const int wave_bits = (__ballot(bits & kSummaryUnbounded) != 0ull ? kSummaryUnbounded : 0) |
-                          (__ballot(bits & kSummaryRadius) != 0ull ? kSummaryRadius : 0) |
-                          (__ballot(bits & kSummarySmall) != 0ull ? kSummarySmall : 0) |
-                          (__ballot(bits & kSummaryMass) != 0ull ? kSummaryMass : 0);
+    const int wave_bits = wave_summary(bits);
     if ((threadIdx.x & (kWave - 1)) == 0) {
         if (rbits != 0u) atomicMax(&tile_rmax[i / kTile], rbits);
         if (wave_bits != 0) atomicOr(&meta->summary, wave_bits);

@@ -45,6 +45,9 @@ Lines (fp32, literal, stock configuration with stock radii):
     trc       stepping with 65536 tracers set, from a fresh upload and a fresh set: trc Stepper  ms | us per step
               N = 262144 (8 steps), trc256 StepperBatch 256 x 1024 with 256 tracers in each
               system (500 steps)
+    io...     upload followed by download, the host path of nbody_block_pack / _unpack: io Stepper   ms per round trip
+              N = 262144 fp32, io64 the same in fp64, io256 StepperBatch 256 x 1024 with every
+              system downloaded; the digest is over the downloaded blocks
 A line passes when the candidate's median is not above the parent's median by more than max(the parent's round spread
 (max - min), |control median - parent median|).  Exit status 1 if a line does not pass.
 """
@@ -64,9 +67,10 @@ REPLY_TIMEOUT_S = 240           # a side that does not answer within this is kil
 LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024", "d256x1024", "d64x4096",
          "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256",
          "enc", "enc256", "bin", "bin256", "gpe", "gpe256", "shl", "shlpts", "shl256", "shm", "shmpts", "shm256",
-         "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "trc", "trc256")
+         "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "trc", "trc256", "io", "io64", "io256")
 BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
 STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
+IO = {"io": 20, "io64": 12, "io256": 20}     # round trips per window
 TRACERS = {"trc": 8, "trc256": 500}     # steps per window with M_POINTS tracers set
 ROWS = {"": 3, "pts": 8, "256": 100}    # the row queries' shapes (field_probe.py, neighbor_probe.py): calls per window;
                                         # the tides' too: 51 to 71 ms a call on own rows, 16 to 21 on the points
@@ -190,6 +194,18 @@ class Line:
                 self.unit, m = "ms per step", M_POINTS
             self.reps = self.steps
             self.pts = np.random.default_rng(2).uniform(0, 1, size=(m, 2)) * [cfg.fieldWidth, cfg.fieldHeight]
+        elif name in IO:
+            self.unit, self.reps = "ms per round trip", IO[name]
+            if name == "io256":
+                cfg = nb.stock_config(particleCount=1024)
+                self.bodies = [nb.init_bodies(cfg, seed=1 + s) for s in range(256)]
+                self.st = self.batch = nb.StepperBatch(256, 1024, cfg=cfg)
+            else:
+                precision = nb.F64 if name == "io64" else nb.F32
+                cfg = nb.stock_config(particleCount=N_BIG)
+                self.bodies = nb.init_bodies(cfg, precision, seed=1)
+                self.st = nb.Stepper(cfg, precision=precision)
+            self.st.upload(self.bodies)
         elif name in STEPS:
             shape = name[1:]
             self.steps = 200 if short else STEPS[name]
@@ -229,6 +245,13 @@ class Line:
                 o, ids = (st.download(s), st.ids(s)) if self.batch else (st.download(), st.ids())
                 parts += [b"%d:" % o.numBodies, o.block.tobytes(), ids.tobytes()]
             return seconds, digest_of(parts)
+        if name in IO:
+            t0 = time.perf_counter()
+            for _ in range(self.reps):                                      # both ends synchronise
+                st.upload(self.bodies)
+                got = [st.download(s) for s in range(self.batch.systems)] if self.batch else [st.download()]
+            seconds = time.perf_counter() - t0
+            return seconds, digest_of([p for o in got for p in (b"%d:" % o.numBodies, o.block.tobytes())])
         if name in TRACERS:
             st.upload(self.bodies)
             st.set_tracers(self.pts)                                        # zeroes their counters; synchronises

@@ -6,13 +6,16 @@
  *   driver peek <file>       nbody_state_peek on an arbitrary file
  *   driver state <file> <p>  save / peek / load round trip and refusals through a host-only stand-in context
  *   driver pgm <file>        nbody_write_pgm of a small image
- *   driver partition         nbody_partition over many (n, world): covering, contiguous, block-aligned, level */
+ *   driver partition         nbody_partition over many (n, world): covering, contiguous, block-aligned, level
+ *   driver pack {<file> <p> <n>}  the block of n bodies in <file> through nbody_block_pack / nbody_block_unpack (what an
+ *                            upload and a download do on the host): summary, tile radius bits, FNV-1a of the round trip */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
 #include "nbody.h"
+#include "nbody_screen.h"
 
 /* A host-only stand-in for the device context, so that the state file code (csrc/nbody_state.c) can run under
  * the sanitizers: it keeps one body block in RAM behind the four context entry points that code calls. */
@@ -128,6 +131,38 @@ static int do_blocks(void) {
     return 0;
 }
 
+/* Exactly sized buffers, so that an index past a part of the block or of the records is seen by the sanitizer. */
+static int do_pack(const char* path, int prec, int n) {
+    const size_t bytes = nbody_block_bytes(n, prec), real = prec == NBODY_F64 ? 8 : 4;
+    const int n_tiles = n / NBODY_BLOCK + 2;               /* as a context of this capacity has them */
+    void* in = nbody_block_alloc(n, prec);
+    void* back = nbody_block_alloc(n, prec);
+    unsigned char* rec = (unsigned char*)malloc(4 * real * (size_t)n + 1);
+    unsigned char* vel = (unsigned char*)malloc(2 * real * (size_t)n + 1);
+    uint32_t* tiles = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)n_tiles);
+    FILE* f = fopen(path, "rb");
+    if (!in || !back || !rec || !vel || !tiles || !f || fread(in, 1, bytes, f) != bytes) return 1;
+    fclose(f);
+    memset(tiles, 0xff, sizeof(uint32_t) * (size_t)n_tiles);   /* pack clears them */
+    const int summary = nbody_block_pack(in, n, prec, rec, vel, tiles, n_tiles);
+    if (nbody_block_pack(in, n, prec, rec, NULL, NULL, 0) != summary) return 1;   /* the forms without bounds / velocities */
+    memset(back, 0x5a, bytes);
+    nbody_block_unpack(back, n, prec, rec, NULL);          /* velocities left to the caller: as nbody_download copies them */
+    if (n > 0) memcpy(nbody_block_velocity(back, n, prec, 0), vel, 2 * real * (size_t)n);
+    void* both = nbody_block_alloc(n, prec);
+    if (!both) return 1;
+    nbody_block_unpack(both, n, prec, rec, vel);
+    if (memcmp(both, back, bytes) != 0) return 1;
+    uint64_t h = 0xcbf29ce484222325ULL;
+    for (size_t k = 0; k < bytes; ++k) h = (h ^ ((const unsigned char*)back)[k]) * 0x100000001b3ULL;
+    printf("summary %d hash %016llx tiles", summary, (unsigned long long)h);
+    for (int k = 0; k < n_tiles; ++k) printf(" %08x", (unsigned)tiles[k]);
+    printf("\n");
+    nbody_block_free(in); nbody_block_free(back); nbody_block_free(both);
+    free(rec); free(vel); free(tiles);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !strcmp(argv[1], "parse")) return do_parse(argv[2]);
     if (argc >= 2 && !strcmp(argv[1], "blocks")) return do_blocks();
@@ -142,6 +177,11 @@ int main(int argc, char** argv) {
         unsigned char img[7 * 5];
         for (int i = 0; i < 35; ++i) img[i] = (unsigned char)(i * 7);
         printf("rc=%d\n", nbody_write_pgm(argv[2], img, 7, 5));
+        return 0;
+    }
+    if (argc >= 5 && !strcmp(argv[1], "pack")) {            /* any number of <file> <p> <n>, a line of output each */
+        for (int k = 2; k + 2 < argc; k += 3)
+            if (do_pack(argv[k], atoi(argv[k + 1]), atoi(argv[k + 2])) != 0) { printf("pack failed: %s\n", argv[k]); return 1; }
         return 0;
     }
     if (argc >= 2 && !strcmp(argv[1], "partition")) {
@@ -166,6 +206,6 @@ int main(int argc, char** argv) {
         printf("partition ok (%ld ranges)\n", checked);
         return 0;
     }
-    fprintf(stderr, "usage: driver parse|blocks|peek|pgm|partition ...\n");
+    fprintf(stderr, "usage: driver parse|blocks|peek|pgm|partition|pack ...\n");
     return 2;
 }

@@ -304,6 +304,86 @@ def extreme_bodies(n=2048):
     return b
 
 
+# ---------------------------------------------------------------------------------------------------------
+# planted states: ONE value at ONE index of a calm state, at the edges of every per-body rule
+# ---------------------------------------------------------------------------------------------------------
+PLANT_N = 257                                     # two whole tiles and one body: more than one block, not a multiple of any
+PLANT_INDICES = (0, 63, 64, 127, 128, 255, 256)   # first and last lane of a wave, both sides of a tile edge, the ragged end
+
+
+def planted_values(precision):
+    """[(label, field, value, summary, tiles_changed)]: field is "x" / "y" coordinate, "m" or "r"; summary is what the
+    state must show with that ONE value planted in a calm state (summary 0), WRITTEN DOWN here from the rule's statement
+    in this file's docstring; tiles_changed is how many tile_rmax entries differ from the calm state's (all 0):
+        -0.0 is not +0 (bit 1) but |-0.0| has the bits of 0; a NaN radius is skipped; a denormal, 3.0 and inf are kept;
+        1e-60 (fp64) is not +0 but rounds to 0 as a float."""
+    t = np.float64 if precision == F64 else np.float32
+    below = lambda v: np.nextafter(t(v), t(0))                # the predecessor in magnitude
+    B, F, MB = t(2.0 ** 38), t(2.0 ** -16), t(2.0 ** 90)
+    f32 = precision == F32
+    unb, small, mass = (UNBOUNDED, SMALL, MASS) if f32 else (0, 0, 0)    # what 2^38, 2^-16, 2^90 mean in an fp64 context
+    out = [("+2^38", "c", B, unb, 0), ("-2^38", "c", -B, unb, 0), ("below 2^38", "c", below(B), 0, 0),
+           ("-below 2^38", "c", -below(B), 0, 0), ("2^-16", "c", F, 0, 0), ("below 2^-16", "c", below(F), small, 0),
+           ("+0", "c", t(0.0), small, 0), ("-0", "c", -t(0.0), small, 0), ("nan", "c", t(np.nan), UNBOUNDED | small, 0),
+           ("inf", "c", t(np.inf), UNBOUNDED, 0),
+           ("+2^90", "m", MB, mass, 0), ("-2^90", "m", -MB, mass, 0), ("below 2^90", "m", below(MB), 0, 0),
+           ("nan", "m", t(np.nan), mass, 0), ("inf", "m", t(np.inf), mass, 0),
+           ("-0", "r", -t(0.0), RADIUS, 0), ("denormal", "r", t(1e-42) if f32 else t(5e-324), RADIUS, 1 if f32 else 0),
+           ("-3", "r", t(-3.0), RADIUS, 1), ("nan", "r", t(np.nan), RADIUS, 0), ("inf", "r", t(np.inf), RADIUS, 1)]
+    if not f32:
+        B64 = t(2.0 ** 249)
+        out += [("2^249", "c", B64, UNBOUNDED, 0), ("below 2^249", "c", below(B64), 0, 0),
+                ("1e-60", "r", t(1e-60), RADIUS, 0), ("float denormal", "r", t(1e-42), RADIUS, 1)]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def planted_states(precision=F32):
+    """[dict(name, bodies, index, field, value, summary, tiles_changed)]: every value of planted_values at every index of
+    PLANT_INDICES; coordinates go to x and y in turn."""
+    calm = _calm(PLANT_N, precision)
+    assert expected_summary(calm.Positions, calm.Masses, calm.Radii, precision) == 0
+    with np.errstate(over="ignore"):
+        assert float(np.abs(calm.Positions).max()) < 2.0 ** 30 and float(np.abs(calm.Positions).min()) > 2.0 ** -8
+    out = []
+    for k, (label, field, value, summary, tiles) in enumerate(planted_values(precision)):
+        for j, i in enumerate(PLANT_INDICES):
+            b = calm.copy()
+            f = field if field != "c" else "xy"[(k + j) % 2]
+            if f in "xy":
+                b.Positions[i, "xy".index(f)] = value
+            else:
+                (b.Masses if f == "m" else b.Radii)[i] = value
+            out.append(dict(name="%s %s at %d%s" % (f, label, i, "-f64" if precision == F64 else ""), bodies=b, index=i,
+                            field=f, value=value, summary=summary, tiles_changed=tiles))
+    return out
+
+
+def prefix_block(bodies, n):
+    """The block of the first n bodies of `bodies`, re-carved (a contiguous array of 6 n reals)."""
+    return np.concatenate([bodies.Positions[:n].ravel(), bodies.Velocities[:n].ravel(), bodies.Masses[:n],
+                           bodies.Radii[:n]]).astype(bodies.dtype)
+
+
+STRADDLE_N = 300             # over 2 ranks: blocks [0, 128) and [128, 300)
+STRADDLE_PAIR = (10, 20)     # coincide at upload; 20 is the lighter one and is deleted by step 1
+STRADDLE_RADII = {128: 0.25, 129: 0.5, 5: 0.125}     # old indices: 128 / 129 become 127 / 128, either side of the tile edge
+
+
+@functools.lru_cache(maxsize=None)
+def case_wave_straddles_a_tile():
+    """StepperGroup(2), n = 300: step 1 deletes body 20 of rank 0's range [0, 128), so rank 1's slot is unpacked at offset
+    127 - its first wave writes bodies 127 ... 190, one in tile 0 and 63 in tile 1 - and the radii planted on the old
+    bodies 128 and 129 land on the two sides of that tile edge INSIDE that wave.  Growth 0: no radius changes."""
+    b = _calm(STRADDLE_N)
+    i, j = STRADDLE_PAIR
+    b.Positions[j] = b.Positions[i]
+    b.Masses[j] = b.Masses[i] / 2
+    for k, r in STRADDLE_RADII.items():
+        b.Radii[k] = r
+    return _case("wave-straddles-a-tile", b, [RADIUS, RADIUS], summary0=RADIUS, growth=0.0)
+
+
 def mid_run_cases_f32():
     return [case_small_enters_and_leaves(), case_small_pair_below_the_chain_domain(),
             case_body_leaves_the_bound("tile0"), case_body_leaves_the_bound("middle"),

@@ -118,6 +118,55 @@ def test_regime_changes_mid_run_fp64(nb, case, kind, variant, trajectory):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# C'. planted states: one value at one index, at the edges of every per-body rule (tests/regime_cases.py)
+# ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", [rc.F32, rc.F64], ids=["f32", "f64"])
+def test_planted_states_at_upload_and_after_a_step(nb, precision):
+    """nbody_upload's rule (the host's nbody_block_pack) and unpack_slots' rule against the numpy statement, for every
+    planted state, in ONE context per precision that is given one state after the other.  Time step 0, so that a planted
+    value survives the step wherever the arithmetic lets it (x + 0 * v; a NaN or infinite value spreads, a radius in reach
+    of another body deletes): the state after the step is the oracle's, bit for bit, and the bookkeeping is compared with
+    the numpy statement of THAT state."""
+    field = 100000
+    real = float if precision == rc.F64 else np.float32
+    ctx = nb.StepperGroup(1, capacity=rc.PLANT_N, precision=precision, timestep=0.0, growthRate=0.1, fieldWidth=field,
+                          fieldHeight=field)
+    kept = 0
+    try:
+        for s in rc.planted_states(precision):
+            b = s["bodies"]
+            ctx.upload(b)
+            rc.assert_screen_state(ctx, b, s["name"] + " upload")
+            assert ranks_of(ctx)[0].screen_state()[0] == s["summary"], s["name"]
+            ctx.step(1)
+            out = ctx.download()
+            blk = b.block.copy()
+            n, *_ = ol.port_step(blk, rc.PLANT_N, real(0.0), field, field, real(0.1), want_events=False)
+            assert out.numBodies == n and nan_aware_equal(out.block, blk[:6 * n]), s["name"] + " step 1: != oracle"
+            rc.assert_screen_state(ctx, out, s["name"] + " step 1")
+            kept += int(n == rc.PLANT_N and nan_aware_equal(out.Positions.ravel(), b.Positions.ravel()) and
+                        nan_aware_equal(out.Radii, b.Radii) and nan_aware_equal(out.Masses, b.Masses))
+    finally:
+        ctx.close()
+    assert kept >= len(rc.planted_states(precision)) // 2, kept   # most planted values do survive a step of length 0
+
+
+def test_wave_of_unpack_slots_straddles_two_tiles(nb, trajectory):
+    """Two ranks, n = 300: after step 1 rank 1's slot is unpacked at offset 127, and the two planted radii lie on the two
+    sides of the tile edge inside its first wave (tests/test_regime_cases_cpu.py proves both with the oracle)."""
+    case = rc.case_wave_straddles_a_tile()
+    run_case(nb, case, 2, 0, trajectory)
+    ctx = case_ctx(nb, case, 2)
+    try:
+        ctx.upload(case["bodies"])
+        ctx.step(1)
+        for r in ranks_of(ctx):
+            assert r.screen_state()[1][:3].tolist() == [0.25, 0.5, 0.0]
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
 # D. one context, several different states
 # ---------------------------------------------------------------------------------------------------------
 DT, GROWTH = np.float32(0.2), np.float32(0.1)
@@ -222,6 +271,8 @@ def edge_states():
     out = [("calm n=20000", big.block, 20000, DT, GROWTH, 100000)]
     for c in F32_CASES:
         out.append((c["name"], c["bodies"].block, c["n"], c["dt"], c["growth"], c["field"]))
+    for c in rc.planted_states(rc.F32):                       # n = 257: two whole blocks and a body that gets no thread
+        out.append(("planted " + c["name"], c["bodies"].block, rc.PLANT_N, DT, GROWTH, 100000))
     _, rb, field = rc.radius_bounds_bodies(3000)
     out.append(("radius bounds n=3000", rb.block, 3000, DT, GROWTH, field))
     out.append(("coincident bodies", rc.coincident_bodies(4096).block, 4096, DT, GROWTH, 100000))

@@ -222,3 +222,37 @@ def test_config_parser_under_sanitizers(asan_driver, tmp_path):
         p.write_bytes(b"\n".join(lines) + (b"\n" if rng.integers(0, 2) else b""))
         out = asan_driver("parse", str(p))
         assert out.startswith("rc=")
+
+
+def _fnv1a(data):
+    h = 0xcbf29ce484222325
+    for byte in data:
+        h = ((h ^ byte) * 0x100000001b3) & 0xffffffffffffffff
+    return h
+
+
+@pytest.mark.parametrize("precision", [0, 1], ids=["f32", "f64"])
+def test_block_packing_under_sanitizers(asan_driver, tmp_path, precision):
+    """nbody_block_pack / nbody_block_unpack - the host half of every upload and download - on the planted states of
+    tests/regime_cases.py, cut to n = 0, 1, 127, 128, 129 and 257 bodies: the summary and the tile radius bits equal the
+    numpy statement, and the block comes back bit for bit.  Exactly sized buffers under ASan + UBSan."""
+    import regime_cases as rc
+    args, want = [], []
+    for n in (0, 1, 127, 128, 129, 257):
+        states = [s for s in rc.planted_states(precision) if s["index"] < n] or rc.planted_states(precision)[:1]
+        for k, s in enumerate(states):
+            blk = rc.prefix_block(s["bodies"], n)
+            assert blk.nbytes == (48 if precision else 24) * n
+            path = tmp_path / ("p%d_%d_%d.bin" % (precision, n, k))
+            path.write_bytes(blk.tobytes())
+            args += [str(path), str(precision), str(n)]
+            P, _, M, R = blk[:2 * n], None, blk[4 * n:5 * n], blk[5 * n:]
+            tiles = rc.expected_tile_rmax(R, n // 128 + 2).view(np.uint32)
+            want.append("summary %d hash %016x tiles %s" % (rc.expected_summary(P, M, R, precision), _fnv1a(blk.tobytes()),
+                                                          " ".join("%08x" % t for t in tiles)))
+            if n == 257:                                     # the whole state: what the list itself declares
+                assert want[-1].startswith("summary %d " % s["summary"]), s["name"]
+    got = asan_driver("pack", *args).strip().split("\n")
+    assert len(got) == len(want) and len(want) > 300
+    for g, w, a in zip(got, want, args[::3]):
+        assert g == w, a

@@ -225,3 +225,57 @@ def test_reuse_states_are_what_the_context_test_needs():
     for _ in range(k2):
         cur, *_ = ol.port_step(blk, cur, f32(0.2), rc.REUSE_FIELD, rc.REUSE_FIELD, f32(0.1), want_events=False)
         assert cur == 1500 and rc.expected_summary(*[ol.carve(blk, cur)[k] for k in (0, 2, 3)], rc.F32) == 0
+
+
+# ---------------------------------------------------------------------------------------------------------
+# planted states (one value at one index of a calm state): what the GPU and host tests rest on
+# ---------------------------------------------------------------------------------------------------------
+# One planted value can set: nothing (a value just inside a bound); bit 0 (a coordinate at the bound or infinite); bit 2 (a
+# coordinate below the floor); bits 0 and 2 together (a NaN coordinate is neither below the bound nor at or above the
+# floor); bit 3 (a mass); bit 1 (a radius).  No single value sets bit 1 or 3 with another bit: each rests on one field.
+# An fp64 context has bits 0 and 1 only.
+REACHABLE = {rc.F32: {0, rc.UNBOUNDED, rc.SMALL, rc.UNBOUNDED | rc.SMALL, rc.MASS, rc.RADIUS},
+             rc.F64: {0, rc.UNBOUNDED, rc.RADIUS}}
+
+
+@pytest.mark.parametrize("precision", [rc.F32, rc.F64])
+def test_planted_states_reach_every_summary_one_value_can(precision):
+    states = rc.planted_states(precision)
+    calm_tiles = np.zeros(rc.PLANT_N // 128 + 2, np.uint32)
+    seen = {}
+    for s in states:
+        b = s["bodies"]
+        assert b.numBodies == rc.PLANT_N == 257 and b.precision == precision
+        got = rc.expected_summary(b.Positions, b.Masses, b.Radii, precision)
+        assert got == s["summary"], "%s: the numpy statement gives %d, the list declares %d" % (s["name"], got, s["summary"])
+        seen.setdefault(got, set()).add(s["index"])
+        tiles = rc.expected_tile_rmax(b.Radii, len(calm_tiles)).view(np.uint32)
+        changed = np.nonzero(tiles != calm_tiles)[0].tolist()
+        assert len(changed) == s["tiles_changed"], (s["name"], changed)
+        assert changed in ([], [s["index"] // 128]), (s["name"], changed)
+        if s["field"] != "r":
+            assert s["tiles_changed"] == 0
+    assert set(seen) == REACHABLE[precision], sorted(seen)
+    for value, where in seen.items():                        # every value at every index: both wave ends, both tile sides
+        assert where == set(rc.PLANT_INDICES), (value, sorted(where))
+    # each radius of the issue's list either moves one bound or none - and both kinds occur
+    assert {s["tiles_changed"] for s in states if s["field"] == "r"} == {0, 1}
+    assert {s["field"] for s in states} == {"x", "y", "m", "r"}
+
+
+def test_wave_straddles_a_tile_as_the_case_says(nb):
+    c = rc.case_wave_straddles_a_tile()
+    i, j = rc.STRADDLE_PAIR
+    lo0, cnt0 = nb.partition(c["n"], 0, 2)
+    assert (lo0, cnt0) == (0, 128) and c["n"] == 300 and i < 128 and j < 128
+    (n1, blk1, ab1, de1), (n2, _, ab2, de2) = rc.oracle_trajectory(c, want_events=True)
+    assert n1 == 299 and de1.tolist() == [j] and ab1.tolist() == [[i, j]]           # the merge happens, inside rank 0's range
+    assert n2 == 299 and len(ab2) == 0                                              # and nothing else does
+    offset = cnt0 - 1                                        # survivors of rank 0 = where rank 1's slot is unpacked
+    assert offset == 127 and offset % 64 != 0 and offset // 128 != (offset + 63) // 128    # that wave covers two tiles
+    R1 = ol.carve(blk1, n1)[3]
+    assert R1[offset] == f32(0.25) and R1[offset + 1] == f32(0.5) and offset // 128 == 0 and (offset + 1) // 128 == 1
+    want = rc.expected_tile_rmax(R1, 5)
+    assert want.tolist() == [0.25, 0.5, 0, 0, 0]             # tile 0's bound comes from the straddling wave alone
+    assert rc.summaries_of(c) == c["summaries"] and \
+        rc.expected_summary(c["bodies"].Positions, c["bodies"].Masses, c["bodies"].Radii, rc.F32) == c["summary0"]
