@@ -1171,6 +1171,73 @@ int nbody_batch_get_cells(struct nbody_batch* b, const nbody_grid* grid, uint32_
                           nbody_cells_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Radius queries on the cell list (the reference has none): for every current body, or for every one of m
+ * probe points, the number of bodies within a distance h, the nearest of them, how many of them overlap the row and, on
+ * request, the neighbour list in CSR form - what a contact model, an SPH-style density, a local crowding measure or a
+ * per-step collision monitor is built from.  The first near-field query that walks the cell list of nbody_get_cells instead
+ * of all n sources per row: O(n) on a grid whose cells are about h wide.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma.  The grid
+ * is an nbody_grid as for nbody_get_cells; inside(j) and cell(j) are exactly the cell sums' definitions.
+ *   Sources: the current bodies with inside(j).  A body outside the grid is no source and is counted in info.outside.
+ *   Rows (points == NULL): every current body, inside the grid or not, with its own radius r and its own term left out by
+ *   index.  Rows (points != NULL): the m points with r = +0.  For a row at (x, y), (X_j, Y_j, R_j) widened exactly:
+ *     dx = X_j - x;  dy = Y_j - y;  d2_j = (dx*dx) + (dy*dy)               the d2 of nbody_get_neighbors, same bits
+ *     near(j)  <=>  inside(j) && j != i && d2_j <= h2
+ *     count    = the number of near j
+ *     nearest  : d2 = +inf, index = -1; over the near j in ANY order:
+ *                if (d2_j < d2 || (d2_j == d2 && j < index)) { d2 = d2_j; index = j; }
+ *     overlaps = the number of near j with d2_j <= s*s,  s = r + R_j
+ *     cell     = the row's own cell under the grid, -1 outside
+ * A d2 of +inf never becomes the nearest (it is counted where h2 is +inf); a NaN d2 is never near.
+ * The optional lists: start[rows + 1] (int64) is the exclusive prefix sum of count in row order, start[rows] = info.total;
+ * list[start[k] .. start[k+1]) holds the near sources of row k in ASCENDING j.  list needs start; cap is the room of list
+ * in entries, at most 2^31 - 1.  info.total > cap with a list is NBODY_ERR_CAPACITY: list is untouched, out, start and info
+ * are complete, and the caller repeats with that cap (the rule of nbody_get_binaries).  Without list, cap is only checked
+ * for its sign.
+ * h2 is the squared radius: >= 0 and not NaN, +inf allowed.  With points == NULL, m is the room of out in rows (and of start
+ * in rows + 1): m < n is NBODY_ERR_CAPACITY with nothing written, as for nbody_get_neighbors.
+ * info: total = the sum of count (the length of the list); n; rows; inside and outside (inside + outside == n); largest =
+ * the greatest count and largest_row = the lowest row that has it (0 and row 0 where there is no row).
+ * What follows from the definition:
+ *   - every output is an integer, a minimum under a total order or a sorted list, so none depends on the order in which the
+ *     sources are visited: apart from `cell`, the result is a function of the state, the set of inside bodies and h2 only.
+ *     Two grids that both hold every body give the same bytes in d2, index, count, overlaps, start and list;
+ *   - with outside == 0 and h2 = +inf, {d2, index, overlaps} has the bits of nbody_get_neighbors for the same rows;
+ *   - with outside == 0, finite h2 and own rows, the sum of count equals 2 * counts[0] of nbody_get_pair_counts with
+ *     edges2 = {0, nextafter(h2, +inf)};
+ *   - with outside == 0, count summed over points equals the point-body count of nbody_get_pair_counts with those edges;
+ *   - it is not a function of rank, world, transport, force kernel or the order the device's waves ran in.
+ * The window rule, by which the walk over cells finds exactly the near sources (csrc/nbody_within.hpp; DESIGN.md 4.21 has
+ * the proof): a row looks at the columns (int)max(tx - wx, 0) .. (int)min(tx + wx, nx - 1) with tx = (x - x0) * sx,
+ * wx = wx0 + (2^-20 + (|tx| + wx0) * 2^-40), wx0 = fl(fl(sqrt(h2)) * sx), and at the rows of cells by the same rule; a
+ * window is skipped only where a compare proves it empty, and a tx that is not finite, a NaN in this arithmetic or a grid
+ * of more than 2^400 cells per unit length means the whole grid.  The rule costs time, never a result: with a grid much
+ * finer than h, or all bodies in a few cells, the call approaches the n^2 pair tests of nbody_get_neighbors, read from
+ * memory instead of LDS.  Use a grid matched to h (Python: within_grid).
+ * nbody_get_within synchronises (twice with a list), reads positions and radii of the replica only and never changes what
+ * later steps compute.  It is NOT collective: any rank of any world may call it on its own and each gives the same bits.
+ * Device scratch and pinned staging are allocated on the first call; a handle that never calls it allocates nothing and
+ * launches nothing more, and the kernels it runs keep their code.  An empty system: every point's row {+inf, -1, 0, 0, cell}.
+ * NBODY_ERR_INVALID, found before any device call, the values before the handle: everything nbody_get_cells rejects about
+ * the grid; a NaN or negative h2; list without start; cap < 0; m < 0 or m x 24 bytes (x systems) above 2^31; a NULL handle,
+ * out or info.  NBODY_ERR_CAPACITY: above, and a batch with systems * nx * ny above 1 << 22.  NBODY_ERR_STATE: before an
+ * upload.  Not built: ordered fp64 sums over the neighbourhood (mass within h), see DESIGN.md 9.
+ * nbody_batch_get_within: the same query for every system of a batch, each stage ONE launch whatever S is, with one grid,
+ * one h2, one set of points and one cap for all of them.  System s's rows at out[s * per + k] and its starts at
+ * start[s * (per + 1) + k] with per = the batch's capacity for own rows and m for points, its list at list[s * cap + .],
+ * info[s]; the rest of every slice is left unchanged.  System s gives exactly the bits an nbody_ctx holding that system's
+ * state gives.  A count outside [0, capacity] is treated as 0 and reported for that system, as by nbody_batch_get_cells.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_within { double d2; int32_t index, count, overlaps, cell; } nbody_within;                  /* 24 bytes */
+typedef struct nbody_within_info { int64_t total; int32_t n, rows, inside, outside, largest, largest_row; } nbody_within_info;
+int nbody_get_within(nbody_ctx* ctx, const nbody_grid* grid, double h2, const nbody_vec2* points /* NULL: the bodies */, int m,
+                     nbody_within* out, int64_t* start /* [rows+1] or NULL */, int32_t* list /* [cap] or NULL */, int cap,
+                     nbody_within_info* info);
+int nbody_batch_get_within(struct nbody_batch* b, const nbody_grid* grid, double h2, const nbody_vec2* points, int m,
+                           nbody_within* out /* [systems*per] */, int64_t* start /* [systems*(per+1)] or NULL */,
+                           int32_t* list /* [systems*cap] or NULL */, int cap, nbody_within_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

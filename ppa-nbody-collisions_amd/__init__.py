@@ -150,6 +150,10 @@ CELL_DTYPE = np.dtype([("mass", np.float64), ("px", np.float64), ("py", np.float
                        ("first", np.int32)])
 CELLS_INFO_DTYPE = np.dtype([("n", np.int32), ("inside", np.int32), ("outside", np.int32), ("occupied", np.int32),
                              ("largest", np.int32), ("largest_cell", np.int32)])
+# nbody_within (24 bytes) and nbody_within_info (32 bytes): one row and the summary of within()
+WITHIN_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("count", np.int32), ("overlaps", np.int32), ("cell", np.int32)])
+WITHIN_INFO_DTYPE = np.dtype([("total", np.int64), ("n", np.int32), ("rows", np.int32), ("inside", np.int32),
+                              ("outside", np.int32), ("largest", np.int32), ("largest_row", np.int32)])
 GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
 # nbody_group_energy_info (24 bytes) and nbody_group_record (80 bytes), include/nbody.h
 GROUP_ENERGY_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32),
@@ -261,6 +265,8 @@ SYMBOLS = {
     "nbody_get_groups": (_i, [_vp, _d, _d, _vp, _i, _vp]),
     "nbody_get_cells": (_i, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _i, _vp]),
     "nbody_batch_get_cells": (_i, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "nbody_get_within": (_i, [_vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "nbody_batch_get_within": (_i, [_vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
     "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
     "nbody_group_catalog": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
@@ -842,6 +848,58 @@ def _cells_dict(cells, cell_of, start, order, info, grid):
     return out
 
 
+def within_grid(field, radius, squared=False, most=1024):
+    """The default grid of within(): the field's bounds [-w, w) x [-h, h) (field = (w, h)) in cells no smaller than `radius`
+    per side (a squared length with squared=True) and at most `most` per axis - the grid on which a row's window is 3 x 3
+    cells.  radius 0 gives `most` cells per axis, +inf one."""
+    w, h = (float(v) for v in field)
+    r = float(radius)
+    r = float(np.sqrt(np.float64(r))) if squared else r
+    most = max(int(most), 1)
+
+    def along(extent):
+        if not r > 0.0:
+            return most
+        return int(min(max(np.floor(extent / r), 1.0), float(most)))
+    return make_grid(along(2.0 * w), along(2.0 * h), (-w, w, -h, h))
+
+
+def _within(call, systems, per_own, radius, points, grid, squared, lists):
+    """nbody_get_within through `call(grid, h2, points, m, out, start, list, cap, info)` for `systems` systems (None: a
+    context) -> one dict per system: {"rows": WITHIN_DTYPE (rows,), "info", "grid"} and with `lists` "start": int64
+    (rows + 1,) and "list": int32 (total,).  radius is squared with one float64 multiply unless `squared`.  On
+    NBODY_ERR_CAPACITY the call is repeated once with the largest info.total."""
+    h = float(radius)
+    h2 = h if squared else h * h
+    pts = _field_points(points)
+    S = 1 if systems is None else max(systems, 1)
+    per = per_own if pts is None else len(pts)
+    rows = np.empty((S, max(per, 1)), dtype=WITHIN_DTYPE)       # only what the library has filled is handed out
+    info = np.zeros(S, dtype=WITHIN_INFO_DTYPE)
+    start = np.empty((S, per + 1), dtype=np.int64) if lists else None
+    cap = max(16 * per, 64) if lists else 0                     # the first guess of the room
+    lst = np.empty((S, cap), dtype=np.int32) if lists else None
+
+    def once():
+        return call(grid.ctypes.data, h2, None if pts is None else pts.ctypes.data, per, rows.ctypes.data,
+                    start.ctypes.data if lists else None, lst.ctypes.data if lists else None, cap, info.ctypes.data)
+    status = once()
+    if status == -7 and lists and int(info["total"].max()) > cap:   # NBODY_ERR_CAPACITY: info is complete
+        cap = int(info["total"].max())
+        lst = np.empty((S, cap), dtype=np.int32)
+        status = once()
+    _check(status)
+    out = []
+    for s in range(S if systems is None else systems):
+        k = int(info["rows"][s])
+        d = {"rows": rows[s, :k], "info": {f: int(info[f][s]) for f in WITHIN_INFO_DTYPE.names}, "grid": grid[0].copy()}
+        if lists:
+            d["start"] = start[s, :k + 1]
+            d["list"] = lst[s, :int(info["total"][s])]
+        out.append(d)
+    return out
+
+
 def cell_maps(result):
     """What the sums of cells() are for, on the host in numpy, from its result (a dict with "cells" and "grid", one system):
     {"area": of one cell, "surface_density": mass / area, "mean_velocity": (ny, nx, 2) p / mass, "dispersion": the velocity
@@ -1269,6 +1327,19 @@ class Stepper:
         return _cells_dict(cells[0], None if cell_of is None else cell_of[0], None if start is None else start[0],
                            None if order is None else order[0], info[0], grid)
 
+    def within(self, radius, points=None, grid=None, squared=False, lists=False):
+        """nbody_get_within: everything within `radius` (a length; a squared length with squared=True; inf allowed) of every
+        row - each of `points` (m, 2), or with points=None each current body (its own term left out by index) - found
+        through the cell list of `grid` (a make_grid record; None: within_grid(field, radius)) in O(n) where the cells are
+        about `radius` wide: {"rows": a WITHIN_DTYPE array {"d2", "index": the nearest source within the radius (+inf, -1:
+        none), "count": the sources within it, "overlaps": those of them with d2 <= (r + r_j)^2, "cell": the row's own cell,
+        -1 outside the grid}, "info": total, n, rows, inside, outside, largest, largest_row, "grid"}; with lists=True also
+        "start": int64 (rows + 1,) and "list": int32 (total,), the sources within the radius of row k in ascending index at
+        list[start[k]:start[k+1]].  Only bodies inside the grid are sources; apart from "cell" the result does not depend on
+        the grid otherwise.  Not collective: any rank of any world may call it on its own."""
+        g = within_grid(_field_bounds(self._field)[1::2], radius, squared) if grid is None else make_grid(grid)
+        return _within(lambda *a: lib.nbody_get_within(self._ctx, *a), None, self.capacity, radius, points, g, squared, lists)[0]
+
     def groups(self, link, radius_scale=1.0):
         """nbody_get_groups: friends-of-friends groups of the current bodies, i and j linked where d2 <= s*s with
         s = radius_scale * (r_i + r_j) + link (fp64): {"label": int32 (n,), label[i] the lowest index of body i's group,
@@ -1395,6 +1466,10 @@ class StepperGroup:
         """Stepper.cells through one rank, moments=False only (a rank holds only its own velocities): every rank's replica
         holds every position and mass, each gives the same bits."""
         return self.ranks[rank].cells(grid_or_nx, ny, bounds, moments, lists)
+
+    def within(self, radius, points=None, grid=None, squared=False, lists=False, rank=0):
+        """Stepper.within through one rank: every rank's replica holds every position and radius, each gives the same bits."""
+        return self.ranks[rank].within(radius, points, grid, squared, lists)
 
     def groups(self, link, radius_scale=1.0, rank=0):
         """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
@@ -1651,6 +1726,19 @@ class StepperBatch:
         if lists:
             out.update(cell_of=cell_of[:self.systems], start=start[:self.systems], order=order[:self.systems])
         return out
+
+    def within(self, radius, points=None, grid=None, squared=False, lists=False):
+        """nbody_batch_get_within: Stepper.within for every system, each stage one launch for the whole batch, with the one
+        grid (None: within_grid over the field of system 0, as many cells as a batch call may have), radius and set of
+        points for all of them: a list of S dicts in the form (and with the bits) a Stepper holding the system's state
+        gives."""
+        if grid is None:
+            most = int(np.sqrt((1 << 22) // max(self.systems, 1)))
+            g = within_grid(_field_bounds(self._field)[1::2], radius, squared, min(most, 1024))
+        else:
+            g = make_grid(grid)
+        return _within(lambda *a: lib.nbody_batch_get_within(self._b, *a), self.systems, self.capacity, radius, points, g,
+                       squared, lists)
 
     def groups(self, link, radius_scale=1.0):
         """nbody_batch_get_groups: Stepper.groups for every system, every pair walk one launch for the whole batch: a list

@@ -32,6 +32,7 @@
 #include "nbody_shells.hpp"
 #include "nbody_shell_moments.hpp"
 #include "nbody_cells.hpp"
+#include "nbody_within.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -103,6 +104,8 @@ struct nbody_batch {
     ShellMomentState shm;
     // cell sums (nbody_batch_get_cells, nbody_cells.hpp): nothing is allocated before the first call
     CellState cel;
+    // radius queries (nbody_within.hpp): the cell list of `cel` and these; nothing is allocated before the first call
+    WithinState wth;
     // encounter queries (nbody_batch_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_batch_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -141,6 +144,7 @@ void free_all(nbody_batch* b) {
     rows_free(b->shl);
     shell_moments_free(b->shm);
     cells_free(b->cel);
+    within_free(b->wth);
     tracers_free(b->trc);
     (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
     if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
@@ -896,6 +900,24 @@ int nbody_batch_get_cells(nbody_batch* b, const nbody_grid* grid, uint32_t flags
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
         return cells_run<decltype(t), RowsBatchCount>(who, site, b->cel, b->V, *grid, flags, cells, cell_of, start, order, info, sync);
+    });
+}
+
+}  // extern "C"
+
+// Radius queries (nbody_within.hpp): one grid, one h2, one set of points and one cap for every system, each stage ONE launch
+// for the whole batch.
+extern "C" {
+
+int nbody_batch_get_within(nbody_batch* b, const nbody_grid* grid, double h2, const nbody_vec2* points, int m, nbody_within* out,
+                           int64_t* start, int32_t* list, int cap, nbody_within_info* info) {
+    const char* who = "nbody_batch_get_within";
+    RowsSite site;
+    int rc = within_check_args(who, {b, out, info}, grid, h2, m, start, list, cap, b ? (unsigned long long)b->S : 1);
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return within_run<decltype(t), RowsBatchCount>(who, site, b->cel, b->wth, *grid, h2, points, m, out, start, list, cap, info,
+                                                       sync);
     });
 }
 

@@ -430,8 +430,9 @@ inline hipError_t cells_reserve_device(RowsArray<E>& f, size_t n) {
     return e;
 }
 
-inline int cells_reserve(CellState& g, size_t systems, size_t cells, size_t bodies, const char* who) {
-    hipError_t e = rows_reserve(g.cells, systems * cells);
+// sums: with the cell records; a caller that needs the list only (nbody_within.hpp) leaves them out.
+inline int cells_reserve(CellState& g, size_t systems, size_t cells, size_t bodies, const char* who, bool sums = true) {
+    hipError_t e = sums ? rows_reserve(g.cells, systems * cells) : hipSuccess;
     if (e == hipSuccess) e = rows_reserve(g.start, systems * (cells + 1));
     if (e == hipSuccess) e = rows_reserve(g.cell_of, bodies > 0 ? bodies : 1);
     if (e == hipSuccess) e = rows_reserve(g.order, bodies > 0 ? bodies : 1);
@@ -470,21 +471,18 @@ inline int cells_check_args(const char* who, std::initializer_list<const void*> 
     return rows_check_args(who, required, 0, 0, "");
 }
 
-// One call, from the reservation to the caller's arrays; the site, Count and read_meta as for rows_run (nbody_rows.hpp).
-// V: the velocities, indexed like the site's J, read only with NBODY_CELLS_MOMENTS.  A list the caller did not ask for is
-// built all the same - the sums run over it - and not copied.
-template <typename T, typename Count, typename ReadMeta>
-int cells_run(const char* who, const RowsSite& s, CellState& g, const void* V, const nbody_grid& grid, uint32_t flags,
-              nbody_cell* cells_out, int32_t* cell_of, int32_t* start, int32_t* order, nbody_cells_info* info, ReadMeta read_meta) {
-    const size_t S = (size_t)s.systems, C = (size_t)grid.nx * (size_t)grid.ny, bodies = S * (size_t)s.stride;
+// The list stages on the site's stream, no wait: the memset of the counts and cursors, cells_assign, cells_scan, cells_place
+// and cells_rank.  Leaves g.cell_of, g.start, g.order and g.info on the device; g is reserved by the caller.  What both the
+// cell sums and the radius queries (nbody_within.hpp) run first.
+template <typename T, typename Count>
+int cells_list_run(const RowsSite& s, CellState& g, const nbody_grid& grid) {
+    const size_t S = (size_t)s.systems, C = (size_t)grid.nx * (size_t)grid.ny;
     const int cells = (int)C;
-    int rc = cells_reserve(g, S, C, bodies, who);
-    if (rc != NBODY_OK) return rc;
     const Rec<T>* J = (const Rec<T>*)s.J;
     const int n_one = s.n_one<Count>();
     unsigned* count = g.words.d;
     unsigned* cursor = g.words.d + S * C;
-    const dim3 per_body = s.grid(s.n_bound), per_cell((unsigned)((C + kDiagBlock - 1) / kDiagBlock), (unsigned)S);
+    const dim3 per_body = s.grid(s.n_bound);
     NBK_ROWS_TRY(hipMemsetAsync(g.words.d, 0, 2 * S * C * sizeof(unsigned), s.stream));
     if (s.n_bound > 0) {
         hipLaunchKernelGGL((cells_assign<T, Count>), per_body, dim3(kDiagBlock), 0, s.stream, J, s.meta, s.counters, s.stride,
@@ -502,6 +500,23 @@ int cells_run(const char* who, const RowsSite& s, CellState& g, const void* V, c
                            (const int32_t*)g.cell_of.d, (const int32_t*)g.start.d, (const int32_t*)g.slot.d, g.order.d);
         NBK_ROWS_TRY(hipGetLastError());
     }
+    return NBODY_OK;
+}
+
+// One call, from the reservation to the caller's arrays; the site, Count and read_meta as for rows_run (nbody_rows.hpp).
+// V: the velocities, indexed like the site's J, read only with NBODY_CELLS_MOMENTS.  A list the caller did not ask for is
+// built all the same - the sums run over it - and not copied.
+template <typename T, typename Count, typename ReadMeta>
+int cells_run(const char* who, const RowsSite& s, CellState& g, const void* V, const nbody_grid& grid, uint32_t flags,
+              nbody_cell* cells_out, int32_t* cell_of, int32_t* start, int32_t* order, nbody_cells_info* info, ReadMeta read_meta) {
+    const size_t S = (size_t)s.systems, C = (size_t)grid.nx * (size_t)grid.ny, bodies = S * (size_t)s.stride;
+    const int cells = (int)C;
+    int rc = cells_reserve(g, S, C, bodies, who);
+    if (rc != NBODY_OK) return rc;
+    const Rec<T>* J = (const Rec<T>*)s.J;
+    const int n_one = s.n_one<Count>();
+    const dim3 per_cell((unsigned)((C + kDiagBlock - 1) / kDiagBlock), (unsigned)S);
+    if ((rc = cells_list_run<T, Count>(s, g, grid)) != NBODY_OK) return rc;
     if (flags & NBODY_CELLS_MOMENTS)
         hipLaunchKernelGGL((cells_sum<T, Count, true>), per_cell, dim3(kDiagBlock), 0, s.stream, J, (const Vec2<T>*)V, s.meta,
                            s.stride, n_one, cells, (const int32_t*)g.start.d, (const int32_t*)g.order.d, g.cells.d);

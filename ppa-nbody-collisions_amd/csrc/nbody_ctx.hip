@@ -35,6 +35,7 @@
 #include "nbody_shells.hpp"
 #include "nbody_shell_moments.hpp"
 #include "nbody_cells.hpp"
+#include "nbody_within.hpp"
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
@@ -209,6 +210,8 @@ struct nbody_ctx {
     ShellMomentState shm;
     // cell sums (nbody_get_cells, nbody_cells.hpp): nothing is allocated before the first call
     CellState cel;
+    // radius queries (nbody_within.hpp): the cell list of `cel` and these; nothing is allocated before the first call
+    WithinState wth;
     // encounter queries (nbody_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
     EncState enc;
     // bound-pair queries (nbody_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
@@ -682,6 +685,7 @@ void free_all(nbody_ctx* c) {
     rows_free(c->shl);
     shell_moments_free(c->shm);
     cells_free(c->cel);
+    within_free(c->wth);
     tracers_free(c->trc);
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_meta) hipHostFree(c->h_meta);
@@ -1906,6 +1910,26 @@ int nbody_get_cells(nbody_ctx* c, const nbody_grid* grid, uint32_t flags, nbody_
     return ctx_rows_run(c, [&](auto t, auto sync) {
         return cells_run<decltype(t), RowsOneCount>(who, site, c->cel, c->Vown, *grid, flags, cells, cell_of, start, order, info,
                                                     sync);
+    });
+}
+
+}  // extern "C"
+
+// Radius queries (nbody_within.hpp): positions and radii of the replica only, so any context may call them on its own.  After
+// everything else, for the group energies' reason.
+extern "C" {
+
+int nbody_get_within(nbody_ctx* c, const nbody_grid* grid, double h2, const nbody_vec2* points, int m, nbody_within* out,
+                     int64_t* start, int32_t* list, int cap, nbody_within_info* info) {
+    const char* who = "nbody_get_within";
+    RowsSite site;
+    int rc = within_check_args(who, {c, out, info}, grid, h2, m, start, list, cap, 1);
+    if (rc != NBODY_OK || (rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if (!points && m < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d rows, the context holds %d bodies", who, m, site.n_bound);
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return within_run<decltype(t), RowsOneCount>(who, site, c->cel, c->wth, *grid, h2, points, m, out, start, list, cap, info,
+                                                     sync);
     });
 }
 
