@@ -19,23 +19,7 @@
 #include "nbody_error.h"
 #include "nbody_batch_kernels.hpp"
 #include "nbody_batch_diag.hpp"
-#include "nbody_rows.hpp"
-#include "nbody_field.hpp"
-#include "nbody_tracers.hpp"
-#include "nbody_ids.hpp"
-#include "nbody_tracks.hpp"
-#include "nbody_neighbors.hpp"
-#include "nbody_groups.hpp"
-#include "nbody_group_energy.hpp"
-#include "nbody_pairs.hpp"
-#include "nbody_knn.hpp"
-#include "nbody_shells.hpp"
-#include "nbody_shell_moments.hpp"
-#include "nbody_cells.hpp"
-#include "nbody_within.hpp"
-#include "nbody_encounters.hpp"
-#include "nbody_binaries.hpp"
-#include "nbody_tides.hpp"
+#include "nbody_queries.hpp"
 
 using namespace nbk;
 
@@ -55,6 +39,7 @@ struct nbody_batch {
     int K = 1;                  // lanes per body of the force kernel
     int num_cus = 256;
     hipStream_t stream = nullptr;
+    RowsOwned own;              // every device and pinned block made at create
     // device memory
     Rec<float>* J = nullptr;            // [S * cap]
     Vec2<float>* V = nullptr;           // [S * cap]
@@ -74,46 +59,18 @@ struct nbody_batch {
     bool uploaded = false;
     int64_t steps = 0;
     // diagnostics (nbody_batch_diagnostics, nbody_batch_diag_*): nothing is allocated until one of them is called
-    DiagTile* dg_tiles = nullptr;       // [S * ceil(cap / 128)] tile partials, first diagnostics call of any kind
-    DiagOut* dg_out = nullptr;          // [S] records of one nbody_batch_diagnostics call
-    DiagOut* h_dg_out = nullptr;        // pinned [S]
-    double* dg_phi = nullptr;           // [S * cap], first call that asks for phi
-    double* h_dg_phi = nullptr;         // pinned [S * cap]
-    DiagOut* dg_log = nullptr;          // [log_cap * S] recorded series (nbody_batch_diag_reserve)
+    RowsArray<DiagTile> dg_tiles;       // device [S * ceil(cap / 128)] tile partials, first diagnostics call of any kind
+    RowsArray<DiagOut> dg_out;          // [S] records of one nbody_batch_diagnostics call: device and pinned
+    RowsArray<double> dg_phi;           // [S * cap], first call that asks for phi: device and pinned
+    RowsArray<DiagOut> dg_log;          // device [log_cap * S] recorded series (nbody_batch_diag_reserve)
     int log_cap = 0;                    // samples reserved
     int log_rows = 0;                   // samples recorded since the reservation or the last upload: the next row
     // identities (NBODY_FLAG_TRACK_IDS, nbody_ids.hpp): nothing is allocated without the flag
     IdsState ids;                       // the map [S * cap] twice, the lineage [S * ev_cap], [S] translated-up-to counters
     // track log (nbody_batch_track_*, nbody_tracks.hpp): nothing is allocated without a reservation
     TrackState trk;
-    // field evaluation (nbody_batch_get_field, nbody_field.hpp): nothing is allocated before the first call
-    FieldState fld;
-    // neighbour queries (nbody_batch_get_neighbors, nbody_neighbors.hpp): nothing is allocated before the first call
-    NeighborState nbr;
-    // group finding (nbody_batch_get_groups, nbody_groups.hpp): nothing is allocated before the first call
-    GroupsState grp;
-    // group energies (nbody_batch_get_group_potential, nbody_group_energy.hpp): nothing is allocated before the first call
-    GroupEnergyState gen;
-    // pair-separation counts (nbody_batch_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
-    PairsState prs;
-    // k nearest neighbours (nbody_batch_get_knn, nbody_knn.hpp): nothing is allocated before the first call
-    KnnState knn;
-    // shell sums (nbody_batch_get_shells, nbody_shells.hpp): nothing is allocated before the first call
-    ShellState shl;
-    // shell moments (nbody_batch_get_shell_moments, nbody_shell_moments.hpp): nothing is allocated before the first call
-    ShellMomentState shm;
-    // cell sums (nbody_batch_get_cells, nbody_cells.hpp): nothing is allocated before the first call
-    CellState cel;
-    // radius queries (nbody_within.hpp): the cell list of `cel` and these; nothing is allocated before the first call
-    WithinState wth;
-    // encounter queries (nbody_batch_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
-    EncState enc;
-    // bound-pair queries (nbody_batch_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
-    BinState bin;
-    // tidal tensor and jerk (nbody_batch_get_tides, nbody_tides.hpp): nothing is allocated before the first call
-    TidesState tid;
-    // tracer particles (nbody_batch_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
-    TracerState trc;
+    // the queries (nbody_queries.hpp): nothing is allocated before the first call of each
+    QueryStates q;
 };
 
 namespace {
@@ -127,30 +84,11 @@ void free_all(nbody_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->desc.device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    (void)hipFree(b->J); (void)hipFree(b->V); (void)hipFree(b->S_J); (void)hipFree(b->S_V);
-    (void)hipFree(b->meta); (void)hipFree(b->counters); (void)hipFree(b->params); (void)hipFree(b->events);
-    (void)hipFree(b->blk_counts);
-    (void)hipFree(b->ids.map[0]); (void)hipFree(b->ids.map[1]); (void)hipFree(b->ids.lineage); (void)hipFree(b->ids.done);
-    (void)hipFree(b->trk.buf); (void)hipFree(b->trk.sel);
-    rows_free(b->fld);
-    rows_free(b->nbr);
-    groups_free(b->grp);
-    rows_free(b->gen);
-    pairs_free(b->prs);
-    pair_log_free(b->enc);
-    pair_log_free(b->bin);
-    tides_free(b->tid);
-    rows_free(b->knn);
-    rows_free(b->shl);
-    shell_moments_free(b->shm);
-    cells_free(b->cel);
-    within_free(b->wth);
-    tracers_free(b->trc);
-    (void)hipFree(b->dg_tiles); (void)hipFree(b->dg_out); (void)hipFree(b->dg_phi); (void)hipFree(b->dg_log);
-    if (b->h_dg_out) (void)hipHostFree(b->h_dg_out);
-    if (b->h_dg_phi) (void)hipHostFree(b->h_dg_phi);
-    if (b->h_meta) (void)hipHostFree(b->h_meta);
-    if (b->h_counters) (void)hipHostFree(b->h_counters);
+    b->own.release();
+    ids_free(b->ids);
+    track_free(b->trk);
+    queries_free(b->q);
+    rows_free(b->dg_tiles); rows_free(b->dg_out); rows_free(b->dg_phi); rows_free(b->dg_log);
     free(b->h_stage);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     (void)hipGetLastError();
@@ -208,8 +146,8 @@ int enqueue_step(nbody_batch* b) {
         case 4: launch_forces_k<4>(b, nblocks, log); break;
         default: launch_forces_k<8>(b, nblocks, log); break;
     }
-    if (b->trc.on()) {                                     // tracers: J still holds step t until the commit
-        const int rc = tracers_enqueue<float, TracersBatch>(b->trc, b->stream, b->S, (const Rec<float>*)b->J, (const Meta*)b->meta,
+    if (b->q.trc.on()) {                                   // tracers: J still holds step t until the commit
+        const int rc = tracers_enqueue<float, TracersBatch>(b->q.trc, b->stream, b->S, (const Rec<float>*)b->J, (const Meta*)b->meta,
                                                             b->counters, b->cap, TracerParams{}, (const StepParams<float>*)b->params);
         if (rc != NBODY_OK) return rc;
     }
@@ -243,19 +181,13 @@ int check_system(const nbody_batch* b, int system, const char* who) {
 // ---------------------------------------------------------------------------------------------------------
 // Diagnostics (kernels in nbody_batch_diag.hpp)
 // ---------------------------------------------------------------------------------------------------------
-int diag_fail_alloc(hipError_t e, const char* what) {
-    (void)hipGetLastError();
-    return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "batch diagnostics, %s: %s", what,
-                      hipGetErrorString(e));
-}
-
 // The tile partials: S * ceil(cap / 128) records, cleared once so that no later read sees memory nobody wrote.
 int diag_alloc_tiles(nbody_batch* b) {
-    if (b->dg_tiles) return NBODY_OK;
-    const size_t bytes = (size_t)b->S * (size_t)batch_diag_tiles(b->cap) * sizeof(DiagTile);
-    hipError_t e = hipMalloc((void**)&b->dg_tiles, bytes);
-    if (e != hipSuccess) { b->dg_tiles = nullptr; return diag_fail_alloc(e, "tile partials"); }
-    HIP_TRY(hipMemsetAsync(b->dg_tiles, 0, bytes, b->stream));
+    if (b->dg_tiles.d) return NBODY_OK;
+    const size_t tiles = (size_t)b->S * (size_t)batch_diag_tiles(b->cap);
+    const hipError_t e = rows_reserve_device(b->dg_tiles, tiles);
+    if (e != hipSuccess) return rows_alloc_failed(e, "batch diagnostics", "tile partials");
+    HIP_TRY(hipMemsetAsync(b->dg_tiles.d, 0, tiles * sizeof(DiagTile), b->stream));
     return NBODY_OK;
 }
 
@@ -266,13 +198,13 @@ int enqueue_diagnostics(nbody_batch* b, DiagOut* out, double* phi) {
         const dim3 grid((b->n_upper + kDiagBlock - 1) / kDiagBlock, b->S);
         if (phi)
             hipLaunchKernelGGL((batch_diag_potential<true>), grid, dim3(kDiagBlock), 0, b->stream, (const Rec<float>*)b->J,
-                               (const Vec2<float>*)b->V, (const Meta*)b->meta, b->cap, G, phi, b->dg_tiles);
+                               (const Vec2<float>*)b->V, (const Meta*)b->meta, b->cap, G, phi, b->dg_tiles.d);
         else
             hipLaunchKernelGGL((batch_diag_potential<false>), grid, dim3(kDiagBlock), 0, b->stream, (const Rec<float>*)b->J,
-                               (const Vec2<float>*)b->V, (const Meta*)b->meta, b->cap, G, (double*)nullptr, b->dg_tiles);
+                               (const Vec2<float>*)b->V, (const Meta*)b->meta, b->cap, G, (double*)nullptr, b->dg_tiles.d);
     }
     hipLaunchKernelGGL((batch_diag_reduce<kWave>), dim3((b->S + kWave - 1) / kWave), dim3(kWave), 0, b->stream,
-                       (const DiagTile*)b->dg_tiles, (const Meta*)b->meta, b->counters, b->S, b->cap, out);
+                       (const DiagTile*)b->dg_tiles.d, (const Meta*)b->meta, b->counters, b->S, b->cap, out);
     HIP_TRY(hipGetLastError());
     return NBODY_OK;
 }
@@ -346,33 +278,24 @@ int nbody_batch_create(nbody_batch** out, const nbody_batch_desc* d, const nbody
     do {                                                                                                  \
         hipError_t e__ = (expr);                                                                          \
         if (e__ != hipSuccess) {                                                                          \
-            int rc__ = nbody_fail(e__ == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP,           \
-                                  "%s failed: %s", #expr, hipGetErrorString(e__));                        \
+            int rc__ = rows_alloc_failed(e__, "nbody_batch_create", #expr);                               \
             free_all(b);                                                                                  \
             return rc__;                                                                                  \
         }                                                                                                 \
     } while (0)
     BATCH_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    BATCH_TRY(hipMalloc((void**)&b->J, bodies * sizeof(Rec<float>)));
-    BATCH_TRY(hipMalloc((void**)&b->V, bodies * sizeof(Vec2<float>)));
-    BATCH_TRY(hipMalloc((void**)&b->S_J, bodies * sizeof(Rec<float>)));
-    BATCH_TRY(hipMalloc((void**)&b->S_V, bodies * sizeof(Vec2<float>)));
-    BATCH_TRY(hipMalloc((void**)&b->meta, sizeof(Meta) * (size_t)b->S));
-    BATCH_TRY(hipMalloc((void**)&b->counters, sizeof(Counters) * (size_t)b->S));
-    BATCH_TRY(hipMalloc((void**)&b->params, sizeof(StepParams<float>) * (size_t)b->S));
-    BATCH_TRY(hipMalloc((void**)&b->blk_counts, sizeof(int) * (size_t)b->S * (size_t)(b->cap / kCommitLarge + 1)));
-    if (log) BATCH_TRY(hipMalloc((void**)&b->events, sizeof(Event) * (size_t)b->S * (size_t)ev_cap));
-    if (d->flags & NBODY_FLAG_TRACK_IDS) {
-        BATCH_TRY(hipMalloc((void**)&b->ids.map[0], bodies * sizeof(int32_t)));
-        BATCH_TRY(hipMalloc((void**)&b->ids.map[1], bodies * sizeof(int32_t)));
-        if (log) {
-            BATCH_TRY(hipMalloc((void**)&b->ids.lineage, sizeof(IdPair) * (size_t)b->S * (size_t)ev_cap));
-            BATCH_TRY(hipMalloc((void**)&b->ids.done, sizeof(unsigned long long) * (size_t)b->S));
-            BATCH_TRY(hipMemsetAsync(b->ids.done, 0, sizeof(unsigned long long) * (size_t)b->S, b->stream));
-        }
-    }
-    BATCH_TRY(hipHostMalloc((void**)&b->h_meta, sizeof(Meta) * (size_t)b->S, hipHostMallocDefault));
-    BATCH_TRY(hipHostMalloc((void**)&b->h_counters, sizeof(Counters) * (size_t)b->S, hipHostMallocDefault));
+    BATCH_TRY(b->own.device(&b->J, bodies * sizeof(Rec<float>)));
+    BATCH_TRY(b->own.device(&b->V, bodies * sizeof(Vec2<float>)));
+    BATCH_TRY(b->own.device(&b->S_J, bodies * sizeof(Rec<float>)));
+    BATCH_TRY(b->own.device(&b->S_V, bodies * sizeof(Vec2<float>)));
+    BATCH_TRY(b->own.device(&b->meta, sizeof(Meta) * (size_t)b->S));
+    BATCH_TRY(b->own.device(&b->counters, sizeof(Counters) * (size_t)b->S));
+    BATCH_TRY(b->own.device(&b->params, sizeof(StepParams<float>) * (size_t)b->S));
+    BATCH_TRY(b->own.device(&b->blk_counts, sizeof(int) * (size_t)b->S * (size_t)(b->cap / kCommitLarge + 1)));
+    if (log) BATCH_TRY(b->own.device(&b->events, sizeof(Event) * (size_t)b->S * (size_t)ev_cap));
+    if (d->flags & NBODY_FLAG_TRACK_IDS) BATCH_TRY(ids_alloc(b->ids, b->stream, (size_t)b->S, (size_t)b->cap, (size_t)ev_cap));
+    BATCH_TRY(b->own.host(&b->h_meta, sizeof(Meta) * (size_t)b->S));
+    BATCH_TRY(b->own.host(&b->h_counters, sizeof(Counters) * (size_t)b->S));
     memset(b->h_meta, 0, sizeof(Meta) * (size_t)b->S);
     memset(b->h_counters, 0, sizeof(Counters) * (size_t)b->S);
     b->h_stage_bytes = bodies * (sizeof(Rec<float>) + sizeof(Vec2<float>));
@@ -506,11 +429,7 @@ int nbody_batch_get_events(nbody_batch* b, int system, nbody_event* out, int cap
     HIP_TRY(hipSetDevice(b->desc.device));
     rc = read_meta(b);
     if (rc != NBODY_OK) return rc;
-    const unsigned long long tot = b->h_counters[system].events;
-    *total = (int64_t)tot;
-    const unsigned long long ncopy = log_prefix(tot, b->ev_cap, cap);
-    if (ncopy) HIP_TRY(hipMemcpy(out, b->events + (size_t)system * (size_t)b->ev_cap, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
-    return NBODY_OK;
+    return events_read(b->events + (size_t)system * (size_t)b->ev_cap, b->h_counters[system].events, b->ev_cap, out, cap, total);
 }
 
 int nbody_batch_get_ids(nbody_batch* b, int system, int32_t* ids, int cap, int* n_out) {
@@ -522,14 +441,8 @@ int nbody_batch_get_ids(nbody_batch* b, int system, int32_t* ids, int cap, int* 
     HIP_TRY(hipSetDevice(b->desc.device));
     rc = read_meta(b);
     if (rc != NBODY_OK) return rc;
-    const int n = b->h_meta[system].n;
-    if (n < 0 || n > b->cap) return nbody_fail(NBODY_ERR_STATE, "system %d reports %d bodies, capacity %d", system, n, b->cap);
-    const int k = n < cap ? n : cap;
-    if (k > 0)
-        HIP_TRY(hipMemcpy(ids, b->ids.map[b->ids.cur] + (size_t)system * (size_t)b->cap, sizeof(int32_t) * (size_t)k,
-                          hipMemcpyDeviceToHost));
-    *n_out = n;
-    return NBODY_OK;
+    return ids_read("nbody_batch_get_ids", b->ids.current() + (size_t)system * (size_t)b->cap, b->h_meta[system].n, b->cap, ids, cap,
+                    n_out);
 }
 
 int nbody_batch_get_lineage(nbody_batch* b, int system, nbody_lineage* out, int cap, int64_t* total) {
@@ -542,12 +455,9 @@ int nbody_batch_get_lineage(nbody_batch* b, int system, nbody_lineage* out, int 
     HIP_TRY(hipSetDevice(b->desc.device));
     rc = read_meta(b);                                     // synchronises; a failed index check of a translation ends here
     if (rc != NBODY_OK) return rc;
-    const unsigned long long tot = b->h_counters[system].events;
-    *total = (int64_t)tot;
-    const unsigned long long ncopy = log_prefix(tot, b->ev_cap, cap);
     const size_t first = (size_t)system * (size_t)b->ev_cap;
-    if (ncopy) HIP_TRY(lineage_read(b->events + first, b->ids.lineage + first, b->ids.done + system, ncopy, out));
-    return NBODY_OK;
+    return lineage_read(b->events + first, b->ids.lineage + first, b->ids.done + system, b->h_counters[system].events, b->ev_cap, out,
+                        cap, total);
 }
 
 int nbody_batch_get_stats(nbody_batch* b, int system, nbody_stats* out) {
@@ -570,36 +480,23 @@ int nbody_batch_diagnostics(nbody_batch* b, nbody_diag* out, double* phi) {
     HIP_TRY(hipSetDevice(b->desc.device));
     int rc = diag_alloc_tiles(b);
     if (rc != NBODY_OK) return rc;
-    if (!b->dg_out) {
-        hipError_t e = hipMalloc((void**)&b->dg_out, sizeof(DiagOut) * (size_t)b->S);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_dg_out, sizeof(DiagOut) * (size_t)b->S, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void)hipFree(b->dg_out);
-            b->dg_out = nullptr; b->h_dg_out = nullptr;
-            return diag_fail_alloc(e, "output records");
-        }
-    }
     const size_t bodies = (size_t)b->S * (size_t)b->cap;
-    if (phi && !b->dg_phi) {
-        hipError_t e = hipMalloc((void**)&b->dg_phi, bodies * sizeof(double));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_dg_phi, bodies * sizeof(double), hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void)hipFree(b->dg_phi);
-            b->dg_phi = nullptr; b->h_dg_phi = nullptr;
-            return diag_fail_alloc(e, "potential buffer");
-        }
-    }
-    rc = enqueue_diagnostics(b, b->dg_out, phi ? b->dg_phi : nullptr);
+    hipError_t e = rows_reserve(b->dg_out, (size_t)b->S);
+    if (e != hipSuccess) return rows_alloc_failed(e, "batch diagnostics", "output records");
+    if (phi && (e = rows_reserve(b->dg_phi, bodies)) != hipSuccess) return rows_alloc_failed(e, "batch diagnostics", "potential buffer");
+    rc = enqueue_diagnostics(b, b->dg_out.d, phi ? b->dg_phi.d : nullptr);
     if (rc != NBODY_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(b->h_dg_out, b->dg_out, sizeof(DiagOut) * (size_t)b->S, hipMemcpyDeviceToHost, b->stream));
-    if (phi) HIP_TRY(hipMemcpyAsync(b->h_dg_phi, b->dg_phi, bodies * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->dg_out.h, b->dg_out.d, sizeof(DiagOut) * (size_t)b->S, hipMemcpyDeviceToHost, b->stream));
+    if (phi) HIP_TRY(hipMemcpyAsync(b->dg_phi.h, b->dg_phi.d, bodies * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     rc = read_meta(b);                                     // synchronises; a system whose count failed its check ends here
     if (rc != NBODY_OK) return rc;
-    memcpy(out, b->h_dg_out, sizeof(DiagOut) * (size_t)b->S);
+    const DiagOut* h_out = reinterpret_cast<const DiagOut*>(b->dg_out.h);
+    const double* h_phi = reinterpret_cast<const double*>(b->dg_phi.h);
+    memcpy(out, h_out, sizeof(DiagOut) * (size_t)b->S);
     if (phi)
         for (int s = 0; s < b->S; ++s) {
-            const long long n = b->h_dg_out[s].n_bodies;   // what the kernels used: 0..cap
-            if (n > 0) memcpy(phi + (size_t)s * b->cap, b->h_dg_phi + (size_t)s * b->cap, (size_t)n * sizeof(double));
+            const long long n = h_out[s].n_bodies;         // what the kernels used: 0..cap
+            if (n > 0) memcpy(phi + (size_t)s * b->cap, h_phi + (size_t)s * b->cap, (size_t)n * sizeof(double));
         }
     return NBODY_OK;
 }
@@ -613,16 +510,15 @@ int nbody_batch_diag_reserve(nbody_batch* b, int samples) {
                           samples, b->S, bytes);
     HIP_TRY(hipSetDevice(b->desc.device));
     HIP_TRY(hipStreamSynchronize(b->stream));              // records in flight write the log that is about to go
-    if (b->dg_log) HIP_TRY(hipFree(b->dg_log));
-    b->dg_log = nullptr;
+    rows_free(b->dg_log);
     b->log_cap = 0;
     b->log_rows = 0;
     if (samples == 0) return NBODY_OK;
     int rc = diag_alloc_tiles(b);                          // here, so that a record allocates nothing
     if (rc != NBODY_OK) return rc;
-    hipError_t e = hipMalloc((void**)&b->dg_log, (size_t)bytes);
-    if (e != hipSuccess) { b->dg_log = nullptr; return diag_fail_alloc(e, "recorded series"); }
-    HIP_TRY(hipMemsetAsync(b->dg_log, 0, (size_t)bytes, b->stream));
+    const hipError_t e = rows_reserve_device(b->dg_log, (size_t)samples * (size_t)b->S);
+    if (e != hipSuccess) return rows_alloc_failed(e, "batch diagnostics", "recorded series");
+    HIP_TRY(hipMemsetAsync(b->dg_log.d, 0, (size_t)bytes, b->stream));
     b->log_cap = samples;
     return NBODY_OK;
 }
@@ -630,11 +526,11 @@ int nbody_batch_diag_reserve(nbody_batch* b, int samples) {
 int nbody_batch_diag_record(nbody_batch* b) {
     if (!b) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_diag_record: NULL batch");
     if (!b->uploaded) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_diag_record before nbody_batch_upload");
-    if (!b->dg_log) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_diag_record without a reservation (nbody_batch_diag_reserve)");
+    if (!b->dg_log.d) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_diag_record without a reservation (nbody_batch_diag_reserve)");
     if (b->log_rows >= b->log_cap)
         return nbody_fail(NBODY_ERR_CAPACITY, "nbody_batch_diag_record: the log holds its %d samples already", b->log_cap);
     HIP_TRY(hipSetDevice(b->desc.device));
-    int rc = enqueue_diagnostics(b, b->dg_log + (size_t)b->log_rows * (size_t)b->S, nullptr);
+    int rc = enqueue_diagnostics(b, b->dg_log.d + (size_t)b->log_rows * (size_t)b->S, nullptr);
     if (rc != NBODY_OK) return rc;
     b->log_rows += 1;
     return NBODY_OK;
@@ -648,7 +544,7 @@ int nbody_batch_diag_read(nbody_batch* b, nbody_diag* out, int cap_samples, int*
     if (rc != NBODY_OK) return rc;
     const int rows = b->log_rows < cap_samples ? b->log_rows : cap_samples;
     if (rows > 0)
-        HIP_TRY(hipMemcpy(out, b->dg_log, (size_t)rows * (size_t)b->S * sizeof(DiagOut), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, b->dg_log.d, (size_t)rows * (size_t)b->S * sizeof(DiagOut), hipMemcpyDeviceToHost));
     *n_samples = b->log_rows;
     return NBODY_OK;
 }
@@ -684,7 +580,7 @@ void ids_step(nbody_batch* b, int nblk, int threads) {
 int ids_restart(nbody_batch* b) {
     ids_enqueue_fill<kIdsBlock>(b->ids, b->stream, b->S, b->cap);
     HIP_TRY(hipGetLastError());
-    if (b->ids.done) HIP_TRY(hipMemsetAsync(b->ids.done, 0, sizeof(unsigned long long) * (size_t)b->S, b->stream));
+    HIP_TRY(ids_clear_done(b->ids, b->stream, (size_t)b->S));
     return NBODY_OK;
 }
 
@@ -707,7 +603,7 @@ int nbody_batch_track_record(nbody_batch* b) {
     if (!b->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_batch_track_record: the batch was created without NBODY_FLAG_TRACK_IDS");
     return track_record<float>(b->trk, b->stream, b->desc.device, "nbody_batch_track_record", b->uploaded,
                                (const Rec<float>*)b->J, (const Vec2<float>*)b->V, (const Meta*)b->meta, b->counters,
-                               (const int32_t*)b->ids.map[b->ids.cur], b->cap);
+                               b->ids.current(), b->cap);
 }
 
 int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int32_t* index, double* phi, int cap_samples,
@@ -729,6 +625,9 @@ int nbody_batch_track_read(nbody_batch* b, nbody_track_row* rows, void* rec, int
 // of points and edges for all of them.  At the end of the file for the reason the identities are.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
+
+// The systems as an entry point's argument checks count them: those come before the check of the handle itself.
+unsigned long long batch_systems(const nbody_batch* b) { return b ? (unsigned long long)b->S : 1; }
 
 // What every row query of a batch begins with.  It makes no read before the launch: the grid covers the largest uploaded
 // count (site.n_bound), each system's count comes from Meta on the device.
@@ -761,32 +660,32 @@ extern "C" {
 
 int nbody_batch_get_field(nbody_batch* b, const nbody_vec2* points, int m, nbody_field* out, int64_t* coincident) {
     const int rc = rows_check_args("nbody_batch_get_field", {b, out, coincident}, m,
-                                   (b ? (unsigned long long)b->S : 1) * sizeof(nbody_field), " of results");
+                                   batch_systems(b) * sizeof(nbody_field), " of results");
     if (rc != NBODY_OK) return rc;
-    return batch_rows(b, "nbody_batch_get_field", b->fld, FieldQuery{(double)kG, coincident}, points, m, out);
+    return batch_rows(b, "nbody_batch_get_field", b->q.fld, FieldQuery{(double)kG, coincident}, points, m, out);
 }
 
 int nbody_batch_get_neighbors(nbody_batch* b, const nbody_vec2* points, int m, nbody_neighbor* out) {
     const int rc = rows_check_args("nbody_batch_get_neighbors", {b, out}, m,
-                                   (b ? (unsigned long long)b->S : 1) * sizeof(nbody_neighbor), " of results");
+                                   batch_systems(b) * sizeof(nbody_neighbor), " of results");
     if (rc != NBODY_OK) return rc;
-    return batch_rows(b, "nbody_batch_get_neighbors", b->nbr, NeighborQuery{}, points, m, out);
+    return batch_rows(b, "nbody_batch_get_neighbors", b->q.nbr, NeighborQuery{}, points, m, out);
 }
 
 int nbody_batch_get_knn(nbody_batch* b, const nbody_vec2* points, int m, int k, double* d2, int32_t* index) {
-    const int rc = knn_check_args("nbody_batch_get_knn", {b, d2, index}, m, k, b ? (unsigned long long)b->S : 1);
+    const int rc = knn_check_args("nbody_batch_get_knn", {b, d2, index}, m, k, batch_systems(b));
     if (rc != NBODY_OK) return rc;
     KnnResult out{d2, index};
-    return batch_rows(b, "nbody_batch_get_knn", b->knn, KnnQuery{k}, points, m, &out);
+    return batch_rows(b, "nbody_batch_get_knn", b->q.knn, KnnQuery{k}, points, m, &out);
 }
 
 int nbody_batch_get_shells(nbody_batch* b, const nbody_vec2* points, int m, const double* edges2, int bins, double* mass,
                            int32_t* count) {
     const int rc = shells_check_args("nbody_batch_get_shells", {b, edges2, mass, count}, m, edges2, bins,
-                                     b ? (unsigned long long)b->S : 1);
+                                     batch_systems(b));
     if (rc != NBODY_OK) return rc;
     ShellResult out{mass, count};
-    return batch_rows(b, "nbody_batch_get_shells", b->shl, ShellQuery{edges2, bins}, points, m, &out);
+    return batch_rows(b, "nbody_batch_get_shells", b->q.shl, ShellQuery{edges2, bins}, points, m, &out);
 }
 
 // Shell moments (nbody_shell_moments.hpp): one set of points, point velocities and edges for every system, one launch.
@@ -794,10 +693,10 @@ int nbody_batch_get_shell_moments(nbody_batch* b, const nbody_vec2* points, cons
                                   const double* edges2, int bins, nbody_shell_moment* out) {
     const char* who = "nbody_batch_get_shell_moments";
     RowsSite site;
-    int rc = shell_moments_check_args(who, {b, out}, points, point_vel, m, edges2, bins, b ? (unsigned long long)b->S : 1);
+    int rc = shell_moments_check_args(who, {b, out}, points, point_vel, m, edges2, bins, batch_systems(b));
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return shell_moments_run<decltype(t), RowsBatchCount>(who, site, b->shm, b->V, points, point_vel, m, edges2, bins, out,
+        return shell_moments_run<decltype(t), RowsBatchCount>(who, site, b->q.shm, b->V, points, point_vel, m, edges2, bins, out,
                                                               sync);
     });
 }
@@ -808,7 +707,7 @@ int nbody_batch_get_groups(nbody_batch* b, double link, double radius_scale, int
     int rc = groups_check_args(who, link, radius_scale, {b, label, info});
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return groups_run<decltype(t), RowsBatchCount>(who, site, b->grp, link, radius_scale, label, info, sync);
+        return groups_run<decltype(t), RowsBatchCount>(who, site, b->q.grp, link, radius_scale, label, info, sync);
     });
 }
 
@@ -819,7 +718,7 @@ int nbody_batch_get_pair_counts(nbody_batch* b, const nbody_vec2* points, int m,
     int rc = pairs_check_args(who, {b, edges2, counts, info}, m, edges2, bins);
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return pairs_run<decltype(t), RowsBatchCount>(who, site, b->prs, points, m, edges2, bins, counts, info, sync);
+        return pairs_run<decltype(t), RowsBatchCount>(who, site, b->q.prs, points, m, edges2, bins, counts, info, sync);
     });
 }
 
@@ -827,10 +726,10 @@ int nbody_batch_get_pair_counts(nbody_batch* b, const nbody_vec2* points, int m,
 int nbody_batch_get_encounters(nbody_batch* b, double horizon, nbody_encounter* out, int cap, nbody_encounter_info* info) {
     const char* who = "nbody_batch_get_encounters";
     RowsSite site;
-    int rc = pair_log_check_args(who, b, EncQuery{horizon}, out, cap, info, b ? (unsigned long long)b->S : 1);
+    int rc = pair_log_check_args(who, b, EncQuery{horizon}, out, cap, info, batch_systems(b));
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return pair_log_run<decltype(t), RowsBatchCount>(who, site, b->V, b->enc, EncQuery{horizon}, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsBatchCount>(who, site, b->V, b->q.enc, EncQuery{horizon}, out, cap, info, sync);
     });
 }
 
@@ -838,10 +737,10 @@ int nbody_batch_get_encounters(nbody_batch* b, double horizon, nbody_encounter* 
 int nbody_batch_get_binaries(nbody_batch* b, double sep2, nbody_binary* out, int cap, nbody_binary_info* info) {
     const char* who = "nbody_batch_get_binaries";
     RowsSite site;
-    int rc = pair_log_check_args(who, b, BinQuery{sep2}, out, cap, info, b ? (unsigned long long)b->S : 1);
+    int rc = pair_log_check_args(who, b, BinQuery{sep2}, out, cap, info, batch_systems(b));
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return pair_log_run<decltype(t), RowsBatchCount>(who, site, b->V, b->bin, BinQuery{sep2}, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsBatchCount>(who, site, b->V, b->q.bin, BinQuery{sep2}, out, cap, info, sync);
     });
 }
 
@@ -850,10 +749,10 @@ int nbody_batch_get_tides(nbody_batch* b, const nbody_vec2* points, const nbody_
                           nbody_vec2* jerk, int64_t* coincident) {
     const char* who = "nbody_batch_get_tides";
     RowsSite site;
-    int rc = tides_check_args(who, {b, tide, coincident}, points, point_vel, jerk, m, b ? (unsigned long long)b->S : 1);
+    int rc = tides_check_args(who, {b, tide, coincident}, points, point_vel, jerk, m, batch_systems(b));
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return tides_run<decltype(t), RowsBatchCount>(who, site, b->tid, (double)kG, b->V, points, point_vel, m, tide, jerk,
+        return tides_run<decltype(t), RowsBatchCount>(who, site, b->q.tid, (double)kG, b->V, points, point_vel, m, tide, jerk,
                                                       coincident, sync);
     });
 }
@@ -861,16 +760,16 @@ int nbody_batch_get_tides(nbody_batch* b, const nbody_vec2* points, const nbody_
 // Tracers (nbody_tracers.hpp): the same m for every system, one launch per ensemble step.
 int nbody_batch_tracers_set(nbody_batch* b, const nbody_tracer* t, int m, uint32_t flags) {
     const char* who = "nbody_batch_tracers_set";
-    const int rc = tracers_check_set(who, b, t, m, flags, b ? b->S : 1);
+    const int rc = tracers_check_set(who, b, t, m, flags, (int)batch_systems(b));
     if (rc != NBODY_OK) return rc;
     HIP_TRY(hipSetDevice(b->desc.device));
-    return tracers_set(who, b->trc, b->stream, b->S, t, m, flags);
+    return tracers_set(who, b->q.trc, b->stream, b->S, t, m, flags);
 }
 
 int nbody_batch_tracers_get(nbody_batch* b, nbody_tracer* out, nbody_field* last, nbody_tracer_info* info) {
     if (!b || !info) return nbody_fail(NBODY_ERR_INVALID, "nbody_batch_tracers_get: NULL argument");
     HIP_TRY(hipSetDevice(b->desc.device));
-    return tracers_get(b->trc, b->stream, b->S, out, last, out ? b->trc.m : 0, info, [b] { return read_meta(b); });
+    return tracers_get(b->q.trc, b->stream, b->S, out, last, out ? b->q.trc.m : 0, info, [b] { return read_meta(b); });
 }
 
 // Group energies (nbody_group_energy.hpp): every sweep and the potential ONE launch each for the whole batch.
@@ -881,7 +780,7 @@ int nbody_batch_get_group_potential(nbody_batch* b, double link, double radius_s
     int rc = groups_check_args(who, link, radius_scale, {b, label, phi_in, info});
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return group_energy_run<decltype(t), RowsBatchCount>(who, site, b->grp, b->gen, (double)kG, link, radius_scale, label, phi_in,
+        return group_energy_run<decltype(t), RowsBatchCount>(who, site, b->q.grp, b->q.gen, (double)kG, link, radius_scale, label, phi_in,
                                                              info, sync);
     });
 }
@@ -896,10 +795,10 @@ int nbody_batch_get_cells(nbody_batch* b, const nbody_grid* grid, uint32_t flags
                           int32_t* start, int32_t* order, nbody_cells_info* info) {
     const char* who = "nbody_batch_get_cells";
     RowsSite site;
-    int rc = cells_check_args(who, {b, cells, info}, grid, flags, cell_of, start, order, 0, b ? (unsigned long long)b->S : 1);
+    int rc = cells_check_args(who, {b, cells, info}, grid, flags, cell_of, start, order, 0, batch_systems(b));
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return cells_run<decltype(t), RowsBatchCount>(who, site, b->cel, b->V, *grid, flags, cells, cell_of, start, order, info, sync);
+        return cells_run<decltype(t), RowsBatchCount>(who, site, b->q.cel, b->V, *grid, flags, cells, cell_of, start, order, info, sync);
     });
 }
 
@@ -913,10 +812,10 @@ int nbody_batch_get_within(nbody_batch* b, const nbody_grid* grid, double h2, co
                            int64_t* start, int32_t* list, int cap, nbody_within_info* info) {
     const char* who = "nbody_batch_get_within";
     RowsSite site;
-    int rc = within_check_args(who, {b, out, info}, grid, h2, m, start, list, cap, b ? (unsigned long long)b->S : 1);
+    int rc = within_check_args(who, {b, out, info}, grid, h2, m, start, list, cap, batch_systems(b));
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return within_run<decltype(t), RowsBatchCount>(who, site, b->cel, b->wth, *grid, h2, points, m, out, start, list, cap, info,
+        return within_run<decltype(t), RowsBatchCount>(who, site, b->q.cel, b->q.wth, *grid, h2, points, m, out, start, list, cap, info,
                                                        sync);
     });
 }

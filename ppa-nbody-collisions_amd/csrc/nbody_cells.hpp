@@ -420,16 +420,6 @@ inline void cells_free(CellState& g) {
     rows_free(g.slot);
 }
 
-// Device only: the scratch nothing reads back.
-template <typename E>
-inline hipError_t cells_reserve_device(RowsArray<E>& f, size_t n) {
-    if (n <= f.cap) return hipSuccess;
-    rows_free(f);
-    const hipError_t e = hipMalloc((void**)&f.d, n * sizeof(E));
-    if (e == hipSuccess) f.cap = n;
-    return e;
-}
-
 // sums: with the cell records; a caller that needs the list only (nbody_within.hpp) leaves them out.
 inline int cells_reserve(CellState& g, size_t systems, size_t cells, size_t bodies, const char* who, bool sums = true) {
     hipError_t e = sums ? rows_reserve(g.cells, systems * cells) : hipSuccess;
@@ -437,12 +427,11 @@ inline int cells_reserve(CellState& g, size_t systems, size_t cells, size_t bodi
     if (e == hipSuccess) e = rows_reserve(g.cell_of, bodies > 0 ? bodies : 1);
     if (e == hipSuccess) e = rows_reserve(g.order, bodies > 0 ? bodies : 1);
     if (e == hipSuccess) e = rows_reserve(g.info, systems);
-    if (e == hipSuccess) e = cells_reserve_device(g.words, 2 * systems * cells);
-    if (e == hipSuccess) e = cells_reserve_device(g.slot, bodies > 0 ? bodies : 1);
+    if (e == hipSuccess) e = rows_reserve_device(g.words, 2 * systems * cells);
+    if (e == hipSuccess) e = rows_reserve_device(g.slot, bodies > 0 ? bodies : 1);
     if (e == hipSuccess) return NBODY_OK;
-    (void)hipGetLastError();
     cells_free(g);
-    return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, cell buffers: %s", who, hipGetErrorString(e));
+    return rows_alloc_failed(e, who, "cell buffers");
 }
 
 // The argument checks an entry point makes before any device call, the values before the handle so that each can be seen

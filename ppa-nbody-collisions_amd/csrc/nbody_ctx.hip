@@ -22,23 +22,7 @@
 #include "nbody_error.h"
 #include "nbody_kernels.hpp"
 #include "nbody_diag.hpp"
-#include "nbody_rows.hpp"
-#include "nbody_field.hpp"
-#include "nbody_tracers.hpp"
-#include "nbody_ids.hpp"
-#include "nbody_tracks.hpp"
-#include "nbody_neighbors.hpp"
-#include "nbody_groups.hpp"
-#include "nbody_group_energy.hpp"
-#include "nbody_pairs.hpp"
-#include "nbody_knn.hpp"
-#include "nbody_shells.hpp"
-#include "nbody_shell_moments.hpp"
-#include "nbody_cells.hpp"
-#include "nbody_within.hpp"
-#include "nbody_encounters.hpp"
-#include "nbody_binaries.hpp"
-#include "nbody_tides.hpp"
+#include "nbody_queries.hpp"
 
 using namespace nbk;
 
@@ -118,6 +102,7 @@ struct nbody_ctx {
     int cap = 0;                // global capacity
     int cap_own = 0;            // own-range capacity
     hipStream_t stream = nullptr;
+    RowsOwned own;              // every device and pinned block made at create
     // device memory
     void* J = nullptr;          // Rec<T>[cap]
     void* Vown = nullptr;       // Vec2<T>[cap_own]
@@ -142,8 +127,7 @@ struct nbody_ctx {
     Counters* counters = nullptr;
     Event* events = nullptr;
     int ev_cap = 0;
-    unsigned char* d_img = nullptr;   // raster target, grown on demand
-    size_t d_img_bytes = 0;
+    RowsArray<unsigned char> d_img;   // device: raster target, grown on demand
     // host mirrors / staging
     void* h_stage = nullptr;    // pinned, max(cap*rec, cap*2*real ...)
     size_t h_stage_bytes = 0;
@@ -185,41 +169,15 @@ struct nbody_ctx {
     double xchg_ms = 0.0;
     int64_t xchg_launches = 0;
     // diagnostics (nbody_get_diagnostics): allocated on the first call
-    DiagTile* dg_tiles = nullptr;      // per own tile: partial sums (cap_own / 128 records)
-    double* dg_phi = nullptr;          // phi of the own range (cap_own doubles)
-    unsigned char* dg_gather = nullptr;    // world * (tiles | phi) of the padded per-rank areas
+    RowsArray<DiagTile> dg_tiles;      // device, per own tile: partial sums (cap_own / 128 records)
+    RowsArray<double> dg_phi;          // device: phi of the own range (cap_own doubles)
+    RowsArray<unsigned char> dg_gather;    // device: world * (tiles | phi) of the padded per-rank areas
     // identities (NBODY_FLAG_TRACK_IDS, nbody_ids.hpp): nothing is allocated without the flag
     IdsState ids;                          // the map [cap_own] twice, the lineage [ev_cap], the translated-up-to counter
     // track log (nbody_track_*, nbody_tracks.hpp): nothing is allocated without a reservation
     TrackState trk;
-    // field evaluation (nbody_get_field, nbody_field.hpp): nothing is allocated before the first call
-    FieldState fld;
-    // neighbour queries (nbody_get_neighbors, nbody_neighbors.hpp): nothing is allocated before the first call
-    NeighborState nbr;
-    // group finding (nbody_get_groups, nbody_groups.hpp): nothing is allocated before the first call
-    GroupsState grp;
-    // group energies (nbody_get_group_potential, nbody_group_energy.hpp): nothing is allocated before the first call
-    GroupEnergyState gen;
-    // pair-separation counts (nbody_get_pair_counts, nbody_pairs.hpp): nothing is allocated before the first call
-    PairsState prs;
-    // k nearest neighbours (nbody_get_knn, nbody_knn.hpp): nothing is allocated before the first call
-    KnnState knn;
-    // shell sums (nbody_get_shells, nbody_shells.hpp): nothing is allocated before the first call
-    ShellState shl;
-    // shell moments (nbody_get_shell_moments, nbody_shell_moments.hpp): nothing is allocated before the first call
-    ShellMomentState shm;
-    // cell sums (nbody_get_cells, nbody_cells.hpp): nothing is allocated before the first call
-    CellState cel;
-    // radius queries (nbody_within.hpp): the cell list of `cel` and these; nothing is allocated before the first call
-    WithinState wth;
-    // encounter queries (nbody_get_encounters, nbody_encounters.hpp): nothing is allocated before the first call
-    EncState enc;
-    // bound-pair queries (nbody_get_binaries, nbody_binaries.hpp): nothing is allocated before the first call
-    BinState bin;
-    // tidal tensor and jerk (nbody_get_tides, nbody_tides.hpp): nothing is allocated before the first call
-    TidesState tid;
-    // tracer particles (nbody_tracers_set, nbody_tracers.hpp): nothing is allocated before the first set
-    TracerState trc;
+    // the queries (nbody_queries.hpp): nothing is allocated before the first call of each
+    QueryStates q;
 };
 
 namespace {
@@ -587,8 +545,8 @@ const unsigned char* part_of(const nbody_ctx* c, Part what) {
     switch (what) {
         case Part::Slot: return c->slot;
         case Part::Velocities: return (const unsigned char*)c->Vown;
-        case Part::DiagTiles: return (const unsigned char*)c->dg_tiles;
-        case Part::Potential: return (const unsigned char*)c->dg_phi;
+        case Part::DiagTiles: return (const unsigned char*)c->dg_tiles.d;
+        case Part::Potential: return (const unsigned char*)c->dg_phi.d;
         default: return (const unsigned char*)c->meta;
     }
 }
@@ -637,9 +595,9 @@ int compute_phase(nbody_ctx* c) {
 // Tracers (nbody_tracers.hpp): after the compute phase and before the commit, where J still holds step t.
 int tracer_phase(nbody_ctx* c) {
     if (c->desc.precision == NBODY_F64)
-        return tracers_enqueue<double, TracersOne>(c->trc, c->stream, 1, (const Rec<double>*)c->J, (const Meta*)c->meta, c->counters,
+        return tracers_enqueue<double, TracersOne>(c->q.trc, c->stream, 1, (const Rec<double>*)c->J, (const Meta*)c->meta, c->counters,
                                                    c->cap, tracer_params(make_params<double>(c->desc)), nullptr);
-    return tracers_enqueue<float, TracersOne>(c->trc, c->stream, 1, (const Rec<float>*)c->J, (const Meta*)c->meta, c->counters, c->cap,
+    return tracers_enqueue<float, TracersOne>(c->q.trc, c->stream, 1, (const Rec<float>*)c->J, (const Meta*)c->meta, c->counters, c->cap,
                                               tracer_params(make_params<float>(c->desc)), nullptr);
 }
 int commit_phase(nbody_ctx* c) {
@@ -663,34 +621,14 @@ void free_all(nbody_ctx* c) {
     for (hipEvent_t e : c->ev_free) hipEventDestroy(e);
     for (nbody_ctx::Landed& L : c->lag) {
         if (L.ev) hipEventDestroy(L.ev);
-        if (L.block) hipHostFree(L.block);
     }
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    hipFree(c->J); hipFree(c->Vown); hipFree(c->S_J); hipFree(c->S_V);
-    if (c->gather && c->gather != c->slot) hipFree(c->gather);
-    hipFree(c->slot);
-    hipFree(c->blk_counts); hipFree(c->tile_rmax); hipFree(c->Jt); hipFree(c->q_head); hipFree(c->q_done); hipFree(c->q_state); hipFree(c->meta); hipFree(c->meta_all); hipFree(c->events); hipFree(c->d_img);
-    hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
-    hipFree(c->ids.map[0]); hipFree(c->ids.map[1]); hipFree(c->ids.lineage); hipFree(c->ids.done);
-    hipFree(c->trk.buf); hipFree(c->trk.sel);
-    rows_free(c->fld);
-    rows_free(c->nbr);
-    groups_free(c->grp);
-    rows_free(c->gen);
-    pairs_free(c->prs);
-    pair_log_free(c->enc);
-    pair_log_free(c->bin);
-    tides_free(c->tid);
-    rows_free(c->knn);
-    rows_free(c->shl);
-    shell_moments_free(c->shm);
-    cells_free(c->cel);
-    within_free(c->wth);
-    tracers_free(c->trc);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->h_meta) hipHostFree(c->h_meta);
-    if (c->h_meta_async) hipHostFree(c->h_meta_async);
-    if (c->h_counters) hipHostFree(c->h_counters);
+    c->own.release();
+    ids_free(c->ids);
+    track_free(c->trk);
+    queries_free(c->q);
+    rows_free(c->d_img);
+    rows_free(c->dg_tiles); rows_free(c->dg_phi); rows_free(c->dg_gather);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -704,18 +642,13 @@ size_t diag_tile_area(const nbody_ctx* c, int n) { return (size_t)(own_upper_of(
 size_t diag_phi_area(const nbody_ctx* c, int n) { return (size_t)own_upper_of(c, n) * sizeof(double); }
 
 int diag_alloc(nbody_ctx* c) {
-    if (c->dg_gather) return NBODY_OK;
-    const size_t tb = (size_t)(c->cap_own / kTile) * sizeof(DiagTile), pb = (size_t)c->cap_own * sizeof(double);
-    hipError_t e = hipMalloc((void**)&c->dg_tiles, tb);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->dg_phi, pb);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->dg_gather, (tb + pb) * (size_t)c->desc.world);
-    if (e != hipSuccess) {
-        hipFree(c->dg_tiles); hipFree(c->dg_phi); hipFree(c->dg_gather);
-        c->dg_tiles = nullptr; c->dg_phi = nullptr; c->dg_gather = nullptr;
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "diagnostics buffers: %s",
-                          hipGetErrorString(e));
-    }
-    return NBODY_OK;
+    const size_t tiles = (size_t)(c->cap_own / kTile), tb = tiles * sizeof(DiagTile), pb = (size_t)c->cap_own * sizeof(double);
+    hipError_t e = rows_reserve_device(c->dg_tiles, tiles);
+    if (e == hipSuccess) e = rows_reserve_device(c->dg_phi, (size_t)c->cap_own);
+    if (e == hipSuccess) e = rows_reserve_device(c->dg_gather, (tb + pb) * (size_t)c->desc.world);
+    if (e == hipSuccess) return NBODY_OK;
+    rows_free(c->dg_tiles); rows_free(c->dg_phi); rows_free(c->dg_gather);
+    return rows_alloc_failed(e, "diagnostics", "tile, potential and gather buffers");
 }
 
 // The own range's kernels, on the context's stream.  Needs the exact {n, lo, cnt} of a read_meta just before.
@@ -727,9 +660,9 @@ int diag_launch_t(nbody_ctx* c) {
         return nbody_fail(NBODY_ERR_STATE, "own range [%d, +%d) of %d bodies does not fit the context", lo, cnt, n);
     const int tiles = (cnt + kTile - 1) / kTile;
     hipLaunchKernelGGL((diag_moments<T>), dim3((tiles + kWave - 1) / kWave), dim3(kWave), 0, c->stream,
-                       (const Rec<T>*)c->J, (const Vec2<T>*)c->Vown, lo, cnt, c->dg_tiles);
+                       (const Rec<T>*)c->J, (const Vec2<T>*)c->Vown, lo, cnt, c->dg_tiles.d);
     hipLaunchKernelGGL((diag_potential<T>), dim3((cnt + kDiagBlock - 1) / kDiagBlock), dim3(kDiagBlock), 0, c->stream,
-                       (const Rec<T>*)c->J, n, lo, cnt, (double)kG, c->dg_phi, c->dg_tiles);
+                       (const Rec<T>*)c->J, n, lo, cnt, (double)kG, c->dg_phi.d, c->dg_tiles.d);
     HIP_TRY(hipGetLastError());
     return NBODY_OK;
 }
@@ -746,13 +679,13 @@ int diag_collect(nbody_ctx* c, nbody_diag* out, double* phi) {
     const int n = c->h_meta->n, world = c->desc.world;
     const int U = own_upper_of(c, n);
     const size_t tb = diag_tile_area(c, n), pb = diag_phi_area(c, n);
-    unsigned char* gt = c->dg_gather;
-    unsigned char* gp = c->dg_gather + tb * world;
+    unsigned char* gt = c->dg_gather.d;
+    unsigned char* gp = c->dg_gather.d + tb * world;
     std::vector<Meta> h_all(world);
     if (world == 1 && !c->comm) {
         h_all[0] = *c->h_meta;
-        if (tb) HIP_TRY(hipMemcpyAsync(gt, c->dg_tiles, tb, hipMemcpyDeviceToDevice, c->stream));
-        if (pb && phi) HIP_TRY(hipMemcpyAsync(gp, c->dg_phi, pb, hipMemcpyDeviceToDevice, c->stream));
+        if (tb) HIP_TRY(hipMemcpyAsync(gt, c->dg_tiles.d, tb, hipMemcpyDeviceToDevice, c->stream));
+        if (pb && phi) HIP_TRY(hipMemcpyAsync(gp, c->dg_phi.d, pb, hipMemcpyDeviceToDevice, c->stream));
     } else if (c->comm || c->peers) {
         int rc = tb ? all_gather(c, Part::DiagTiles, gt, tb) : NBODY_OK;    // n is the same on every rank
         if (rc == NBODY_OK && pb) rc = all_gather(c, Part::Potential, gp, pb);
@@ -854,55 +787,47 @@ int nbody_ctx_create(nbody_ctx** out, const nbody_ctx_desc* d) {
     do {                                                                                                  \
         hipError_t e__ = (expr);                                                                          \
         if (e__ != hipSuccess) {                                                                          \
-            int rc__ = nbody_fail(e__ == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP,           \
-                                  "%s failed: %s", #expr, hipGetErrorString(e__));                        \
+            int rc__ = rows_alloc_failed(e__, "nbody_ctx_create", #expr);                                 \
             free_all(c);                                                                                  \
             return rc__;                                                                                  \
         }                                                                                                 \
     } while (0)
 
     CTX_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    CTX_TRY(hipMalloc(&c->J, (size_t)c->cap * c->rec_bytes));
-    CTX_TRY(hipMalloc(&c->Vown, (size_t)c->cap_own * 2 * c->real_bytes));
-    CTX_TRY(hipMalloc(&c->S_J, (size_t)c->cap_own * c->rec_bytes));
-    CTX_TRY(hipMalloc(&c->S_V, (size_t)c->cap_own * 2 * c->real_bytes));
-    CTX_TRY(hipMalloc((void**)&c->slot, c->slot_bytes));
+    CTX_TRY(c->own.device(&c->J, (size_t)c->cap * c->rec_bytes));
+    CTX_TRY(c->own.device(&c->Vown, (size_t)c->cap_own * 2 * c->real_bytes));
+    CTX_TRY(c->own.device(&c->S_J, (size_t)c->cap_own * c->rec_bytes));
+    CTX_TRY(c->own.device(&c->S_V, (size_t)c->cap_own * 2 * c->real_bytes));
+    CTX_TRY(c->own.device(&c->slot, c->slot_bytes));
     const bool use_comm = (d->world > 1 && !(d->flags & NBODY_FLAG_GROUP_EXCHANGE)) || (d->flags & NBODY_FLAG_FORCE_COMM);
-    if (d->world > 1 || use_comm) CTX_TRY(hipMalloc((void**)&c->gather, c->slot_bytes * d->world));
+    if (d->world > 1 || use_comm) CTX_TRY(c->own.device(&c->gather, c->slot_bytes * d->world));
     else c->gather = c->slot;
-    CTX_TRY(hipMalloc((void**)&c->blk_counts, sizeof(int) * (size_t)(c->cap_own / kCompactBlock + 2)));
+    CTX_TRY(c->own.device(&c->blk_counts, sizeof(int) * (size_t)(c->cap_own / kCompactBlock + 2)));
     c->n_tiles = c->cap / kTile + 2;
-    CTX_TRY(hipMalloc((void**)&c->tile_rmax, sizeof(unsigned) * (size_t)c->n_tiles));
+    CTX_TRY(c->own.device(&c->tile_rmax, sizeof(unsigned) * (size_t)c->n_tiles));
     CTX_TRY(hipMemset(c->tile_rmax, 0, sizeof(unsigned) * (size_t)c->n_tiles));
     if (d->precision != NBODY_F64) {
-        CTX_TRY(hipMalloc((void**)&c->Jt, sizeof(float) * 4 * kTile * (size_t)c->n_tiles));
+        CTX_TRY(c->own.device(&c->Jt, sizeof(float) * 4 * kTile * (size_t)c->n_tiles));
         CTX_TRY(hipMemset(c->Jt, 0, sizeof(float) * 4 * kTile * (size_t)c->n_tiles));
         c->q_rings_cap = 2 * (c->cap_own / kTile + 2);
-        CTX_TRY(hipMalloc((void**)&c->q_head, 64));
+        CTX_TRY(c->own.device(&c->q_head, 64));
         CTX_TRY(hipMemset(c->q_head, 0, 64));
-        CTX_TRY(hipMalloc((void**)&c->q_done, sizeof(unsigned long long) * (size_t)c->q_rings_cap));
+        CTX_TRY(c->own.device(&c->q_done, sizeof(unsigned long long) * (size_t)c->q_rings_cap));
         CTX_TRY(hipMemset(c->q_done, 0, sizeof(unsigned long long) * (size_t)c->q_rings_cap));
-        CTX_TRY(hipMalloc((void**)&c->q_state, sizeof(unsigned long long) * 4 * 64 * (size_t)c->q_rings_cap));
+        CTX_TRY(c->own.device(&c->q_state, sizeof(unsigned long long) * 4 * 64 * (size_t)c->q_rings_cap));
     }
     // Meta and Counters share one device block (and one pinned host block): the per-step look at them is ONE copy
-    CTX_TRY(hipMalloc((void**)&c->meta, kMetaBlockBytes));
+    CTX_TRY(c->own.device(&c->meta, kMetaBlockBytes));
     c->counters = reinterpret_cast<Counters*>(reinterpret_cast<unsigned char*>(c->meta) + kCountersOffset);
-    if (use_comm || d->world > 1) CTX_TRY(hipMalloc((void**)&c->meta_all, sizeof(Meta) * (size_t)d->world));
+    if (use_comm || d->world > 1) CTX_TRY(c->own.device(&c->meta_all, sizeof(Meta) * (size_t)d->world));
     for (nbody_ctx::Landed& L : c->lag) {
         CTX_TRY(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
-        CTX_TRY(hipHostMalloc((void**)&L.block, kMetaBlockBytes, hipHostMallocDefault));
+        CTX_TRY(c->own.host(&L.block, kMetaBlockBytes));
         memset(L.block, 0, kMetaBlockBytes);
     }
-    CTX_TRY(hipMalloc((void**)&c->events, sizeof(Event) * (size_t)c->ev_cap));
-    if (d->flags & NBODY_FLAG_TRACK_IDS) {
-        CTX_TRY(hipMalloc((void**)&c->ids.map[0], sizeof(int32_t) * (size_t)c->cap_own));
-        CTX_TRY(hipMalloc((void**)&c->ids.map[1], sizeof(int32_t) * (size_t)c->cap_own));
-        if (d->flags & NBODY_FLAG_RECORD_EVENTS) {
-            CTX_TRY(hipMalloc((void**)&c->ids.lineage, sizeof(IdPair) * (size_t)c->ev_cap));
-            CTX_TRY(hipMalloc((void**)&c->ids.done, sizeof(unsigned long long)));
-            CTX_TRY(hipMemsetAsync(c->ids.done, 0, sizeof(unsigned long long), c->stream));
-        }
-    }
+    CTX_TRY(c->own.device(&c->events, sizeof(Event) * (size_t)c->ev_cap));
+    if (d->flags & NBODY_FLAG_TRACK_IDS)
+        CTX_TRY(ids_alloc(c->ids, c->stream, 1, (size_t)c->cap_own, (d->flags & NBODY_FLAG_RECORD_EVENTS) ? (size_t)c->ev_cap : 0));
     // on the context's own stream and waited for: hipMemset() on device memory runs on the NULL stream and may
     // return before the fill has executed; the context's stream is non-blocking, so a late fill could land
     // after nbody_upload's copy of Meta (seen once as a step that found n = 0)
@@ -910,11 +835,11 @@ int nbody_ctx_create(nbody_ctx** out, const nbody_ctx_desc* d) {
     CTX_TRY(hipMemsetAsync(c->meta, 0, sizeof(Meta), c->stream));
     CTX_TRY(hipStreamSynchronize(c->stream));
     c->h_stage_bytes = (size_t)c->cap * c->rec_bytes;
-    CTX_TRY(hipHostMalloc(&c->h_stage, c->h_stage_bytes, hipHostMallocDefault));
-    CTX_TRY(hipHostMalloc((void**)&c->h_meta, sizeof(Meta), hipHostMallocDefault));
-    CTX_TRY(hipHostMalloc((void**)&c->h_meta_async, kMetaBlockBytes, hipHostMallocDefault));
+    CTX_TRY(c->own.host(&c->h_stage, c->h_stage_bytes));
+    CTX_TRY(c->own.host(&c->h_meta, sizeof(Meta)));
+    CTX_TRY(c->own.host(&c->h_meta_async, kMetaBlockBytes));
     c->h_counters_async = reinterpret_cast<Counters*>(reinterpret_cast<unsigned char*>(c->h_meta_async) + kCountersOffset);
-    CTX_TRY(hipHostMalloc((void**)&c->h_counters, sizeof(Counters), hipHostMallocDefault));
+    CTX_TRY(c->own.host(&c->h_counters, sizeof(Counters)));
     memset(c->h_counters, 0, sizeof(Counters));
     memset(c->h_counters_async, 0, sizeof(Counters));
 #undef CTX_TRY
@@ -1149,7 +1074,7 @@ int nbody_step(nbody_ctx* c, int nsteps) {
     for (int s = 0; s < nsteps; ++s) {
         int rc = compute_phase(c);
         if (rc != NBODY_OK) return rc;
-        if (c->trc.on() && (rc = tracer_phase(c)) != NBODY_OK) return rc;
+        if (c->q.trc.on() && (rc = tracer_phase(c)) != NBODY_OK) return rc;
         rc = do_exchange(c);
         if (rc != NBODY_OK) return rc;
         rc = commit_phase(c);
@@ -1263,23 +1188,18 @@ int nbody_render_image(nbody_ctx* c, unsigned char* img, int width, int height) 
     int rc0 = read_meta(c);
     if (rc0 != NBODY_OK) return rc0;
     const size_t bytes = (size_t)width * height;
-    if (bytes > c->d_img_bytes) {
-        hipFree(c->d_img);
-        c->d_img = nullptr; c->d_img_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_img, bytes));
-        c->d_img_bytes = bytes;
-    }
-    HIP_TRY(hipMemsetAsync(c->d_img, 254, bytes, c->stream));                 // src/nbody.cu:534
+    HIP_TRY(rows_reserve_device(c->d_img, bytes));
+    HIP_TRY(hipMemsetAsync(c->d_img.d, 254, bytes, c->stream));               // src/nbody.cu:534
     const int literal = c->desc.semantics == NBODY_LITERAL;
     const int grid = (c->n_upper + 255) / 256 > 0 ? (c->n_upper + 255) / 256 : 1;
     if (c->desc.precision == NBODY_F64)
         hipLaunchKernelGGL(render_discs<double>, dim3(grid), dim3(256), 0, c->stream, (const Rec<double>*)c->J,
-                           (const Meta*)c->meta, literal, c->d_img, width, height, c->desc.fieldWidth, c->desc.fieldHeight);
+                           (const Meta*)c->meta, literal, c->d_img.d, width, height, c->desc.fieldWidth, c->desc.fieldHeight);
     else
         hipLaunchKernelGGL(render_discs<float>, dim3(grid), dim3(256), 0, c->stream, (const Rec<float>*)c->J,
-                           (const Meta*)c->meta, literal, c->d_img, width, height, c->desc.fieldWidth, c->desc.fieldHeight);
+                           (const Meta*)c->meta, literal, c->d_img.d, width, height, c->desc.fieldWidth, c->desc.fieldHeight);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(img, c->d_img, bytes, hipMemcpyDeviceToHost, c->stream));   // :537
+    HIP_TRY(hipMemcpyAsync(img, c->d_img.d, bytes, hipMemcpyDeviceToHost, c->stream));   // :537
     HIP_TRY(hipStreamSynchronize(c->stream));
     return NBODY_OK;
 }
@@ -1289,18 +1209,14 @@ int nbody_get_events(nbody_ctx* c, nbody_event* out, int cap, int64_t* total) {
     HIP_TRY(hipSetDevice(c->desc.device));
     HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const unsigned long long tot = c->h_counters->events;
-    *total = (int64_t)tot;
-    const unsigned long long ncopy = log_prefix(tot, c->ev_cap, cap);
-    if (ncopy) HIP_TRY(hipMemcpy(out, c->events, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
-    return NBODY_OK;
+    return events_read(c->events, c->h_counters->events, c->ev_cap, out, cap, total);
 }
 
 int nbody_clear_events(nbody_ctx* c) {
     if (!c) return nbody_fail(NBODY_ERR_INVALID, "NULL context");
     HIP_TRY(hipSetDevice(c->desc.device));
     HIP_TRY(hipMemsetAsync(&c->counters->events, 0, sizeof(unsigned long long), c->stream));
-    if (c->ids.done) HIP_TRY(hipMemsetAsync(c->ids.done, 0, sizeof(unsigned long long), c->stream));   // the lineage with it
+    HIP_TRY(ids_clear_done(c->ids, c->stream, 1));         // the lineage with it
     return NBODY_OK;
 }
 
@@ -1311,12 +1227,7 @@ int nbody_get_ids(nbody_ctx* c, int32_t* ids, int cap, int* n_out) {
     HIP_TRY(hipSetDevice(c->desc.device));
     int rc = read_meta(c);
     if (rc != NBODY_OK) return rc;
-    const int n = c->h_meta->n;
-    if (n < 0 || n > c->cap_own) return nbody_fail(NBODY_ERR_STATE, "nbody_get_ids: %d bodies, capacity %d", n, c->cap_own);
-    const int k = n < cap ? n : cap;
-    if (k > 0) HIP_TRY(hipMemcpy(ids, c->ids.map[c->ids.cur], sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost));
-    *n_out = n;
-    return NBODY_OK;
+    return ids_read("nbody_get_ids", c->ids.current(), c->h_meta->n, c->cap_own, ids, cap, n_out);
 }
 
 int nbody_get_lineage(nbody_ctx* c, nbody_lineage* out, int cap, int64_t* total) {
@@ -1327,11 +1238,7 @@ int nbody_get_lineage(nbody_ctx* c, nbody_lineage* out, int cap, int64_t* total)
     HIP_TRY(hipSetDevice(c->desc.device));
     int rc = read_meta(c);                                 // synchronises; a failed index check of a translation ends here
     if (rc != NBODY_OK) return rc;
-    const unsigned long long tot = c->h_counters->events;
-    *total = (int64_t)tot;
-    const unsigned long long ncopy = log_prefix(tot, c->ev_cap, cap);
-    if (ncopy) HIP_TRY(lineage_read(c->events, c->ids.lineage, c->ids.done, ncopy, out));
-    return NBODY_OK;
+    return lineage_read(c->events, c->ids.lineage, c->ids.done, c->h_counters->events, c->ev_cap, out, cap, total);
 }
 
 int nbody_set_kernel_timing(nbody_ctx* c, int enable) {
@@ -1626,7 +1533,7 @@ int ids_step(nbody_ctx* c) {
 int ids_restart(nbody_ctx* c) {
     ids_enqueue_fill<kIdsBlock>(c->ids, c->stream, 1, c->cap_own);
     HIP_TRY(hipGetLastError());
-    if (c->ids.done) HIP_TRY(hipMemsetAsync(c->ids.done, 0, sizeof(unsigned long long), c->stream));
+    HIP_TRY(ids_clear_done(c->ids, c->stream, 1));
     return NBODY_OK;
 }
 
@@ -1649,7 +1556,7 @@ int nbody_track_reserve(nbody_ctx* c, int samples, const int32_t* ids, int k, ui
 int nbody_track_record(nbody_ctx* c) {
     if (!c) return nbody_fail(NBODY_ERR_INVALID, "nbody_track_record: NULL context");
     if (!c->ids.on()) return nbody_fail(NBODY_ERR_STATE, "nbody_track_record: the context was created without NBODY_FLAG_TRACK_IDS");
-    const int32_t* map = c->ids.map[c->ids.cur];
+    const int32_t* map = c->ids.current();
     if (c->desc.precision == NBODY_F64)
         return track_record<double>(c->trk, c->stream, c->desc.device, "nbody_track_record", c->uploaded,
                                     (const Rec<double>*)c->J, (const Vec2<double>*)c->Vown, (const Meta*)c->meta, c->counters, map, c->cap);
@@ -1737,20 +1644,20 @@ extern "C" {
 int nbody_get_field(nbody_ctx* c, const nbody_vec2* points, int m, nbody_field* out, int* n_out, int64_t* coincident) {
     const int rc = rows_check_args("nbody_get_field", {c, out, n_out, coincident}, m, sizeof(nbody_field), " of results");
     if (rc != NBODY_OK) return rc;
-    return ctx_rows(c, "nbody_get_field", c->fld, FieldQuery{(double)kG, coincident}, points, m, out, n_out);
+    return ctx_rows(c, "nbody_get_field", c->q.fld, FieldQuery{(double)kG, coincident}, points, m, out, n_out);
 }
 
 int nbody_get_neighbors(nbody_ctx* c, const nbody_vec2* points, int m, nbody_neighbor* out, int* n_out) {
     const int rc = rows_check_args("nbody_get_neighbors", {c, out, n_out}, m, sizeof(nbody_neighbor), " of results");
     if (rc != NBODY_OK) return rc;
-    return ctx_rows(c, "nbody_get_neighbors", c->nbr, NeighborQuery{}, points, m, out, n_out);
+    return ctx_rows(c, "nbody_get_neighbors", c->q.nbr, NeighborQuery{}, points, m, out, n_out);
 }
 
 int nbody_get_knn(nbody_ctx* c, const nbody_vec2* points, int m, int k, double* d2, int32_t* index, int* n_out) {
     const int rc = knn_check_args("nbody_get_knn", {c, d2, index, n_out}, m, k, 1);
     if (rc != NBODY_OK) return rc;
     KnnResult out{d2, index};
-    return ctx_rows(c, "nbody_get_knn", c->knn, KnnQuery{k}, points, m, &out, n_out);
+    return ctx_rows(c, "nbody_get_knn", c->q.knn, KnnQuery{k}, points, m, &out, n_out);
 }
 
 int nbody_get_shells(nbody_ctx* c, const nbody_vec2* points, int m, const double* edges2, int bins, double* mass, int32_t* count,
@@ -1758,7 +1665,7 @@ int nbody_get_shells(nbody_ctx* c, const nbody_vec2* points, int m, const double
     const int rc = shells_check_args("nbody_get_shells", {c, edges2, mass, count, n_out}, m, edges2, bins, 1);
     if (rc != NBODY_OK) return rc;
     ShellResult out{mass, count};
-    return ctx_rows(c, "nbody_get_shells", c->shl, ShellQuery{edges2, bins}, points, m, &out, n_out);
+    return ctx_rows(c, "nbody_get_shells", c->q.shl, ShellQuery{edges2, bins}, points, m, &out, n_out);
 }
 
 // Shell moments (nbody_shell_moments.hpp): the shell sums with the velocities, so the encounters' restriction holds.
@@ -1770,7 +1677,7 @@ int nbody_get_shell_moments(nbody_ctx* c, const nbody_vec2* points, const nbody_
     if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "shell moments need", kOwnVelocities)) != NBODY_OK) return rc;
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK || (rc = ctx_rows_room(who, site, points, m, n_out)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return shell_moments_run<decltype(t), RowsOneCount>(who, site, c->shm, c->Vown, points, point_vel, m, edges2, bins, out,
+        return shell_moments_run<decltype(t), RowsOneCount>(who, site, c->q.shm, c->Vown, points, point_vel, m, edges2, bins, out,
                                                             sync);
     });
 }
@@ -1785,7 +1692,7 @@ int nbody_get_groups(nbody_ctx* c, double link, double radius_scale, int32_t* la
     if (cap < site.n_bound)
         return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d labels, the context holds %d bodies", who, cap, site.n_bound);
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return groups_run<decltype(t), RowsOneCount>(who, site, c->grp, link, radius_scale, label, info, sync);
+        return groups_run<decltype(t), RowsOneCount>(who, site, c->q.grp, link, radius_scale, label, info, sync);
     });
 }
 
@@ -1796,7 +1703,7 @@ int nbody_get_pair_counts(nbody_ctx* c, const nbody_vec2* points, int m, const d
     int rc = pairs_check_args(who, {c, edges2, counts, info}, m, edges2, bins);
     if (rc != NBODY_OK || (rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return pairs_run<decltype(t), RowsOneCount>(who, site, c->prs, points, m, edges2, bins, counts, info, sync);
+        return pairs_run<decltype(t), RowsOneCount>(who, site, c->q.prs, points, m, edges2, bins, counts, info, sync);
     });
 }
 
@@ -1809,7 +1716,7 @@ int nbody_get_encounters(nbody_ctx* c, double horizon, nbody_encounter* out, int
     if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "encounters need", kOwnVelocities)) != NBODY_OK) return rc;
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->enc, EncQuery{horizon}, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->q.enc, EncQuery{horizon}, out, cap, info, sync);
     });
 }
 
@@ -1821,7 +1728,7 @@ int nbody_get_binaries(nbody_ctx* c, double sep2, nbody_binary* out, int cap, nb
     if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "binaries need", kOwnVelocities)) != NBODY_OK) return rc;
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->bin, BinQuery{sep2}, out, cap, info, sync);
+        return pair_log_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->q.bin, BinQuery{sep2}, out, cap, info, sync);
     });
 }
 
@@ -1835,7 +1742,7 @@ int nbody_get_tides(nbody_ctx* c, const nbody_vec2* points, const nbody_vec2* po
     if (rc != NBODY_OK || (jerk && (rc = ctx_single_rank(c, who, "the jerk needs", kOwnVelocities)) != NBODY_OK)) return rc;
     if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK || (rc = ctx_rows_room(who, site, points, m, n_out)) != NBODY_OK) return rc;
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return tides_run<decltype(t), RowsOneCount>(who, site, c->tid, (double)kG, c->Vown, points, point_vel, m, tide, jerk,
+        return tides_run<decltype(t), RowsOneCount>(who, site, c->q.tid, (double)kG, c->Vown, points, point_vel, m, tide, jerk,
                                                     coincident, sync);
     });
 }
@@ -1848,7 +1755,7 @@ int nbody_tracers_set(nbody_ctx* c, const nbody_tracer* t, int m, uint32_t flags
     if (rc == NBODY_OK) rc = ctx_single_rank(c, who, "tracers need", "an advance against a rank's lagging replica is not built");
     if (rc != NBODY_OK) return rc;
     HIP_TRY(hipSetDevice(c->desc.device));
-    return tracers_set(who, c->trc, c->stream, 1, t, m, flags);
+    return tracers_set(who, c->q.trc, c->stream, 1, t, m, flags);
 }
 
 int nbody_tracers_get(nbody_ctx* c, nbody_tracer* out, nbody_field* last, int cap, nbody_tracer_info* info) {
@@ -1857,7 +1764,7 @@ int nbody_tracers_get(nbody_ctx* c, nbody_tracer* out, nbody_field* last, int ca
     if (cap < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: cap = %d", who, cap);
     if (!out && cap > 0) return nbody_fail(NBODY_ERR_INVALID, "%s: NULL out with cap = %d", who, cap);
     HIP_TRY(hipSetDevice(c->desc.device));
-    return tracers_get(c->trc, c->stream, 1, out, last, cap < c->trc.m ? cap : c->trc.m, info, [c] { return nbody_sync(c); });
+    return tracers_get(c->q.trc, c->stream, 1, out, last, cap < c->q.trc.m ? cap : c->q.trc.m, info, [c] { return nbody_sync(c); });
 }
 
 }  // extern "C"
@@ -1886,7 +1793,7 @@ int nbody_get_group_potential(nbody_ctx* c, double link, double radius_scale, in
     if (cap < site.n_bound)
         return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d rows, the context holds %d bodies", who, cap, site.n_bound);
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return group_energy_run<decltype(t), RowsOneCount>(who, site, c->grp, c->gen, (double)kG, link, radius_scale, label, phi_in,
+        return group_energy_run<decltype(t), RowsOneCount>(who, site, c->q.grp, c->q.gen, (double)kG, link, radius_scale, label, phi_in,
                                                            info, sync);
     });
 }
@@ -1908,7 +1815,7 @@ int nbody_get_cells(nbody_ctx* c, const nbody_grid* grid, uint32_t flags, nbody_
     if ((cell_of || order) && cap < site.n_bound)
         return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d list entries, the context holds %d bodies", who, cap, site.n_bound);
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return cells_run<decltype(t), RowsOneCount>(who, site, c->cel, c->Vown, *grid, flags, cells, cell_of, start, order, info,
+        return cells_run<decltype(t), RowsOneCount>(who, site, c->q.cel, c->Vown, *grid, flags, cells, cell_of, start, order, info,
                                                     sync);
     });
 }
@@ -1928,7 +1835,7 @@ int nbody_get_within(nbody_ctx* c, const nbody_grid* grid, double h2, const nbod
     if (!points && m < site.n_bound)
         return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d rows, the context holds %d bodies", who, m, site.n_bound);
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return within_run<decltype(t), RowsOneCount>(who, site, c->cel, c->wth, *grid, h2, points, m, out, start, list, cap, info,
+        return within_run<decltype(t), RowsOneCount>(who, site, c->q.cel, c->q.wth, *grid, h2, points, m, out, start, list, cap, info,
                                                      sync);
     });
 }

@@ -151,11 +151,7 @@ int group_energy_run(const char* who, const RowsSite& s, GroupsState& g, GroupEn
     if (s.n_bound > 0) {
         const size_t total = (size_t)s.systems * (size_t)s.stride;
         const hipError_t e = rows_reserve(buf, total);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, result buffers: %s", who,
-                              hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return rows_alloc_failed(e, who, "result buffers");
         hipLaunchKernelGGL((group_potential<T, Count>), s.grid(s.n_bound), dim3(kDiagBlock), 0, s.stream, (const Rec<T>*)s.J, s.meta,
                            s.counters, s.stride, s.n_one<Count>(), (const int32_t*)g.label, G, buf.d);
         NBK_ROWS_TRY(hipGetLastError());

@@ -161,11 +161,9 @@ inline int groups_reserve(GroupsState& g, size_t total, size_t systems, const ch
     if (e == hipSuccess) e = hipMalloc((void**)&g.changed, 2 * systems * sizeof(int));
     if (e == hipSuccess) e = hipHostMalloc((void**)&g.h, total * sizeof(int32_t) + systems * sizeof(int), hipHostMallocDefault);
     if (e != hipSuccess) {
-        (void)hipGetLastError();
         g.h = nullptr;
         groups_free(g);
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, parent and label buffers: %s", who,
-                          hipGetErrorString(e));
+        return rows_alloc_failed(e, who, "parent and label buffers");
     }
     return NBODY_OK;
 }

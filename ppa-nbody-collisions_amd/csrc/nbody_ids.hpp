@@ -18,6 +18,7 @@
 
 #include "nbody.h"
 #include "nbody_kernels.hpp"
+#include "nbody_rows.hpp"
 
 namespace nbk {
 
@@ -108,32 +109,75 @@ struct IdsState {
     IdPair* lineage = nullptr;              // [systems * ev_cap], next to the event buffer (with NBODY_FLAG_RECORD_EVENTS)
     unsigned long long* done = nullptr;     // [systems] events translated so far
     bool on() const { return map[0] != nullptr; }
+    const int32_t* current() const { return map[cur]; }
 };
 
-// Reading a log back (nbody_get_events / nbody_get_lineage and their batch twins): the first min(total, ev_cap, cap)
-// records - what was stored and fits the caller's buffer.
+// Create with NBODY_FLAG_TRACK_IDS: the two maps, and for a handle that logs `events` (> 0) events per system the lineage
+// and the cleared counters.  A failure leaves what was made to ids_free.
+inline hipError_t ids_alloc(IdsState& st, hipStream_t stream, size_t systems, size_t stride, size_t events) {
+    hipError_t e = hipMalloc((void**)&st.map[0], systems * stride * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&st.map[1], systems * stride * sizeof(int32_t));
+    if (e != hipSuccess || events == 0) return e;
+    e = hipMalloc((void**)&st.lineage, systems * events * sizeof(IdPair));
+    if (e == hipSuccess) e = hipMalloc((void**)&st.done, systems * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(st.done, 0, systems * sizeof(unsigned long long), stream);
+    return e;
+}
+
+inline void ids_free(IdsState& st) {
+    (void)hipFree(st.map[0]); (void)hipFree(st.map[1]); (void)hipFree(st.lineage); (void)hipFree(st.done);
+    st = IdsState{};
+}
+
+// The lineage starts empty with the event log: an upload, nbody_clear_events.
+inline hipError_t ids_clear_done(IdsState& st, hipStream_t stream, size_t systems) {
+    return st.done ? hipMemsetAsync(st.done, 0, systems * sizeof(unsigned long long), stream) : hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Reading back (nbody_get_events / _ids / _lineage and their batch twins), from where the handle knows its count: a context
+// has read its one Meta and Counters, a batch those of every system.  The pointers are one system's slices.
+// ---------------------------------------------------------------------------------------------------------
+// The first min(total, ev_cap, cap) records of a log: what was stored and fits the caller's buffer.
 static_assert(sizeof(nbody_event) == sizeof(Event), "event layouts must match");
 inline unsigned long long log_prefix(unsigned long long total, int ev_cap, int cap) {
     const unsigned long long stored = log_stored(total, ev_cap);
     return stored < (unsigned long long)cap ? stored : (unsigned long long)cap;
 }
 
-// The first ncopy (> 0) lineage records of one system: ev / who / done point at that system's slices.  An event past
-// `done` belongs to no committed step and has not been translated: it reads -1.
-inline hipError_t lineage_read(const Event* ev_dev, const IdPair* who_dev, const unsigned long long* done_dev,
-                               unsigned long long ncopy, nbody_lineage* out) {
+inline int events_read(const Event* ev_dev, unsigned long long logged, int ev_cap, nbody_event* out, int cap, int64_t* total) {
+    *total = (int64_t)logged;
+    const unsigned long long ncopy = log_prefix(logged, ev_cap, cap);
+    if (ncopy) NBK_ROWS_TRY(hipMemcpy(out, ev_dev, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
+    return NBODY_OK;
+}
+
+// n: the system's count as Meta has it; it is checked against the stride before it sizes the copy.
+inline int ids_read(const char* who, const int32_t* map_dev, int n, int stride, int32_t* ids, int cap, int* n_out) {
+    if (n < 0 || n > stride) return nbody_fail(NBODY_ERR_STATE, "%s: %d bodies, capacity %d", who, n, stride);
+    const int k = n < cap ? n : cap;
+    if (k > 0) NBK_ROWS_TRY(hipMemcpy(ids, map_dev, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost));
+    *n_out = n;
+    return NBODY_OK;
+}
+
+// An event past `done` belongs to no committed step and has not been translated: it reads -1.
+inline int lineage_read(const Event* ev_dev, const IdPair* who_dev, const unsigned long long* done_dev, unsigned long long logged,
+                        int ev_cap, nbody_lineage* out, int cap, int64_t* total) {
+    *total = (int64_t)logged;
+    const unsigned long long ncopy = log_prefix(logged, ev_cap, cap);
+    if (ncopy == 0) return NBODY_OK;
     unsigned long long done = 0;
     std::vector<Event> ev((size_t)ncopy);
     std::vector<IdPair> who((size_t)ncopy);
-    hipError_t e = hipMemcpy(&done, done_dev, sizeof(done), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ev.data(), ev_dev, ncopy * sizeof(Event), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(who.data(), who_dev, ncopy * sizeof(IdPair), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return e;
+    NBK_ROWS_TRY(hipMemcpy(&done, done_dev, sizeof(done), hipMemcpyDeviceToHost));
+    NBK_ROWS_TRY(hipMemcpy(ev.data(), ev_dev, ncopy * sizeof(Event), hipMemcpyDeviceToHost));
+    NBK_ROWS_TRY(hipMemcpy(who.data(), who_dev, ncopy * sizeof(IdPair), hipMemcpyDeviceToHost));
     for (unsigned long long k = 0; k < ncopy; ++k) {
         const bool have = k < done;
         out[k] = nbody_lineage{ev[k].step, have ? who[k].id_i : -1, have ? who[k].id_j : -1, ev[k].kind};
     }
-    return hipSuccess;
+    return NBODY_OK;
 }
 
 // Upload: identity = index, for every system; the caller empties `done` with the event counters.

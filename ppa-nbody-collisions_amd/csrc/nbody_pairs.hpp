@@ -145,10 +145,8 @@ inline int pairs_reserve(PairsState& g, size_t systems, size_t n_pts, const char
     }
     if (e == hipSuccess) e = rows_reserve(g.pts, n_pts);
     if (e != hipSuccess) {
-        (void)hipGetLastError();
         pairs_free(g);
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, edge, histogram and point buffers: %s",
-                          who, hipGetErrorString(e));
+        return rows_alloc_failed(e, who, "edge, histogram and point buffers");
     }
     return NBODY_OK;
 }

@@ -32,6 +32,7 @@
 #include <stddef.h>
 #include <string.h>
 #include <initializer_list>
+#include <vector>
 
 #include "nbody.h"
 #include "nbody_error.h"
@@ -215,6 +216,37 @@ constexpr unsigned long long kFieldMaxBytes = 1ull << 31;   // of the caller's `
                               __FILE__, __LINE__);                                                        \
     } while (0)
 
+// The one place a HIP error becomes a status, and the epilogue of every failed allocation: the error is cleared, the
+// message says who was allocating what.  The caller frees what it holds first or after; nothing here touches it.
+inline int rows_status(hipError_t e) { return e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP; }
+inline int rows_alloc_failed(hipError_t e, const char* who, const char* what) {
+    (void)hipGetLastError();
+    return nbody_fail(rows_status(e), "%s, %s: %s", who, what, hipGetErrorString(e));
+}
+
+// What a handle allocates when it is created: every block is recorded here where it is made, and release() is all the
+// handle's free_all knows of them - whatever was made before a create failed half way, and each block once.
+struct RowsOwned {
+    std::vector<void*> dev, pinned;
+    template <typename P>
+    hipError_t device(P** p, size_t bytes) {
+        const hipError_t e = hipMalloc((void**)p, bytes);
+        if (e == hipSuccess) dev.push_back(*p);
+        return e;
+    }
+    template <typename P>
+    hipError_t host(P** p, size_t bytes) {
+        const hipError_t e = hipHostMalloc((void**)p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) pinned.push_back(*p);
+        return e;
+    }
+    void release() {
+        for (void* p : dev) (void)hipFree(p);
+        for (void* p : pinned) (void)hipHostFree(p);
+        dev.clear(); pinned.clear();
+    }
+};
+
 // A device array and the pinned memory it is sent from or read back into, allocated on the first use and grown to the
 // largest request seen.  RowPoints: the explicit points of one query of one context or batch.
 template <typename E>
@@ -242,6 +274,16 @@ inline hipError_t rows_reserve(RowsArray<E>& f, size_t n) {
     return e;
 }
 
+// Device only: scratch nothing reads back, or an array read back into the caller's memory.  h stays NULL.
+template <typename E>
+inline hipError_t rows_reserve_device(RowsArray<E>& f, size_t n) {
+    if (n <= f.cap) return hipSuccess;
+    rows_free(f);
+    const hipError_t e = hipMalloc((void**)&f.d, n * sizeof(E));
+    if (e == hipSuccess) f.cap = n;
+    return e;
+}
+
 // Enqueues the copy of the caller's m points (reserved before) to the device.
 inline hipError_t rows_upload(RowPoints& f, const nbody_vec2* points, int m, hipStream_t stream) {
     memcpy(f.h, points, (size_t)m * sizeof(FieldPoint));
@@ -255,11 +297,7 @@ inline int rows_point_vel(const char* who, RowPoints& vel, const nbody_vec2* poi
     *pv = nullptr;
     if (!point_vel || m <= 0) return NBODY_OK;
     const hipError_t e = rows_reserve(vel, (size_t)m);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point velocities: %s", who,
-                          hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return rows_alloc_failed(e, who, "point velocities");
     NBK_ROWS_TRY(rows_upload(vel, point_vel, m, stream));
     *pv = vel.d;
     return NBODY_OK;
@@ -279,10 +317,7 @@ template <typename Out>
 inline int rows_reserve(PointBuffers<Out>& f, size_t n_pts, size_t n_out, const char* who) {
     hipError_t e = rows_reserve(f.pts, n_pts);
     if (e == hipSuccess) e = rows_reserve(f.out, n_out);
-    if (e == hipSuccess) return NBODY_OK;
-    (void)hipGetLastError();
-    return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, point and result buffers: %s", who,
-                      hipGetErrorString(e));
+    return e == hipSuccess ? NBODY_OK : rows_alloc_failed(e, who, "point and result buffers");
 }
 
 // The argument checks every entry point makes before any device call; a query's own value checks stay next to the query.
@@ -374,36 +409,20 @@ int rows_run(const char* who, const RowsSite& s, PointBuffers<typename Q::Device
 // ---------------------------------------------------------------------------------------------------------
 template <typename Q>
 struct PairLogState {
-    typename Q::Counts* cnt = nullptr;      // [systems]
-    typename Q::Counts* h_cnt = nullptr;    // pinned [systems]
+    RowsArray<typename Q::Counts> cnt;      // [systems]: device and pinned
     RowsArray<typename Q::Raw> log;         // [systems * cap]: device and pinned
 };
 
 template <typename Q>
-inline void pair_log_free(PairLogState<Q>& g) {
-    (void)hipFree(g.cnt);
-    if (g.h_cnt) (void)hipHostFree(g.h_cnt);
-    rows_free(g.log);
-    g = PairLogState<Q>{};
-}
+inline void pair_log_free(PairLogState<Q>& g) { rows_free(g.cnt); rows_free(g.log); }
 
 template <typename Q>
 inline int pair_log_reserve(PairLogState<Q>& g, size_t systems, size_t cap, const char* who) {
-    using Counts = typename Q::Counts;
-    hipError_t e = hipSuccess;
-    if (!g.h_cnt) {
-        e = hipMalloc((void**)&g.cnt, systems * sizeof(Counts));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&g.h_cnt, systems * sizeof(Counts), hipHostMallocDefault);
-        if (e != hipSuccess) g.h_cnt = nullptr;
-    }
+    hipError_t e = rows_reserve(g.cnt, systems);
     if (e == hipSuccess) e = rows_reserve(g.log, systems * (cap > 0 ? cap : 1));     // never a NULL log
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        pair_log_free(g);
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, counters and log: %s", who,
-                          hipGetErrorString(e));
-    }
-    return NBODY_OK;
+    if (e == hipSuccess) return NBODY_OK;
+    pair_log_free(g);
+    return rows_alloc_failed(e, who, "counters and log");
 }
 
 // The argument checks an entry point makes before any device call; the value's own check is the query's.
@@ -433,19 +452,20 @@ int pair_log_run(const char* who, const RowsSite& s, const void* V, PairLogState
     if (launched) {
         const int rc = pair_log_reserve(g, S, (size_t)cap, who);
         if (rc != NBODY_OK) return rc;
-        NBK_ROWS_TRY(hipMemsetAsync(g.cnt, 0, S * sizeof(Counts), s.stream));
+        NBK_ROWS_TRY(hipMemsetAsync(g.cnt.d, 0, S * sizeof(Counts), s.stream));
         q.template launch<T, Count>(s.grid(s.n_bound), s.stream, (const Rec<T>*)s.J, (const Vec2<T>*)V, s.meta, s.counters, s.stride,
-                                    s.n_one<Count>(), g.log.d, cap, g.cnt);
+                                    s.n_one<Count>(), g.log.d, cap, g.cnt.d);
         NBK_ROWS_TRY(hipGetLastError());
-        NBK_ROWS_TRY(hipMemcpyAsync(g.h_cnt, g.cnt, S * sizeof(Counts), hipMemcpyDeviceToHost, s.stream));
+        NBK_ROWS_TRY(hipMemcpyAsync(g.cnt.h, g.cnt.d, S * sizeof(Counts), hipMemcpyDeviceToHost, s.stream));
     }
     const int rc = s.sync<Count>(launched, read_meta);
     if (rc != NBODY_OK) return rc;
+    const Counts* h_cnt = reinterpret_cast<const Counts*>(g.cnt.h);
     int over = -1;
     size_t used = 0;                                             // records of the log up to the last one written
     for (int sys = 0; sys < s.systems; ++sys) {
         const int64_t n = s.count(sys);
-        const Counts c = launched && n > 0 ? g.h_cnt[sys] : Counts{};
+        const Counts c = launched && n > 0 ? h_cnt[sys] : Counts{};
         info[sys] = q.info(n, c);
         if (c.pairs > (unsigned long long)cap && over < 0) over = sys;
         if (c.pairs) used = (size_t)sys * (size_t)cap + (size_t)c.pairs;

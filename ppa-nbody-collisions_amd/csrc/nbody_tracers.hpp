@@ -147,8 +147,7 @@ inline int tracers_set(const char* who, TracerState& s, hipStream_t stream, int 
     if (e != hipSuccess) {
         s.h = nullptr;
         tracers_free(s);
-        (void)hipGetLastError();
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, tracer buffers: %s", who, hipGetErrorString(e));
+        return rows_alloc_failed(e, who, "tracer buffers");
     }
     memcpy(s.h, t, total * sizeof(Tracer));
     NBK_ROWS_TRY(hipMemcpyAsync(s.d, s.h, total * sizeof(Tracer), hipMemcpyHostToDevice, stream));

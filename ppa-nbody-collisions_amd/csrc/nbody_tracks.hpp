@@ -29,6 +29,7 @@
 #include "nbody.h"
 #include "nbody_error.h"
 #include "nbody_diag.hpp"
+#include "nbody_rows.hpp"
 #include "nbody_ids.hpp"
 
 #pragma clang fp contract(off)
@@ -132,9 +133,15 @@ struct TrackState {
     do {                                                                                                  \
         hipError_t e__ = (expr);                                                                          \
         if (e__ != hipSuccess)                                                                            \
-            return nbody_fail(e__ == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP,               \
-                              "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return nbody_fail(rows_status(e__), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__),   \
+                              __FILE__, __LINE__);                                                        \
     } while (0)
+
+// The handle's free_all, after its stream synchronise.
+inline void track_free(TrackState& st) {
+    (void)hipFree(st.buf); (void)hipFree(st.sel);
+    st = TrackState{};
+}
 
 inline int track_release(TrackState& st, hipStream_t stream) {
     NBK_TRACK_TRY(hipStreamSynchronize(stream));            // records in flight write the log that is about to go
@@ -180,8 +187,7 @@ inline int track_reserve(TrackState& st, hipStream_t stream, int device, const c
     if (e == hipSuccess) e = hipStreamSynchronize(stream);  // `ids` is the caller's
     if (e != hipSuccess) {
         (void)hipFree(buf); (void)hipFree(sel);
-        (void)hipGetLastError();
-        return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+        return rows_alloc_failed(e, who, "track log");
     }
     const size_t plane = (size_t)cells * (size_t)columns;
     st.buf = buf;

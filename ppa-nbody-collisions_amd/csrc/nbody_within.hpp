@@ -408,9 +408,8 @@ inline void within_free(WithinState& w) {
 }
 
 inline int within_fail_alloc(WithinState& w, hipError_t e, const char* who, const char* what) {
-    (void)hipGetLastError();
     within_free(w);
-    return nbody_fail(e == hipErrorOutOfMemory ? NBODY_ERR_NOMEM : NBODY_ERR_HIP, "%s, %s: %s", who, what, hipGetErrorString(e));
+    return rows_alloc_failed(e, who, what);
 }
 
 // The argument checks an entry point makes before any device call, the values before the handle; `required`: the handle,
@@ -448,14 +447,14 @@ int within_run(const char* who, const RowsSite& s, CellState& g, WithinState& ws
     const int lanes = own ? 2 * s.n_bound : m;
     int rc = cells_reserve(g, S, C, bodies, who, false);
     if (rc != NBODY_OK) return rc;
-    hipError_t e = cells_reserve_device(ws.sorted, (bodies > 0 ? bodies : 1) * sizeof(WithinRec<T>));
+    hipError_t e = rows_reserve_device(ws.sorted, (bodies > 0 ? bodies : 1) * sizeof(WithinRec<T>));
     if (e == hipSuccess) e = rows_reserve(ws.pts, own || m == 0 ? 1 : (size_t)m);
     if (e == hipSuccess) e = rows_reserve(ws.out, S * per > 0 ? S * per : 1);
     if (e == hipSuccess) e = rows_reserve(ws.rstart, S * (per + 1));
     if (e == hipSuccess) e = rows_reserve(ws.info, S);
     const size_t rows_bound = own ? (size_t)s.n_bound : (size_t)m;         // rows of a system that can hold a result
     const size_t nblk = rows_bound > 0 ? (rows_bound + kWithinBlockRows - 1) / kWithinBlockRows : 1;
-    if (e == hipSuccess) e = cells_reserve_device(ws.blocks, 3 * S * nblk);
+    if (e == hipSuccess) e = rows_reserve_device(ws.blocks, 3 * S * nblk);
     if (e != hipSuccess) return within_fail_alloc(ws, e, who, "row buffers");
     const Rec<T>* J = (const Rec<T>*)s.J;
     WithinRec<T>* sorted = reinterpret_cast<WithinRec<T>*>(ws.sorted.d);
@@ -525,7 +524,7 @@ int within_run(const char* who, const RowsSite& s, CellState& g, WithinState& ws
         return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d list entries, system %d has %lld: call again with that cap", who, cap,
                           over, (long long)info[over].total);
     if (most == 0) return NBODY_OK;
-    e = cells_reserve_device(ws.raw, S * (size_t)most);
+    e = rows_reserve_device(ws.raw, S * (size_t)most);
     if (e == hipSuccess) e = rows_reserve(ws.list, S * (size_t)most);
     if (e != hipSuccess) return within_fail_alloc(ws, e, who, "list buffers");
     walk(std::true_type{}, most);

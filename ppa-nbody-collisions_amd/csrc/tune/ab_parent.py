@@ -4,7 +4,8 @@ compaction's offsets (compact_count / compact_scatter, batch_count / batch_commi
 (diag_potential, batch_diag_potential, track_potential, and with it field_at, tides_at and tracers_advance: the ordered
 walk and the exact walk of nbody_diag.hpp), the finish of the diagnostics (batch_diag_reduce) and the row queries'
 prologue, tile walk and host drivers (field_at, neighbors_at, groups_sweep, pair_counts, encounters_walk, binaries_walk,
-group_potential, shells_at, shell_moments_at; nbody_rows.hpp).
+group_potential, shells_at, shell_moments_at; nbody_rows.hpp), and the host drivers of the cell sums and the radius queries
+(nbody_cells.hpp, nbody_within.hpp), whose buffers are the handles' to keep and free.
 
     python3 csrc/tune/ab_parent.py --baseline-root DIR [--lines a,b256,...] [--rounds 3] [--out FILE]
     python3 csrc/tune/ab_parent.py --trace [--root DIR]     (every line once, target of rocprofv3 --kernel-trace --stats)
@@ -42,6 +43,10 @@ Lines (fp32, literal, stock configuration with stock radii):
     tid, tidj the shapes of tides_probe.py: Stepper N = 262144, tides() / tides(jerk=True); tidpts,   ms per call
               tidjpts: the same state with 65536 explicit points, tidjpts' moving; tid256,
               tidj256: StepperBatch 256 x 1024 after 3 steps, points=None
+    cel, wth  the shapes of cells_probe.py and within_probe.py: Stepper N = 262144, cells() on the   ms per call
+              256 x 256 grid over the field with moments and lists / within(h = that grid's cell
+              side) on that grid with lists; wthpts: the same from 65536 explicit points; cel256,
+              wth256: StepperBatch 256 x 1024 after 3 steps on 32 x 32 cells, h = the cell side
     trc       stepping with 65536 tracers set, from a fresh upload and a fresh set: trc Stepper  ms | us per step
               N = 262144 (8 steps), trc256 StepperBatch 256 x 1024 with 256 tracers in each
               system (500 steps)
@@ -67,7 +72,8 @@ REPLY_TIMEOUT_S = 240           # a side that does not answer within this is kil
 LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024", "d256x1024", "d64x4096",
          "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256",
          "enc", "enc256", "bin", "bin256", "gpe", "gpe256", "shl", "shlpts", "shl256", "shm", "shmpts", "shm256",
-         "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "trc", "trc256", "io", "io64", "io256")
+         "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "cel", "cel256", "wth", "wthpts", "wth256",
+         "trc", "trc256", "io", "io64", "io256")
 BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
 STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
 IO = {"io": 20, "io64": 12, "io256": 20}     # round trips per window
@@ -77,7 +83,10 @@ ROWS = {"": 3, "pts": 8, "256": 100}    # the row queries' shapes (field_probe.p
 SCANS = {"grp": 8, "grp256": 100, "prs": 20, "prspts": 30, "prs256": 200,     # the queries on the state after 3 steps:
          "enc": 6, "enc256": 100, "bin": 20, "bin256": 80, "gpe": 6, "gpe256": 80,    # calls per window
          "shl": 20, "shlpts": 20, "shl256": 60, "shm": 20, "shmpts": 20, "shm256": 40}
-ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm", "tid")
+# whole cells() / within() calls (profiles/cells_probe.txt, profiles/within_probe.txt): 0.62 and 1.2 ms a call for cel and
+# cel256, 1.4 ms for wth and wth256 with their lists; wthpts builds the same cell list for a quarter of the rows
+GRIDS = {"cel": 250, "cel256": 120, "wth": 100, "wthpts": 250, "wth256": 100}
+ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm", "tid", "cel", "wth")
 N_BIG = 262144
 M_POINTS = 65536
 
@@ -132,7 +141,7 @@ class Line:
                 self.st.step(8)
                 self.sel = [int(x) for x in np.unique(np.linspace(0, N_BIG - 1, 64).astype(np.int32))]
         elif name[:3] in ROW_LINES:
-            self.unit, self.reps = "ms per call", SCANS[name] if name in SCANS else ROWS[name[3:].lstrip("j")]
+            self.unit, self.reps = "ms per call", {**SCANS, **GRIDS}.get(name) or ROWS[name[3:].lstrip("j")]
             self.pts = None
             if name.endswith("256"):
                 cfg = nb.stock_config(particleCount=1024)
@@ -173,6 +182,13 @@ class Line:
                     if self.pts is not None:
                         vel = np.random.default_rng(3).uniform(-1, 1, size=(M_POINTS, 2)) * np.abs(np.asarray(down.Velocities)).max()
                     self.call = lambda pts: self.st.shell_moments(e2, pts, vel, squared=True)
+            elif name[:3] in ("cel", "wth"):
+                nx, W = 32 if self.batch else 256, float(cfg.fieldWidth)
+                grid = nb.make_grid(nx, nx, (-W, W, -W, W))
+                if name.startswith("cel"):
+                    self.call = lambda pts: self.st.cells(grid, lists=True)
+                else:
+                    self.call = lambda pts: self.st.within(2.0 * W / nx, pts, grid=grid, lists=True)
             elif name.startswith("tid"):
                 jerk, vel = name[3:4] == "j", None
                 if jerk and self.pts is not None:

@@ -155,6 +155,29 @@ def test_product_does_not_touch_the_oracle(nb):
         assert needle not in blob
 
 
+def test_makefile_prerequisites_come_from_the_compiler(nb):
+    """csrc/Makefile names no header: with the tree built (the `nb` fixture's import needs the library), make -n -W HEADER
+    shows what a changed header rebuilds.  A query header reaches the two HIP objects and no C object; nbody_error.h
+    reaches all nine objects.  -n: neither run builds anything."""
+    import subprocess
+    csrc = os.path.join(ROOT, "ppa-nbody-collisions_amd", "csrc")
+    objects = ["nbody_error", "nbody_config", "nbody_bodies", "nbody_state", "nbody_encounters", "nbody_binaries",
+               "nbody_group_energy", "nbody_ctx", "nbody_batch"]
+
+    def rebuilt(header):
+        before = {f: os.stat(os.path.join(ROOT, "build", "csrc", f + ".o")).st_mtime_ns for f in objects}
+        r = subprocess.run(["make", "-C", csrc, "-n", "-W", header, "all"], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert before == {f: os.stat(os.path.join(ROOT, "build", "csrc", f + ".o")).st_mtime_ns for f in objects}
+        lines = [ln for ln in r.stdout.splitlines() if " -c " in ln]                  # the compile lines
+        got = [f for f in objects if any(ln.endswith(" -o ../../build/csrc/%s.o" % f) for ln in lines)]
+        assert len(got) == len(lines), lines
+        return got
+
+    assert rebuilt("nbody_within.hpp") == ["nbody_ctx", "nbody_batch"]
+    assert rebuilt("nbody_error.h") == objects
+
+
 # ---------------------------------------------------------------------------------------------------------
 # The C host code under AddressSanitizer + UBSan (host code only; no GPU code is linked)
 # ---------------------------------------------------------------------------------------------------------
