@@ -1238,6 +1238,75 @@ int nbody_batch_get_within(struct nbody_batch* b, const nbody_grid* grid, double
                            int32_t* list /* [systems*cap] or NULL */, int cap, nbody_within_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Groups on the cell list (the reference has none): the friends-of-friends labels of nbody_get_groups,
+ * found through the cell list of nbody_get_cells instead of a walk over all pairs: O(n) per sweep on a grid whose cells are
+ * about as wide as the reach of a TYPICAL body, where nbody_get_groups is O(n^2) per sweep.
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma.  The grid
+ * is an nbody_grid as for nbody_get_cells; inside(j) is exactly the cell sums' definition.  For two bodies i != j
+ *     linked_grid(i, j)  <=>  inside(i) && inside(j) && linked(i, j)
+ * with linked(i, j) the predicate of nbody_get_groups, bit for bit: dx = X_j - X_i; dy = Y_j - Y_i; d2 = (dx*dx) + (dy*dy);
+ * s = (radius_scale * (R_i + R_j)) + link; d2 <= s*s.  link >= 0, +inf allowed; radius_scale finite and >= 0.  A group is a
+ * connected component of the graph of these links and label[i] is the LOWEST INDEX in body i's group.  A body outside the
+ * grid is linked to nobody: it is a group of its own, label[i] = i, and is counted in info.outside.
+ * info: n_bodies = n; n_groups and largest over ALL n bodies, the outside ones included; sweeps = the walks over the cells
+ * the call made, informational (for a batch the one number of the whole call); inside + outside == n.
+ * What follows from the definition:
+ *   - with outside == 0 the labels, n_groups and largest are exactly nbody_get_groups' for the same link and radius_scale;
+ *   - the result is a function of the state, the two parameters and the SET of inside bodies only - an integer function of
+ *     the set of links, so neither the order in which the cells are visited nor the cells themselves show: two grids that
+ *     both hold every body give the same bytes in label, n_groups and largest;
+ *   - with (link, radius_scale) = (0, 1) and outside == 0, body i is alone in its group - label[i] == i and no other body
+ *     carries i as its label - exactly where nbody_get_within's `overlaps` (h2 = +inf) is 0 for row i;
+ *   - label[label[i]] == label[i] and label[i] <= i; a NaN coordinate is outside every grid; a NaN radius links nothing;
+ *   - it is not a function of rank, world, transport, force kernel or the order the device's waves ran in.
+ * The window rule, by which the walk over cells sees every link (csrc/nbody_groups_grid.hpp; DESIGN.md 4.22 has the proof):
+ * a link has to be seen from ONE of its two ends, and the end with the larger |radius| finds it.  Row i looks, with
+ * a = |R_i|, S_i = (radius_scale * (a + a)) + link and h2_i = S_i * S_i, at the cells of nbody_get_within's window rule with
+ * h = S_i - per row, not per call - and tests the exact predicate on every source there with d2 <= h2_i.  A source of no
+ * larger |radius| that is linked to i has d2 <= h2_i; of two linked bodies one has no larger |radius| than the other.  One
+ * large body widens its own window only.  The rule costs time, never a result: a grid much finer than the typical reach, a
+ * link that percolates, or every body in a few cells brings the call towards the n^2 pair tests of nbody_get_groups, read
+ * from memory instead of LDS and with one lane walking each long window.  Use a grid matched to the reach of a typical
+ * body, not of the largest (Python: groups_grid).
+ * nbody_get_groups_grid follows nbody_get_groups in every other respect: it synchronises (once per sweep), reads positions
+ * and radii of the replica only and never changes what later steps compute; it is NOT collective - any rank of any world
+ * may call it on its own and each gives the same labels; cap is the room in label, cap < n is NBODY_ERR_CAPACITY with
+ * nothing written; n == 0 launches nothing and gives {0, 0, 0, 0, 0, 0}.  It allocates nothing of its own: the cell list of
+ * nbody_get_cells, the sorted records of nbody_get_within and the parents and labels of nbody_get_groups, each on the first
+ * call of whichever query needs it; a handle that never calls it allocates nothing and launches nothing more, and the
+ * kernels it runs keep their code.
+ * NBODY_ERR_INVALID, found before any device call, the values before the handle: everything nbody_get_cells rejects about
+ * the grid; a NaN or negative link; a NaN, negative or infinite radius_scale; a NULL handle, label or info; cap < 0.
+ * NBODY_ERR_CAPACITY: above, and a batch with systems * nx * ny above 1 << 22.  NBODY_ERR_STATE: before an upload.
+ * How: the list stages of the cell sums, the gather of the radius queries, then hook and repeat as nbody_get_groups - one
+ * lane per inside body in cell order walks its window and, on a linked pair with different roots, lowers the larger root's
+ * parent to the smaller with one atomicMin; repeated until a walk changes nothing (at most n + 1 walks; 4 bytes per system
+ * come back after each), then label[i] = root of i.  No device-side waiting, no retry loop.
+ * Cost (one MI355X, fp32; profiles/groups_grid_probe.txt; nbody_get_groups timed in the same runs): the stock state of
+ * N = 262144, n = 130965 bodies after 3 steps, radii median 124.5, largest 363.3, on the grid of groups_grid with the median
+ * radius.  A whole call with (link, radius_scale) = (0, 1) 0.67 ms (804 x 804 cells, 3 sweeps of 0.011 ms, 0.39 ms of list
+ * stages - the one-workgroup scan over the cells) against 14.6 ms; with the many-small-groups link 381.8 0.49 ms (3 sweeps of
+ * 0.017 ms) against 14.7 - 22.0 ms; with the percolating link 824.8 1.18 ms (the first sweep 0.86 ms: two finds and an atomic
+ * per linked pair, seen from both ends; the confirming one 0.08 ms) against 16.9 ms.  Where it LOSES: on 1 x 1 cells every row
+ * walks all n records from L2, 11.7 - 13.3 ms a sweep and 26 - 27 ms a call, 1.2 - 1.8 times nbody_get_groups; and a batch of
+ * 256 x 1024, whose kernels win (sweeps 0.014 against 0.234 ms) but whose whole call is 1.23 - 1.30 ms against 0.99 - 1.23 ms:
+ * at 1024 bodies per system the triangular sweep is 0.12 ms and the call is bound by its fixed work.  A grid matched to the
+ * LARGEST radius (2.9 times the median here) was not slower on this state: 0.36 ms with (0, 1), its scan has 8.5 times fewer
+ * cells.  The widest window was 49 cells (mean 10.2); the share of a sweep spent by its slowest workgroup is not measured.
+ * nbody_batch_get_groups_grid: the same for every system of a batch, with one grid, one link and one radius_scale for all
+ * of them, every stage and every sweep ONE launch whatever S is; the batch sweeps until no system changed, systems that have
+ * converged leave at once.  System s's labels go to label + s * capacity, one per current body, the rest of the slice is
+ * left unchanged; info: one record per system.  System s gives exactly what an nbody_ctx holding that system's state gives;
+ * an empty system gives {0, 0, 0, sweeps, 0, 0}.  A count outside [0, capacity] is treated as 0 and reported for that
+ * system, as by nbody_batch_get_cells.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_groups_grid_info { int32_t n_bodies, n_groups, largest, sweeps, inside, outside; } nbody_groups_grid_info;   /* 24 bytes */
+int nbody_get_groups_grid(nbody_ctx* ctx, const nbody_grid* grid, double link, double radius_scale, int32_t* label, int cap,
+                          nbody_groups_grid_info* info);
+int nbody_batch_get_groups_grid(struct nbody_batch* b, const nbody_grid* grid, double link, double radius_scale,
+                                int32_t* label /* [systems*capacity] */, nbody_groups_grid_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

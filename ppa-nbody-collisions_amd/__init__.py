@@ -155,6 +155,9 @@ WITHIN_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("count", np.i
 WITHIN_INFO_DTYPE = np.dtype([("total", np.int64), ("n", np.int32), ("rows", np.int32), ("inside", np.int32),
                               ("outside", np.int32), ("largest", np.int32), ("largest_row", np.int32)])
 GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
+# nbody_groups_grid_info (24 bytes): the summary of groups(grid=...)
+GROUPS_GRID_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32),
+                                   ("inside", np.int32), ("outside", np.int32)])
 # nbody_group_energy_info (24 bytes) and nbody_group_record (80 bytes), include/nbody.h
 GROUP_ENERGY_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32),
                                     ("coincident", np.int64)])
@@ -267,6 +270,8 @@ SYMBOLS = {
     "nbody_batch_get_cells": (_i, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "nbody_get_within": (_i, [_vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "nbody_batch_get_within": (_i, [_vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "nbody_get_groups_grid": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp]),
+    "nbody_batch_get_groups_grid": (_i, [_vp, _vp, _d, _d, _vp, _vp]),
     "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
     "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
     "nbody_group_catalog": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
@@ -623,6 +628,12 @@ def _groups_dict(label, info):
     return {"label": label, "n_groups": int(info["n_groups"]), "largest": int(info["largest"]), "sweeps": int(info["sweeps"])}
 
 
+def _groups_grid_dict(label, info, grid):
+    d = _groups_dict(label, info)
+    d.update(inside=int(info["inside"]), outside=int(info["outside"]), grid=grid[0].copy())
+    return d
+
+
 def _group_potential_dict(label, phi, info):
     d = _groups_dict(label, info)
     d["phi"] = phi
@@ -862,6 +873,15 @@ def within_grid(field, radius, squared=False, most=1024):
             return most
         return int(min(max(np.floor(extent / r), 1.0), float(most)))
     return make_grid(along(2.0 * w), along(2.0 * h), (-w, w, -h, h))
+
+
+def groups_grid(field, link, radius_scale, r_typical, most=1024):
+    """The grid to hand groups(grid=...): within_grid(field, radius_scale * 2 * r_typical + link, most=most), the field's
+    bounds in cells no smaller than the reach of a TYPICAL body - the median radius of the state, say - and at most `most`
+    per axis.  The cell side should match the typical reach, not the largest: a row's window is as wide as its OWN radius
+    asks, so a body ten times the typical size walks more cells itself and widens nobody else's window, while cells sized
+    to the largest body would make every small body test all of a large cell's members."""
+    return within_grid(field, float(radius_scale) * 2.0 * float(r_typical) + float(link), most=most)
 
 
 def _within(call, systems, per_own, radius, points, grid, squared, lists):
@@ -1340,12 +1360,22 @@ class Stepper:
         g = within_grid(_field_bounds(self._field)[1::2], radius, squared) if grid is None else make_grid(grid)
         return _within(lambda *a: lib.nbody_get_within(self._ctx, *a), None, self.capacity, radius, points, g, squared, lists)[0]
 
-    def groups(self, link, radius_scale=1.0):
+    def groups(self, link, radius_scale=1.0, grid=None):
         """nbody_get_groups: friends-of-friends groups of the current bodies, i and j linked where d2 <= s*s with
         s = radius_scale * (r_i + r_j) + link (fp64): {"label": int32 (n,), label[i] the lowest index of body i's group,
         "n_groups", "largest": the size of the biggest group, "sweeps": pair walks the call took}.  (0, 1) links the
-        overlapping bodies of neighbors(); radius_scale=0 is friends-of-friends on the centres.  Not collective."""
+        overlapping bodies of neighbors(); radius_scale=0 is friends-of-friends on the centres.  Not collective.
+        grid (a make_grid record, or what make_grid accepts; groups_grid() makes a matched one): nbody_get_groups_grid, the
+        same labels found through the cell list in O(n) per sweep, among the bodies inside the grid only - a body outside
+        is a group of its own; the dict also has "inside", "outside" and "grid".  With outside == 0 the labels are those of
+        grid=None, whatever the grid."""
         label = np.zeros(max(self.capacity, 1), dtype=np.int32)
+        if grid is not None:
+            g = make_grid(grid)
+            info = np.zeros(1, dtype=GROUPS_GRID_INFO_DTYPE)
+            _check(lib.nbody_get_groups_grid(self._ctx, g.ctypes.data, link, radius_scale, label.ctypes.data, self.capacity,
+                                             info.ctypes.data))
+            return _groups_grid_dict(label[:int(info["n_bodies"][0])].copy(), info[0], g)
         info = np.zeros(1, dtype=GROUPS_INFO_DTYPE)
         _check(lib.nbody_get_groups(self._ctx, link, radius_scale, label.ctypes.data, self.capacity, info.ctypes.data))
         return _groups_dict(label[:int(info["n_bodies"][0])].copy(), info[0])
@@ -1471,9 +1501,10 @@ class StepperGroup:
         """Stepper.within through one rank: every rank's replica holds every position and radius, each gives the same bits."""
         return self.ranks[rank].within(radius, points, grid, squared, lists)
 
-    def groups(self, link, radius_scale=1.0, rank=0):
-        """Stepper.groups through one rank: every rank's replica holds every body, each gives the same labels."""
-        return self.ranks[rank].groups(link, radius_scale)
+    def groups(self, link, radius_scale=1.0, rank=0, grid=None):
+        """Stepper.groups through one rank, with or without a grid: every rank's replica holds every body, each gives the
+        same labels."""
+        return self.ranks[rank].groups(link, radius_scale, grid)
 
     def group_potential(self, link, radius_scale=1.0, rank=0):
         """Stepper.group_potential through one rank: every rank's replica holds every position and mass."""
@@ -1740,10 +1771,16 @@ class StepperBatch:
         return _within(lambda *a: lib.nbody_batch_get_within(self._b, *a), self.systems, self.capacity, radius, points, g,
                        squared, lists)
 
-    def groups(self, link, radius_scale=1.0):
+    def groups(self, link, radius_scale=1.0, grid=None):
         """nbody_batch_get_groups: Stepper.groups for every system, every pair walk one launch for the whole batch: a list
-        of S dicts in the form (and with the labels) a Stepper holding the system's state gives."""
+        of S dicts in the form (and with the labels) a Stepper holding the system's state gives.  grid: one grid for every
+        system, nbody_batch_get_groups_grid - the list stages and every sweep one launch each."""
         label = np.zeros((self.systems, max(self.capacity, 1)), dtype=np.int32)
+        if grid is not None:
+            g = make_grid(grid)
+            info = np.zeros(max(self.systems, 1), dtype=GROUPS_GRID_INFO_DTYPE)
+            _check(lib.nbody_batch_get_groups_grid(self._b, g.ctypes.data, link, radius_scale, label.ctypes.data, info.ctypes.data))
+            return [_groups_grid_dict(label[s, :int(info["n_bodies"][s])].copy(), info[s], g) for s in range(self.systems)]
         info = np.zeros(max(self.systems, 1), dtype=GROUPS_INFO_DTYPE)
         _check(lib.nbody_batch_get_groups(self._b, link, radius_scale, label.ctypes.data, info.ctypes.data))
         return [_groups_dict(label[s, :int(info["n_bodies"][s])].copy(), info[s]) for s in range(self.systems)]

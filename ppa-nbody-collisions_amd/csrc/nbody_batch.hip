@@ -821,3 +821,21 @@ int nbody_batch_get_within(nbody_batch* b, const nbody_grid* grid, double h2, co
 }
 
 }  // extern "C"
+
+// Groups on the cell list (nbody_groups_grid.hpp): one grid, one link and one scale for every system, the list stages and
+// every sweep ONE launch each for the whole batch.
+extern "C" {
+
+int nbody_batch_get_groups_grid(nbody_batch* b, const nbody_grid* grid, double link, double radius_scale, int32_t* label,
+                                nbody_groups_grid_info* info) {
+    const char* who = "nbody_batch_get_groups_grid";
+    RowsSite site;
+    int rc = groups_grid_check_args(who, {b, label, info}, grid, link, radius_scale, batch_systems(b));
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return groups_grid_run<decltype(t), RowsBatchCount>(who, site, b->q.cel, b->q.wth, b->q.grp, *grid, link, radius_scale, label,
+                                                            info, sync);
+    });
+}
+
+}  // extern "C"

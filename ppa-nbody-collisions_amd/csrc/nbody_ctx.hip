@@ -1841,3 +1841,25 @@ int nbody_get_within(nbody_ctx* c, const nbody_grid* grid, double h2, const nbod
 }
 
 }  // extern "C"
+
+// Groups on the cell list (nbody_groups_grid.hpp): nbody_get_groups' arguments and errors after the grid's, and positions and
+// radii of the replica only - any rank may call it.  After everything else, for the group energies' reason.
+extern "C" {
+
+int nbody_get_groups_grid(nbody_ctx* c, const nbody_grid* grid, double link, double radius_scale, int32_t* label, int cap,
+                          nbody_groups_grid_info* info) {
+    const char* who = "nbody_get_groups_grid";
+    RowsSite site;
+    int rc = groups_grid_check_args(who, {c, label, info}, grid, link, radius_scale, 1);
+    if (rc != NBODY_OK) return rc;
+    if (cap < 0) return nbody_fail(NBODY_ERR_INVALID, "%s: cap = %d", who, cap);
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if (cap < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d labels, the context holds %d bodies", who, cap, site.n_bound);
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return groups_grid_run<decltype(t), RowsOneCount>(who, site, c->q.cel, c->q.wth, c->q.grp, *grid, link, radius_scale, label,
+                                                          info, sync);
+    });
+}
+
+}  // extern "C"

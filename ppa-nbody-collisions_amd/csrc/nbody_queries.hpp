@@ -5,6 +5,8 @@
 // What a new query adds to the handles: its header here, one member of QueryStates, one line of queries_free, and its two
 // entry points (nbody_get_* in nbody_ctx.hip, nbody_batch_get_* in nbody_batch.hip).  Nothing is allocated before a query's
 // first call (tracers: the first set); each state grows to the largest request seen and is released by queries_free.
+// A query that is another walk over what the states already hold adds no member: the groups on the cell list
+// (nbody_groups_grid.hpp) use `cel`, the sorted records of `wth` and `grp`.
 // IdsState and TrackState are not queries - they are set up at create and by a reservation - and stay members of the
 // handles, with ids_free and track_free next to them.
 #pragma once
@@ -25,6 +27,7 @@
 #include "nbody_encounters.hpp"
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
+#include "nbody_groups_grid.hpp"
 
 namespace nbk {
 
