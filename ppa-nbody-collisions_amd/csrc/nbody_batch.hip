@@ -833,7 +833,7 @@ int nbody_batch_get_groups_grid(nbody_batch* b, const nbody_grid* grid, double l
     int rc = groups_grid_check_args(who, {b, label, info}, grid, link, radius_scale, batch_systems(b));
     if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
     return batch_rows_run(b, [&](auto t, auto sync) {
-        return groups_grid_run<decltype(t), RowsBatchCount>(who, site, b->q.cel, b->q.wth, b->q.grp, *grid, link, radius_scale, label,
+        return groups_grid_run<decltype(t), RowsBatchCount>(who, site, b->q.cel, b->q.grp, *grid, link, radius_scale, label,
                                                             info, sync);
     });
 }

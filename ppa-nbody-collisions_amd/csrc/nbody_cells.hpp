@@ -46,6 +46,16 @@
 //                            instruction per member for all four chains, each lane's add waiting for its own previous
 //                            one only; the 64 terms of a full gather are read ahead of their adds.  Without kMoments the
 //                            velocities are never read and px, py, k2 stay +0.0.
+// What every query on the grid shares lives here as well (nbody_within.hpp and nbody_groups_grid.hpp walk the list):
+//   CellView, cells_view<Count>   one system's list as a kernel sees it - sys, n, cells, inside (held to [0, n]), the offset of
+//                            its per-body arrays and its start: the preamble of every kernel of the family.
+//   cells_coords             the cell coordinates (tx, ty): cells_cell sorts by them, the window walk places its window by them.
+//   CellRec<T>, cells_gather<T, Count>, cells_gather_run   the list's records {x, y, r, j} in cell order (CellState::sorted),
+//                            one lane per slot of `order`, launched after cells_list_run by the queries that walk the list.
+//   cells_span, cells_window_walk   the window along one axis, and the one walk over the row-of-cells ranges of a window:
+//                            pair(rec) per record, four records loaded ahead.
+//   cells_block_prefix<V, kBlock>   a workgroup's exclusive prefix (cells_scan here, the row scan of nbody_within.hpp).
+//   cells_fine               the host's guard for a grid too fine for the window's proof.
 // Every index that comes out of memory (a cell of cell_of, an entry of slot or order, a start) is range-checked before it is
 // used as one; by construction none fails.  A batch's count goes through batch_checked_count; cells_assign reports a bad
 // one once as kIndexError (rows_prologue), every kernel treats the system as empty.
@@ -61,16 +71,19 @@
 // of 256 x 1024 on 32 x 32 cells: 0.044 ms of kernels, 1.21 ms for StepperBatch.cells() with its lists.
 //
 // Registers (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage; fp32 and fp64 records of a context, fp32
-// of a batch: 16 instantiations; VGPRs f32 / f64 for the kernels that read records, SGPRs a context / a batch):
+// of a batch: 19 instantiations; VGPRs f32 / f64 for the kernels that read records, SGPRs a context / a batch):
 //     kernel                       lanes   VGPRs   SGPRs   scratch   LDS bytes   waves per SIMD
 //     cells_assign  f32 / f64       256    10 / 12    26 / 28      0           0           8
-//     cells_scan                   1024      47       72 / 74      0         256           8
-//     cells_place                   256      12       18 / 24      0           0           8
+//     cells_scan                   1024      59       72 / 74      0         256           8
+//     cells_place                   256      12       18 / 26      0           0           8
 //     cells_rank                    256      38       37 / 40      0        8192           8
 //     cells_sum     no moments      256    36 / 36    33 / 35      0        2112           8
 //     cells_sum     moments         256    46 / 48    35 / 37      0        8448           8
-// No instantiation uses scratch.
+//     cells_gather  f32 / f64       256    10 / 14    20 / 20      0           0           8
+// No instantiation uses scratch.  (profiles/grid_walk_refactor.txt has every instantiation next to its form before the pieces
+// above were shared.)
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
@@ -100,13 +113,64 @@ __device__ __forceinline__ int cells_n(const Meta* __restrict__ meta_all, int sy
     return chk < 0 ? 0 : chk;
 }
 
+// One system's cell list as a kernel sees it: what every kernel of the grid family starts from.  at: where the system's
+// entries begin in a per-body array (cell_of, slot, order, the sorted records, J), so `x_all + cl.at` is the system's x.
+// inside: the last start, held to [0, n] - every index a kernel takes from the list is checked against it.
+struct CellView {
+    int sys, n, cells, inside;
+    size_t at;
+    const int32_t* __restrict__ start;                           // [cells + 1]
+};
+// Without a list (cells_scan, which writes it, and the row scan of nbody_within.hpp): sys, n and at only; inside is 0.
+template <typename Count>
+__device__ __forceinline__ CellView cells_view(const Meta* __restrict__ meta_all, int stride, int n_one, int cells = 0,
+                                               const int32_t* __restrict__ start_all = nullptr) {
+    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
+    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
+    const int32_t* __restrict__ start = start_all ? start_all + (size_t)sys * (size_t)(cells + 1) : nullptr;
+    const int last = start && n > 0 ? start[cells] : 0;
+    return CellView{sys, n, cells, last < 0 ? 0 : last > n ? n : last, (size_t)sys * (size_t)stride, start};
+}
+
+// The cell coordinates of the definition.  cells_cell sorts a body by them and cells_window_walk places a row's window by
+// them: one function, so a body lies in the window around the cell it was sorted into.
+struct CellCoords { double tx, ty; };
+__device__ __forceinline__ CellCoords cells_coords(const nbody_grid& g, double x, double y) {
+    return CellCoords{(x - g.x0) * g.sx, (y - g.y0) * g.sy};
+}
+
 // cell(j) of the definition.  The compares are on the doubles; what is converted has passed them (or is +0.0), so no
 // value outside [0, nx) or [0, ny) ever reaches a float-to-int conversion.
 __device__ __forceinline__ int cells_cell(const nbody_grid& g, double x, double y) {
-    const double tx = (x - g.x0) * g.sx, ty = (y - g.y0) * g.sy;
-    const bool inside = 0.0 <= tx && tx < (double)g.nx && 0.0 <= ty && ty < (double)g.ny;
-    const int ix = (int)(inside ? tx : 0.0), iy = (int)(inside ? ty : 0.0);
+    const CellCoords t = cells_coords(g, x, y);
+    const bool inside = 0.0 <= t.tx && t.tx < (double)g.nx && 0.0 <= t.ty && t.ty < (double)g.ny;
+    const int ix = (int)(inside ? t.tx : 0.0), iy = (int)(inside ? t.ty : 0.0);
     return inside ? iy * g.nx + ix : -1;
+}
+
+// A workgroup's exclusive prefix over its lanes' values: the lane's offset, and the workgroup's total in every lane.  A
+// wave scan by shuffles, the wave totals through wsum (shared, kBlock / kWave entries).  Every lane of the workgroup
+// calls it; a caller that calls it again puts a barrier in between, since wsum is written again.
+template <typename V> struct BlockPrefix { V at, total; };
+template <typename V, int kBlock>
+__device__ __forceinline__ BlockPrefix<V> cells_block_prefix(V mine, V* wsum) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    V x = mine;                                                  // inclusive over the wave
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const V y = __shfl_up(x, d, kWave);
+        if (lane >= d) x += y;
+    }
+    if (lane == kWave - 1) wsum[wave] = x;
+    __syncthreads();
+    V before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; ++w) {
+        const V t = wsum[w];
+        before += w < wave ? t : 0;
+        total += t;
+    }
+    return BlockPrefix<V>{before + x - mine, total};
 }
 
 // The runs of equal cells along a wave's lanes: a lane heads a run where its predecessor holds another cell (lane 0 always
@@ -149,8 +213,8 @@ __global__ __launch_bounds__(kCellScanBlock) void cells_scan(const Meta* __restr
                                                              const unsigned* __restrict__ count_all,
                                                              int32_t* __restrict__ start_all,
                                                              nbody_cells_info* __restrict__ info_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one);
+    const int sys = cl.sys, n = cl.n;
     const unsigned* __restrict__ count = count_all + (size_t)sys * (size_t)cells;
     int32_t* __restrict__ start = start_all + (size_t)sys * (size_t)(cells + 1);
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -174,22 +238,8 @@ __global__ __launch_bounds__(kCellScanBlock) void cells_scan(const Meta* __restr
             const long long c = (long long)c0 + kCellScanChunk + u;
             nv[u] = c < cells ? (int)count[c] : 0;
         }
-        int x = mine;                                            // inclusive over the wave
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int y = __shfl_up(x, d, kWave);
-            if (lane >= d) x += y;
-        }
-        if (lane == kWave - 1) wsum[wave] = x;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const int t = wsum[w];
-            before += w < wave ? t : 0;
-            total += t;
-        }
-        int at = carry + before + x - mine;
+        const BlockPrefix<int> p = cells_block_prefix<int, kCellScanBlock>(mine, wsum);
+        int at = carry + p.at;
 #pragma unroll
         for (int u = 0; u < kCellScanPer; ++u) {
             if (c0 + u < cells) {
@@ -199,7 +249,7 @@ __global__ __launch_bounds__(kCellScanBlock) void cells_scan(const Meta* __restr
                 at += v[u];
             }
         }
-        carry += total;
+        carry += p.total;
         __syncthreads();                                         // wsum is written again in the next trip
     }
     if (tid == 0) start[cells] = carry;
@@ -227,20 +277,19 @@ __global__ __launch_bounds__(kDiagBlock) void cells_place(const Meta* __restrict
                                                           const int32_t* __restrict__ cell_of_all,
                                                           const int32_t* __restrict__ start_all, unsigned* __restrict__ cursor_all,
                                                           int32_t* __restrict__ slot_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
-    if ((int)(blockIdx.x * kDiagBlock) >= n) return;             // the whole workgroup
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one, cells, start_all);
+    if ((int)(blockIdx.x * kDiagBlock) >= cl.n) return;          // the whole workgroup
     const int j = blockIdx.x * kDiagBlock + threadIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
-    int c = j < n ? cell_of_all[(size_t)sys * (size_t)stride + j] : -1;
+    int c = j < cl.n ? cell_of_all[cl.at + j] : -1;
     if ((unsigned)c >= (unsigned)cells) c = -1;
     const CellRun run = cells_wave_runs(c);
     unsigned base = 0;
-    if (run.head && c >= 0) base = atomicAdd(cursor_all + (size_t)sys * (size_t)cells + (size_t)c, (unsigned)run.len);
+    if (run.head && c >= 0) base = atomicAdd(cursor_all + (size_t)cl.sys * (size_t)cells + (size_t)c, (unsigned)run.len);
     base = __shfl(base, run.head_lane, kWave);
     if (c >= 0) {
-        const long long pos = (long long)start_all[(size_t)sys * (size_t)(cells + 1) + c] + base + (lane - run.head_lane);
-        if (pos >= 0 && pos < n) slot_all[(size_t)sys * (size_t)stride + pos] = j;
+        const long long pos = (long long)cl.start[c] + base + (lane - run.head_lane);
+        if (pos >= 0 && pos < cl.n) slot_all[cl.at + pos] = j;
     }
 }
 
@@ -250,23 +299,20 @@ __global__ __launch_bounds__(kDiagBlock) void cells_rank(const Meta* __restrict_
                                                          const int32_t* __restrict__ cell_of_all,
                                                          const int32_t* __restrict__ start_all,
                                                          const int32_t* __restrict__ slot_all, int32_t* __restrict__ order_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
-    const int32_t* __restrict__ cell_of = cell_of_all + (size_t)sys * (size_t)stride;
-    const int32_t* __restrict__ start = start_all + (size_t)sys * (size_t)(cells + 1);
-    const int32_t* __restrict__ slot = slot_all + (size_t)sys * (size_t)stride;
-    int inside = n > 0 ? start[cells] : 0;
-    inside = inside < 0 ? 0 : inside > n ? n : inside;
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one, cells, start_all);
+    const int32_t* __restrict__ cell_of = cell_of_all + cl.at;
+    const int32_t* __restrict__ slot = slot_all + cl.at;
+    const int inside = cl.inside;
     const int e0 = blockIdx.x * kDiagBlock, tid = threadIdx.x;
     if (e0 >= inside) return;                                    // the whole workgroup, before any barrier
     // a slot's index, cell and segment; nothing that fails its check becomes an index
     const auto segment = [&](int e, int& idx, int& s0, int& s1) {
         idx = slot[e];
         s0 = s1 = 0;
-        if ((unsigned)idx >= (unsigned)n) return false;
+        if ((unsigned)idx >= (unsigned)cl.n) return false;
         const int c = cell_of[idx];
         if ((unsigned)c >= (unsigned)cells) return false;
-        s0 = start[c]; s1 = start[c + 1];
+        s0 = cl.start[c]; s1 = cl.start[c + 1];
         if (s0 < 0 || s1 > inside || s0 > s1) { s0 = s1 = 0; return false; }
         return true;
     };
@@ -301,7 +347,67 @@ __global__ __launch_bounds__(kDiagBlock) void cells_rank(const Meta* __restrict_
         }
         for (; k < end; ++k) rank += tile[b][k] < idx ? 1 : 0;
     }
-    if (valid && s0 + rank < s1) order_all[(size_t)sys * (size_t)stride + s0 + rank] = idx;
+    if (valid && s0 + rank < s1) order_all[cl.at + s0 + rank] = idx;
+}
+
+// A source in cell order: what a walk over the list reads instead of an index and a record per pair.
+template <typename T> struct CellRec;
+template <> struct alignas(16) CellRec<float> { float x, y, r; int j; };
+template <> struct alignas(32) CellRec<double> { double x, y, r; int j; };
+static_assert(sizeof(CellRec<float>) == 16 && sizeof(CellRec<double>) == 32, "a record is one 16 or 32 byte load");
+
+// One lane per slot of `order`: the record {x, y, r, j} into sorted_all ([systems * stride]), in cell order.
+template <typename T, typename Count>
+__global__ __launch_bounds__(kDiagBlock) void cells_gather(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
+                                                           int stride, int n_one, int cells,
+                                                           const int32_t* __restrict__ start_all,
+                                                           const int32_t* __restrict__ order_all,
+                                                           CellRec<T>* __restrict__ sorted_all) {
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one, cells, start_all);
+    const int e = blockIdx.x * kDiagBlock + threadIdx.x;
+    if (e >= cl.inside) return;
+    const int idx = order_all[cl.at + e];
+    CellRec<T> w{(T)__builtin_nan(""), (T)0, (T)0, 0};            // an entry that fails its check: d2 = NaN, never near
+    if ((unsigned)idx < (unsigned)cl.n) {
+        const Rec<T> r = J_all[cl.at + idx];
+        w = CellRec<T>{r.x, r.y, r.r, idx};
+    }
+    sorted_all[cl.at + e] = w;
+}
+
+// The window along one axis around the cell coordinate t, w0 cells to either side and a margin (DESIGN.md 4.21 has the
+// rule and its proof): cells lo .. hi, hi < lo for none.
+struct CellSpan { int lo, hi; };
+__device__ __forceinline__ CellSpan cells_span(double t, double w0, int cells) {
+    const double w = w0 + (0x1p-20 + (fabs(t) + w0) * 0x1p-40);
+    const double lo = t - w, hi = t + w;
+    if (!(fabs(t) < __builtin_inf()) || lo != lo || hi != hi) return CellSpan{0, cells - 1};
+    if (hi < 0.0 || lo >= (double)cells) return CellSpan{0, -1};
+    // lo < cells and hi >= 0: what is converted lies in [0, cells)
+    return CellSpan{lo > 0.0 ? (int)lo : 0, hi < (double)(cells - 1) ? (int)hi : cells - 1};
+}
+
+// The one walk over the cells around a place: pair(rec) for every sorted record of the window around the cell coordinates
+// (tx, ty) of cells_coords, wx0 and wy0 cells wide to either side.  The grid is row-major, so the members of columns lo .. hi
+// of one row of cells are ONE contiguous range of the sorted records, start[yy * nx + lo] .. start[yy * nx + hi + 1]; a range
+// that fails its check is skipped; four records are loaded ahead of their pairs.
+template <typename T, typename Pair>
+__device__ __forceinline__ void cells_window_walk(const CellView& cl, const CellRec<T>* __restrict__ sorted, const nbody_grid& g,
+                                                  double tx, double ty, double wx0, double wy0, Pair pair) {
+    const CellSpan cx = cells_span(tx, wx0, g.nx), cy = cells_span(ty, wy0, g.ny);
+    if (cx.lo > cx.hi) return;
+    for (int yy = cy.lo; yy <= cy.hi; ++yy) {
+        const int a = cl.start[yy * g.nx + cx.lo], b = cl.start[yy * g.nx + cx.hi + 1];
+        if (a < 0 || b > cl.inside || a >= b) continue;
+        for (int k = a; k < b; k += 4) {                         // four loads ahead of their pairs
+            CellRec<T> s[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s[u] = sorted[k + u < b ? k + u : b - 1];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (k + u < b) pair(s[u]);
+        }
+    }
 }
 
 // One member's terms, widened exactly; kMoments: with the velocity.
@@ -325,19 +431,18 @@ __global__ __launch_bounds__(kDiagBlock) void cells_sum(const Rec<T>* __restrict
                                                         const Meta* __restrict__ meta_all, int stride, int n_one, int cells,
                                                         const int32_t* __restrict__ start_all,
                                                         const int32_t* __restrict__ order_all, nbody_cell* __restrict__ cells_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
-    const Rec<T>* __restrict__ J = J_all + (size_t)sys * (size_t)stride;
-    const Vec2<T>* __restrict__ V = kMoments ? V_all + (size_t)sys * (size_t)stride : nullptr;
-    const int32_t* __restrict__ start = start_all + (size_t)sys * (size_t)(cells + 1);
-    const int32_t* __restrict__ order = order_all + (size_t)sys * (size_t)stride;
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one, cells, start_all);
+    const int n = cl.n;
+    const Rec<T>* __restrict__ J = J_all + cl.at;
+    const Vec2<T>* __restrict__ V = kMoments ? V_all + cl.at : nullptr;
+    const int32_t* __restrict__ order = order_all + cl.at;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const int c = blockIdx.x * kDiagBlock + tid;
     const bool live = c < cells;
     int s0 = 0, cnt = 0;
     if (live && n > 0) {
-        s0 = start[c];
-        cnt = start[c + 1] - s0;
+        s0 = cl.start[c];
+        cnt = cl.start[c + 1] - s0;
         if (s0 < 0 || cnt < 0 || s0 > n || cnt > n - s0) { s0 = 0; cnt = 0; }
     }
     // an entry of the list as an index into J and V
@@ -399,7 +504,7 @@ __global__ __launch_bounds__(kDiagBlock) void cells_sum(const Rec<T>* __restrict
         if constexpr (kMoments) { a1 = __shfl(acc, 1, kWave); a2 = __shfl(acc, 2, kWave); a3 = __shfl(acc, 3, kWave); }
         if (lane == src) { mass = a0; px = a1; py = a2; k2 = a3; }
     }
-    if (live) cells_all[(size_t)sys * (size_t)cells + c] = nbody_cell{mass, px, py, k2, cnt, first};
+    if (live) cells_all[(size_t)cl.sys * (size_t)cells + c] = nbody_cell{mass, px, py, k2, cnt, first};
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -413,16 +518,18 @@ struct CellState {
     RowsArray<nbody_cells_info> info;   // [systems]
     RowsArray<unsigned> words;          // device [2][systems * cells]: the counts, then the cursors of cells_place
     RowsArray<int32_t> slot;            // device [systems * stride]: the list as cells_place leaves it
+    RowsArray<unsigned char> sorted;    // device [systems * stride] CellRec<T>: the list's records, for the queries that walk it
 };
 
 inline void cells_free(CellState& g) {
     rows_free(g.cells); rows_free(g.start); rows_free(g.cell_of); rows_free(g.order); rows_free(g.info); rows_free(g.words);
-    rows_free(g.slot);
+    rows_free(g.slot); rows_free(g.sorted);
 }
 
-// sums: with the cell records; a caller that needs the list only (nbody_within.hpp) leaves them out.
-inline int cells_reserve(CellState& g, size_t systems, size_t cells, size_t bodies, const char* who, bool sums = true) {
-    hipError_t e = sums ? rows_reserve(g.cells, systems * cells) : hipSuccess;
+// rec_bytes: 0 for the cell sums, which need the cell records; sizeof(CellRec<T>) for a query that walks the list
+// (nbody_within.hpp, nbody_groups_grid.hpp), which needs the sorted records instead.
+inline int cells_reserve(CellState& g, size_t systems, size_t cells, size_t bodies, const char* who, size_t rec_bytes = 0) {
+    hipError_t e = rec_bytes ? rows_reserve_device(g.sorted, (bodies > 0 ? bodies : 1) * rec_bytes) : rows_reserve(g.cells, systems * cells);
     if (e == hipSuccess) e = rows_reserve(g.start, systems * (cells + 1));
     if (e == hipSuccess) e = rows_reserve(g.cell_of, bodies > 0 ? bodies : 1);
     if (e == hipSuccess) e = rows_reserve(g.order, bodies > 0 ? bodies : 1);
@@ -461,8 +568,8 @@ inline int cells_check_args(const char* who, std::initializer_list<const void*> 
 }
 
 // The list stages on the site's stream, no wait: the memset of the counts and cursors, cells_assign, cells_scan, cells_place
-// and cells_rank.  Leaves g.cell_of, g.start, g.order and g.info on the device; g is reserved by the caller.  What both the
-// cell sums and the radius queries (nbody_within.hpp) run first.
+// and cells_rank.  Leaves g.cell_of, g.start, g.order and g.info on the device; g is reserved by the caller.  What the cell
+// sums, the radius queries (nbody_within.hpp) and the groups on the grid (nbody_groups_grid.hpp) run first.
 template <typename T, typename Count>
 int cells_list_run(const RowsSite& s, CellState& g, const nbody_grid& grid) {
     const size_t S = (size_t)s.systems, C = (size_t)grid.nx * (size_t)grid.ny;
@@ -491,6 +598,22 @@ int cells_list_run(const RowsSite& s, CellState& g, const nbody_grid& grid) {
     }
     return NBODY_OK;
 }
+
+// After cells_list_run, on the same stream, no wait: cells_gather into g.sorted.  A function of its own: the cell sums do not
+// read the records, and their entry point must not name the kernel.
+template <typename T, typename Count>
+int cells_gather_run(const RowsSite& s, CellState& g, const nbody_grid& grid) {
+    if (s.n_bound <= 0) return NBODY_OK;
+    hipLaunchKernelGGL((cells_gather<T, Count>), s.grid(s.n_bound), dim3(kDiagBlock), 0, s.stream, (const Rec<T>*)s.J, s.meta,
+                       s.stride, s.n_one<Count>(), grid.nx * grid.ny, (const int32_t*)g.start.d, (const int32_t*)g.order.d,
+                       reinterpret_cast<CellRec<T>*>(g.sorted.d));
+    NBK_ROWS_TRY(hipGetLastError());
+    return NBODY_OK;
+}
+
+// A grid too fine for the proof of the window's margin (more than 2^400 cells per unit length: dx*dx can underflow for
+// bodies many cells apart): a walk over it looks at every cell.
+inline bool cells_fine(const nbody_grid& grid) { return !(grid.sx <= 0x1p400 && grid.sy <= 0x1p400); }
 
 // One call, from the reservation to the caller's arrays; the site, Count and read_meta as for rows_run (nbody_rows.hpp).
 // V: the velocities, indexed like the site's J, read only with NBODY_CELLS_MOMENTS.  A list the caller did not ask for is

@@ -1857,7 +1857,7 @@ int nbody_get_groups_grid(nbody_ctx* c, const nbody_grid* grid, double link, dou
     if (cap < site.n_bound)
         return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d labels, the context holds %d bodies", who, cap, site.n_bound);
     return ctx_rows_run(c, [&](auto t, auto sync) {
-        return groups_grid_run<decltype(t), RowsOneCount>(who, site, c->q.cel, c->q.wth, c->q.grp, *grid, link, radius_scale, label,
+        return groups_grid_run<decltype(t), RowsOneCount>(who, site, c->q.cel, c->q.grp, *grid, link, radius_scale, label,
                                                           info, sync);
     });
 }

@@ -17,22 +17,23 @@
 //     S_i = (radius_scale * (a + a)) + link;   h2_i = S_i * S_i            the roundings of s
 // For |R_j| <= a: |fl(R_i + R_j)| <= 2a, so |s_ij| <= S_i (rounding is monotone, radius_scale and link are >= 0), so
 // fl(s_ij * s_ij) <= h2_i: a linked j has d2 <= h2_i.  Of the two ends of a link one has the other's |radius| <= its own.
-// The cells of row i are within_span's with w0 = fl(S_i * sx) and fl(S_i * sy), per lane; a grid of more than 2^400 cells per
-// unit length means every cell (`fine`, from the host, as within_window decides it); S_i = +inf means every cell through
-// within_span as it stands; a NaN S_i (a NaN radius, or radius_scale = 0 with an infinite one) links nothing in the
-// definition either - every s_ij of that row is NaN - and the lane leaves.
+// The cells of row i are cells_span's with w0 = fl(S_i * sx) and fl(S_i * sy), per lane; a grid of more than 2^400 cells per
+// unit length means every cell (`fine`, from the host: cells_fine); S_i = +inf means every cell through cells_span as it
+// stands; a NaN S_i (a NaN radius, or radius_scale = 0 with an infinite one) links nothing in the definition either - every
+// s_ij of that row is NaN - and the lane leaves.
 // One body ten times the typical size widens its own window only: the price is that one lane walks it.
 //
-// Kernels, on the handle's stream: the four list stages of the cell sums (cells_list_run), within_gather into the sorted
-// {x, y, r, j} records of the radius queries (the same buffer), groups_init, then groups_grid_sweep until a sweep changes
-// nothing, then groups_flatten - groups_init, groups_find, groups_hook, groups_flatten and GroupsState as nbody_groups.hpp
-// has them.  Bodies outside the grid get no lane: groups_init leaves them their own root.
+// Kernels, on the handle's stream: the four list stages of the cell sums (cells_list_run), the gather of the list's sorted
+// {x, y, r, j} records (cells_gather_run; the buffer the radius queries walk), groups_init, then groups_grid_sweep until a
+// sweep changes nothing, then groups_flatten - groups_init, groups_find, groups_hook, groups_flatten and GroupsState as
+// nbody_groups.hpp has them.  Bodies outside the grid get no lane: groups_init leaves them their own root.
 //   groups_grid_sweep<T, Count>  one lane per slot q < inside of the cell list (lane = slot: the 64 rows of a wave share a few
-//                             cells).  The row-of-cells ranges of the lane's window are walked as within_walk walks them,
-//                             four records loaded ahead of their pairs.  Per pair: 2 subtractions, 2 multiplies, 1 add and
-//                             the compare with the lane's h2_i (and j != self); behind that branch the exact predicate - s
-//                             from both radii, d2 <= s*s, which may still fail, or hold for a j of larger radius: a true
-//                             link is a true link - and groups_hook.  No j < i: the end that sees a pair may be either.
+//                             cells).  The row-of-cells ranges of the lane's window are walked by cells_window_walk
+//                             (nbody_cells.hpp), the walk of within_walk: four records loaded ahead of their pairs.
+//                             Per pair: 2 subtractions, 2 multiplies, 1 add and the compare with the lane's h2_i (and
+//                             j != self); behind that branch the exact predicate - s from both radii, d2 <= s*s, which
+//                             may still fail, or hold for a j of larger radius: a true link is a true link - and
+//                             groups_hook.  No j < i: the end that sees a pair may be either.
 // The `changed` words are groups_sweep's: set where unequal roots are SEEN; a batch's words of the last sweep are read at the
 // prologue and a system that had converged leaves there as a whole workgroup; the host reads 4 bytes per system after each
 // sweep and gives up after n_bound + 1.  The proofs of nbody_groups.hpp - a find ends, a sweep that sets no word has seen
@@ -61,23 +62,19 @@ namespace nbk {
 static_assert(sizeof(nbody_groups_grid_info) == 24 && offsetof(nbody_groups_grid_info, inside) == 16, "nbody_groups_grid_info layout");
 
 // One lane per slot; grid = (ceil(n_bound / kDiagBlock), systems).  prev / cur: the systems' `changed` words of the last
-// sweep and of this one.  fine: every cell (within_window's guard).
+// sweep and of this one.  fine: every cell (cells_fine).
 template <typename T, typename Count>
-__global__ __launch_bounds__(kDiagBlock) void groups_grid_sweep(const WithinRec<T>* __restrict__ sorted_all,
+__global__ __launch_bounds__(kDiagBlock) void groups_grid_sweep(const CellRec<T>* __restrict__ sorted_all,
                                                                 const Meta* __restrict__ meta_all, int stride, int n_one,
                                                                 const nbody_grid g, double link, double scale, int fine,
                                                                 const int32_t* __restrict__ start_all, int32_t* parent_all,
                                                                 const int* __restrict__ prev, int* __restrict__ cur) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    if (prev[sys] == 0) return;                                  // converged in an earlier sweep: the whole workgroup
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
-    const int cells = g.nx * g.ny;
-    const int32_t* __restrict__ start = start_all + (size_t)sys * (size_t)(cells + 1);
-    const WithinRec<T>* __restrict__ sorted = sorted_all + (size_t)sys * (size_t)stride;
-    const int inside = within_inside(start, cells, n);
-    const int q = blockIdx.x * kDiagBlock + threadIdx.x;
-    if (q >= inside) return;                                     // no barrier follows
-    const WithinRec<T> me = sorted[q];
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one, g.nx * g.ny, start_all);
+    if (prev[cl.sys] == 0) return;                               // converged in an earlier sweep: the whole workgroup
+    const CellRec<T>* __restrict__ sorted = sorted_all + cl.at;
+    const int q = blockIdx.x * kDiagBlock + threadIdx.x, n = cl.n;
+    if (q >= cl.inside) return;                                  // no barrier follows
+    const CellRec<T> me = sorted[q];
     const int self = me.j;
     if ((unsigned)self >= (unsigned)n) return;
     const double x = (double)me.x, y = (double)me.y, r = (double)me.r;
@@ -86,36 +83,22 @@ __global__ __launch_bounds__(kDiagBlock) void groups_grid_sweep(const WithinRec<
     if (S != S) return;                                          // every s of this row is NaN: it links nothing
     const double h2 = S * S;
     const double inf = __builtin_inf();
-    const double tx = (x - g.x0) * g.sx, ty = (y - g.y0) * g.sy; // cells_cell's, same bits
-    const WithinSpan cx = within_span(tx, fine ? inf : S * g.sx, g.nx), cy = within_span(ty, fine ? inf : S * g.sy, g.ny);
-    int32_t* parent = parent_all + (size_t)sys * (size_t)stride;
-    int* changed = cur + sys;
-    const auto pair = [&](const WithinRec<T>& s) {
+    const CellCoords t = cells_coords(g, x, y);
+    int32_t* parent = parent_all + cl.at;
+    int* changed = cur + cl.sys;
+    cells_window_walk(cl, sorted, g, t.tx, t.ty, fine ? inf : S * g.sx, fine ? inf : S * g.sy, [&](const CellRec<T>& s) {
         const double dx = (double)s.x - x, dy = (double)s.y - y;
         const double d2 = (dx * dx) + (dy * dy);
         if (d2 <= h2 && s.j != self) {                           // the rest only for a pair that passes
             const double sum = (scale * (r + (double)s.r)) + link;
             if (d2 <= sum * sum && (unsigned)s.j < (unsigned)n) groups_hook(parent, changed, self, s.j);
         }
-    };
-    if (cx.lo > cx.hi) return;
-    for (int yy = cy.lo; yy <= cy.hi; ++yy) {
-        const int a0 = start[yy * g.nx + cx.lo], b = start[yy * g.nx + cx.hi + 1];
-        if (a0 < 0 || b > inside || a0 >= b) continue;
-        for (int k = a0; k < b; k += 4) {                        // four loads ahead of their pairs
-            WithinRec<T> s[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = sorted[k + u < b ? k + u : b - 1];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (k + u < b) pair(s[u]);
-        }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Host side.  No buffers of its own: the cell list of CellState, the sorted records of WithinState, the parents and labels of
-// GroupsState - each allocated by whichever query of the handle asks first.
+// Host side.  No buffers of its own: the cell list and its sorted records of CellState, the parents and labels of GroupsState -
+// each allocated by whichever query of the handle asks first.
 // ---------------------------------------------------------------------------------------------------------
 
 // The argument checks an entry point makes before any device call, the values before the handle: the grid as the cell sums
@@ -127,28 +110,20 @@ inline int groups_grid_check_args(const char* who, std::initializer_list<const v
 }
 
 // One call, from the reservation to the caller's labels; the site, Count and read_meta as for rows_run (nbody_rows.hpp).  One
-// wait per sweep and one at the end.
+// wait per sweep and one at the end.  The host loop is groups_run's (nbody_groups.hpp) with another sweep; it is written
+// out here as well, because a shared driver would name groups_sweep before groups_init and move both in the code object.
 template <typename T, typename Count, typename ReadMeta>
-int groups_grid_run(const char* who, const RowsSite& s, CellState& g, WithinState& ws, GroupsState& gs, const nbody_grid& grid,
-                    double link, double radius_scale, int32_t* label, nbody_groups_grid_info* info, ReadMeta read_meta) {
+int groups_grid_run(const char* who, const RowsSite& s, CellState& g, GroupsState& gs, const nbody_grid& grid, double link,
+                    double radius_scale, int32_t* label, nbody_groups_grid_info* info, ReadMeta read_meta) {
     const size_t S = (size_t)s.systems, C = (size_t)grid.nx * (size_t)grid.ny, total = S * (size_t)s.stride;
     int sweeps = 0;
     if (s.n_bound > 0) {
-        int rc = cells_reserve(g, S, C, total, who, false);
-        if (rc != NBODY_OK) return rc;
-        const hipError_t e = rows_reserve_device(ws.sorted, total * sizeof(WithinRec<T>));
-        if (e != hipSuccess) return within_fail_alloc(ws, e, who, "sorted records");
-        if ((rc = groups_reserve(gs, total, S, who)) != NBODY_OK) return rc;
+        int rc = cells_reserve(g, S, C, total, who, sizeof(CellRec<T>));
+        if (rc != NBODY_OK || (rc = groups_reserve(gs, total, S, who)) != NBODY_OK) return rc;
         const dim3 per_body = s.grid(s.n_bound), block(kDiagBlock);
-        const Rec<T>* J = (const Rec<T>*)s.J;
-        const int n_one = s.n_one<Count>(), cells = (int)C;
-        const int fine = !(grid.sx <= 0x1p400 && grid.sy <= 0x1p400);       // within_window's guard
-        WithinRec<T>* sorted = reinterpret_cast<WithinRec<T>*>(ws.sorted.d);
+        const int n_one = s.n_one<Count>(), fine = cells_fine(grid);
         int* h_changed = reinterpret_cast<int*>(gs.h + total * sizeof(int32_t));
-        if ((rc = cells_list_run<T, Count>(s, g, grid)) != NBODY_OK) return rc;
-        hipLaunchKernelGGL((within_gather<T, Count>), per_body, block, 0, s.stream, J, s.meta, s.stride, n_one, cells,
-                           (const int32_t*)g.start.d, (const int32_t*)g.order.d, sorted);
-        NBK_ROWS_TRY(hipGetLastError());
+        if ((rc = cells_list_run<T, Count>(s, g, grid)) != NBODY_OK || (rc = cells_gather_run<T, Count>(s, g, grid)) != NBODY_OK) return rc;
         hipLaunchKernelGGL((groups_init<Count>), per_body, block, 0, s.stream, gs.parent, s.stride, s.n_bound);
         NBK_ROWS_TRY(hipGetLastError());
         int* prev = gs.changed;
@@ -159,8 +134,8 @@ int groups_grid_run(const char* who, const RowsSite& s, CellState& g, WithinStat
             if (sweeps > s.n_bound)
                 return nbody_fail(NBODY_ERR_HIP, "%s: did not converge in %d sweeps over at most %d bodies", who, sweeps, s.n_bound);
             NBK_ROWS_TRY(hipMemsetAsync(cur, 0, S * sizeof(int), s.stream));
-            hipLaunchKernelGGL((groups_grid_sweep<T, Count>), per_body, block, 0, s.stream, (const WithinRec<T>*)sorted, s.meta,
-                               s.stride, n_one, grid, link, radius_scale, fine, (const int32_t*)g.start.d, gs.parent,
+            hipLaunchKernelGGL((groups_grid_sweep<T, Count>), per_body, block, 0, s.stream, reinterpret_cast<const CellRec<T>*>(g.sorted.d),
+                               s.meta, s.stride, n_one, grid, link, radius_scale, fine, (const int32_t*)g.start.d, gs.parent,
                                (const int*)prev, cur);
             NBK_ROWS_TRY(hipGetLastError());
             ++sweeps;
@@ -170,8 +145,8 @@ int groups_grid_run(const char* who, const RowsSite& s, CellState& g, WithinStat
             for (size_t k = 0; k < S; ++k) again = again || h_changed[k] != 0;
             int* t = prev; prev = cur; cur = t;
         }
-        hipLaunchKernelGGL((groups_flatten<T, Count>), per_body, block, 0, s.stream, J, s.meta, s.counters, s.stride, n_one,
-                           (const int32_t*)gs.parent, gs.label);
+        hipLaunchKernelGGL((groups_flatten<T, Count>), per_body, block, 0, s.stream, (const Rec<T>*)s.J, s.meta, s.counters, s.stride,
+                           n_one, (const int32_t*)gs.parent, gs.label);
         NBK_ROWS_TRY(hipGetLastError());
         const size_t copied = Count::kBatch ? total : (size_t)s.n_bound;
         NBK_ROWS_TRY(hipMemcpyAsync(gs.h, gs.label, copied * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));

@@ -6,7 +6,7 @@
 // entry points (nbody_get_* in nbody_ctx.hip, nbody_batch_get_* in nbody_batch.hip).  Nothing is allocated before a query's
 // first call (tracers: the first set); each state grows to the largest request seen and is released by queries_free.
 // A query that is another walk over what the states already hold adds no member: the groups on the cell list
-// (nbody_groups_grid.hpp) use `cel`, the sorted records of `wth` and `grp`.
+// (nbody_groups_grid.hpp) use `cel` and `grp`.
 // IdsState and TrackState are not queries - they are set up at create and by a reservation - and stay members of the
 // handles, with ids_free and track_free next to them.
 #pragma once
@@ -40,7 +40,7 @@ struct QueryStates {
     KnnState knn;               // k nearest neighbours (nbody_knn.hpp)
     ShellState shl;             // shell sums (nbody_shells.hpp)
     ShellMomentState shm;       // shell moments (nbody_shell_moments.hpp)
-    CellState cel;              // cell sums (nbody_cells.hpp)
+    CellState cel;              // cell sums (nbody_cells.hpp): the cell list and its sorted records, for every query on the grid
     WithinState wth;            // radius queries (nbody_within.hpp): the cell list of `cel` and these
     EncState enc;               // encounter queries (nbody_encounters.hpp)
     BinState bin;               // bound-pair queries (nbody_binaries.hpp)

@@ -14,22 +14,23 @@
 // cells are walked as they lie and the result has the bits of the brute-force definition - PROVIDED the window holds every
 // cell that can hold a near source.
 //
-// The window rule (within_span; tests/within_cases.py restates it, DESIGN.md 4.21 has the derivation).  Per axis, with the
+// The window rule (cells_span, nbody_cells.hpp; tests/within_cases.py restates it, DESIGN.md 4.21 has the derivation).  Per axis, with the
 // row's cell coordinate t = (x - x0) * sx as the cell sums compute it and w0 = fl(h * sx), h = fl(sqrt(h2)), both once on the
 // host:   w = w0 + (2^-20 + (|t| + w0) * 2^-40);   columns (int)max(t - w, 0) .. (int)min(t + w, nx - 1).
 // A window is empty only where t + w < 0 or t - w >= nx holds as a compare; a t that is not finite, or a NaN in t - w or
 // t + w (inf - inf), means every column.  A grid of more than 2^400 cells per unit length means every column too (w0 = +inf
 // from the host): there the product dx*dx can underflow for bodies many cells apart.
 //
-// Kernels, on the handle's stream after the four list stages of the cell sums (cells_list_run):
-//   within_gather<T, Count>   one lane per slot of `order`: the record {x, y, r, j} (16 bytes fp32, 32 fp64) into an array in
-//                             cell order, so that the walk reads contiguous memory and no index per pair.
+// Kernels, on the handle's stream after the four list stages of the cell sums (cells_list_run) and the gather of the list's
+// sorted records {x, y, r, j} (cells_gather_run), so that the walk reads contiguous memory and no index per pair.  The view of
+// a system's list, the cell coordinates, the window walk and the workgroup prefix are the list's (nbody_cells.hpp: cells_view,
+// cells_coords, cells_window_walk, cells_block_prefix); this file has the rows, the pair and the row scan.
 //   within_walk<T, kOwn, Count, kList>  one lane per row.  Own rows inside the grid are taken in cell order (lane = slot: the
 //                             64 rows of a wave share a few cells, nearly one window, and their loads hit the same lines);
 //                             own rows outside the grid follow, one lane per body that leaves unless its cell is -1; points
 //                             in the order given.  The grid is row-major, so the members of columns c0 .. c1 of one row of
 //                             cells are ONE contiguous range of the sorted records: a lane walks r1 - r0 + 1 ranges, four
-//                             records loaded ahead of their pairs.  Per pair: 2 subtractions, 2 multiplies, 1 add and the
+//                             records loaded ahead of their pairs (cells_window_walk).  Per pair: 2 subtractions, 2 multiplies, 1 add and the
 //                             compare with h2; the count, the minimum, the overlap compare and the list store sit behind the
 //                             branch that compare makes.  kList: the second pass, which stores the near j at the row's start.
 //   within_block_sums<Count>, within_block_scan<Count>, within_block_starts<Count>   the exclusive 64-bit prefix sum of
@@ -68,62 +69,17 @@ static_assert(offsetof(nbody_within, d2) == 0 && offsetof(nbody_within, index) =
               offsetof(WithinOut, cell) == 20, "nbody_within and its device mirror");
 static_assert(sizeof(nbody_within_info) == 32 && offsetof(nbody_within_info, n) == 8, "nbody_within_info layout");
 
-// A source in cell order.
-template <typename T> struct WithinRec;
-template <> struct alignas(16) WithinRec<float> { float x, y, r; int j; };
-template <> struct alignas(32) WithinRec<double> { double x, y, r; int j; };
-static_assert(sizeof(WithinRec<float>) == 16 && sizeof(WithinRec<double>) == 32, "a record is one 16 or 32 byte load");
-
 constexpr int kWithinScanPer = 4;                                // consecutive rows per lane of the row scan
 constexpr int kWithinBlockRows = kDiagBlock * kWithinScanPer;    // rows per workgroup of the row scan
 
 struct WithinWin { double h2, wx0, wy0; };                       // the call's values: h2, and h in cells per axis
-
-// The window along one axis: cells lo .. hi, hi < lo for none.
-struct WithinSpan { int lo, hi; };
-__device__ __forceinline__ WithinSpan within_span(double t, double w0, int cells) {
-    const double w = w0 + (0x1p-20 + (fabs(t) + w0) * 0x1p-40);
-    const double lo = t - w, hi = t + w;
-    if (!(fabs(t) < __builtin_inf()) || lo != lo || hi != hi) return WithinSpan{0, cells - 1};
-    if (hi < 0.0 || lo >= (double)cells) return WithinSpan{0, -1};
-    // lo < cells and hi >= 0: what is converted lies in [0, cells)
-    return WithinSpan{lo > 0.0 ? (int)lo : 0, hi < (double)(cells - 1) ? (int)hi : cells - 1};
-}
-
-// `inside` of a system as the kernels take it: the last start of the cell list, held to [0, n].
-__device__ __forceinline__ int within_inside(const int32_t* __restrict__ start, int cells, int n) {
-    const int inside = n > 0 ? start[cells] : 0;
-    return inside < 0 ? 0 : inside > n ? n : inside;
-}
-
-// One lane per slot.  sorted_all: [systems * stride].
-template <typename T, typename Count>
-__global__ __launch_bounds__(kDiagBlock) void within_gather(const Rec<T>* __restrict__ J_all, const Meta* __restrict__ meta_all,
-                                                            int stride, int n_one, int cells,
-                                                            const int32_t* __restrict__ start_all,
-                                                            const int32_t* __restrict__ order_all,
-                                                            WithinRec<T>* __restrict__ sorted_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
-    const int inside = within_inside(start_all + (size_t)sys * (size_t)(cells + 1), cells, n);
-    const int e = blockIdx.x * kDiagBlock + threadIdx.x;
-    if (e >= inside) return;
-    const size_t at = (size_t)sys * (size_t)stride;
-    const int idx = order_all[at + e];
-    WithinRec<T> w{(T)__builtin_nan(""), (T)0, (T)0, 0};          // an entry that fails its check: d2 = NaN, never near
-    if ((unsigned)idx < (unsigned)n) {
-        const Rec<T> r = J_all[at + idx];
-        w = WithinRec<T>{r.x, r.y, r.r, idx};
-    }
-    sorted_all[at + e] = w;
-}
 
 // One lane per row; grid = (ceil(lanes / kDiagBlock), systems) with lanes = 2 * n_bound for own rows - lane q < n is slot q
 // of the cell list, lane n + j is body j and has a row only where cell_of[j] is -1 - and m for points.
 // kList = false: the counting pass, which writes the record of every row.  kList = true: the filling pass, which writes
 // nothing but the near j of every row, from rstart[row] on, into raw_all ([systems * list_stride]).
 template <typename T, bool kOwn, typename Count, bool kList>
-__global__ __launch_bounds__(kDiagBlock) void within_walk(const Rec<T>* __restrict__ J_all, const WithinRec<T>* __restrict__ sorted_all,
+__global__ __launch_bounds__(kDiagBlock) void within_walk(const Rec<T>* __restrict__ J_all, const CellRec<T>* __restrict__ sorted_all,
                                                           const Meta* __restrict__ meta_all, int stride, int n_one,
                                                           const nbody_grid g, const WithinWin win,
                                                           const int32_t* __restrict__ cell_of_all,
@@ -132,14 +88,11 @@ __global__ __launch_bounds__(kDiagBlock) void within_walk(const Rec<T>* __restri
                                                           WithinOut* __restrict__ out_all,
                                                           const long long* __restrict__ rstart_all,
                                                           int32_t* __restrict__ raw_all, long long list_stride) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one, g.nx * g.ny, start_all);
+    const int n = cl.n, sys = cl.sys;
     const int lanes = kOwn ? 2 * n : m;
     if ((int)(blockIdx.x * kDiagBlock) >= lanes) return;
-    const int cells = g.nx * g.ny;
-    const int32_t* __restrict__ start = start_all + (size_t)sys * (size_t)(cells + 1);
-    const WithinRec<T>* __restrict__ sorted = sorted_all + (size_t)sys * (size_t)stride;
-    const int inside = within_inside(start, cells, n);
+    const CellRec<T>* __restrict__ sorted = sorted_all + cl.at;
     const int q = blockIdx.x * kDiagBlock + threadIdx.x;
     const size_t per = kOwn ? (size_t)stride : (size_t)m;        // rows of one system in out and rstart
 
@@ -147,13 +100,13 @@ __global__ __launch_bounds__(kDiagBlock) void within_walk(const Rec<T>* __restri
     int row = -1, self = -1;
     double x = 0.0, y = 0.0, r = 0.0;
     if (kOwn) {
-        if (q < inside) {
-            const WithinRec<T> w = sorted[q];
+        if (q < cl.inside) {
+            const CellRec<T> w = sorted[q];
             if ((unsigned)w.j < (unsigned)n) { row = self = w.j; x = (double)w.x; y = (double)w.y; r = (double)w.r; }
         } else if (q >= n && q < lanes) {
             const int j = q - n;
-            if (cell_of_all[(size_t)sys * (size_t)stride + j] < 0) {
-                const Rec<T> b = J_all[(size_t)sys * (size_t)stride + j];
+            if (cell_of_all[cl.at + j] < 0) {
+                const Rec<T> b = J_all[cl.at + j];
                 row = self = j; x = (double)b.x; y = (double)b.y; r = (double)b.r;
             }
         }
@@ -163,8 +116,6 @@ __global__ __launch_bounds__(kDiagBlock) void within_walk(const Rec<T>* __restri
     }
     if (row < 0) return;                                         // no barrier follows
 
-    const double tx = (x - g.x0) * g.sx, ty = (y - g.y0) * g.sy; // cells_cell's, same bits
-    const WithinSpan cx = within_span(tx, win.wx0, g.nx), cy = within_span(ty, win.wy0, g.ny);
     double best = __builtin_inf();
     int index = -1, count = 0, overlaps = 0;
     long long at = 0, end = 0;                                   // kList: where the row's next entry goes, and its segment's end
@@ -175,7 +126,8 @@ __global__ __launch_bounds__(kDiagBlock) void within_walk(const Rec<T>* __restri
         if (at < 0 || end > list_stride || at > end) at = end = 0;
         raw = raw_all + (size_t)sys * (size_t)list_stride;
     }
-    const auto pair = [&](const WithinRec<T>& s) {
+    const CellCoords t = cells_coords(g, x, y);
+    cells_window_walk(cl, sorted, g, t.tx, t.ty, win.wx0, win.wy0, [&](const CellRec<T>& s) {
         const double dx = (double)s.x - x, dy = (double)s.y - y;
         const double d2 = (dx * dx) + (dy * dy);
         if (d2 <= win.h2 && s.j != self) {                       // the rest only for a pair that passes
@@ -189,48 +141,12 @@ __global__ __launch_bounds__(kDiagBlock) void within_walk(const Rec<T>* __restri
                 overlaps += d2 <= sum * sum ? 1 : 0;
             }
         }
-    };
-    if (cx.lo <= cx.hi) {
-        for (int yy = cy.lo; yy <= cy.hi; ++yy) {
-            const int a = start[yy * g.nx + cx.lo], b = start[yy * g.nx + cx.hi + 1];
-            if (a < 0 || b > inside || a >= b) continue;
-            for (int k = a; k < b; k += 4) {                     // four loads ahead of their pairs
-                WithinRec<T> s[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) s[u] = sorted[k + u < b ? k + u : b - 1];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (k + u < b) pair(s[u]);
-            }
-        }
-    }
+    });
     if constexpr (!kList)
         out_all[(size_t)sys * per + row] = WithinOut{best, index, count, overlaps, cells_cell(g, x, y)};
 }
 
-// The row scan's pieces.  A workgroup's exclusive prefix over its lanes' sums: the lane's offset, and the workgroup's total in
-// every lane.  wsum: shared, one entry per wave; every lane of the workgroup calls it, once per kernel.
-__device__ __forceinline__ long long within_group_offset(long long mine, long long& total, long long* wsum) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    long long x = mine;                                          // inclusive over the wave
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const long long y = __shfl_up(x, d, kWave);
-        if (lane >= d) x += y;
-    }
-    if (lane == kWave - 1) wsum[wave] = x;
-    __syncthreads();
-    long long before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kDiagBlock / kWave; ++w) {
-        const long long t = wsum[w];
-        before += w < wave ? t : 0;
-        total += t;
-    }
-    return before + x - mine;
-}
-
+// The row scan's pieces; the workgroup's exclusive prefix is cells_block_prefix (nbody_cells.hpp).
 // (count, row) as one word whose maximum is the greatest count and, among equal counts, the lowest row.
 __device__ __forceinline__ unsigned long long within_key(int count, int row) {
     return ((unsigned long long)(unsigned)count << 32) | (unsigned long long)(0xffffffffu - (unsigned)row);
@@ -268,8 +184,8 @@ __global__ __launch_bounds__(kDiagBlock) void within_block_sums(const Meta* __re
                                                                 const WithinOut* __restrict__ out_all,
                                                                 long long* __restrict__ bsum_all,
                                                                 unsigned long long* __restrict__ bkey_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int rows = m < 0 ? cells_n<Count>(meta_all, sys, stride, n_one) : m;
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one);
+    const int sys = cl.sys, rows = m < 0 ? cl.n : m;
     if ((long long)blockIdx.x * kWithinBlockRows >= rows) return;               // the whole workgroup
     const size_t per = m < 0 ? (size_t)stride : (size_t)m;
     __shared__ long long wsum[kDiagBlock / kWave];
@@ -277,7 +193,7 @@ __global__ __launch_bounds__(kDiagBlock) void within_block_sums(const Meta* __re
     int v[kWithinScanPer];
     within_load_counts(out_all + (size_t)sys * per, rows, v);
     const int r0 = blockIdx.x * kWithinBlockRows + threadIdx.x * kWithinScanPer;
-    long long mine = 0, total;
+    long long mine = 0;
     unsigned long long key = 0;
 #pragma unroll
     for (int u = 0; u < kWithinScanPer; ++u) {
@@ -285,7 +201,7 @@ __global__ __launch_bounds__(kDiagBlock) void within_block_sums(const Meta* __re
         const unsigned long long k = r0 + u < rows ? within_key(v[u], r0 + u) : 0ull;
         key = k > key ? k : key;
     }
-    (void)within_group_offset(mine, total, wsum);
+    const long long total = cells_block_prefix<long long, kDiagBlock>(mine, wsum).total;
     key = within_group_max(key, wkey);
     if (threadIdx.x == 0) {
         const size_t at = (size_t)sys * (size_t)gridDim.x + blockIdx.x;
@@ -304,9 +220,8 @@ __global__ __launch_bounds__(kDiagBlock) void within_block_scan(const Meta* __re
                                                                 long long* __restrict__ rstart_all,
                                                                 const nbody_cells_info* __restrict__ cinfo_all,
                                                                 nbody_within_info* __restrict__ info_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
-    const int rows = m < 0 ? n : m;
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one);
+    const int sys = cl.sys, n = cl.n, rows = m < 0 ? n : m;
     const size_t per = m < 0 ? (size_t)stride : (size_t)m;
     int mine_blocks = (int)(((long long)rows + kWithinBlockRows - 1) / kWithinBlockRows);
     mine_blocks = mine_blocks > blocks ? blocks : mine_blocks;
@@ -319,10 +234,9 @@ __global__ __launch_bounds__(kDiagBlock) void within_block_scan(const Meta* __re
         const int b = base + threadIdx.x;
         const long long x = b < mine_blocks ? bsum_all[at + b] : 0;
         if (b < mine_blocks) key = bkey_all[at + b] > key ? bkey_all[at + b] : key;
-        long long total;
-        const long long off = within_group_offset(x, total, wsum);
-        if (b < mine_blocks) boff_all[at + b] = carry + off;
-        carry += total;
+        const BlockPrefix<long long> p = cells_block_prefix<long long, kDiagBlock>(x, wsum);
+        if (b < mine_blocks) boff_all[at + b] = carry + p.at;
+        carry += p.total;
         __syncthreads();                                         // wsum is written again in the next trip
     }
     key = within_group_max(key, wkey);
@@ -340,18 +254,18 @@ __global__ __launch_bounds__(kDiagBlock) void within_block_starts(const Meta* __
                                                                   const WithinOut* __restrict__ out_all,
                                                                   const long long* __restrict__ boff_all,
                                                                   long long* __restrict__ rstart_all) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int rows = m < 0 ? cells_n<Count>(meta_all, sys, stride, n_one) : m;
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one);
+    const int sys = cl.sys, rows = m < 0 ? cl.n : m;
     if ((long long)blockIdx.x * kWithinBlockRows >= rows) return;               // the whole workgroup
     const size_t per = m < 0 ? (size_t)stride : (size_t)m;
     __shared__ long long wsum[kDiagBlock / kWave];
     int v[kWithinScanPer];
     within_load_counts(out_all + (size_t)sys * per, rows, v);
     const int r0 = blockIdx.x * kWithinBlockRows + threadIdx.x * kWithinScanPer;
-    long long mine = 0, total;
+    long long mine = 0;
 #pragma unroll
     for (int u = 0; u < kWithinScanPer; ++u) mine += v[u];
-    long long at = boff_all[(size_t)sys * (size_t)gridDim.x + blockIdx.x] + within_group_offset(mine, total, wsum);
+    long long at = boff_all[(size_t)sys * (size_t)gridDim.x + blockIdx.x] + cells_block_prefix<long long, kDiagBlock>(mine, wsum).at;
     long long* __restrict__ rstart = rstart_all + (size_t)sys * (per + 1);
 #pragma unroll
     for (int u = 0; u < kWithinScanPer; ++u) {
@@ -366,9 +280,8 @@ __global__ __launch_bounds__(kDiagBlock) void within_rank(const Meta* __restrict
                                                           const long long* __restrict__ rstart_all,
                                                           const int32_t* __restrict__ raw_all, int32_t* __restrict__ list_all,
                                                           long long list_stride) {
-    const int sys = Count::kBatch ? (int)blockIdx.y : 0;
-    const int n = cells_n<Count>(meta_all, sys, stride, n_one);
-    const int rows = m < 0 ? n : m;
+    const CellView cl = cells_view<Count>(meta_all, stride, n_one);
+    const int sys = cl.sys, rows = m < 0 ? cl.n : m;
     const size_t per = m < 0 ? (size_t)stride : (size_t)m;
     const long long* __restrict__ rstart = rstart_all + (size_t)sys * (per + 1);
     const long long total = rows > 0 ? rstart[rows] : 0;
@@ -392,7 +305,6 @@ __global__ __launch_bounds__(kDiagBlock) void within_rank(const Meta* __restrict
 // Host side.  The buffers of one context or batch, next to its CellState: nothing before the first call.
 // ---------------------------------------------------------------------------------------------------------
 struct WithinState {
-    RowsArray<unsigned char> sorted;        // device [systems * stride] WithinRec<T>
     RowPoints pts;
     RowsArray<WithinOut> out;               // [systems * per]: device and pinned
     RowsArray<long long> rstart;            // [systems * (per + 1)]
@@ -403,8 +315,7 @@ struct WithinState {
 };
 
 inline void within_free(WithinState& w) {
-    rows_free(w.sorted); rows_free(w.pts); rows_free(w.out); rows_free(w.rstart); rows_free(w.blocks); rows_free(w.info); rows_free(w.raw);
-    rows_free(w.list);
+    rows_free(w.pts); rows_free(w.out); rows_free(w.rstart); rows_free(w.blocks); rows_free(w.info); rows_free(w.raw); rows_free(w.list);
 }
 
 inline int within_fail_alloc(WithinState& w, hipError_t e, const char* who, const char* what) {
@@ -427,7 +338,7 @@ inline int within_check_args(const char* who, std::initializer_list<const void*>
 // The call's window values: h once, in cells per axis; a grid too fine for the margin's proof looks at every cell.
 inline WithinWin within_window(const nbody_grid& grid, double h2) {
     const double h = sqrt(h2);
-    const bool fine = !(grid.sx <= 0x1p400 && grid.sy <= 0x1p400);
+    const bool fine = cells_fine(grid);
     return WithinWin{h2, fine ? __builtin_inf() : h * grid.sx, fine ? __builtin_inf() : h * grid.sy};
 }
 
@@ -443,12 +354,11 @@ int within_run(const char* who, const RowsSite& s, CellState& g, WithinState& ws
     const bool own = points == nullptr;
     const size_t S = (size_t)s.systems, C = (size_t)grid.nx * (size_t)grid.ny, bodies = S * (size_t)s.stride;
     const size_t per = own ? (size_t)s.stride : (size_t)m;
-    const int cells = (int)C, n_one = s.n_one<Count>(), m_dev = own ? -1 : m;
+    const int n_one = s.n_one<Count>(), m_dev = own ? -1 : m;
     const int lanes = own ? 2 * s.n_bound : m;
-    int rc = cells_reserve(g, S, C, bodies, who, false);
+    int rc = cells_reserve(g, S, C, bodies, who, sizeof(CellRec<T>));
     if (rc != NBODY_OK) return rc;
-    hipError_t e = rows_reserve_device(ws.sorted, (bodies > 0 ? bodies : 1) * sizeof(WithinRec<T>));
-    if (e == hipSuccess) e = rows_reserve(ws.pts, own || m == 0 ? 1 : (size_t)m);
+    hipError_t e = rows_reserve(ws.pts, own || m == 0 ? 1 : (size_t)m);
     if (e == hipSuccess) e = rows_reserve(ws.out, S * per > 0 ? S * per : 1);
     if (e == hipSuccess) e = rows_reserve(ws.rstart, S * (per + 1));
     if (e == hipSuccess) e = rows_reserve(ws.info, S);
@@ -457,26 +367,21 @@ int within_run(const char* who, const RowsSite& s, CellState& g, WithinState& ws
     if (e == hipSuccess) e = rows_reserve_device(ws.blocks, 3 * S * nblk);
     if (e != hipSuccess) return within_fail_alloc(ws, e, who, "row buffers");
     const Rec<T>* J = (const Rec<T>*)s.J;
-    WithinRec<T>* sorted = reinterpret_cast<WithinRec<T>*>(ws.sorted.d);
+    const CellRec<T>* sorted = reinterpret_cast<const CellRec<T>*>(g.sorted.d);
     const WithinWin win = within_window(grid, h2);
-    if ((rc = cells_list_run<T, Count>(s, g, grid)) != NBODY_OK) return rc;
-    if (s.n_bound > 0) {
-        hipLaunchKernelGGL((within_gather<T, Count>), s.grid(s.n_bound), dim3(kDiagBlock), 0, s.stream, J, s.meta, s.stride, n_one,
-                           cells, (const int32_t*)g.start.d, (const int32_t*)g.order.d, sorted);
-        NBK_ROWS_TRY(hipGetLastError());
-    }
+    if ((rc = cells_list_run<T, Count>(s, g, grid)) != NBODY_OK || (rc = cells_gather_run<T, Count>(s, g, grid)) != NBODY_OK) return rc;
     if (!own && m > 0) NBK_ROWS_TRY(rows_upload(ws.pts, points, m, s.stream));
     const auto walk = [&](auto fill, long long list_stride) {
         constexpr bool kList = decltype(fill)::value;
         if (lanes <= 0) return;
         if (own)
             hipLaunchKernelGGL((within_walk<T, true, Count, kList>), s.grid(lanes), dim3(kDiagBlock), 0, s.stream, J,
-                               (const WithinRec<T>*)sorted, s.meta, s.stride, n_one, grid, win, (const int32_t*)g.cell_of.d,
+                               sorted, s.meta, s.stride, n_one, grid, win, (const int32_t*)g.cell_of.d,
                                (const int32_t*)g.start.d, (const FieldPoint*)nullptr, 0, ws.out.d, (const long long*)ws.rstart.d,
                                ws.raw.d, list_stride);
         else
             hipLaunchKernelGGL((within_walk<T, false, Count, kList>), s.grid(lanes), dim3(kDiagBlock), 0, s.stream, J,
-                               (const WithinRec<T>*)sorted, s.meta, s.stride, n_one, grid, win, (const int32_t*)g.cell_of.d,
+                               sorted, s.meta, s.stride, n_one, grid, win, (const int32_t*)g.cell_of.d,
                                (const int32_t*)g.start.d, (const FieldPoint*)ws.pts.d, m, ws.out.d, (const long long*)ws.rstart.d,
                                ws.raw.d, list_stride);
     };

@@ -4,8 +4,9 @@ compaction's offsets (compact_count / compact_scatter, batch_count / batch_commi
 (diag_potential, batch_diag_potential, track_potential, and with it field_at, tides_at and tracers_advance: the ordered
 walk and the exact walk of nbody_diag.hpp), the finish of the diagnostics (batch_diag_reduce) and the row queries'
 prologue, tile walk and host drivers (field_at, neighbors_at, groups_sweep, pair_counts, encounters_walk, binaries_walk,
-group_potential, shells_at, shell_moments_at; nbody_rows.hpp), and the host drivers of the cell sums and the radius queries
-(nbody_cells.hpp, nbody_within.hpp), whose buffers are the handles' to keep and free.
+group_potential, shells_at, shell_moments_at; nbody_rows.hpp), and the cell list with the three queries on it - the cell sums,
+the radius queries and the groups on the grid (nbody_cells.hpp, nbody_within.hpp, nbody_groups_grid.hpp), which share the
+list's view, its window walk and its sorted records, and whose buffers are the handles' to keep and free.
 
     python3 csrc/tune/ab_parent.py --baseline-root DIR [--lines a,b256,...] [--rounds 3] [--out FILE]
     python3 csrc/tune/ab_parent.py --trace [--root DIR]     (every line once, target of rocprofv3 --kernel-trace --stats)
@@ -47,6 +48,9 @@ Lines (fp32, literal, stock configuration with stock radii):
               256 x 256 grid over the field with moments and lists / within(h = that grid's cell
               side) on that grid with lists; wthpts: the same from 65536 explicit points; cel256,
               wth256: StepperBatch 256 x 1024 after 3 steps on 32 x 32 cells, h = the cell side
+    ggr       the matched grid of groups_grid_probe.py's overlap case on the grp state: groups(0, 1,        ms per call
+              grid=groups_grid(the field widened to the bodies, 0, 1, the median radius)); ggr256: the
+              same on StepperBatch 256 x 1024 after 3 steps, one grid of at most 128 x 128 cells
     trc       stepping with 65536 tracers set, from a fresh upload and a fresh set: trc Stepper  ms | us per step
               N = 262144 (8 steps), trc256 StepperBatch 256 x 1024 with 256 tracers in each
               system (500 steps)
@@ -72,7 +76,7 @@ REPLY_TIMEOUT_S = 240           # a side that does not answer within this is kil
 LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024", "d256x1024", "d64x4096",
          "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256",
          "enc", "enc256", "bin", "bin256", "gpe", "gpe256", "shl", "shlpts", "shl256", "shm", "shmpts", "shm256",
-         "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "cel", "cel256", "wth", "wthpts", "wth256",
+         "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "cel", "cel256", "wth", "wthpts", "wth256", "ggr", "ggr256",
          "trc", "trc256", "io", "io64", "io256")
 BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
 STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
@@ -82,11 +86,12 @@ ROWS = {"": 3, "pts": 8, "256": 100}    # the row queries' shapes (field_probe.p
                                         # the tides' too: 51 to 71 ms a call on own rows, 16 to 21 on the points
 SCANS = {"grp": 8, "grp256": 100, "prs": 20, "prspts": 30, "prs256": 200,     # the queries on the state after 3 steps:
          "enc": 6, "enc256": 100, "bin": 20, "bin256": 80, "gpe": 6, "gpe256": 80,    # calls per window
-         "shl": 20, "shlpts": 20, "shl256": 60, "shm": 20, "shmpts": 20, "shm256": 40}
+         "shl": 20, "shlpts": 20, "shl256": 60, "shm": 20, "shmpts": 20, "shm256": 40,
+         "ggr": 200, "ggr256": 100}             # profiles/groups_grid_probe.txt: 0.67 and 1.2 ms a call on the matched grid
 # whole cells() / within() calls (profiles/cells_probe.txt, profiles/within_probe.txt): 0.62 and 1.2 ms a call for cel and
 # cel256, 1.4 ms for wth and wth256 with their lists; wthpts builds the same cell list for a quarter of the rows
 GRIDS = {"cel": 250, "cel256": 120, "wth": 100, "wthpts": 250, "wth256": 100}
-ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm", "tid", "cel", "wth")
+ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm", "tid", "cel", "wth", "ggr")
 N_BIG = 262144
 M_POINTS = 65536
 
@@ -160,6 +165,18 @@ class Line:
                 self.call = lambda pts: self.st.groups(0.0, 1.0)
             elif name.startswith("gpe"):
                 self.call = lambda pts: self.st.group_potential(0.0, 1.0)
+            elif name.startswith("ggr"):                                    # groups_grid_probe.py: nothing is outside the grid
+                downs = [self.st.download(s) for s in range(256)] if self.batch else [self.st.download()]
+                P = [np.abs(np.asarray(d.Positions[:d.numBodies], dtype=np.float64).reshape(-1, 2)) for d in downs]
+                median = float(np.median(np.asarray(downs[0].Radii[:downs[0].numBodies], dtype=np.float64)))
+                if self.batch:
+                    reach = max(float(p.max()) for p in P) * 1.001
+                    field = (max(float(cfg.fieldWidth), reach), max(float(cfg.fieldHeight), reach))
+                    grid = nb.groups_grid(field, 0.0, 1.0, median, most=int(np.sqrt((1 << 22) // 256)))
+                else:
+                    field = (max(float(cfg.fieldWidth), float(P[0][:, 0].max()) * 1.001), max(float(cfg.fieldHeight), float(P[0][:, 1].max()) * 1.001))
+                    grid = nb.groups_grid(field, 0.0, 1.0, median)
+                self.call = lambda pts: self.st.groups(0.0, 1.0, grid=grid)
             elif name[:3] in ("enc", "bin"):
                 if name.startswith("enc"):
                     query = lambda cap: self.st.encounters(float(np.float32(cfg.timestep)), cap=cap)

@@ -147,7 +147,7 @@ def report(trace_dir, host_log):
             cur = {"sweep": [], "grid": False, "other": collections.defaultdict(float)}
         elif "groups_init" in name:
             cur["other"]["init + flatten"] += ms
-        elif "cells_" in name or "within_gather" in name:
+        elif "cells_" in name:                               # the list's stages and cells_gather
             cur["other"]["list + gather"] += ms
     host = [line for line in open(host_log)]
     labels = [json.loads(line)["call"] for line in host if line.startswith("{")]
@@ -158,7 +158,7 @@ def report(trace_dir, host_log):
     med = lambda v: sorted(v)[len(v) // 2]
     print("# csrc/tune/groups_grid_probe.py on one MI355X: groups_grid_sweep next to groups_sweep, fp32, the stock state after %d steps" % gp.STEPS)
     print("# kernel trace: rocprofv3 --kernel-trace --stats -- python groups_grid_probe.py kernels 3 (a run of its own); ms, median over "
-          "the sweeps of the rounds (spread); list + gather: the cell list's stages and within_gather of one call")
+          "the sweeps of the rounds (spread); list + gather: the cell list's stages and cells_gather of one call")
     for k, label in enumerate(labels):
         mine = calls[k::per_round]
         assert all(c["grid"] == ("triangular" not in label) for c in mine), label

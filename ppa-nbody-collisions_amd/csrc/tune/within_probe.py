@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of the radius queries (nbody_get_within, nbody_batch_get_within): the kernels of a call - the four
-list stages of the cell sums, then within_gather, within_walk, the row scan and, with lists, the second walk and within_rank -
+list stages of the cell sums, then cells_gather, within_walk, the row scan and, with lists, the second walk and within_rank -
 next to neighbors_at, the O(n^2) yardstick, timed in the same run on the same state, and whole calls under the host clock
 next to Stepper.neighbors().
 
@@ -30,7 +30,7 @@ N_ONE, BATCH_S, BATCH_N = 262144, 256, 1024
 ROUNDS = 3                                                   # what `report` expects of `kernels`
 SAMPLE = 1024
 FIRST = "cells_assign"                                       # the kernel a call opens with
-STAGES = ["cells_assign", "cells_scan", "cells_place", "cells_rank", "within_gather", "within_walk", "within_block_sums",
+STAGES = ["cells_assign", "cells_scan", "cells_place", "cells_rank", "cells_gather", "within_walk", "within_block_sums",
           "within_block_scan", "within_block_starts", "within_rank"]
 LISTS_ONLY = ("within_block_starts", "within_rank")
 CASES = [("stock 256 x 256, h = cell", False), ("stock 256 x 256, h = cell, lists", True), ("stock 1024 x 1024, h = cell", False),

@@ -267,6 +267,59 @@ def test_every_rank_of_a_group(nb):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 5b. the row scan past one block of 1024 rows and past one trip of 256 blocks (within_cases.scan_cases)
+# ---------------------------------------------------------------------------------------------------------------------
+def scan_ask(nb, case):
+    nx, ny, bounds, h2 = case.asks[0]
+    return nb.make_grid(nx, ny, bounds), h2
+
+
+@pytest.mark.parametrize("name", wc.scan_case_names("scan-bodies-"))
+def test_row_scan_across_blocks(nb, name):
+    """Rows either side of one and two blocks: start[row] = the block's offset + the prefix inside the block."""
+    case, want = wc.scan_cases()[name], wc.scan_reference(name)
+    precision = PRECISION_OF[case.dtype]
+    grid, h2 = scan_ask(nb, case)
+    with small_stepper(nb, precision, len(case.P)) as st:
+        st.upload(bodies_of(nb, case.P, case.R, precision))
+        got = st.within(h2, grid=grid, squared=True, lists=True)
+    wc.assert_same(got, want, name, lists=True)
+    assert got["start"][len(case.P)] == want["info"]["total"] > len(case.P)
+
+
+def test_row_scan_batch_with_an_empty_block(nb):
+    """Two systems `stride` = 1025 apart holding 1025 and 3 bodies: two blocks each, the second system's block 1 has no row."""
+    names = wc.scan_case_names("scan-batch-")
+    cases = [wc.scan_cases()[k] for k in names]
+    assert tuple(len(c.P) for c in cases) == wc.SCAN_BATCH
+    grid, h2 = scan_ask(nb, cases[0])
+    with nb.StepperBatch(len(cases), wc.SCAN_BATCH[0], params=[(0.2, 0.1, 100, 100)] * len(cases)) as batch:
+        batch.upload([bodies_of(nb, c.P, c.R, 0) for c in cases])
+        got = batch.within(h2, grid=grid, squared=True, lists=True)
+    for s, name in enumerate(names):
+        wc.assert_same(got[s], wc.scan_reference(name), name, lists=True)
+    assert got[0]["info"]["total"] > wc.SCAN_BLOCK_ROWS and got[1]["info"]["rows"] == 3
+
+
+def test_row_scan_second_trip_of_the_block_scan(nb):
+    """m = 256 * 1024 + 1025 points: 258 blocks, so the block scan makes a second trip, of one full and one partial block."""
+    name = "scan-points-f32"
+    case, want = wc.scan_cases()[name], wc.scan_reference(name)
+    m = len(case.points)
+    assert m == wc.SCAN_POINTS and -(-m // wc.SCAN_BLOCK_ROWS) == wc.SCAN_TRIP_BLOCKS + 2
+    grid, h2 = scan_ask(nb, case)
+    with small_stepper(nb, 0, len(case.P)) as st:
+        st.upload(bodies_of(nb, case.P, case.R, 0))
+        got = st.within(h2, case.points, grid=grid, squared=True, lists=True)
+    assert got["start"][m] == want["start"][m] == want["info"]["total"] == got["info"]["total"] > m
+    assert got["info"]["largest_row"] == want["info"]["largest_row"]
+    for row in wc.scan_sample(m):
+        a, b = (r["list"][r["start"][row]:r["start"][row + 1]] for r in (got, want))
+        assert np.array_equal(a, b), (row, a, b)
+    wc.assert_same(got, want, name, lists=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 6. invalid arguments, each found before the handle is looked at
 # ---------------------------------------------------------------------------------------------------------------------
 def test_invalid_arguments(nb):

@@ -109,6 +109,52 @@ def test_window_on_the_lattice_and_at_awkward_rows():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 2b. the cases of the row scan: their shapes, their references inside the budget, the window rule on them
+# ---------------------------------------------------------------------------------------------------------------------
+def test_scan_cases_cross_the_blocks_and_the_trip():
+    """What the cases are for, held here: rows either side of one and two blocks, a batch whose second system has an empty
+    block 1, and points that need a second trip of the block scan, of one full and one partial block."""
+    B, T = wc.SCAN_BLOCK_ROWS, wc.SCAN_TRIP_BLOCKS
+    assert sorted(n for _, n in wc.SCAN_BODIES) == [B - 1, B, B + 1, B + 1, 2 * B + 1]
+    assert wc.SCAN_BATCH == (B + 1, 3) and [len(wc.scan_cases()[k].P) for k in wc.scan_case_names("scan-batch-")] == [B + 1, 3]
+    m = len(wc.scan_cases()["scan-points-f32"].points)
+    blocks = -(-m // B)
+    assert m == T * B + 1025 and blocks == T + 2 and m - (T + 1) * B == 1 and len(wc.scan_cases()["scan-points-f32"].P) == 65
+    sample = wc.scan_sample(m)
+    assert len(sample) == 64 == len(set(sample.tolist())) and sample[0] == 0 and sample[-1] == m - 1
+    for edge in (B, 2 * B, (T - 1) * B, T * B, (T + 1) * B):
+        assert edge - 1 in sample and edge in sample, edge
+
+
+def test_scan_references_within_budget():
+    """A condition, not a measurement: no reference of the row-scan cases may take more than the suite's 10 s."""
+    import large_cases as lg
+    for name in wc.scan_case_names():
+        ref = wc.scan_reference(name)
+        assert wc.scan_reference(name) is ref                      # computed once
+        assert ref["info"]["total"] == ref["start"][-1] == len(ref["list"]) > 0
+    print("seconds: " + "   ".join("%s %.1f" % (name, wc.SCAN_TIMES[name]) for name in wc.scan_case_names()))
+    for name in wc.scan_case_names():
+        assert wc.SCAN_TIMES[name] <= lg.BUDGET_S, (name, wc.SCAN_TIMES[name])
+    with pytest.raises(ValueError):
+        wc.scan_reference("scan-points-f32")["start"][0] = 1       # read-only
+
+
+@pytest.mark.parametrize("name", wc.scan_case_names())
+def test_window_holds_every_near_source_of_the_scan_cases(name):
+    case = wc.scan_cases()[name]
+    grid, h2 = case.grid(case.asks[0]), case.asks[0][3]
+    xy = case.rows_xy()
+    for a in range(0, len(xy), 1 << 16):                         # the points in slices: (rows, sources) masks
+        rows = xy[a:a + (1 << 16)]
+        with np.errstate(over="ignore", invalid="ignore"):
+            dx, dy = case.P[None, :, 0] - rows[:, None, 0], case.P[None, :, 1] - rows[:, None, 1]
+            near = (cc.cell_index(case.P, grid) >= 0)[None, :] & ((dx * dx) + (dy * dy) <= h2)
+        missed = np.argwhere(near & ~wc.window_model(case.P, grid, h2, rows))
+        assert len(missed) == 0, (name, "%d near pairs outside the window, first %s" % (len(missed), missed[0]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 3. what follows from the definition
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])

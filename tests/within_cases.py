@@ -11,8 +11,8 @@ grid (cell_cases.cell_index).  A row at (x, y) with radius r (+0 for a probe poi
     start = the exclusive prefix sum of count;  list = the near j of every row, ascending
 model_within is brute force over all sources; loop_within is the definition as a scalar loop that visits the sources in
 DESCENDING j, so that the tie rule and the sorted list are what make the two agree; window_model restates the rule by which
-the device picks the cells a row looks at (csrc/nbody_within.hpp, within_span and within_window) and returns the sources in
-those cells: test_within_cases_cpu.py holds that they include every near source, for every case below."""
+the device picks the cells a row looks at (cells_span of csrc/nbody_cells.hpp, within_window of csrc/nbody_within.hpp) and
+returns the sources in those cells: test_within_cases_cpu.py holds that they include every near source, for every case below."""
 import functools
 
 import numpy as np
@@ -126,7 +126,7 @@ def loop_within(P, R, grid, h2, points=None):
 
 
 def _span(t, w0, cells):
-    """within_span: the window along one axis -> (lo, hi) int64 per row; hi < lo: none."""
+    """cells_span: the window along one axis -> (lo, hi) int64 per row; hi < lo: none."""
     with np.errstate(over="ignore", invalid="ignore"):
         w = w0 + (2.0 ** -20 + (np.abs(t) + w0) * 2.0 ** -40)
         lo, hi = t - w, t + w
@@ -265,3 +265,70 @@ def cases():
 
 def case_names(prefix=""):
     return [k for k in cases() if k.startswith(prefix)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the row scan past one block and past one trip of the block scan.  The device takes the exclusive prefix of the counts in
+# blocks of SCAN_BLOCK_ROWS rows (a workgroup each), then one workgroup scans the block sums SCAN_TRIP_BLOCKS at a time.
+# Every case: the 8 x 8 grid over its field, h = one cell side.  Each reference is computed once (scan_reference) and must
+# stay inside the suite's CPU budget (large_cases.BUDGET_S; test_within_cases_cpu.py holds it).
+# ---------------------------------------------------------------------------------------------------------------------
+SCAN_BLOCK_ROWS = 1024
+SCAN_TRIP_BLOCKS = 256
+SCAN_BODIES = (("f32", 1023), ("f32", 1024), ("f32", 1025), ("f32", 2049), ("f64", 1025))   # rows around one and two blocks
+SCAN_BATCH = (1025, 3)                                          # stride 1025: the second system's block 1 leaves at once
+SCAN_POINTS = SCAN_TRIP_BLOCKS * SCAN_BLOCK_ROWS + 1025         # 258 blocks: a second trip of one full and one partial block
+SCAN_POINT_BODIES = 65
+SCAN_TIMES = {}                                                 # name -> seconds its reference took
+
+
+def _scan_ask(f):
+    return (8, 8, (0, f, 0, f), (f / 8) ** 2)
+
+
+@functools.lru_cache(maxsize=None)
+def scan_cases():
+    """The cases of the row scan, by name; "scan-batch-k-f32" are the systems of the one batch, all on system 0's grid."""
+    out = []
+    for tag, n in SCAN_BODIES:
+        P, R, f = state(n, DTYPES[tag])
+        out.append(Case("scan-bodies-%d-%s" % (n, tag), DTYPES[tag], P, R, [_scan_ask(f)]))
+    f0 = cc.tenth_field(SCAN_BATCH[0])
+    for k, n in enumerate(SCAN_BATCH):
+        P, R, _ = state(n, np.float32)
+        out.append(Case("scan-batch-%d-f32" % k, np.float32, P, R, [_scan_ask(f0)]))
+    P, R, f = state(SCAN_POINT_BODIES, np.float32)
+    pts = np.random.default_rng(STATE_SEED).uniform(-0.05 * f, 1.05 * f, size=(SCAN_POINTS, 2))   # a few outside the grid
+    out.append(Case("scan-points-f32", np.float32, P, R, [_scan_ask(f)], pts))
+    return {c.name: c for c in out}
+
+
+def scan_case_names(prefix="scan-"):
+    return [k for k in scan_cases() if k.startswith(prefix)]
+
+
+@functools.lru_cache(maxsize=None)
+def scan_reference(name):
+    """model_within of the case's one ask, computed once, read-only."""
+    import time
+    case = scan_cases()[name]
+    t0 = time.perf_counter()
+    ref = model_within(case.P, case.R, case.grid(case.asks[0]), case.asks[0][3], case.points)
+    SCAN_TIMES[name] = time.perf_counter() - t0
+    for k in ("rows", "start", "list"):
+        ref[k].setflags(write=False)
+    return ref
+
+
+def scan_sample(m):
+    """64 rows of m: the first, the last, the rows either side of multiples of SCAN_BLOCK_ROWS - the first two, the last, and
+    those around every multiple of SCAN_TRIP_BLOCKS * SCAN_BLOCK_ROWS - and rows evenly spread between."""
+    blocks = (m - 1) // SCAN_BLOCK_ROWS
+    edges = {1, 2, blocks} | set(range(SCAN_TRIP_BLOCKS - 1, blocks + 1, SCAN_TRIP_BLOCKS)) | set(range(SCAN_TRIP_BLOCKS, blocks + 1, SCAN_TRIP_BLOCKS))
+    rows = {0, m - 1}
+    for b in sorted(e for e in edges if 0 < e * SCAN_BLOCK_ROWS < m):
+        rows |= {b * SCAN_BLOCK_ROWS - 1, b * SCAN_BLOCK_ROWS}
+    for r in np.linspace(0, m - 1, 200).astype(np.int64):
+        if len(rows) < 64:
+            rows.add(int(r))
+    return np.array(sorted(rows), dtype=np.int64)
