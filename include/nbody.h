@@ -1307,6 +1307,77 @@ int nbody_batch_get_groups_grid(struct nbody_batch* b, const nbody_grid* grid, d
                                 int32_t* label /* [systems*capacity] */, nbody_groups_grid_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * k nearest neighbours on the cell list (the reference has none): nbody_get_knn's result for every current
+ * body, or for every one of m probe points, found through the cell list of nbody_get_cells instead of a walk over all n
+ * sources per row, with an optional cut: the k nearest within a radius.  O(n) on a grid whose cells hold about k bodies
+ * (Python: knn_grid), where nbody_get_knn is O(n^2).
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma.  The grid
+ * is an nbody_grid as for nbody_get_cells; inside(j) is exactly the cell sums' definition.
+ *   Sources: the current bodies with inside(j).  A body outside the grid is no source and is counted in info.outside.
+ *   Rows (points == NULL): every current body, inside the grid or not, with its own term left out by index.  Rows
+ *   (points != NULL): the m points.  For a row at (x, y), own index i, and (X_j, Y_j) widened exactly:
+ *     dx = X_j - x;  dy = Y_j - y;  d2_j = (dx*dx) + (dy*dy)               the d2 of nbody_get_neighbors and nbody_get_knn
+ *     eligible(j)  <=>  inside(j) && j != i && d2_j < +inf && d2_j <= h2_max
+ *   Result: the first k eligible sources under the total order (d2, j) ascending, then {+inf, -1} up to k; entry c of a row
+ *   is d2[row * k + c], index[row * k + c], rows by body index or in the order given, as nbody_get_knn.
+ * k: 1 .. NBODY_KNN_MAX.  h2_max: the squared cut, >= 0, +inf for none.  h0: the radius of the first round below, finite and
+ * >= 2^-500 (below that h0*h0 can round up among the subnormals, which the guarantee below does not survive).  With
+ * points == NULL, m is the room of d2 and index in rows: m < n is NBODY_ERR_CAPACITY with nothing written.
+ * What follows from the definition:
+ *   - with outside == 0 and h2_max = +inf the bytes of d2 and index are nbody_get_knn's, whatever the grid and h0;
+ *   - entry 0 has the bits of nbody_get_within's {d2, index} for h2 = h2_max;
+ *   - the number of non-empty entries of a row is min(k, count) of nbody_get_within for h2 = h2_max, except that a source
+ *     at d2 = +inf is counted there (h2 = +inf) and never listed here;
+ *   - the non-empty indices are the first k of that row's list of nbody_get_within, re-sorted by (d2, j);
+ *   - the result is a function of the state, the SET of inside bodies, k and h2_max only: two grids that both hold every
+ *     body, and any two h0, give the same bytes in d2 and index;
+ *   - it is not a function of rank, world, transport, force kernel or the order the device's waves ran in.
+ * The widening rule, by which the walk over cells finds exactly these entries; it is part of the contract, since info
+ * reports it (csrc/nbody_knn_grid.hpp; DESIGN.md 4.23 has the proof).  Round t = 0, 1, ... of a row:
+ *   - h_t = h0 * 2^t and H2_t = fl(h0*h0) * 4^t, both scalings exact, an overflow to +inf allowed; from t = 48 both are +inf;
+ *   - where H2_t >= h2_max the round takes h = fl(sqrt(h2_max)), computed once on the host, and H2 = h2_max, and is final;
+ *   - the window is cells_span(tx, fl(h*sx), nx) x cells_span(ty, fl(h*sy), ny), the span of nbody_get_within's window rule,
+ *     per axis never narrower than in the round before; a grid of more than 2^400 cells per unit length looks at every
+ *     cell in round 0; a round whose spans are both the whole axis is final;
+ *   - after a round the row is done if the round was final, or if its list holds k entries and the k-th d2 <= H2_t.
+ * A round after the first looks only at the cells its spans add, so no source is looked at twice.  Every inside source with
+ * d2 <= H2_t lies in the window of round t (the window rule's proof, with room to spare for sqrt(H2_t) <= h_t (1 + 2^-52)),
+ * so an unseen source has d2 > H2_t >= d2_k, strictly: it can neither enter the list nor tie with its last entry.
+ * info: n; rows; inside and outside (inside + outside == n); rounds = the greatest number of rounds a row took (0 where
+ * there is no row); widened = the number of rows that took more than one.  Both are functions of the state, the grid, k,
+ * h0 and h2_max; they tell a caller whether the grid and h0 match k: on a matched grid widened is a small part of rows.
+ * The rule costs time, never a result: with every body in a few cells, or a grid much finer than the distance to the k-th
+ * neighbour, the call approaches the n^2 pair tests of nbody_get_knn, read from memory instead of LDS by one lane per row.
+ * nbody_get_knn_grid synchronises once, reads positions of the replica only and never changes what later steps compute.  It
+ * is NOT collective: any rank of any world may call it on its own and each gives the same bits.  Device scratch and pinned
+ * staging are allocated on the first call; a handle that never calls it allocates nothing and launches nothing more, and
+ * the kernels it runs keep their code.  An empty system: every point's entries {+inf, -1}.
+ * NBODY_ERR_INVALID, found before any device call, the values before the handle: everything nbody_get_cells rejects about
+ * the grid; k outside [1, NBODY_KNN_MAX]; a NaN or negative h2_max; an h0 that is NaN, infinite or below 2^-500; m < 0 or
+ * m x k x 12 bytes (x systems) above 2^31; a NULL handle, d2, index or info.  NBODY_ERR_CAPACITY: above, and a batch with
+ * systems * nx * ny above 1 << 22.  NBODY_ERR_STATE: before an upload.
+ * Cost (one MI355X, fp32, points == NULL, the stock seeded state of N = 262144; profiles/knn_grid_probe.txt, nbody_get_knn
+ * timed in the same runs): k = 8 on the 181 x 181 cells of knn_grid the six kernels 0.164 ms (the walk 0.100) against
+ * knn_at's 20.19 ms, 46 of the rows widened; k = 32 on 90 x 90 cells 1.525 ms (the walk 1.473) against 39.96 ms, 9 rows
+ * widened.  Whole Stepper.knn() calls, which also copy n x k x 12 bytes and split them into two arrays: 6.1 against 25.9 ms
+ * (4.2 times faster) and 28.3 against 67.9 ms (2.4 times) - the copy and the split are now nearly all of the call.  Where
+ * it LOSES: every body in one cell of 8 x 8, k = 8, the walk 43.7 ms and the call 54.8 against 25.8 ms; and a batch of
+ * 256 x 1024 on 32 x 32 cells - one body per cell, 258379 of 262144 rows widen - whose walk is 0.206 ms against 0.378 ms
+ * but whose whole call is 4.25 against 3.71 ms.  Not measured: fp64, explicit points, other states.
+ * nbody_batch_get_knn_grid: the same query for every system of a batch, the list stages and the walk ONE launch each
+ * whatever S is, with one grid, one set of points, one k, one h0 and one h2_max for all of them.  System s's entries at
+ * [(s * per + row) * k + c] with per = the batch's capacity for own rows and m for points, info[s]; the rest of every slice
+ * is left unchanged.  System s gives exactly the bits an nbody_ctx holding that system's state gives.  A count outside
+ * [0, capacity] is treated as 0 and reported for that system, as by nbody_batch_get_cells.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_knn_grid_info { int32_t n, rows, inside, outside, widened, rounds; } nbody_knn_grid_info;  /* 24 bytes */
+int nbody_get_knn_grid(nbody_ctx* ctx, const nbody_grid* grid, const nbody_vec2* points /* NULL: the bodies */, int m, int k,
+                       double h0, double h2_max, double* d2, int32_t* index /* [rows*k] each */, nbody_knn_grid_info* info);
+int nbody_batch_get_knn_grid(struct nbody_batch* b, const nbody_grid* grid, const nbody_vec2* points, int m, int k, double h0,
+                             double h2_max, double* d2, int32_t* index /* [systems*per*k] each */,
+                             nbody_knn_grid_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

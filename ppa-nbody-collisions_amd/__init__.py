@@ -155,6 +155,9 @@ WITHIN_DTYPE = np.dtype([("d2", np.float64), ("index", np.int32), ("count", np.i
 WITHIN_INFO_DTYPE = np.dtype([("total", np.int64), ("n", np.int32), ("rows", np.int32), ("inside", np.int32),
                               ("outside", np.int32), ("largest", np.int32), ("largest_row", np.int32)])
 GROUPS_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32)])
+# nbody_knn_grid_info (24 bytes): the summary of knn(grid=...)
+KNN_GRID_INFO_DTYPE = np.dtype([("n", np.int32), ("rows", np.int32), ("inside", np.int32), ("outside", np.int32),
+                                ("widened", np.int32), ("rounds", np.int32)])
 # nbody_groups_grid_info (24 bytes): the summary of groups(grid=...)
 GROUPS_GRID_INFO_DTYPE = np.dtype([("n_bodies", np.int32), ("n_groups", np.int32), ("largest", np.int32), ("sweeps", np.int32),
                                    ("inside", np.int32), ("outside", np.int32)])
@@ -272,6 +275,8 @@ SYMBOLS = {
     "nbody_batch_get_within": (_i, [_vp, _vp, _d, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "nbody_get_groups_grid": (_i, [_vp, _vp, _d, _d, _vp, _i, _vp]),
     "nbody_batch_get_groups_grid": (_i, [_vp, _vp, _d, _d, _vp, _vp]),
+    "nbody_get_knn_grid": (_i, [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp]),
+    "nbody_batch_get_knn_grid": (_i, [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp]),
     "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
     "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
     "nbody_group_catalog": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
@@ -884,6 +889,46 @@ def groups_grid(field, link, radius_scale, r_typical, most=1024):
     return within_grid(field, float(radius_scale) * 2.0 * float(r_typical) + float(link), most=most)
 
 
+def knn_grid(field, k, n, most=1024):
+    """The grid to hand knn(grid=...): the field's bounds [-w, w) x [-h, h) (field = (w, h)) in square-ish cells that hold
+    about k of n bodies each at uniform density - side sqrt(area * k / n) - and at most `most` per axis: the grid on which
+    a row's first window of 3 x 3 cells holds about 9 k candidates."""
+    w, h = (float(v) for v in field)
+    k, n, most = max(int(k), 1), max(int(n), 1), max(int(most), 1)
+    side = float(np.sqrt(np.float64(4.0 * w * h) * k / n))
+
+    def along(extent):
+        if not side > 0.0:
+            return most
+        return int(min(max(np.floor(extent / side), 1.0), float(most)))
+    return make_grid(along(2.0 * w), along(2.0 * h), (-w, w, -h, h))
+
+
+def _knn_grid(call, systems, per_own, k, points, grid, h0, max_radius, squared):
+    """nbody_get_knn_grid through `call(grid, points, m, k, h0, h2_max, d2, index, info)` for `systems` systems (None: a
+    context) -> (d2 (S, per, k), index (S, per, k), info (S,), whether the rows are points).  h0=None: the larger cell side;
+    max_radius=None: +inf, otherwise squared with one float64 multiply unless `squared`."""
+    pts = _field_points(points)
+    k = int(k)
+    S = 1 if systems is None else max(systems, 1)
+    per = per_own if pts is None else len(pts)
+    if h0 is None:
+        h0 = max(1.0 / float(grid["sx"][0]), 1.0 / float(grid["sy"][0]))
+    r = np.inf if max_radius is None else float(max_radius)
+    h2_max = r if squared or max_radius is None else r * r
+    d2, index = _knn_buffers((S, max(per, 1), max(k, 1)))
+    info = np.zeros(S, dtype=KNN_GRID_INFO_DTYPE)
+    _check(call(grid.ctypes.data, None if pts is None else pts.ctypes.data, per, k, float(h0), h2_max, d2.ctypes.data,
+                index.ctypes.data, info.ctypes.data))
+    return d2, index, info, pts is not None
+
+
+def _knn_grid_dict(d2, index, info, grid):
+    rows = int(info["rows"])
+    return {"d2": d2[:rows].copy(), "index": index[:rows].copy(), "info": {f: int(info[f]) for f in KNN_GRID_INFO_DTYPE.names},
+            "grid": grid[0].copy()}
+
+
 def _within(call, systems, per_own, radius, points, grid, squared, lists):
     """nbody_get_within through `call(grid, h2, points, m, out, start, list, cap, info)` for `systems` systems (None: a
     context) -> one dict per system: {"rows": WITHIN_DTYPE (rows,), "info", "grid"} and with `lists` "start": int64
@@ -1284,11 +1329,23 @@ class Stepper:
         NEIGHBOR_DTYPE array.  Not collective: any rank of any world may call it on its own."""
         return _neighbors(lambda *a: lib.nbody_get_neighbors(self._ctx, *a), points, self.capacity)
 
-    def knn(self, k, points=None):
+    def knn(self, k, points=None, grid=None, h0=None, max_radius=None, squared=False):
         """nbody_get_knn: for every row - each of `points` (m, 2), or with points=None each current body (self term left
         out by index) - the k nearest current bodies under (d2, index) ascending, 1 <= k <= KNN_MAX: {"d2": float64
         (rows, k) squared distances, "index": int32 (rows, k)}, entries past the last eligible source {+inf, -1}.  Entry 0
-        has the bits of neighbors().  Not collective: any rank of any world may call it on its own."""
+        has the bits of neighbors().  Not collective: any rank of any world may call it on its own.
+        grid (a make_grid record, or what make_grid accepts; knn_grid() makes a matched one): nbody_get_knn_grid, the same
+        entries found through the cell list in O(n), among the bodies inside the grid only; the dict gains "info": n, rows,
+        inside, outside, widened, rounds and "grid".  h0: the radius of a row's first window (None: the larger cell side),
+        doubled until the row has its k; max_radius: only sources within it (a length; a squared length with squared=True;
+        None: no cut) - it needs a grid, the brute-force call has no cut."""
+        if grid is not None:
+            g = make_grid(grid)
+            d2, index, info, _ = _knn_grid(lambda *a: lib.nbody_get_knn_grid(self._ctx, *a), None, self.capacity, k, points, g, h0,
+                                           max_radius, squared)
+            return _knn_grid_dict(d2[0], index[0], info[0], g)
+        if max_radius is not None or h0 is not None:
+            raise ValueError("knn(): max_radius and h0 need a grid - the brute-force call has no cut and no window")
         pts = _field_points(points)
         k = int(k)
         m = self.capacity if pts is None else len(pts)
@@ -1484,9 +1541,10 @@ class StepperGroup:
         """Stepper.neighbors through one rank: every rank's replica holds every body, each gives the same bits."""
         return self.ranks[rank].neighbors(points)
 
-    def knn(self, k, points=None, rank=0):
-        """Stepper.knn through one rank: every rank's replica holds every body, each gives the same bits."""
-        return self.ranks[rank].knn(k, points)
+    def knn(self, k, points=None, rank=0, grid=None, h0=None, max_radius=None, squared=False):
+        """Stepper.knn through one rank, with or without a grid: every rank's replica holds every body, each gives the same
+        bits."""
+        return self.ranks[rank].knn(k, points, grid, h0, max_radius, squared)
 
     def shells(self, edges, points=None, squared=False, rank=0):
         """Stepper.shells through one rank: every rank's replica holds every body, each gives the same bits."""
@@ -1698,10 +1756,19 @@ class StepperBatch:
             return [buf[s, :int(k)].copy() for s, k in enumerate(self.counts())]
         return np.ascontiguousarray(buf[:, :m])
 
-    def knn(self, k, points=None):
+    def knn(self, k, points=None, grid=None, h0=None, max_radius=None, squared=False):
         """nbody_batch_get_knn: Stepper.knn for every system in one launch, with the one set of points and the one k for all
         of them, system s having the bits a Stepper holding its state gives.  points=None: a list of S dicts, one row per
-        current body of the system; otherwise one dict of arrays of shape (S, m, k)."""
+        current body of the system; otherwise one dict of arrays of shape (S, m, k).
+        grid: nbody_batch_get_knn_grid, one grid, h0 and max_radius for every system, the list stages and the walk one
+        launch each: a list of S dicts in the form (and with the bits) Stepper.knn(grid=...) gives for the system's state."""
+        if grid is not None:
+            g = make_grid(grid)
+            d2, index, info, _ = _knn_grid(lambda *a: lib.nbody_batch_get_knn_grid(self._b, *a), self.systems, self.capacity, k,
+                                           points, g, h0, max_radius, squared)
+            return [_knn_grid_dict(d2[s], index[s], info[s], g) for s in range(self.systems)]
+        if max_radius is not None or h0 is not None:
+            raise ValueError("knn(): max_radius and h0 need a grid - the brute-force call has no cut and no window")
         pts = _field_points(points)
         k = int(k)
         m = self.capacity if pts is None else len(pts)

@@ -839,3 +839,21 @@ int nbody_batch_get_groups_grid(nbody_batch* b, const nbody_grid* grid, double l
 }
 
 }  // extern "C"
+
+// The k nearest on the cell list (nbody_knn_grid.hpp): one grid, one set of points, one k, one h0 and one h2_max for every
+// system, the list stages and the walk ONE launch each for the whole batch.
+extern "C" {
+
+int nbody_batch_get_knn_grid(nbody_batch* b, const nbody_grid* grid, const nbody_vec2* points, int m, int k, double h0,
+                             double h2_max, double* d2, int32_t* index, nbody_knn_grid_info* info) {
+    const char* who = "nbody_batch_get_knn_grid";
+    RowsSite site;
+    int rc = knn_grid_check_args(who, {b, d2, index, info}, grid, m, k, h0, h2_max, batch_systems(b));
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return knn_grid_run<decltype(t), RowsBatchCount>(who, site, b->q.cel, b->q.kng, *grid, points, m, k, h0, h2_max, d2, index,
+                                                         info, sync);
+    });
+}
+
+}  // extern "C"

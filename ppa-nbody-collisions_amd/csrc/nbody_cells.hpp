@@ -54,6 +54,7 @@
 //                            one lane per slot of `order`, launched after cells_list_run by the queries that walk the list.
 //   cells_span, cells_window_walk   the window along one axis, and the one walk over the row-of-cells ranges of a window:
 //                            pair(rec) per record, four records loaded ahead.
+//   cells_frame_walk         the same walk over integer spans less an inner rectangle already covered (nbody_knn_grid.hpp).
 //   cells_block_prefix<V, kBlock>   a workgroup's exclusive prefix (cells_scan here, the row scan of nbody_within.hpp).
 //   cells_fine               the host's guard for a grid too fine for the window's proof.
 // Every index that comes out of memory (a cell of cell_of, an entry of slot or order, a start) is range-checked before it is
@@ -406,6 +407,36 @@ __device__ __forceinline__ void cells_window_walk(const CellView& cl, const Cell
 #pragma unroll
             for (int u = 0; u < 4; ++u)
                 if (k + u < b) pair(s[u]);
+        }
+    }
+}
+
+// The walk over a window given by its integer spans, less an inner rectangle that an earlier walk has covered: pair(rec) for
+// every sorted record of the cells of cx x cy that do not lie in ix x iy.  The inner spans lie inside the outer ones, or one
+// of them is empty (hi < lo) and nothing is left out.  Per row of cells that is one contiguous range of the sorted records
+// where the inner rectangle does not reach the row, and at most two where it does: columns cx.lo .. ix.lo - 1 and
+// ix.hi + 1 .. cx.hi.  Ranges and records are checked and loaded as in cells_window_walk.  The k nearest on the list
+// (nbody_knn_grid.hpp) widen a row's window with it: no record is handed over twice.
+template <typename T, typename Pair>
+__device__ __forceinline__ void cells_frame_walk(const CellView& cl, const CellRec<T>* __restrict__ sorted, const nbody_grid& g,
+                                                 CellSpan cx, CellSpan cy, CellSpan ix, CellSpan iy, Pair pair) {
+    if (cx.lo > cx.hi) return;
+    const bool hole = ix.lo <= ix.hi && iy.lo <= iy.hi;
+    for (int yy = cy.lo; yy <= cy.hi; ++yy) {
+        const bool cut = hole && iy.lo <= yy && yy <= iy.hi;
+        for (int part = 0; part < (cut ? 2 : 1); ++part) {
+            const int c0 = part == 0 ? cx.lo : ix.hi + 1, c1 = cut && part == 0 ? ix.lo - 1 : cx.hi;
+            if (c0 > c1) continue;
+            const int a = cl.start[yy * g.nx + c0], b = cl.start[yy * g.nx + c1 + 1];
+            if (a < 0 || b > cl.inside || a >= b) continue;
+            for (int k = a; k < b; k += 4) {                     // four loads ahead of their pairs
+                CellRec<T> s[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s[u] = sorted[k + u < b ? k + u : b - 1];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (k + u < b) pair(s[u]);
+            }
         }
     }
 }

@@ -1863,3 +1863,23 @@ int nbody_get_groups_grid(nbody_ctx* c, const nbody_grid* grid, double link, dou
 }
 
 }  // extern "C"
+
+// The k nearest on the cell list (nbody_knn_grid.hpp): positions of the replica only, so any context may call them on its
+// own.  After everything else, for the group energies' reason.
+extern "C" {
+
+int nbody_get_knn_grid(nbody_ctx* c, const nbody_grid* grid, const nbody_vec2* points, int m, int k, double h0, double h2_max,
+                       double* d2, int32_t* index, nbody_knn_grid_info* info) {
+    const char* who = "nbody_get_knn_grid";
+    RowsSite site;
+    int rc = knn_grid_check_args(who, {c, d2, index, info}, grid, m, k, h0, h2_max, 1);
+    if (rc != NBODY_OK || (rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    if (!points && m < site.n_bound)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d rows, the context holds %d bodies", who, m, site.n_bound);
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return knn_grid_run<decltype(t), RowsOneCount>(who, site, c->q.cel, c->q.kng, *grid, points, m, k, h0, h2_max, d2, index,
+                                                       info, sync);
+    });
+}
+
+}  // extern "C"

@@ -28,6 +28,7 @@
 #include "nbody_binaries.hpp"
 #include "nbody_tides.hpp"
 #include "nbody_groups_grid.hpp"
+#include "nbody_knn_grid.hpp"
 
 namespace nbk {
 
@@ -46,6 +47,7 @@ struct QueryStates {
     BinState bin;               // bound-pair queries (nbody_binaries.hpp)
     TidesState tid;             // tidal tensor and jerk (nbody_tides.hpp)
     TracerState trc;            // tracer particles (nbody_tracers.hpp)
+    KnnGridState kng;           // the k nearest on the cell list (nbody_knn_grid.hpp): the cell list of `cel` and these
 };
 
 // After the handle has synchronised its stream.
@@ -64,6 +66,7 @@ inline void queries_free(QueryStates& q) {
     pair_log_free(q.bin);
     tides_free(q.tid);
     tracers_free(q.trc);
+    knn_grid_free(q.kng);
 }
 
 }  // namespace nbk

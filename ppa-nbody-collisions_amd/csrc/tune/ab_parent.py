@@ -51,6 +51,8 @@ Lines (fp32, literal, stock configuration with stock radii):
     ggr       the matched grid of groups_grid_probe.py's overlap case on the grp state: groups(0, 1,        ms per call
               grid=groups_grid(the field widened to the bodies, 0, 1, the median radius)); ggr256: the
               same on StepperBatch 256 x 1024 after 3 steps, one grid of at most 128 x 128 cells
+    kng       the shape of knn_grid_probe.py: Stepper N = 262144, knn(8, grid=knn_grid(the field, 8, n));   ms per call
+              kng256: StepperBatch 256 x 1024 after 3 steps, knn(8) on 32 x 32 cells over the field
     trc       stepping with 65536 tracers set, from a fresh upload and a fresh set: trc Stepper  ms | us per step
               N = 262144 (8 steps), trc256 StepperBatch 256 x 1024 with 256 tracers in each
               system (500 steps)
@@ -77,7 +79,7 @@ LINES = ("a", "b256", "b256phi", "b64", "b64phi", "c", "dctx262144", "dctx1024",
          "fld", "fldpts", "fld256", "nbr", "nbrpts", "nbr256", "grp", "grp256", "prs", "prspts", "prs256",
          "enc", "enc256", "bin", "bin256", "gpe", "gpe256", "shl", "shlpts", "shl256", "shm", "shmpts", "shm256",
          "tid", "tidj", "tidpts", "tidjpts", "tid256", "tidj256", "cel", "cel256", "wth", "wthpts", "wth256", "ggr", "ggr256",
-         "trc", "trc256", "io", "io64", "io256")
+         "kng", "kng256", "trc", "trc256", "io", "io64", "io256")
 BATCH = {"b256": (256, 1024), "b64": (64, 4096)}
 STEPS = {"dctx262144": 20, "dctx1024": 2000, "d256x1024": 1000, "d64x4096": 500}
 IO = {"io": 20, "io64": 12, "io256": 20}     # round trips per window
@@ -90,8 +92,9 @@ SCANS = {"grp": 8, "grp256": 100, "prs": 20, "prspts": 30, "prs256": 200,     # 
          "ggr": 200, "ggr256": 100}             # profiles/groups_grid_probe.txt: 0.67 and 1.2 ms a call on the matched grid
 # whole cells() / within() calls (profiles/cells_probe.txt, profiles/within_probe.txt): 0.62 and 1.2 ms a call for cel and
 # cel256, 1.4 ms for wth and wth256 with their lists; wthpts builds the same cell list for a quarter of the rows
-GRIDS = {"cel": 250, "cel256": 120, "wth": 100, "wthpts": 250, "wth256": 100}
-ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm", "tid", "cel", "wth", "ggr")
+GRIDS = {"cel": 250, "cel256": 120, "wth": 100, "wthpts": 250, "wth256": 100,
+         "kng": 60, "kng256": 60}               # profiles/knn_grid_probe.txt: whole knn(8, grid=...) calls, a few ms each
+ROW_LINES = ("fld", "nbr", "grp", "prs", "enc", "bin", "gpe", "shl", "shm", "tid", "cel", "wth", "ggr", "kng")
 N_BIG = 262144
 M_POINTS = 65536
 
@@ -206,6 +209,10 @@ class Line:
                     self.call = lambda pts: self.st.cells(grid, lists=True)
                 else:
                     self.call = lambda pts: self.st.within(2.0 * W / nx, pts, grid=grid, lists=True)
+            elif name.startswith("kng"):                                    # knn_grid_probe.py: k = 8 on the matched grid
+                W = float(cfg.fieldWidth)
+                grid = nb.make_grid(32, 32, (-W, W, -W, W)) if self.batch else nb.knn_grid((W, W), 8, N_BIG)
+                self.call = lambda pts: self.st.knn(8, pts, grid=grid)
             elif name.startswith("tid"):
                 jerk, vel = name[3:4] == "j", None
                 if jerk and self.pts is not None:
