@@ -1378,6 +1378,84 @@ int nbody_batch_get_knn_grid(struct nbody_batch* b, const nbody_grid* grid, cons
                              nbody_knn_grid_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Pair counts and bound pairs on the cell list (the reference has none): the histogram of
+ * nbody_get_pair_counts and the list of nbody_get_binaries among the bodies inside a caller-given grid, found through the cell
+ * list of nbody_get_cells instead of a walk over all n sources per row: O(n) on a grid whose cells are about as wide as the
+ * top edge, or the separation (Python: within_grid(field, top_edge_or_max_sep)), where the plain calls are O(n^2).
+ * The definition, which is the whole contract.  Only IEEE fp64 operations, every one rounded on its own, no fma.  The grid
+ * is an nbody_grid as for nbody_get_cells; inside(j) is exactly the cell sums' definition.  The sources are the current
+ * bodies with inside(j); a body outside the grid takes part in no pair and is counted in info.outside; inside + outside == n.
+ * nbody_get_pair_counts_grid.  d2, counts[k], below and the derived rest are those of nbody_get_pair_counts, bit for bit -
+ *     dx = X_j - x;  dy = Y_j - y;  d2 = (dx*dx) + (dy*dy);  counts[k]: edges2[k] <= d2 && d2 < edges2[k+1];  below: d2 < edges2[0]
+ * - over the counted pairs.  points == NULL, the own form: the unordered pairs of inside bodies, each once;
+ * info.pairs = inside * (inside - 1) / 2 and info.rows = n.  points != NULL: every (point, inside body) pair;
+ * info.pairs = m * inside and info.rows = m; a point may lie anywhere - outside the grid, at 1e200, at NaN (it counts nothing).
+ * rest = pairs - below - sum(counts), derived on the host.  edges2 and bins follow nbody_get_pair_counts' rules; a top edge
+ * of +inf is legal and means the whole grid: correct, and slow.
+ * nbody_get_binaries_grid.  The definition of nbody_get_binaries, bit for bit, over the pairs i < j of inside bodies; the
+ * indices of a record are those of the state.  coincident counts the pairs of inside bodies at d2 == 0 (two such bodies share
+ * a cell).  The host half (nbody_binary_finish, the sort by (i, j)), the cap rule - NBODY_ERR_CAPACITY leaves out untouched
+ * with info complete, cap == 0 gives the counts only - and the single-rank restriction are nbody_get_binaries'.
+ * What follows from the definition:
+ *   - with outside == 0: counts, below, rest and pairs are the bytes of nbody_get_pair_counts, and the list and every count
+ *     the bytes of nbody_get_binaries, whatever the grid;
+ *   - with any grid they are what the plain calls give on a context that holds exactly the inside bodies, in their order,
+ *     the binaries' indices mapped back;
+ *   - with outside == 0 and own rows, 2 * counts[0] at edges2 = {0, nextafter(h2, +inf)} equals the sum of `count` of
+ *     nbody_get_within at h2 on the same grid;
+ *   - near + coincident of the binaries == counts[0] of the pair counts on the same grid at {0, nextafter(sep2, +inf)};
+ *   - the results are functions of the state, the values and the SET of inside bodies only: neither the cells nor the order
+ *     of the visit show, nor rank, world, transport, force kernel or the order the device's waves ran in.
+ * The window (csrc/nbody_pairs_grid.hpp): nbody_get_within's fixed-radius rule with h2 = edges2[bins], or sep2 - the same
+ * host values, the same escape for a grid of more than 2^400 cells per unit length, the same span per axis.  It covers
+ * d2 <= h2; the pair counts count d2 < edges2[bins], so a pair exactly at the top edge is visited and not counted, the
+ * binaries take d2 <= sep2.  The rule costs time, never a result: a grid much finer than h, an h of the order of the
+ * system, or every body in a few cells brings the calls towards the n^2 pair tests of the plain ones, read from memory
+ * instead of LDS by one lane per row.
+ * Both synchronise, read only and never change what later steps compute.  nbody_get_pair_counts_grid reads positions of the
+ * replica only and is NOT collective: any rank of any world may call it on its own and each gives the same bytes.
+ * nbody_get_binaries_grid reads the velocities: NBODY_ERR_STATE on a context of more than one rank or with an exchange.
+ * They allocate nothing of their own - the cell list of nbody_get_cells, the sorted records of nbody_get_within, the edges,
+ * histograms and points of nbody_get_pair_counts, the log and counters of nbody_get_binaries, each on the first call of
+ * whichever query needs it; a handle that never calls them allocates nothing and launches nothing more, and every other
+ * kernel keeps its code.  n == 0 launches nothing.
+ * NBODY_ERR_INVALID, found before any device call, the values before the handle: everything nbody_get_cells rejects about
+ * the grid; then what nbody_get_pair_counts rejects (bins outside [1, 256]; a NaN, negative or unordered edge; m < 0 or m
+ * points above 2^31 bytes; a NULL handle, edges2, counts or info) or what nbody_get_binaries rejects (a NaN or negative sep2;
+ * cap < 0; a NULL out with cap > 0; cap records x systems above 2^31 bytes; a NULL handle or info).  NBODY_ERR_CAPACITY: the
+ * cap rule, and a batch with systems * nx * ny above 1 << 22.  NBODY_ERR_STATE: before an upload, and above.
+ * Cost (one MI355X, fp32; profiles/pairs_grid_probe.txt, the plain calls timed in the same runs; the stock state of N = 262144,
+ * n = 130965 after 3 steps, on within_grid(field, top edge or sep)): pair counts with 32 bins up to 381.8 / 824.8, the kernels of
+ * a call 0.197 / 0.088 ms (the walk 0.014 / 0.022) against pair_counts' 5.37 / 5.57 ms, whole calls 0.26 / 0.15 against 5.40 / 5.66 ms.
+ * Binaries, the counts only, at sep 128 / 1024: kernels 0.634 / 0.173 ms (the walk 0.019 / 0.122; at sep 128 the grid is
+ * 1024 x 1024 cells and their one-workgroup scan is 0.6 ms) against 5.38 / 5.79 ms, calls 0.68 / 0.22 against 5.51 / 5.71 ms.  With
+ * the list at sep 1024 (652339 records) the kernels are 1.01 against 9.25 ms and the call about 100 ms either way, inside the spread
+ * of its three rounds: the copy and the sort are the call.  Where it LOSES: on 1 x 1 cells every row walks all n records from
+ * memory - 15.0 against 5.2 ms (pair counts), 13.9 against 5.3 ms (binaries); and a batch of 256 x 1024, whose kernels win
+ * (0.056 - 0.072 against 0.120 - 0.159 ms) but whose whole call loses for the binaries with the list (13.5 against 10.8 ms), is level
+ * for the pair counts (0.49 against 0.49 ms) and wins for the counts-only binaries (0.111 against 0.156 ms).
+ * nbody_batch_get_pair_counts_grid, nbody_batch_get_binaries_grid: the same for every system of a batch, with one grid, one
+ * set of points and edges or one sep2 and one cap for all of them, every stage ONE launch whatever S is.  System s's counts
+ * at counts + s * bins, its list at out + s * cap, info[s]; the tail of every slice is left unchanged.  System s gives
+ * exactly what an nbody_ctx holding that system's state gives.  A count outside [0, capacity] is treated as 0 and reported
+ * for that system, as by nbody_batch_get_cells.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_pair_grid_info { int64_t n_bodies, rows, pairs, below, rest, inside, outside; } nbody_pair_grid_info;   /* 56 bytes */
+typedef struct nbody_binary_grid_info {
+    int64_t n_bodies, pairs, near, coincident, overlapping, approaching; double sep2; int64_t inside, outside;
+} nbody_binary_grid_info;   /* 72 bytes */
+int nbody_get_pair_counts_grid(nbody_ctx* ctx, const nbody_grid* grid, const nbody_vec2* points /* NULL: the bodies */, int m,
+                               const double* edges2 /* [bins + 1] */, int bins, uint64_t* counts /* [bins] */,
+                               nbody_pair_grid_info* info);
+int nbody_batch_get_pair_counts_grid(struct nbody_batch* b, const nbody_grid* grid, const nbody_vec2* points, int m,
+                                     const double* edges2, int bins, uint64_t* counts /* [systems * bins] */,
+                                     nbody_pair_grid_info* info /* [systems] */);
+int nbody_get_binaries_grid(nbody_ctx* ctx, const nbody_grid* grid, double sep2, nbody_binary* out, int cap,
+                            nbody_binary_grid_info* info);
+int nbody_batch_get_binaries_grid(struct nbody_batch* b, const nbody_grid* grid, double sep2, nbody_binary* out /* [systems * cap] */,
+                                  int cap, nbody_binary_grid_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

@@ -172,6 +172,8 @@ GROUP_BOUND = 1                                                 # nbody_group_re
 # struct nbody_pair_info as a numpy record (Stepper.pair_counts, StepperBatch.pair_counts)
 PAIR_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("rows", np.int64), ("pairs", np.int64), ("below", np.int64),
                             ("rest", np.int64)])
+# struct nbody_pair_grid_info (56 bytes): nbody_pair_info, then inside and outside (pair_counts(grid=...))
+PAIR_GRID_INFO_DTYPE = np.dtype(PAIR_INFO_DTYPE.descr + [("inside", np.int64), ("outside", np.int64)])
 
 # struct nbody_encounter, nbody_encounter_info, nbody_encounter_raw as numpy records (Stepper.encounters,
 # StepperBatch.encounters, encounter_finish); ENCOUNTER_DTYPE is what they return: the record without its reserved word
@@ -194,6 +196,8 @@ BINARY_RAW_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("flags", np.uint
                              ("d2", np.float64), ("v2", np.float64), ("mu", np.float64), ("hz", np.float64)])
 BINARY_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("pairs", np.int64), ("near", np.int64), ("coincident", np.int64),
                               ("overlapping", np.int64), ("approaching", np.int64), ("sep2", np.float64)])
+# struct nbody_binary_grid_info (72 bytes): nbody_binary_info, then inside and outside (binaries(grid=...))
+BINARY_GRID_INFO_DTYPE = np.dtype(BINARY_INFO_DTYPE.descr + [("inside", np.int64), ("outside", np.int64)])
 
 # struct nbody_tracer / nbody_tracer_info as numpy records (Stepper.set_tracers / tracers, StepperBatch likewise)
 TRACER_DTYPE = np.dtype([("pos", np.float64, (2,)), ("vel", np.float64, (2,))])
@@ -277,6 +281,10 @@ SYMBOLS = {
     "nbody_batch_get_groups_grid": (_i, [_vp, _vp, _d, _d, _vp, _vp]),
     "nbody_get_knn_grid": (_i, [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp]),
     "nbody_batch_get_knn_grid": (_i, [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp]),
+    "nbody_get_pair_counts_grid": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "nbody_batch_get_pair_counts_grid": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "nbody_get_binaries_grid": (_i, [_vp, _vp, _d, _vp, _i, _vp]),
+    "nbody_batch_get_binaries_grid": (_i, [_vp, _vp, _d, _vp, _i, _vp]),
     "nbody_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _i, _vp]),
     "nbody_batch_get_group_potential": (_i, [_vp, _d, _d, _vp, _vp, _vp]),
     "nbody_group_catalog": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _ip]),
@@ -693,16 +701,23 @@ def _pair_dict(counts, info, edges2):
             "n_bodies": int(info["n_bodies"]), "edges2": edges2}
 
 
-def _pair_counts(call, systems, edges, points, squared):
-    """nbody_get_pair_counts through `call(points, m, edges2, bins, counts, info)` -> one dict per system."""
+def _pair_counts(call, systems, edges, points, squared, grid=None):
+    """nbody_get_pair_counts through `call(points, m, edges2, bins, counts, info)` -> one dict per system.  With a grid (a
+    GRID_DTYPE record) `call` is nbody_get_pair_counts_grid's with the grid bound, and the dicts also have "inside", "outside"
+    and "grid"."""
     e2 = pair_edges2(edges, squared)
     pts = _field_points(points)
     bins = len(e2) - 1
     counts = np.zeros((max(systems, 1), bins), dtype=np.uint64)
-    info = np.zeros(max(systems, 1), dtype=PAIR_INFO_DTYPE)
+    info = np.zeros(max(systems, 1), dtype=PAIR_INFO_DTYPE if grid is None else PAIR_GRID_INFO_DTYPE)
     _check(call(None if pts is None else pts.ctypes.data, 0 if pts is None else len(pts), e2.ctypes.data, bins,
                 counts.ctypes.data, info.ctypes.data))
-    return [_pair_dict(counts[s].copy(), info[s], e2) for s in range(systems)]
+    out = [_pair_dict(counts[s].copy(), info[s], e2) for s in range(systems)]
+    if grid is not None:
+        ins, outs, g = info["inside"].tolist(), info["outside"].tolist(), grid.copy()   # one copy of the grid per call
+        for s, d in enumerate(out):
+            d.update(inside=ins[s], outside=outs[s], grid=g[0])
+    return out
 
 
 def _shell_buffers(shape):
@@ -1056,14 +1071,15 @@ def _binary_info(info):
     return d
 
 
-def _binaries(call, systems, max_sep, squared, cap):
+def _binaries(call, systems, max_sep, squared, cap, grid=None):
     """nbody_get_binaries through `call(sep2, out, cap, info)` -> one (BINARY_DTYPE array, info dict) per system.  max_sep is
     squared with one float64 multiply unless `squared`.  On NBODY_ERR_CAPACITY the call is repeated once with the largest
-    info.pairs."""
+    info.pairs.  With a grid (a GRID_DTYPE record) `call` is nbody_get_binaries_grid's with the grid bound, and the info
+    dicts also have "inside", "outside" and "grid"."""
     sep = float(max_sep)
     sep2 = sep if squared else sep * sep
     S = max(systems, 1)
-    info = np.zeros(S, dtype=BINARY_INFO_DTYPE)
+    info = np.zeros(S, dtype=BINARY_INFO_DTYPE if grid is None else BINARY_GRID_INFO_DTYPE)
     cap = max(int(cap), 0)
     buf = np.zeros((S, max(cap, 1)), dtype=BINARY_RECORD_DTYPE)
     status = call(sep2, buf.ctypes.data, cap, info.ctypes.data)
@@ -1072,7 +1088,12 @@ def _binaries(call, systems, max_sep, squared, cap):
         buf = np.zeros((S, max(cap, 1)), dtype=BINARY_RECORD_DTYPE)
         status = call(sep2, buf.ctypes.data, cap, info.ctypes.data)
     _check(status)
-    return [(_binary_list(buf[s, :int(info["pairs"][s])]), _binary_info(info[s])) for s in range(systems)]
+    out = [(_binary_list(buf[s, :int(info["pairs"][s])]), _binary_info(info[s])) for s in range(systems)]
+    if grid is not None:
+        ins, outs, g = info["inside"].tolist(), info["outside"].tolist(), grid.copy()   # one copy of the grid per call
+        for s, (_, d) in enumerate(out):
+            d.update(inside=ins[s], outside=outs[s], grid=g[0])
+    return out
 
 
 def binary_finish(raw):
@@ -1459,11 +1480,19 @@ class Stepper:
         g = self.group_potential(link, radius_scale)
         return _group_energies(self.download(), g)
 
-    def pair_counts(self, edges, points=None, squared=False):
+    def pair_counts(self, edges, points=None, squared=False, grid=None):
         """nbody_get_pair_counts: the number of pairs in each bin of separation between the B + 1 `edges` (lengths; squared
         lengths with squared=True) - the unordered pairs of current bodies, or with `points` (m, 2) every (point, body)
         pair -> {"counts": uint64 (B,), "below": pairs under the first edge, "rest": pairs at or above the last (or NaN),
-        "pairs": all of them, "n_bodies", "edges2": the squared edges that were sent}.  Not collective."""
+        "pairs": all of them, "n_bodies", "edges2": the squared edges that were sent}.  Not collective.
+        grid (a make_grid record, or what make_grid accepts): nbody_get_pair_counts_grid, the same counts found through the
+        cell list in O(n), among the bodies inside the grid only; the dict also has "inside", "outside" and "grid".  With
+        outside == 0 the numbers are those of grid=None, whatever the grid.  The matched grid is
+        within_grid(field, top_edge): cells no smaller than the last edge."""
+        if grid is not None:
+            g = make_grid(grid)
+            return _pair_counts(lambda *a: lib.nbody_get_pair_counts_grid(self._ctx, g.ctypes.data, *a), 1, edges, points,
+                                squared, g)[0]
         return _pair_counts(lambda *a: lib.nbody_get_pair_counts(self._ctx, *a), 1, edges, points, squared)[0]
 
     def encounters(self, horizon=None, cap=None):
@@ -1480,14 +1509,21 @@ class Stepper:
         cap = max(self.capacity, 64) if cap is None else cap
         return _encounters(lambda *a: lib.nbody_get_encounters(self._ctx, *a), 1, float(horizon), cap)[0]
 
-    def binaries(self, max_sep, squared=False, cap=None):
+    def binaries(self, max_sep, squared=False, cap=None, grid=None):
         """nbody_get_binaries: the pairs of current bodies no further apart than `max_sep` (a length; a squared length with
         squared=True; inf allowed) that are gravitationally bound as an isolated two-body system -> (a BINARY_DTYPE array
         {"a": semi-major axis, "ecc", "period", "sep": the separation now, "i" < "j", "flags": BINARY_OVERLAP |
         BINARY_APPROACHING} sorted by (i, j), {"n_bodies", "pairs", "near": all pairs within max_sep, "coincident",
         "overlapping", "approaching", "sep2"}).  cap: the first guess of the room (None: the capacity); a longer list is
-        fetched with a second call.  Single-rank contexts only."""
+        fetched with a second call.  Single-rank contexts only.
+        grid (a make_grid record, or what make_grid accepts): nbody_get_binaries_grid, the same list found through the cell
+        list in O(n), among the bodies inside the grid only; the info dict also has "inside", "outside" and "grid".  With
+        outside == 0 the list and the counts are those of grid=None, whatever the grid.  The matched grid is
+        within_grid(field, max_sep): cells no smaller than the separation."""
         cap = max(self.capacity, 64) if cap is None else cap
+        if grid is not None:
+            g = make_grid(grid)
+            return _binaries(lambda *a: lib.nbody_get_binaries_grid(self._ctx, g.ctypes.data, *a), 1, max_sep, squared, cap, g)[0]
         return _binaries(lambda *a: lib.nbody_get_binaries(self._ctx, *a), 1, max_sep, squared, cap)[0]
 
     def stats(self):
@@ -1568,9 +1604,10 @@ class StepperGroup:
         """Stepper.group_potential through one rank: every rank's replica holds every position and mass."""
         return self.ranks[rank].group_potential(link, radius_scale)
 
-    def pair_counts(self, edges, points=None, squared=False, rank=0):
-        """Stepper.pair_counts through one rank: every rank's replica holds every body, each gives the same numbers."""
-        return self.ranks[rank].pair_counts(edges, points, squared)
+    def pair_counts(self, edges, points=None, squared=False, rank=0, grid=None):
+        """Stepper.pair_counts through one rank, with or without a grid: every rank's replica holds every body, each gives
+        the same numbers."""
+        return self.ranks[rank].pair_counts(edges, points, squared, grid)
 
     def save_state(self, path):
         """nbody_group_state_save: the group's download under the header of rank 0, the file a plain Stepper writes."""
@@ -1868,10 +1905,15 @@ class StepperBatch:
         """Stepper.group_energies for every system: a list of S GROUP_RECORD_DTYPE arrays."""
         return [_group_energies(self.download(s), g) for s, g in enumerate(self.group_potential(link, radius_scale))]
 
-    def pair_counts(self, edges, points=None, squared=False):
+    def pair_counts(self, edges, points=None, squared=False, grid=None):
         """nbody_batch_get_pair_counts: Stepper.pair_counts for every system in one launch, with the one set of edges and
         points for all of them: a list of S dicts in the form (and with the numbers) a Stepper holding the system's state
-        gives."""
+        gives.  grid: one grid for every system, nbody_batch_get_pair_counts_grid - the list stages and the walk one launch
+        each; the matched grid is within_grid(field, top_edge)."""
+        if grid is not None:
+            g = make_grid(grid)
+            return _pair_counts(lambda *a: lib.nbody_batch_get_pair_counts_grid(self._b, g.ctypes.data, *a), self.systems, edges,
+                                points, squared, g)
         return _pair_counts(lambda *a: lib.nbody_batch_get_pair_counts(self._b, *a), self.systems, edges, points, squared)
 
     def encounters(self, horizon, cap=None):
@@ -1881,10 +1923,16 @@ class StepperBatch:
         cap = max(self.capacity, 64) if cap is None else cap
         return _encounters(lambda *a: lib.nbody_batch_get_encounters(self._b, *a), self.systems, float(horizon), cap)
 
-    def binaries(self, max_sep, squared=False, cap=None):
+    def binaries(self, max_sep, squared=False, cap=None, grid=None):
         """nbody_batch_get_binaries: Stepper.binaries for every system in one launch, with the one separation for all of
-        them: a list of S (array, info) pairs in the form (and with the bits) a Stepper holding the system's state gives."""
+        them: a list of S (array, info) pairs in the form (and with the bits) a Stepper holding the system's state gives.
+        grid: one grid for every system, nbody_batch_get_binaries_grid - the list stages and the walk one launch each; the
+        matched grid is within_grid(field, max_sep)."""
         cap = max(self.capacity, 64) if cap is None else cap
+        if grid is not None:
+            g = make_grid(grid)
+            return _binaries(lambda *a: lib.nbody_batch_get_binaries_grid(self._b, g.ctypes.data, *a), self.systems, max_sep,
+                             squared, cap, g)
         return _binaries(lambda *a: lib.nbody_batch_get_binaries(self._b, *a), self.systems, max_sep, squared, cap)
 
     def reserve_diagnostics(self, samples):

@@ -857,3 +857,32 @@ int nbody_batch_get_knn_grid(nbody_batch* b, const nbody_grid* grid, const nbody
 }
 
 }  // extern "C"
+
+// Pair counts and bound pairs on the cell list (nbody_pairs_grid.hpp): one grid, one set of points and edges or one sep2 and
+// one cap for every system, the list stages and the walk ONE launch each for the whole batch.
+extern "C" {
+
+int nbody_batch_get_pair_counts_grid(nbody_batch* b, const nbody_grid* grid, const nbody_vec2* points, int m, const double* edges2,
+                                     int bins, uint64_t* counts, nbody_pair_grid_info* info) {
+    const char* who = "nbody_batch_get_pair_counts_grid";
+    RowsSite site;
+    int rc = pairs_grid_check_args(who, {b, edges2, counts, info}, grid, m, edges2, bins, batch_systems(b));
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return pairs_grid_run<decltype(t), RowsBatchCount>(who, site, b->q.cel, b->q.prs, *grid, points, m, edges2, bins, counts, info,
+                                                           sync);
+    });
+}
+
+int nbody_batch_get_binaries_grid(nbody_batch* b, const nbody_grid* grid, double sep2, nbody_binary* out, int cap,
+                                  nbody_binary_grid_info* info) {
+    const char* who = "nbody_batch_get_binaries_grid";
+    RowsSite site;
+    int rc = binaries_grid_check_args(who, b, grid, sep2, out, cap, info, batch_systems(b));
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return binaries_grid_run<decltype(t), RowsBatchCount>(who, site, b->V, b->q.cel, b->q.bin, *grid, sep2, out, cap, info, sync);
+    });
+}
+
+}  // extern "C"

@@ -1883,3 +1883,34 @@ int nbody_get_knn_grid(nbody_ctx* c, const nbody_grid* grid, const nbody_vec2* p
 }
 
 }  // extern "C"
+
+// Pair counts and bound pairs on the cell list (nbody_pairs_grid.hpp): the plain calls' arguments and errors after the
+// grid's.  The pair counts read positions of the replica only - any rank may call them; the binaries read the velocities, so
+// the encounters' restriction holds.  After everything else, for the group energies' reason.
+extern "C" {
+
+int nbody_get_pair_counts_grid(nbody_ctx* c, const nbody_grid* grid, const nbody_vec2* points, int m, const double* edges2, int bins,
+                               uint64_t* counts, nbody_pair_grid_info* info) {
+    const char* who = "nbody_get_pair_counts_grid";
+    RowsSite site;
+    int rc = pairs_grid_check_args(who, {c, edges2, counts, info}, grid, m, edges2, bins, 1);
+    if (rc != NBODY_OK || (rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return pairs_grid_run<decltype(t), RowsOneCount>(who, site, c->q.cel, c->q.prs, *grid, points, m, edges2, bins, counts, info,
+                                                         sync);
+    });
+}
+
+int nbody_get_binaries_grid(nbody_ctx* c, const nbody_grid* grid, double sep2, nbody_binary* out, int cap,
+                            nbody_binary_grid_info* info) {
+    const char* who = "nbody_get_binaries_grid";
+    RowsSite site;
+    int rc = binaries_grid_check_args(who, c, grid, sep2, out, cap, info, 1);
+    if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "binaries need", kOwnVelocities)) != NBODY_OK) return rc;
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return binaries_grid_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->q.cel, c->q.bin, *grid, sep2, out, cap, info, sync);
+    });
+}
+
+}  // extern "C"

@@ -6,7 +6,7 @@
 // entry points (nbody_get_* in nbody_ctx.hip, nbody_batch_get_* in nbody_batch.hip).  Nothing is allocated before a query's
 // first call (tracers: the first set); each state grows to the largest request seen and is released by queries_free.
 // A query that is another walk over what the states already hold adds no member: the groups on the cell list
-// (nbody_groups_grid.hpp) use `cel` and `grp`.
+// (nbody_groups_grid.hpp) use `cel` and `grp`, the pair counts and binaries on it (nbody_pairs_grid.hpp) `cel`, `prs` and `bin`.
 // IdsState and TrackState are not queries - they are set up at create and by a reservation - and stay members of the
 // handles, with ids_free and track_free next to them.
 #pragma once
@@ -29,6 +29,7 @@
 #include "nbody_tides.hpp"
 #include "nbody_groups_grid.hpp"
 #include "nbody_knn_grid.hpp"
+#include "nbody_pairs_grid.hpp"
 
 namespace nbk {
 

@@ -439,13 +439,48 @@ inline int pair_log_check_args(const char* who, const void* handle, const Q& q, 
     return NBODY_OK;
 }
 
+// Everything after the first wait of a pair-log call: the counters say whether the log is complete and how much of it to
+// read, then the second wait and the host's O(pairs) part.  write_info(sys, n, counts) writes system sys's info record - the
+// query's own (pair_log_run) or one with more in it (the binaries on the cell list, nbody_pairs_grid.hpp).  On
+// NBODY_ERR_CAPACITY every info is written and out untouched.
+template <typename Q, typename WriteInfo>
+int pair_log_tail(const char* who, const RowsSite& s, PairLogState<Q>& g, const Q& q, bool launched, typename Q::Record* out, int cap,
+                  WriteInfo write_info) {
+    using Raw = typename Q::Raw;
+    using Counts = typename Q::Counts;
+    const Counts* h_cnt = reinterpret_cast<const Counts*>(g.cnt.h);
+    int over = -1;
+    unsigned long long most = 0;                                 // the pairs of the first system that does not fit
+    size_t used = 0;                                             // records of the log up to the last one written
+    for (int sys = 0; sys < s.systems; ++sys) {
+        const int64_t n = s.count(sys);
+        const Counts c = launched && n > 0 ? h_cnt[sys] : Counts{};
+        write_info(sys, n, c);
+        if (c.pairs > (unsigned long long)cap && over < 0) { over = sys; most = c.pairs; }
+        if (c.pairs) used = (size_t)sys * (size_t)cap + (size_t)c.pairs;
+    }
+    if (!out) return NBODY_OK;                                   // cap == 0: the counts only
+    if (over >= 0)
+        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d %s, system %d has %lld: call again with that cap", who, cap, Q::kNoun,
+                          over, (long long)most);
+    if (used == 0) return NBODY_OK;
+    NBK_ROWS_TRY(hipMemcpyAsync(g.log.h, g.log.d, used * sizeof(Raw), hipMemcpyDeviceToHost, s.stream));
+    NBK_ROWS_TRY(hipStreamSynchronize(s.stream));
+    const Raw* raw = reinterpret_cast<const Raw*>(g.log.h);
+    for (int sys = 0; sys < s.systems; ++sys) {
+        const Counts c = launched && s.count(sys) > 0 ? h_cnt[sys] : Counts{};
+        const int fin = q.finish(raw + (size_t)sys * (size_t)cap, (int)c.pairs, out + (size_t)sys * (size_t)cap);
+        if (fin != NBODY_OK) return fin;
+    }
+    return NBODY_OK;
+}
+
 // One call, from the reservation to the caller's list; the site, Count and read_meta as for rows_run.  V: the velocities,
 // indexed like the site's J.  Two waits: the counters first - they say whether the log is complete and how much of it to
-// read - then the records.  On NBODY_ERR_CAPACITY info is complete and out untouched.
+// read - then the records (pair_log_tail).  On NBODY_ERR_CAPACITY info is complete and out untouched.
 template <typename T, typename Count, typename Q, typename ReadMeta>
 int pair_log_run(const char* who, const RowsSite& s, const void* V, PairLogState<Q>& g, const Q& q, typename Q::Record* out, int cap,
                  typename Q::Info* info, ReadMeta read_meta) {
-    using Raw = typename Q::Raw;
     using Counts = typename Q::Counts;
     const size_t S = (size_t)s.systems;
     const bool launched = s.n_bound > 0;
@@ -460,29 +495,7 @@ int pair_log_run(const char* who, const RowsSite& s, const void* V, PairLogState
     }
     const int rc = s.sync<Count>(launched, read_meta);
     if (rc != NBODY_OK) return rc;
-    const Counts* h_cnt = reinterpret_cast<const Counts*>(g.cnt.h);
-    int over = -1;
-    size_t used = 0;                                             // records of the log up to the last one written
-    for (int sys = 0; sys < s.systems; ++sys) {
-        const int64_t n = s.count(sys);
-        const Counts c = launched && n > 0 ? h_cnt[sys] : Counts{};
-        info[sys] = q.info(n, c);
-        if (c.pairs > (unsigned long long)cap && over < 0) over = sys;
-        if (c.pairs) used = (size_t)sys * (size_t)cap + (size_t)c.pairs;
-    }
-    if (!out) return NBODY_OK;                                   // cap == 0: the counts only
-    if (over >= 0)
-        return nbody_fail(NBODY_ERR_CAPACITY, "%s: room for %d %s, system %d has %lld: call again with that cap", who, cap, Q::kNoun,
-                          over, (long long)info[over].pairs);
-    if (used == 0) return NBODY_OK;
-    NBK_ROWS_TRY(hipMemcpyAsync(g.log.h, g.log.d, used * sizeof(Raw), hipMemcpyDeviceToHost, s.stream));
-    NBK_ROWS_TRY(hipStreamSynchronize(s.stream));
-    const Raw* raw = reinterpret_cast<const Raw*>(g.log.h);
-    for (int sys = 0; sys < s.systems; ++sys) {
-        const int fin = q.finish(raw + (size_t)sys * (size_t)cap, (int)info[sys].pairs, out + (size_t)sys * (size_t)cap);
-        if (fin != NBODY_OK) return fin;
-    }
-    return NBODY_OK;
+    return pair_log_tail(who, s, g, q, launched, out, cap, [&](int sys, int64_t n, const Counts& c) { info[sys] = q.info(n, c); });
 }
 
 }  // namespace nbk
