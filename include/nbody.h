@@ -1456,6 +1456,73 @@ int nbody_batch_get_binaries_grid(struct nbody_batch* b, const nbody_grid* grid,
                                   int cap, nbody_binary_grid_info* info /* [systems] */);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Encounters on the cell list (the reference has none): the swept contacts of nbody_get_encounters among the
+ * bodies inside a caller-given grid, found through the cell list of nbody_get_cells instead of a walk over all n sources per
+ * row: O(n) on a grid whose cells are about as wide as the reach of a typical body within the horizon (Python:
+ * encounters_grid(field, horizon, r_typical, v_typical)), where the plain call is O(n^2).  The natural use is a per-step
+ * monitor with h = the time step.
+ * The definition, which is the whole contract.  The result is exactly what nbody_get_encounters defines - swept, flags, t,
+ * the sort by (t, i, j), the counts - over the pairs i < j of bodies that are both inside(.) of the cell sums; the indices of
+ * a record are those of the state.  inside and outside are as in nbody_binary_grid_info: a body outside the grid takes part
+ * in no pair; inside + outside == n.  What follows:
+ *   - with outside == 0 the list and every count are the bytes of nbody_get_encounters, whatever the grid;
+ *   - with any grid they are what nbody_get_encounters gives on a context that holds exactly the inside bodies, in their
+ *     order, the indices mapped back;
+ *   - the raw record does not depend on which end of a pair evaluates it.  nbody_get_encounters evaluates a pair at the
+ *     higher index; here the reporting row may be the lower.  c, b and disc are built from d2, s and products of two
+ *     differences; ex and ey change sign as a whole; R_i + R_j commutes: {lower, higher, flags, c, b, disc} has the same bits
+ *     either way;
+ *   - the result is a function of the state, h and the SET of inside bodies only: neither the cells nor the order of the
+ *     visit show.
+ * Carried over unchanged from nbody_get_encounters: the cap rule (pairs > cap: NBODY_ERR_CAPACITY, out untouched, info
+ * complete; NULL out with cap == 0: the counts only), the host half (nbody_encounter_finish), the single-rank restriction
+ * (NBODY_ERR_STATE on world > 1, NBODY_FLAG_GROUP_EXCHANGE or NBODY_FLAG_FORCE_COMM, and before an upload), "synchronises,
+ * reads only, never changes what later steps compute".  NBODY_ERR_INVALID, found before any device call, the values before
+ * the handle: everything nbody_get_cells rejects about the grid, then what nbody_get_encounters rejects (a NaN or negative
+ * horizon; cap < 0; a NULL out with cap > 0; cap records x systems above 2^31 bytes; a NULL handle or info).
+ * NBODY_ERR_CAPACITY also for a batch with systems * nx * ny above 1 << 22.
+ * The window (csrc/nbody_encounters_grid.hpp; DESIGN.md 4.25 has the proof).  All fp64, each operation rounded on its own, no
+ * fma, on the exactly widened record, with h the horizon:
+ *     rho_i = |R_i| + (h * (|VX_i| + |VY_i|))          the reach: radius plus the L1 norm of the displacement within h
+ *     rho_i = +inf where that is NaN (a NaN velocity or radius, 0 * inf)
+ *     rho_i = +inf where the context is fp64 and any of X, Y, VX, VY, R of body i is not finite, or non-zero with a
+ *             magnitude outside [2^-100, 2^200]
+ *     H_i = (rho_i + rho_i) * (1 + 2^-40);   H2_i = H_i * H_i
+ * Row i owns the pair (i, j) iff rho_i > rho_j, or rho_i == rho_j and i > j - a total order, so every pair has exactly one
+ * owner, and both ends compute rho by the same expression from the same record.  A pair that is swept as the definition
+ * computes it has d2 <= H2 of its owner, so the other end's cell lies in the owner's window of nbody_get_within's span per
+ * axis with h = H_i (per row, as nbody_get_groups_grid passes its S_i; the same escape for a grid of more than 2^400 cells per
+ * unit length).  H_i = +inf (h = +inf; a NaN velocity; the fp64 guard) means every cell for that row: correct, and slow.  The
+ * rule costs time, never a result.  It uses |v|, not the speed relative to the neighbours: a common bulk velocity widens
+ * every window.
+ * It allocates nothing of its own - the cell list of nbody_get_cells, the sorted records of nbody_get_within, the log and
+ * counters of nbody_get_encounters, each on the first call of whichever query needs it; a handle that never calls it
+ * allocates nothing and launches nothing more, and every other kernel keeps its code.  n == 0 launches nothing.
+ * Cost (one MI355X, fp32; profiles/encounters_grid_probe.txt, nbody_get_encounters timed in the same runs; the stock state of
+ * N = 262144, n = 130965 after 3 steps, on encounters_grid(field, h, median radius 124.5, median |vx| + |vy| 65.8): 804 x 804,
+ * 727 x 727 and 390 x 390 cells at h = 0 / 0.2 / 2.0, a median window of 9 cells, the widest 49 / 49 / 64, 2.5 / 2.9 / 9.4
+ * candidates per row of which 0.10 / 0.13 / 0.31 pass the compare).  The walk 0.076 / 0.080 / 0.095 ms with the counts only and
+ * 0.101 / 0.133 / 0.280 ms with the list of 5052 / 9201 / 35603 records, the kernels of a call 0.47 / 0.41 / 0.21 ms (0.39 / 0.33 /
+ * 0.12 of it the list stages) against encounters_walk's 18.4 - 18.9 ms; whole calls 0.51 / 0.46 / 0.26 ms for the counts against
+ * 18.8 - 19.0 ms and 0.91 / 1.28 / 3.71 ms with the list against 19.2 / 19.7 / 22.1 ms.  On 1 x 1 cells every row walks all n
+ * records from memory: 14.7 against 18.4 ms - ahead of the plain call, 30 times behind the matched grid.  A batch of 256 x 1024
+ * at h = 0.2 on 128 x 128 cells: kernels 0.065 against 0.309 ms, whole calls 0.119 against 0.346 ms (counts) and 0.865 against
+ * 1.036 ms (the list).  Not measured: h = +inf (every cell for every row), fp64, a state with a bulk velocity.
+ * nbody_batch_get_encounters_grid: the same for every system of a batch, with one grid, one horizon and one cap for all of
+ * them, every stage ONE launch whatever S is.  System s's list at out + s * cap, info[s]; the tail of every slice is left
+ * unchanged.  System s gives exactly what an nbody_ctx holding that system's state gives.  A count outside [0, capacity] is
+ * treated as 0 and reported for that system, as by nbody_batch_get_cells.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct nbody_encounter_grid_info {
+    int64_t n_bodies, pairs, now, end, missed; double horizon; int64_t inside, outside;
+} nbody_encounter_grid_info;   /* 64 bytes */
+int nbody_get_encounters_grid(nbody_ctx* ctx, const nbody_grid* grid, double horizon, nbody_encounter* out, int cap,
+                              nbody_encounter_grid_info* info);
+int nbody_batch_get_encounters_grid(struct nbody_batch* b, const nbody_grid* grid, double horizon,
+                                    nbody_encounter* out /* [systems * cap] */, int cap,
+                                    nbody_encounter_grid_info* info /* [systems] */);
+
+/* ---------------------------------------------------------------------------------------------------
  * Batched stepper: S independent systems in one context, stepped together -- S copies of the loop body
  * src/nbody.cu:463-510 per call, for ensembles of SMALL systems (seeds, radii, growth rates, time steps).  One system of
  * N = 1024 is eight workgroups and a fixed per-step tail on a 256-CU part; S of them as S nbody_ctx cost S launches and

@@ -184,6 +184,8 @@ ENCOUNTER_INFO_DTYPE = np.dtype([("n_bodies", np.int64), ("pairs", np.int64), ("
                                  ("missed", np.int64), ("horizon", np.float64)])
 ENCOUNTER_RAW_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("flags", np.uint32), ("reserved", np.uint32),
                                 ("c", np.float64), ("b", np.float64), ("disc", np.float64)])
+# struct nbody_encounter_grid_info (64 bytes): nbody_encounter_info, then inside and outside (encounters(grid=...))
+ENCOUNTER_GRID_INFO_DTYPE = np.dtype(ENCOUNTER_INFO_DTYPE.descr + [("inside", np.int64), ("outside", np.int64)])
 
 # struct nbody_binary, nbody_binary_raw, nbody_binary_info as numpy records (Stepper.binaries, StepperBatch.binaries,
 # binary_finish); BINARY_DTYPE is what they return: the record without its reserved word
@@ -291,6 +293,8 @@ SYMBOLS = {
     "nbody_get_pair_counts": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "nbody_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
     "nbody_batch_get_encounters": (_i, [_vp, _d, _vp, _i, _vp]),
+    "nbody_get_encounters_grid": (_i, [_vp, _vp, _d, _vp, _i, _vp]),
+    "nbody_batch_get_encounters_grid": (_i, [_vp, _vp, _d, _vp, _i, _vp]),
     "nbody_encounter_finish": (_i, [_vp, _i, _d, _vp]),
     "nbody_get_binaries": (_i, [_vp, _d, _vp, _i, _vp]),
     "nbody_batch_get_binaries": (_i, [_vp, _d, _vp, _i, _vp]),
@@ -904,6 +908,15 @@ def groups_grid(field, link, radius_scale, r_typical, most=1024):
     return within_grid(field, float(radius_scale) * 2.0 * float(r_typical) + float(link), most=most)
 
 
+def encounters_grid(field, horizon, r_typical, v_typical, most=1024):
+    """The grid to hand encounters(grid=...): within_grid(field, 2 * (r_typical + horizon * v_typical), most=most), the
+    field's bounds in cells no smaller than twice the reach of a TYPICAL body within the horizon - the median radius and the
+    median of |vx| + |vy| of the state, say - and at most `most` per axis: the grid on which a typical row's window is 3 x 3
+    cells.  A row's window is as wide as its OWN reach asks, so one fast or large body walks more cells itself and widens
+    nobody else's window."""
+    return within_grid(field, 2.0 * (float(r_typical) + float(horizon) * float(v_typical)), most=most)
+
+
 def knn_grid(field, k, n, most=1024):
     """The grid to hand knn(grid=...): the field's bounds [-w, w) x [-h, h) (field = (w, h)) in square-ish cells that hold
     about k of n bodies each at uniform density - side sqrt(area * k / n) - and at most `most` per axis: the grid on which
@@ -1015,11 +1028,12 @@ def _encounter_info(info):
     return d
 
 
-def _encounters(call, systems, horizon, cap):
+def _encounters(call, systems, horizon, cap, grid=None):
     """nbody_get_encounters through `call(horizon, out, cap, info)` -> one (ENCOUNTER_DTYPE array, info dict) per system.  On
-    NBODY_ERR_CAPACITY the call is repeated once with the largest info.pairs."""
+    NBODY_ERR_CAPACITY the call is repeated once with the largest info.pairs.  With a grid (a GRID_DTYPE record) `call` is
+    nbody_get_encounters_grid's with the grid bound, and the info dicts also have "inside", "outside" and "grid"."""
     S = max(systems, 1)
-    info = np.zeros(S, dtype=ENCOUNTER_INFO_DTYPE)
+    info = np.zeros(S, dtype=ENCOUNTER_INFO_DTYPE if grid is None else ENCOUNTER_GRID_INFO_DTYPE)
     cap = max(int(cap), 0)
     buf = np.zeros((S, max(cap, 1)), dtype=ENCOUNTER_RECORD_DTYPE)
     status = call(horizon, buf.ctypes.data, cap, info.ctypes.data)
@@ -1028,7 +1042,12 @@ def _encounters(call, systems, horizon, cap):
         buf = np.zeros((S, max(cap, 1)), dtype=ENCOUNTER_RECORD_DTYPE)
         status = call(horizon, buf.ctypes.data, cap, info.ctypes.data)
     _check(status)
-    return [(_encounter_list(buf[s, :int(info["pairs"][s])]), _encounter_info(info[s])) for s in range(systems)]
+    out = [(_encounter_list(buf[s, :int(info["pairs"][s])]), _encounter_info(info[s])) for s in range(systems)]
+    if grid is not None:
+        ins, outs, g = info["inside"].tolist(), info["outside"].tolist(), grid.copy()   # one copy of the grid per call
+        for s, (_, d) in enumerate(out):
+            d.update(inside=ins[s], outside=outs[s], grid=g[0])
+    return out
 
 
 def encounter_finish(raw, horizon):
@@ -1495,18 +1514,25 @@ class Stepper:
                                 squared, g)[0]
         return _pair_counts(lambda *a: lib.nbody_get_pair_counts(self._ctx, *a), 1, edges, points, squared)[0]
 
-    def encounters(self, horizon=None, cap=None):
+    def encounters(self, horizon=None, cap=None, grid=None):
         """nbody_get_encounters: the pairs of current bodies that touch within the next `horizon` seconds if every body keeps
         its velocity (the uniform-motion estimate: no acceleration, no walls) -> (an ENCOUNTER_DTYPE array {"t": time of
         contact, "i" < "j", "flags": ENCOUNTER_NOW | ENCOUNTER_END} sorted by (t, i, j), {"n_bodies", "pairs", "now", "end",
         "missed", "horizon"}); a pair with neither flag touches strictly inside the horizon and overlaps at neither end.
         horizon=None: the context's own time step, widened as the tracers widen it.  cap: the first guess of the room (None:
-        the capacity); a longer list is fetched with a second call.  Single-rank contexts only."""
+        the capacity); a longer list is fetched with a second call.  Single-rank contexts only.
+        grid (a make_grid record, or what make_grid accepts): nbody_get_encounters_grid, the same list found through the
+        cell list in O(n), among the bodies inside the grid only; the info dict also has "inside", "outside" and "grid".
+        With outside == 0 the list and the counts are those of grid=None, whatever the grid.  The matched grid is
+        encounters_grid(field, horizon, r_typical, v_typical)."""
         if horizon is None:
             d, steps = _CtxDesc(), ctypes.c_int64(0)
             _check(lib.nbody_ctx_info(self._ctx, ctypes.byref(d), ctypes.byref(steps)))
             horizon = float(np.float32(d.timestep)) if self.precision == F32 else float(d.timestep)
         cap = max(self.capacity, 64) if cap is None else cap
+        if grid is not None:
+            g = make_grid(grid)
+            return _encounters(lambda *a: lib.nbody_get_encounters_grid(self._ctx, g.ctypes.data, *a), 1, float(horizon), cap, g)[0]
         return _encounters(lambda *a: lib.nbody_get_encounters(self._ctx, *a), 1, float(horizon), cap)[0]
 
     def binaries(self, max_sep, squared=False, cap=None, grid=None):
@@ -1916,11 +1942,17 @@ class StepperBatch:
                                 points, squared, g)
         return _pair_counts(lambda *a: lib.nbody_batch_get_pair_counts(self._b, *a), self.systems, edges, points, squared)
 
-    def encounters(self, horizon, cap=None):
+    def encounters(self, horizon, cap=None, grid=None):
         """nbody_batch_get_encounters: Stepper.encounters for every system in one launch: a list of S (array, info) pairs in
         the form (and with the bits) a Stepper holding the system's state gives.  The kernel takes ONE horizon for the whole
-        batch, so it has to be given: a batch's systems may each have their own time step."""
+        batch, so it has to be given: a batch's systems may each have their own time step.
+        grid: one grid for every system, nbody_batch_get_encounters_grid - the list stages and the walk one launch each; the
+        matched grid is encounters_grid(field, horizon, r_typical, v_typical)."""
         cap = max(self.capacity, 64) if cap is None else cap
+        if grid is not None:
+            g = make_grid(grid)
+            return _encounters(lambda *a: lib.nbody_batch_get_encounters_grid(self._b, g.ctypes.data, *a), self.systems,
+                               float(horizon), cap, g)
         return _encounters(lambda *a: lib.nbody_batch_get_encounters(self._b, *a), self.systems, float(horizon), cap)
 
     def binaries(self, max_sep, squared=False, cap=None, grid=None):

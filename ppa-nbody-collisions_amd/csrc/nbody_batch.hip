@@ -886,3 +886,21 @@ int nbody_batch_get_binaries_grid(nbody_batch* b, const nbody_grid* grid, double
 }
 
 }  // extern "C"
+
+// Encounters on the cell list (nbody_encounters_grid.hpp): one grid, one horizon and one cap for every system, the list
+// stages and the walk ONE launch each for the whole batch.
+extern "C" {
+
+int nbody_batch_get_encounters_grid(nbody_batch* b, const nbody_grid* grid, double horizon, nbody_encounter* out, int cap,
+                                    nbody_encounter_grid_info* info) {
+    const char* who = "nbody_batch_get_encounters_grid";
+    RowsSite site;
+    int rc = encounters_grid_check_args(who, b, grid, horizon, out, cap, info, batch_systems(b));
+    if (rc != NBODY_OK || (rc = batch_rows_site(b, who, site)) != NBODY_OK) return rc;
+    return batch_rows_run(b, [&](auto t, auto sync) {
+        return encounters_grid_run<decltype(t), RowsBatchCount>(who, site, b->V, b->q.cel, b->q.enc, *grid, horizon, out, cap, info,
+                                                                sync);
+    });
+}
+
+}  // extern "C"

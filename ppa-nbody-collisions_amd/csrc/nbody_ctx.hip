@@ -1914,3 +1914,22 @@ int nbody_get_binaries_grid(nbody_ctx* c, const nbody_grid* grid, double sep2, n
 }
 
 }  // extern "C"
+
+// Encounters on the cell list (nbody_encounters_grid.hpp): the plain call's arguments and errors after the grid's; it reads
+// the velocities, so the encounters' restriction holds.  After everything else, for the group energies' reason.
+extern "C" {
+
+int nbody_get_encounters_grid(nbody_ctx* c, const nbody_grid* grid, double horizon, nbody_encounter* out, int cap,
+                              nbody_encounter_grid_info* info) {
+    const char* who = "nbody_get_encounters_grid";
+    RowsSite site;
+    int rc = encounters_grid_check_args(who, c, grid, horizon, out, cap, info, 1);
+    if (rc != NBODY_OK || (rc = ctx_single_rank(c, who, "encounters need", kOwnVelocities)) != NBODY_OK) return rc;
+    if ((rc = ctx_rows_site(c, who, site)) != NBODY_OK) return rc;
+    return ctx_rows_run(c, [&](auto t, auto sync) {
+        return encounters_grid_run<decltype(t), RowsOneCount>(who, site, c->Vown, c->q.cel, c->q.enc, *grid, horizon, out, cap, info,
+                                                              sync);
+    });
+}
+
+}  // extern "C"

@@ -6,7 +6,8 @@
 // entry points (nbody_get_* in nbody_ctx.hip, nbody_batch_get_* in nbody_batch.hip).  Nothing is allocated before a query's
 // first call (tracers: the first set); each state grows to the largest request seen and is released by queries_free.
 // A query that is another walk over what the states already hold adds no member: the groups on the cell list
-// (nbody_groups_grid.hpp) use `cel` and `grp`, the pair counts and binaries on it (nbody_pairs_grid.hpp) `cel`, `prs` and `bin`.
+// (nbody_groups_grid.hpp) use `cel` and `grp`, the pair counts and binaries on it (nbody_pairs_grid.hpp) `cel`, `prs` and `bin`,
+// the encounters on it (nbody_encounters_grid.hpp) `cel` and `enc`.
 // IdsState and TrackState are not queries - they are set up at create and by a reservation - and stay members of the
 // handles, with ids_free and track_free next to them.
 #pragma once
@@ -30,6 +31,7 @@
 #include "nbody_groups_grid.hpp"
 #include "nbody_knn_grid.hpp"
 #include "nbody_pairs_grid.hpp"
+#include "nbody_encounters_grid.hpp"
 
 namespace nbk {
 
